@@ -3,6 +3,11 @@
 
     python bench.py --gpus N --steps K --warmup W            (N > 1: under torch.distributed.run, or it starts its own N ranks;
                                                               --rank-devices 0,0 = two ranks on one GPU)
+    python bench.py ... --full                               (+ cpu_baseline, the live traffic passes and the legs below)
+    python bench.py ... --dump-outputs DIR                   (what the last timed step computed, as DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps and prints the line; `cpu_baseline`, the re-measured `roofline.traffic`
+and `legs` take runs of their own and are measured only with --full.
 
 Workload (default `walk`, BASELINE.json configs[2], the case the north-star target is quoted on):
 semantic pseudo-label generation for a batch of synthetic VOC12-shaped images — 512x512 images,
@@ -83,6 +88,12 @@ def parse(argv=None):
     ap.add_argument("--allow-walk-fallback", action="store_true",
                     help="e2e / steps: record persistent walks that were re-run on the streaming sweeps instead of failing the run (ranks "
                          "sharing one device, a co-tenant on the GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the CPU baselines, roofline.traffic re-measured by "
+                         "rocprofv3 and the legs (walk workload, one rank); --no-cpu-baseline / --no-traffic / --no-legs drop parts of it")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, rank 0's images; "
+                         "a fixed seeded sample of them when the whole batch would exceed 60 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-traffic", action="store_true",
                     help="do not re-measure roofline.traffic (two short rocprofv3 --pmc passes of this script, ~40 s): use profiles/traffic_<workload>.json")
@@ -148,6 +159,43 @@ def algorithmic_bytes_per_sweep(shapes, n_dirs):
 def flops_per_sweep(shapes, n_dirs):
     """F = 2*(2|S|+1) flops per pixel, channel and sweep."""
     return float(sum(2.0 * (2 * n_dirs + 1) * h * w * c for h, w, c in shapes))
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6       # what --dump-outputs may write in all (under 64 MB with the index and shape files)
+
+
+def dump_outputs(out_dir, outputs, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: `outputs` maps a name to a list with one array per image of the last timed step.  Writes
+    <out_dir>/<name>.npy in float32 (float64 arrays stay float64): stacked when every image's array has one shape, else
+    flattened and concatenated, with <name>_shapes.npy giving each image's shape.  index.npy lists which images of the
+    batch were written: all of them, or — when they would exceed `budget` bytes — a fixed seeded sample, the same images
+    for every name.  Returns the file names written."""
+    names = sorted(outputs)
+    n = len(outputs[names[0]]) if names else 0
+    cast = lambda x: np.asarray(x, np.float64 if np.asarray(x).dtype == np.float64 else np.float32)
+    per_image = [sum(cast(outputs[k][i]).nbytes for k in names) for i in range(n)]
+    idx = list(range(n))
+    if sum(per_image) > budget:
+        idx, total = [], 0
+        for i in np.random.RandomState(seed).permutation(n):
+            if total + per_image[i] <= budget:
+                idx.append(int(i))
+                total += per_image[i]
+        idx.sort()
+    os.makedirs(out_dir, exist_ok=True)
+    written = ["index.npy"]
+    np.save(os.path.join(out_dir, "index.npy"), np.asarray(idx, np.float64))
+    for k in names:
+        arrs = [cast(outputs[k][i]) for i in idx]
+        if len({a.shape for a in arrs}) <= 1:
+            data = np.stack(arrs) if arrs else np.zeros((0,), np.float32)
+        else:
+            data = np.concatenate([a.ravel() for a in arrs])
+            np.save(os.path.join(out_dir, k + "_shapes.npy"), np.asarray([a.shape for a in arrs], np.float64))
+            written.append(k + "_shapes.npy")
+        np.save(os.path.join(out_dir, k + ".npy"), data)
+        written.append(k + ".npy")
+    return written
 
 
 # ------------------------------------------------------------------------------------------------
@@ -328,7 +376,7 @@ def timed_loop(step, steps, warmup, dist, parallel, device, after_warmup=None, b
     return parallel.max_over_ranks(time.perf_counter() - t0, dist, device), out
 
 
-def run_walk(a, workload, rank, world, device, dist, parallel, steps, warmup, batch=0):
+def run_walk(a, workload, rank, world, device, dist, parallel, steps, warmup, batch=0, collect=False):
     """walk / walk_r5 / coco: affinity build + random walk + label epilogue on resident tensors."""
     from irn_amd import ops
     from irn_amd.misc import indexing
@@ -363,7 +411,9 @@ def run_walk(a, workload, rank, world, device, dist, parallel, steps, warmup, ba
     checksum = int(sum(int(l.sum().item()) for l in labels[:4]))
     n_sweeps = 2 ** exp_times
     n_applied = walker.steps(n_sweeps)                     # operator applications the schedule spends on T^n_sweeps
-    head = [(labels[i].cpu().numpy(), keys[i].cpu().numpy()) for i in range(min(8, n_unique))]   # for cpu_baseline.label_parity
+    head = [(labels[i].cpu().numpy(), keys[i].cpu().numpy()) for i in range(min(8, n_unique))] if a.full else None   # for cpu_baseline.label_parity
+    # the last timed step's results, as its caller receives them: label maps, and the walk's output they were made from
+    outputs = {"labels": [l.cpu().numpy() for l in labels], "rw": [o.cpu().numpy() for o in outs]} if collect else None
     tuning = walker.tuning()
     fallback_runs = walker.fallback_runs
     walker.close()
@@ -391,10 +441,10 @@ def run_walk(a, workload, rank, world, device, dist, parallel, steps, warmup, ba
             "launches_timed": sweep_launches // max(sweeps_per_launch, 1), "flops_per_launch": flops_per_launch,
             "bytes_per_launch": bytes_per_launch, "sweep_share_of_step": sweep_ms / (1e3 * elapsed),
             "label_checksum": checksum, "head_labels": head, "tuning": tuning, "fallback_runs": fallback_runs, "rounds": rounds,
-            "grid_pixels": int(sum(s[0] * s[1] for s in shapes)), "sizes": sizes}
+            "grid_pixels": int(sum(s[0] * s[1] for s in shapes)), "sizes": sizes, "outputs": outputs}
 
 
-def run_ins(a, workload, rank, world, device, dist, parallel, steps, warmup, batch=0):
+def run_ins(a, workload, rank, world, device, dist, parallel, steps, warmup, batch=0, collect=False):
     """configs[3]: instance pseudo-labels from resident edge / displacement / CAM tensors — centroid refinement,
     clustering, per-instance CAM split + random walk, label epilogue, per-mask connected components, and the transfer
     of the detections to the host (step/make_ins_seg_labels.py:131-152 for every image of the batch)."""
@@ -435,12 +485,18 @@ def run_ins(a, workload, rank, world, device, dist, parallel, steps, warmup, bat
     n_det = sum(0 if isinstance(d, Exception) else len(d["score"]) for d in dets)
     n_fallback = walker.fallback_runs
     walker.close()
+    outputs = None
+    if collect:                   # the detection dicts of the last timed batch (an image without detections: empty arrays)
+        empty = {"score": np.zeros((0,), np.float32), "class": np.zeros((0,), np.float32),
+                 "mask": np.zeros((0,) + tuple(out_hw), np.float32)}
+        dets_ok = [empty if isinstance(d, Exception) else d for d in dets]
+        outputs = {k: [np.asarray(d[k]) for d in dets_ok] for k in ("score", "class", "mask")}
     return {"value": steps * batch * world / elapsed, "ms_per_step": 1e3 * elapsed / steps, "batch": batch,
             "detections_per_image": n_det / float(batch), "fallback_runs": n_fallback,
-            "radius": radius, "beta": beta, "exp_times": exp_times, "out_hw": out_hw, "h": h, "w": w}
+            "radius": radius, "beta": beta, "exp_times": exp_times, "out_hw": out_hw, "h": h, "w": w, "outputs": outputs}
 
 
-def run_backbone(a, workload, rank, world, device, dist, parallel, steps, warmup, batch=0):
+def run_backbone(a, workload, rank, world, device, dist, parallel, steps, warmup, batch=0, collect=False):
     """`cam`  BASELINE configs[1]: multi-scale CAM inference — ResNet-50 CAM on {1.0,0.5,1.5,2.0}x512^2 with
            h-flip, merge to the stride-4 / full-resolution maps (step/make_cam.py:26-56), PyTorch-ROCm fp32.
     `e2e`  cam + EdgeDisplacement forward + random walk (radius 10, beta 10, 2^8) + label epilogue.
@@ -484,9 +540,13 @@ def run_backbone(a, workload, rank, world, device, dist, parallel, steps, warmup
             rws = walker(edges, [c[1] for c in cams], beta=10.0, exp_times=8)
             return ops.label_epilogue(rws, [(H, W)] * batch, 0.25, keys=[c[0] for c in cams])["labels"]
 
-    elapsed, _ = timed_loop(step, steps, warmup, dist, parallel, device)
+    elapsed, last = timed_loop(step, steps, warmup, dist, parallel, device)
     _common.check_split_overflow("bench.py %s" % workload)        # an activation beyond fp16's range would invalidate the run
     out = {"value": steps * batch * world / elapsed, "ms_per_step": 1e3 * elapsed / steps, "batch": batch, "scales": scales}
+    if collect:                   # the last timed step's (keys, cam, high_res) per image, or its label maps (e2e)
+        host = lambda t: t.cpu().numpy()
+        out["outputs"] = ({"keys": [host(c[0]) for c in last], "cam": [host(c[1]) for c in last], "high_res": [host(c[2]) for c in last]}
+                          if workload == "cam" else {"labels": [host(l) for l in last]})
     # convolution flops per image (counted on meta tensors: nothing is computed) against the fp32 matrix peak: the backbones
     # are library kernels (MIOpen, hipBLASLt), so this is a utilisation figure, not a roofline claim of a kernel of ours — and
     # an fp32-EQUIVALENT one: with the split-precision 1x1 convolutions part of the work runs on the fp16 matrix pipe (3 fp16
@@ -547,7 +607,7 @@ def backbone_gflop_per_image(scales, size, with_irn):
     return _GFLOP[key]
 
 
-def run_steps(a, rank, world, device, dist, parallel, steps, warmup, batch=0, voc_sizes=False):
+def run_steps(a, rank, world, device, dist, parallel, steps, warmup, batch=0, voc_sizes=False, collect=False):
     """The drop-in step API itself, in run_sample.py's order (reference run_sample.py:91-131): make_cam.run(args) ->
     make_ins_seg_labels.run(args) -> make_sem_seg_labels.run(args) on a synthetic VOC-shaped directory of 512x512 JPEGs
     with random-init checkpoints: DataLoader + JPEG decode, multi-scale CAM, CAM hand-off, IRNet, walk, detections, PNG /
@@ -642,7 +702,12 @@ def run_steps(a, rank, world, device, dist, parallel, steps, warmup, batch=0, vo
         n_ins = len([f for f in os.listdir(args.ins_seg_out_dir) if f.endswith(".npy")])
         if n_png != batch:
             raise RuntimeError("steps leg: %d label maps written for %d images" % (n_png, batch))
-        return {"value": steps * batch * world / elapsed, "ms_per_step": 1e3 * elapsed / steps, "batch": batch,
+        outputs = None
+        if collect:               # the files the last timed pass wrote, image by image: semantic label maps and the CAMs
+            outputs = {"sem_seg_labels": [np.asarray(Image.open(os.path.join(args.sem_seg_out_dir, n + ".png"))) for n in names],
+                       "cam": [np.load(os.path.join(args.cam_out_dir, n + ".npy"), allow_pickle=True).item()["cam"] for n in names]}
+            outputs["cam"] = [c.numpy() if torch.is_tensor(c) else c for c in outputs["cam"]]
+        return {"value": steps * batch * world / elapsed, "ms_per_step": 1e3 * elapsed / steps, "batch": batch, "outputs": outputs,
                 "cam_store_hits": _common.CAM_STORE.hits - hits0, "cam_store_misses": _common.CAM_STORE.misses - misses0,
                 "edge_store_hits": _common.EDGE_STORE.hits - e_hits0, "loader_workers": args.num_workers, "instance_files": n_ins,
                 "walk_fallback_runs": fallback_runs, "voc_sizes": bool(voc_sizes),
@@ -685,22 +750,24 @@ def describe(workload, r):
             (workload, r.get("scales"), "" if workload.startswith("cam") else "; EdgeDisplacement forward; walk radius 10 beta 10 2^8; label epilogue"))
 
 
-def run_workload(a, workload, rank, world, device, dist, parallel, steps, warmup, batch=0):
+def run_workload(a, workload, rank, world, device, dist, parallel, steps, warmup, batch=0, collect=False):
+    """One workload's timed run -> its result dict; with `collect`, r["outputs"] holds what the last timed step computed
+    (name -> one host array per image, for --dump-outputs)."""
     if workload.endswith("_fp32"):
         # the backbone legs with the split-precision 1x1 convolutions switched off (IRN_SPLIT_GEMM=0): plain fp32 GEMMs everywhere
         from irn_amd.net import resnet50 as _r50
         saved, _r50.SPLIT_GEMM = _r50.SPLIT_GEMM, False
         try:
-            return run_backbone(a, workload[:-5], rank, world, device, dist, parallel, steps, warmup, batch)
+            return run_backbone(a, workload[:-5], rank, world, device, dist, parallel, steps, warmup, batch, collect)
         finally:
             _r50.SPLIT_GEMM = saved
     if workload in WALK_WORKLOADS:
-        return run_walk(a, workload, rank, world, device, dist, parallel, steps, warmup, batch)
+        return run_walk(a, workload, rank, world, device, dist, parallel, steps, warmup, batch, collect)
     if workload in ("ins", "ins_r10"):
-        return run_ins(a, workload, rank, world, device, dist, parallel, steps, warmup, batch)
+        return run_ins(a, workload, rank, world, device, dist, parallel, steps, warmup, batch, collect)
     if workload in ("steps", "steps_voc"):
-        return run_steps(a, rank, world, device, dist, parallel, steps, warmup, batch, voc_sizes=(workload == "steps_voc"))
-    return run_backbone(a, workload, rank, world, device, dist, parallel, steps, warmup, batch)
+        return run_steps(a, rank, world, device, dist, parallel, steps, warmup, batch, voc_sizes=(workload == "steps_voc"), collect=collect)
+    return run_backbone(a, workload, rank, world, device, dist, parallel, steps, warmup, batch, collect)
 
 
 LEG_RUNS = {   # short runs for the `legs` object of the default line: (steps, warmup, batch)
@@ -881,7 +948,10 @@ def main(argv=None):
     # the ranks agree over a gloo control group, and the line says which backend served it
     dist, backend_used = parallel.init_process_group_with_fallback(a.backend, device, rank_devices=a.rank_devices)
 
-    r = run_workload(a, a.workload, rank, world, device, dist, parallel, a.steps, a.warmup, a.batch)
+    r = run_workload(a, a.workload, rank, world, device, dist, parallel, a.steps, a.warmup, a.batch,
+                     collect=bool(a.dump_outputs) and rank == 0)
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, r.pop("outputs"))
     if rank == 0:
         stage = {"walk": "random-walk label generation stage", "walk_r5": "random-walk label generation stage, radius 5",
                  "walk_plain": "random-walk label generation stage, plain 2^exp_times iteration",
@@ -907,7 +977,7 @@ def main(argv=None):
             "roofline": None,
         }
         live = None
-        if world == 1 and a.workload == "walk" and a.variant == 2 and not a.no_traffic and not a.no_legs:
+        if a.full and world == 1 and a.workload == "walk" and a.variant == 2 and not a.no_traffic and not a.no_legs:
             torch.cuda.synchronize()
             live = measure_traffic(a, a.workload, r["batch"])      # (a child process on the same GPU; this one is idle meanwhile)
         res["roofline"] = roofline_object(a, a.workload, r, live)
@@ -919,11 +989,11 @@ def main(argv=None):
             if k in r:
                 res["config"][k] = r[k]
         res["cpu_baseline"] = None
-        if world == 1 and not a.no_cpu_baseline and a.workload in ("walk", "walk_r5", "walk_plain", "coco"):      # (square-grid workloads)
+        if a.full and world == 1 and not a.no_cpu_baseline and a.workload in ("walk", "walk_r5", "walk_plain", "coco"):      # (square-grid workloads)
             res["cpu_baseline"] = cpu_baseline(a, a.workload, a.cpu_images, 1000, gpu_labels=r.get("head_labels"))
             if "label_parity" in res["cpu_baseline"]:
                 res["label_parity"] = res["cpu_baseline"]["label_parity"]
-        if world == 1 and not a.no_legs and a.workload == "walk":
+        if a.full and world == 1 and not a.no_legs and a.workload == "walk":
             legs = {}
             legs_t0 = time.perf_counter()
             for name in [n for n in a.legs.split(",") if n]:

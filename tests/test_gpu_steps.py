@@ -423,14 +423,14 @@ def test_cam_merge_kernel_vs_oracle_and_reference_golden(golden):
 
 
 def test_bench_contract_one_json_line():
-    """python bench.py (small batch) prints ONE JSON line with the driver's fields, the `roofline` object of the dominant
+    """python bench.py --full (small batch) prints ONE JSON line with the driver's fields, the `roofline` object of the dominant
     kernel (binding ceiling at the top level), the `cpu_baseline` object (port + reference algorithm) and the `legs`."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k != "IRN_DETERMINISTIC"}        # the line of the DEFAULT mode, whatever this suite runs under
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "8",
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--batch", "8",
                           "--cpu-images", "2", "--ref-grids", "64", "--legs", "coco,ins,walk_plain,walk_voc,cam"], capture_output=True, text=True,
                          timeout=900, cwd=root, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -480,6 +480,33 @@ def test_bench_contract_one_json_line():
     assert trunk["split_precision_1x1"] == (trunk["layout"] == "channels_last") and 0 < r["legs"]["cam"]["matrix_fp32_frac"] < 2
     cc = cb["cam"]                      # round 6: the CAM half of the metric on the host cores, beside legs.cam
     assert cc["kind"] == "port" and cc["value"] > 0 and cc["cores"] == cb["cores"] and abs(cc["gflop_per_image"] - 974.04) < 0.01
+
+
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """python bench.py without --full times the steps and prints the headline line only (no cpu_baseline, no legs); with
+    --dump-outputs it writes the label maps and walk outputs of the last timed step, and the labels are the ones the line's
+    checksum was taken over."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k != "IRN_DETERMINISTIC"}
+    dump = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "8",
+                          "--dump-outputs", str(dump)], capture_output=True, text=True, timeout=600, cwd=root, env=env)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["ms_per_step"] > 0 and r["unit"] == "images/s" and r["higher_is_better"] is True
+    assert abs(r["value"] - 8 / (r["ms_per_step"] * 1e-3)) / r["value"] < 1e-6
+    assert r["cpu_baseline"] is None and "legs" not in r and "label_parity" not in r
+    assert r["roofline"]["traffic_source"] in (None, "static")
+    labels, rw, index = np.load(dump / "labels.npy"), np.load(dump / "rw.npy"), np.load(dump / "index.npy")
+    assert labels.dtype == np.float32 and labels.shape == (8, 512, 512) and list(index) == list(range(8))
+    assert rw.dtype == np.float32 and np.isfinite(rw).all()
+    assert int(labels[:4].astype(np.int64).sum()) == r["label_checksum"]
+    assert sum(f.stat().st_size for f in dump.iterdir()) <= 64 * 2 ** 20
 
 
 def test_upload_never_blocks_and_equals_cuda():

@@ -43,7 +43,7 @@ bench)
 default)
   # exactly what the driver runs
   T0=$(date +%s)
-  timeout 1500 python bench.py --json-out $OUT/bench_default.json > $OUT/bench_default.log 2> $OUT/bench_default.err; echo "default bench rc=$? wall $(( $(date +%s) - T0 )) s"
+  timeout 1500 python bench.py --full --json-out $OUT/bench_default.json > $OUT/bench_default.log 2> $OUT/bench_default.err; echo "default bench rc=$? wall $(( $(date +%s) - T0 )) s"
   report $OUT/bench_default.json default
   python - <<PY
 import json

@@ -411,6 +411,42 @@ int irn_detect_instance_batch_emit(int n_images, const float *const *rw_up_dev, 
                                    const double *min_area, float *const *score_dev, int32_t *const *channel_dev,
                                    uint8_t *const *mask_dev, void *scratch_dev, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Dense CRF  (replaces misc/imutils.py:156-170 crf_inference_label over pydensecrf, and
+ *             step/cam_to_ir_label.py:22-39)
+ * densecrf numerics: float32, DIAG_KERNEL, NORMALIZE_SYMMETRIC, Potts compatibility; unary from labels
+ * (gt_prob, zero_unsure=False); Gaussian kernel (x/3, y/3) compat 3, bilateral (x/50, y/50, RGB/5)
+ * compat 10; t mean-field iterations.  Lattices are built per image by sort/unique (no float atomics):
+ * every output is bit-reproducible.  Images whose lattice keys would not fit 64 bits give IRN_ERR_ARG.
+ *
+ * irn_crf_filter: the permutohedral filter alone (densecrf Permutohedral::init + compute).
+ *   feat dev fp32 [n][d] (1 <= d <= 5), in / out dev fp32 [n][channels];
+ *   n_vertices (host, may be NULL) receives the lattice size M; keys_dev (dev int32 [M][d], vertices in
+ *   ascending lexicographic key order) and nbr_dev (dev int32 [d+1][M][2], blur neighbours n1 / n2 along
+ *   each axis, -1 = none) are written when not NULL; allocate them for M <= n*(d+1).
+ *   SYNCHRONISES the stream (it reads M back).  workspace: irn_crf_filter_workspace_bytes(n, d, channels).
+ * irn_crf_inference_label: one CRF.  rgb dev uint8 [h][w][3], labels dev int32 [h][w] in [0, n_labels);
+ *   q_dev (dev fp32 [n_labels][h][w], may be NULL) and labels_out_dev (dev int32 [h][w], argmax of Q,
+ *   first maximum) out.  n_labels <= 32.
+ * irn_crf_ir_label: step/cam_to_ir_label.py for one image.  high_res dev fp32 [k][h][w], keys dev int64
+ *   [k] (0-based class ids); the fg / bg seeds are argmax([thr, high_res]) for both thresholds, both CRFs
+ *   run as one filter over 2*(k+1) channels on the shared lattices, and conf dev uint8 [h][w] receives
+ *   fg (0 = background, else key+1), 255 where fg is background, 0 where fg and bg both are.  k == 0
+ *   writes zeros and needs no workspace (ws may be NULL).
+ * workspace of both: irn_crf_workspace_bytes(h, w, n_labels) (n_labels = k+1 for irn_crf_ir_label);
+ *   0 = unsupported size.
+ * ------------------------------------------------------------------------------------------- */
+size_t irn_crf_filter_workspace_bytes(int n, int d, int channels);
+int irn_crf_filter(const float *feat_dev, int n, int d, const float *in_dev, int channels, float *out_dev,
+                   int32_t *n_vertices, int32_t *keys_dev, int32_t *nbr_dev, void *ws, size_t ws_bytes, void *stream);
+size_t irn_crf_workspace_bytes(int h, int w, int n_labels);
+int irn_crf_inference_label(const uint8_t *rgb_dev, const int32_t *labels_dev, int h, int w, int n_labels, int t,
+                            float gt_prob, float *q_dev, int32_t *labels_out_dev, void *ws, size_t ws_bytes,
+                            void *stream);
+int irn_crf_ir_label(const uint8_t *rgb_dev, const float *high_res_dev, const int64_t *keys_dev, int k, int h, int w,
+                     float fg_thres, float bg_thres, int t, float gt_prob, uint8_t *conf_dev, void *ws,
+                     size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 """Image helpers the hot path needs (API mirror of the corresponding reference misc/imutils.py
-functions; the augmentation / CRF / colouring helpers of that file are training-side and out of scope).
+functions; the augmentation / colouring helpers of that file are training-side and out of scope).
 """
 import numpy as np
 from PIL import Image
@@ -41,3 +41,14 @@ def compress_range(arr):
     lut[uniq] = np.arange(uniq.shape[0])
     out = lut[arr]
     return out - np.min(out)
+
+
+def crf_inference_label(img, labels, t=10, n_labels=21, gt_prob=0.7):
+    """misc/imutils.py:156-170 — dense CRF (pydensecrf's numerics) on the GPU (irn_amd/csrc/crf.hip, no CPU fallback).
+    img uint8 [H,W,3] RGB, labels int [H,W] in [0, n_labels).  Returns the argmax labels int64 [H,W] (numpy)."""
+    import torch
+    from .. import ops
+    dev = torch.device("cuda", torch.cuda.current_device())
+    img = torch.from_numpy(np.ascontiguousarray(img, dtype=np.uint8)).to(dev)
+    lab = torch.from_numpy(np.ascontiguousarray(labels).astype(np.int32)).to(dev)
+    return ops.crf_inference_label(img, lab, t=t, n_labels=n_labels, gt_prob=gt_prob).cpu().numpy().astype(np.int64)

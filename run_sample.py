@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""CLI boundary — same flags and step order as reference run_sample.py:8-137, for the three
-label-generation steps this repository implements (make_cam, make_ins_seg, make_sem_seg).
+"""CLI boundary — same flags and step order as reference run_sample.py:8-137, for the four
+label-generation steps this repository implements (make_cam, cam_to_ir_label, make_ins_seg, make_sem_seg).
 
-The training / CRF / evaluation steps of the reference (train_cam, eval_cam, cam_to_ir_label,
-train_irn, eval_ins_seg, eval_sem_seg) are outside the hot-path scope; their
+The training / evaluation steps of the reference (train_cam, eval_cam, train_irn, eval_ins_seg,
+eval_sem_seg) are outside the hot-path scope; their
 `--*_pass` flags are accepted so existing command lines keep working, and asking for one of them
 is an error rather than a silent skip.  Weights are inputs: --cam_weights_name / --irn_weights_name
 must point at checkpoints written by the reference's training steps (or any state dict with the
@@ -41,14 +41,15 @@ def build_parser():
     p.add_argument("--radius", default=5, type=int,
                    help="random-walk radius of the label steps (not a flag of the reference, which hard-codes 5 at "
                         "step/make_sem_seg_labels.py:41 and step/make_ins_seg_labels.py:135; 10 = BASELINE configs[2])")
-    # training / CRF / evaluation hyper-parameters of the reference (run_sample.py:25-40): accepted so that an existing
+    p.add_argument("--conf_fg_thres", default=0.30, type=float, help="cam_to_ir_label: CAM score of a confident foreground seed")
+    p.add_argument("--conf_bg_thres", default=0.05, type=float, help="cam_to_ir_label: CAM score below which a seed is background")
+    # training / evaluation hyper-parameters of the reference (run_sample.py:25-40): accepted so that an existing
     # command line keeps parsing; the steps that read them are not part of this build
     for name, default, typ in (("cam_crop_size", 512, int), ("cam_batch_size", 16, int), ("cam_num_epoches", 5, int),
                                ("cam_learning_rate", 0.1, float), ("cam_weight_decay", 1e-4, float),
-                               ("cam_eval_thres", 0.15, float), ("conf_fg_thres", 0.30, float), ("conf_bg_thres", 0.05, float),
-                               ("irn_crop_size", 512, int), ("irn_batch_size", 32, int), ("irn_num_epoches", 3, int),
+                               ("cam_eval_thres", 0.15, float), ("irn_crop_size", 512, int), ("irn_batch_size", 32, int), ("irn_num_epoches", 3, int),
                                ("irn_learning_rate", 0.1, float), ("irn_weight_decay", 1e-4, float)):
-        p.add_argument("--" + name, default=default, type=typ, help="accepted and ignored (training / CRF side of the reference)")
+        p.add_argument("--" + name, default=default, type=typ, help="accepted and ignored (training side of the reference)")
     p.add_argument("--worker_devices", default="", type=str,
                    help="device ordinal of every worker process, e.g. 0,1,2,3 (default: one per visible GPU like the reference; "
                         "0,0 = two workers sharing GPU 0)")
@@ -96,7 +97,7 @@ def build_parser():
     return p
 
 
-OUT_OF_SCOPE = ("train_cam_pass", "eval_cam_pass", "cam_to_ir_label_pass", "train_irn_pass", "eval_ins_seg_pass",
+OUT_OF_SCOPE = ("train_cam_pass", "eval_cam_pass", "train_irn_pass", "eval_ins_seg_pass",
                 "eval_sem_seg_pass")
 
 
@@ -105,7 +106,7 @@ def main(argv=None):
     for name in OUT_OF_SCOPE:
         if getattr(args, name):
             raise SystemExit("--%s: this step is not part of the MI355X hot-path build; run it with the reference" % name)
-    for d in (args.cam_out_dir, args.sem_seg_out_dir, args.ins_seg_out_dir):
+    for d in (args.cam_out_dir, args.sem_seg_out_dir, args.ins_seg_out_dir) + ((args.ir_label_out_dir,) if args.cam_to_ir_label_pass else ()):
         os.makedirs(d, exist_ok=True)
     if args.split_gemm is not None:
         os.environ["IRN_SPLIT_GEMM"] = str(int(args.split_gemm))           # workers read it when they import the trunk
@@ -119,6 +120,10 @@ def main(argv=None):
         from irn_amd.step import make_cam
         timer = pyutils.Timer("step.make_cam:")
         make_cam.run(args)
+    if args.cam_to_ir_label_pass is True:
+        from irn_amd.step import cam_to_ir_label
+        timer = pyutils.Timer("step.cam_to_ir_label:")
+        cam_to_ir_label.run(args)
     if args.make_ins_seg_pass is True:
         from irn_amd.step import make_ins_seg_labels
         timer = pyutils.Timer("step.make_ins_seg_labels:")

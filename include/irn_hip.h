@@ -447,6 +447,45 @@ int irn_crf_ir_label(const uint8_t *rgb_dev, const float *high_res_dev, const in
                      float fg_thres, float bg_thres, int t, float gt_prob, uint8_t *conf_dev, void *ws,
                      size_t ws_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Evaluation counts  (replace the chainercv counting behind step/eval_cam.py:10-20,
+ *                     step/eval_sem_seg.py:10-17 and step/eval_ins_seg.py:21-22)
+ * Every output is an int64 count in caller-owned device memory that each call ADDS into, so one
+ * accumulator can stay on the device for a whole split; integer counts are exact and independent
+ * of launch order and block count.  GT values are 0..20, or 255 (void: not in a confusion row, but
+ * counted in `void` when it is not NULL, so the caller can reproduce the size chainercv's growing
+ * matrix reaches).  A value outside its documented range (GT 21..254, a NaN CAM, a class key outside
+ * 0..19, a prediction above 20, unsorted thresholds, an instance id above g) is skipped and counted
+ * in `bad_dev` (int64 [1]).  Nothing synchronises.
+ *
+ * irn_cam_confusion: step/eval_cam.py for one image at T thresholds in one pass.  high_res dev fp32
+ *   [k][h][w] (k >= 0; may be NULL when k == 0), keys dev int64 [k] (0-based classes), gt dev uint8
+ *   [h][w], thres dev fp32 [t] (ascending, 1 <= t <= IRN_EVAL_MAX_THRES).  Per pixel, with m the max
+ *   over the k planes and c the first plane that reaches it, the prediction at threshold i is 0 if
+ *   k == 0 or m <= thres[i], else keys[c] + 1 (= argmax of [thres[i], high_res] through the padded
+ *   keys).  hist dev int64 [22][21][t+1] receives the pixel at [row][keys[c]+1][j], j = number of
+ *   thresholds < m (row 21 = GT 255; k == 0: column 0, j = 0).
+ * irn_cam_confusion_reduce: hist -> conf dev int64 [t][21][21] (row = GT, column = prediction) and,
+ *   when not NULL, void dev int64 [t][21] (predictions at GT-255 pixels); adds into both.
+ * irn_label_confusion: step/eval_sem_seg.py.  pred, gt dev uint8 [h][w]; pred 255 reads as
+ *   pred_255_as when that is in 0..20 (< 0: 255 is out of range).  conf dev int64 [21][21],
+ *   void dev int64 [21] (may be NULL).
+ * irn_mask_overlap: the mask_iou counts of step/eval_ins_seg.py.  masks dev uint8 [n][h][w] (nonzero =
+ *   in the mask; may be NULL when n == 0), inst dev uint8 [h][w] (0 = no instance, 1..g = instance).
+ *   inter dev int64 [n][g] (pixels in mask i and instance j+1), area_pred dev int64 [n], area_gt dev
+ *   int64 [g]; n == 0 and g == 0 are valid (the arrays of size 0 may be NULL).
+ * ------------------------------------------------------------------------------------------- */
+#define IRN_EVAL_CLASSES 21
+#define IRN_EVAL_MAX_THRES 256
+int irn_cam_confusion(const float *high_res_dev, const int64_t *keys_dev, int k, const uint8_t *gt_dev, int h, int w,
+                      const float *thres_dev, int t, int64_t *hist_dev, int64_t *bad_dev, void *stream);
+int irn_cam_confusion_reduce(const int64_t *hist_dev, int t, int64_t *conf_dev, int64_t *void_dev, void *stream);
+int irn_label_confusion(const uint8_t *pred_dev, const uint8_t *gt_dev, int h, int w, int pred_255_as,
+                        int64_t *conf_dev, int64_t *void_dev, int64_t *bad_dev, void *stream);
+int irn_mask_overlap(const uint8_t *masks_dev, int n, const uint8_t *inst_dev, int g, int h, int w,
+                     int64_t *inter_dev, int64_t *area_pred_dev, int64_t *area_gt_dev, int64_t *bad_dev,
+                     void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,10 @@ _SIGS = {
     "irn_crf_workspace_bytes": (sz, [i32, i32, i32]),
     "irn_crf_inference_label": (i32, [vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, sz, vp]),
     "irn_crf_ir_label": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, i32, f32, vp, vp, sz, vp]),
+    "irn_cam_confusion": (i32, [vp, vp, i32, vp, i32, i32, vp, i32, vp, vp, vp]),
+    "irn_cam_confusion_reduce": (i32, [vp, i32, vp, vp, vp]),
+    "irn_label_confusion": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+    "irn_mask_overlap": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
 }
 
 EXPORTS = tuple(_SIGS)

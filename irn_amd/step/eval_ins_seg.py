@@ -1,0 +1,62 @@
+"""Instance-segmentation evaluation step — drop-in for reference step/eval_ins_seg.py (`run(args)`).
+
+Reads  args.voc12_root (ImageSets/Segmentation/<args.chainer_eval_set>.txt, SegmentationObject/<id>.png,
+       SegmentationClass/<id>.png), args.ins_seg_out_dir/<id>.npy ({'score', 'mask', 'class'} of make_ins_seg_labels)
+Prints 0.5iou: {'ap': ..., 'map': ...} as the reference does; returns the dict.
+
+Per image the device counts |mask & instance|, |mask| and |instance| for every predicted mask and GT instance
+(`ops.mask_overlap`); the counts of the whole split come back in one copy, and chainercv's matching and VOC AP
+(iou_thresh 0.5, not the 07 metric) run on them in split order (`misc.evaluation.instance_ap_voc`).
+"""
+import os
+
+import numpy as np
+import torch
+
+from .. import ops
+from ..misc import evaluation
+from ..voc12 import eval_data
+from . import _eval
+
+
+def run(args):
+    ids = eval_data.seg_ids(args.voc12_root, args.chainer_eval_set)
+    dev = _eval.device()
+
+    def load(id):
+        inst_map, inst_class = eval_data.instance_label(args.voc12_root, id)
+        det = np.load(os.path.join(args.ins_seg_out_dir, id + ".npy"), allow_pickle=True).item()
+        cls, score = np.asarray(det["class"]).reshape(-1), np.asarray(det["score"]).reshape(-1)
+        mask = np.asarray(det["mask"])
+        if mask.size == 0 and len(cls) == 0:
+            mask = np.zeros((0,) + inst_map.shape, bool)
+        _eval.check_shape(id, "masks", mask.shape, (len(cls),) + inst_map.shape)
+        if len(score) != len(cls):
+            raise ValueError("%d scores for %d classes" % (len(score), len(cls)))
+        return {"inst_map": inst_map, "inst_class": inst_class, "mask": np.ascontiguousarray(mask),
+                "class": cls, "score": score}
+
+    records, counts = [], []
+    with torch.cuda.device(dev):
+        bad = torch.zeros(1, dtype=torch.int64, device=dev)
+        for id, it in _eval.items(ids, load, args):
+            g = int(it["inst_class"].numel())
+            inter, area_pred, area_gt = ops.mask_overlap(it["mask"].to(dev, non_blocking=True),
+                                                         it["inst_map"].to(dev, non_blocking=True), g, bad)
+            counts += [inter.reshape(-1), area_pred, area_gt]
+            records.append({"pred_class": it["class"].numpy(), "pred_score": it["score"].numpy(),
+                            "gt_class": it["inst_class"].numpy()})
+        if not records:
+            raise ValueError("eval_ins_seg: the split %s lists no images" % args.chainer_eval_set)
+        _eval.raise_if_bad(bad, "eval_ins_seg")
+        flat = torch.cat(counts).cpu().numpy()                 # every image's counts in one copy
+    pos = 0
+    for rec in records:
+        n, g = len(rec["pred_class"]), len(rec["gt_class"])
+        for key, size in (("inter", n * g), ("area_pred", n), ("area_gt", g)):
+            rec[key] = flat[pos:pos + size]
+            pos += size
+        rec["inter"] = rec["inter"].reshape(n, g)
+    out = evaluation.instance_ap_voc(records, iou_thresh=0.5)
+    print("0.5iou:", out)
+    return out

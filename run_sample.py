@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
-"""CLI boundary — same flags and step order as reference run_sample.py:8-137, for the four
-label-generation steps this repository implements (make_cam, cam_to_ir_label, make_ins_seg, make_sem_seg).
+"""CLI boundary — same flags and step order as reference run_sample.py:8-137, for the steps this repository
+implements: the label-generation steps (make_cam, cam_to_ir_label, make_ins_seg, make_sem_seg) and the evaluation
+steps that score them (eval_cam, eval_ins_seg, eval_sem_seg).
 
-The training / evaluation steps of the reference (train_cam, eval_cam, train_irn, eval_ins_seg,
-eval_sem_seg) are outside the hot-path scope; their
+The training steps of the reference (train_cam, train_irn) are outside the hot-path scope; their
 `--*_pass` flags are accepted so existing command lines keep working, and asking for one of them
 is an error rather than a silent skip.  Weights are inputs: --cam_weights_name / --irn_weights_name
 must point at checkpoints written by the reference's training steps (or any state dict with the
@@ -47,9 +47,14 @@ def build_parser():
     # command line keeps parsing; the steps that read them are not part of this build
     for name, default, typ in (("cam_crop_size", 512, int), ("cam_batch_size", 16, int), ("cam_num_epoches", 5, int),
                                ("cam_learning_rate", 0.1, float), ("cam_weight_decay", 1e-4, float),
-                               ("cam_eval_thres", 0.15, float), ("irn_crop_size", 512, int), ("irn_batch_size", 32, int), ("irn_num_epoches", 3, int),
+                               ("irn_crop_size", 512, int), ("irn_batch_size", 32, int), ("irn_num_epoches", 3, int),
                                ("irn_learning_rate", 0.1, float), ("irn_weight_decay", 1e-4, float)):
         p.add_argument("--" + name, default=default, type=typ, help="accepted and ignored (training side of the reference)")
+    p.add_argument("--cam_eval_thres", default=0.15, type=float,
+                   help="eval_cam: background score of the CAM argmax (step/eval_cam.py:15)")
+    p.add_argument("--cam_eval_thres_sweep", default=[], type=float, nargs="*",
+                   help="eval_cam: more thresholds counted in the same pass (not in the reference; at most 255); prints the "
+                        "miou of each and the best one")
     p.add_argument("--worker_devices", default="", type=str,
                    help="device ordinal of every worker process, e.g. 0,1,2,3 (default: one per visible GPU like the reference; "
                         "0,0 = two workers sharing GPU 0)")
@@ -97,11 +102,11 @@ def build_parser():
     return p
 
 
-OUT_OF_SCOPE = ("train_cam_pass", "eval_cam_pass", "train_irn_pass", "eval_ins_seg_pass",
-                "eval_sem_seg_pass")
+OUT_OF_SCOPE = ("train_cam_pass", "train_irn_pass")
 
 
 def main(argv=None):
+    """Runs the requested passes in the reference's order; returns {step name: printed dict} of the evaluation passes."""
     args = build_parser().parse_args(argv)
     for name in OUT_OF_SCOPE:
         if getattr(args, name):
@@ -116,10 +121,15 @@ def main(argv=None):
         os.environ["IRN_DETERMINISTIC"] = str(int(args.deterministic))      # read by every process that sets MIOpen up (workers inherit it)
     pyutils.Logger(args.log_name + ".log")
     print(vars(args))
+    results = {}
     if args.make_cam_pass is True:
         from irn_amd.step import make_cam
         timer = pyutils.Timer("step.make_cam:")
         make_cam.run(args)
+    if args.eval_cam_pass is True:
+        from irn_amd.step import eval_cam
+        timer = pyutils.Timer("step.eval_cam:")
+        results["eval_cam"] = eval_cam.run(args)
     if args.cam_to_ir_label_pass is True:
         from irn_amd.step import cam_to_ir_label
         timer = pyutils.Timer("step.cam_to_ir_label:")
@@ -128,12 +138,21 @@ def main(argv=None):
         from irn_amd.step import make_ins_seg_labels
         timer = pyutils.Timer("step.make_ins_seg_labels:")
         make_ins_seg_labels.run(args)
+    if args.eval_ins_seg_pass is True:
+        from irn_amd.step import eval_ins_seg
+        timer = pyutils.Timer("step.eval_ins_seg:")
+        results["eval_ins_seg"] = eval_ins_seg.run(args)
     if args.make_sem_seg_pass is True:
         from irn_amd.step import make_sem_seg_labels
-        timer = pyutils.Timer("step.make_sem_seg_labels:")  # noqa: F841
+        timer = pyutils.Timer("step.make_sem_seg_labels:")
         make_sem_seg_labels.run(args)
+    if args.eval_sem_seg_pass is True:
+        from irn_amd.step import eval_sem_seg
+        timer = pyutils.Timer("step.eval_sem_seg:")  # noqa: F841
+        results["eval_sem_seg"] = eval_sem_seg.run(args)
     from irn_amd.step import _common
     _common.shutdown_workers()           # the per-GPU workers served every pass above
+    return results                       # what the evaluation passes printed, by step name
 
 
 if __name__ == "__main__":

@@ -112,6 +112,29 @@ def check(rc):
         raise IrnHipError("libirn_hip status %d: %s" % (rc, msg.decode() if msg else "?"))
 
 
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _need_cuda(t, what):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise ValueError("%s must be a GPU tensor: the HIP path has no CPU fallback" % what)
+
+
+def _need_cl(t, what, shape=None, device=None):
+    """`t` is a channels-last fp32 4-D tensor (of `shape`, on `device`, where given); `what` = "function: argument"."""
+    if (t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous(memory_format=torch.channels_last)
+            or (shape is not None and tuple(t.shape) != tuple(shape)) or (device is not None and t.device != device)):
+        raise ValueError("%s must be a channels-last fp32 %s tensor%s, got %s %s %s" % (
+            what, "[N, C, H, W]" if shape is None else tuple(shape), "" if device is None else " on %s" % device, t.dtype, tuple(t.shape), t.stride()))
+
+
+def _need_vec(t, what, n, device):
+    """`t` is a contiguous fp32 [n] tensor on `device`."""
+    if t.device != device or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n:
+        raise ValueError("%s must be a contiguous fp32 [%d] tensor on %s" % (what, n, device))
+
+
 def i32_array(values):
     return (C.c_int32 * len(values))(*[int(v) for v in values])
 

@@ -72,19 +72,34 @@ int epilogue_of(bool bias, bool relu) {
     return relu ? HIPBLASLT_EPILOGUE_RELU : HIPBLASLT_EPILOGUE_DEFAULT;
 }
 
-// caller holds g_mu
-int get_plan(hipblasLtHandle_t handle, int dev, int64_t m, int cin, int cout, bool bias, bool residual, bool relu,
-             size_t workspace_bytes, Plan **out, int f16 = 0, int64_t ldx = 0) {
-    Key key(dev, m, cin, cout, bias, residual, relu, workspace_bytes, f16, ldx);
+// Every entry point starts here: the calling thread's device, g_mu for the whole call (the descriptor's bias pointer is per
+// call: one enqueue at a time) and that device's handle.  A full plan cache is emptied HERE and nowhere else, before the call
+// has taken a plan (each call adds at most two): a Plan* from get_plan stays valid until the Session ends.
+struct Session {
+    std::unique_lock<std::mutex> lock;
+    int dev = 0;
+    hipblasLtHandle_t handle = nullptr;
+
+    int open() {
+        IRN_HIP_TRY(hipGetDevice(&dev));
+        lock = std::unique_lock<std::mutex>(g_mu);
+        if (g_plans.size() >= kMaxPlans) {        // nothing is in flight with a plan: g_mu is held for the whole enqueue
+            for (auto &kv : g_plans) destroy_plan(kv.second);
+            g_plans.clear();
+        }
+        return get_handle(dev, &handle);
+    }
+};
+
+// within a Session
+int get_plan(const Session &s, int64_t m, int cin, int cout, bool bias, bool residual, bool relu, size_t workspace_bytes, Plan **out,
+             int f16 = 0, int64_t ldx = 0) {
+    Key key(s.dev, m, cin, cout, bias, residual, relu, workspace_bytes, f16, ldx);
     const hipDataType ab_type = f16 ? HIP_R_16F : HIP_R_32F;      // operands; C / D / bias / scale stay fp32, fp32 accumulation
     auto it = g_plans.find(key);
     if (it != g_plans.end()) {
         *out = it->second;
         return IRN_OK;
-    }
-    if (g_plans.size() >= kMaxPlans) {        // nothing is in flight with a plan: the caller holds g_mu for the whole enqueue
-        for (auto &kv : g_plans) destroy_plan(kv.second);
-        g_plans.clear();
     }
     // owned here until it is in the cache: a failing call below frees the descriptors made so far
     std::unique_ptr<Plan, void (*)(Plan *)> owner(new Plan(), destroy_plan);
@@ -110,7 +125,7 @@ int get_plan(hipblasLtHandle_t handle, int dev, int64_t m, int cin, int cout, bo
     const uint64_t ws = workspace_bytes;
     IRN_LT_TRY(hipblasLtMatmulPreferenceSetAttribute(pref, HIPBLASLT_MATMUL_PREF_MAX_WORKSPACE_BYTES, &ws, sizeof ws));
     int found = 0;
-    hipblasStatus_t st = hipblasLtMatmulAlgoGetHeuristic(handle, p->desc, p->a, p->b, p->c, p->d, pref, kMaxAlgos, p->algo, &found);
+    hipblasStatus_t st = hipblasLtMatmulAlgoGetHeuristic(s.handle, p->desc, p->a, p->b, p->c, p->d, pref, kMaxAlgos, p->algo, &found);
     (void)hipblasLtMatmulPreferenceDestroy(pref);
     if (st != HIPBLAS_STATUS_SUCCESS || found < 1) {
         return fail(IRN_ERR_STATE, "hipBLASLt has no %s kernel for the 1x1 convolution m=%lld cin=%d cout=%d (status %d, %d found)",
@@ -128,6 +143,42 @@ int check_shape(int64_t m, int cin, int cout) {
     return IRN_OK;
 }
 
+int algo_count(int64_t m, int k, int cout, int has_bias, int has_residual, int relu, size_t workspace_bytes, int *count_out, int f16,
+               const char *name) {
+    if (!count_out) return fail(IRN_ERR_ARG, "%s_algo_count: count_out is NULL", name);
+    if (int rc = check_shape(m, k, cout)) return rc;
+    Session s;
+    if (int rc = s.open()) return rc;
+    Plan *p = nullptr;
+    if (int rc = get_plan(s, m, k, cout, has_bias != 0, has_residual != 0, relu != 0, workspace_bytes, &p, f16)) return rc;
+    *count_out = p->n_algos;
+    return IRN_OK;
+}
+
+// out[m, cout] = act(alpha * a[m, k] . b[cout, k]^T + bias (+ residual)): a = the activation, b = the weight, both fp32 or (f16)
+// both fp16 — the split-precision form: a = [x_hi | x_hi | x_lo'] (irn_split16, k = 3 cin), b = [w_hi | w_lo | w_hi 2^-11]; one
+// fp16 MFMA GEMM with fp32 accumulation, the same epilogue.
+int run_1x1(const void *a, const void *b, const float *bias, const float *residual, float *out, int64_t m, int k, int cout, int relu,
+            float alpha, int rank, void *workspace, size_t workspace_bytes, void *stream, int f16, const char *name) {
+    if (!a || !b || !out) return fail(IRN_ERR_ARG, "%s: %s and out must not be NULL", name, f16 ? "a, b" : "x, w");
+    if (int rc = check_shape(m, k, cout)) return rc;
+    if (f16 && (k & 7)) return fail(IRN_ERR_ARG, "%s: k = %d must be a multiple of 8 (16-byte rows)", name, k);
+    if (workspace_bytes && !workspace) return fail(IRN_ERR_ARG, "%s: workspace_bytes > 0 with a NULL workspace", name);
+    Session s;
+    if (int rc = s.open()) return rc;
+    Plan *p = nullptr;
+    if (int rc = get_plan(s, m, k, cout, bias != nullptr, residual != nullptr, relu != 0, workspace_bytes, &p, f16)) return rc;
+    if (rank < 0 || rank >= p->n_algos)
+        return fail(IRN_ERR_ARG, "%s: algo_rank %d outside hipBLASLt's list of %d for m=%lld %s=%d cout=%d", name, rank, p->n_algos,
+                    (long long)m, f16 ? "k" : "cin", k, cout);
+    if (bias) IRN_LT_TRY(hipblasLtMatmulDescSetAttribute(p->desc, HIPBLASLT_MATMUL_DESC_BIAS_POINTER, &bias, sizeof bias));
+    const float beta = residual ? 1.0f : 0.0f;
+    const float *c = residual ? residual : out;
+    IRN_LT_TRY(hipblasLtMatmul(s.handle, p->desc, &alpha, b, p->a, a, p->b, &beta, c, p->c, out, p->d, &p->algo[rank].algo, workspace,
+                               workspace_bytes, (hipStream_t)stream));
+    return IRN_OK;
+}
+
 }  // namespace
 }  // namespace irn
 
@@ -137,86 +188,25 @@ size_t irn_conv1x1_workspace_bytes(void) { return irn::kWorkspaceBytes; }
 
 int irn_conv1x1_algo_count(int64_t m, int cin, int cout, int has_bias, int has_residual, int relu, size_t workspace_bytes,
                            int *count_out) {
-    using namespace irn;
-    if (!count_out) return fail(IRN_ERR_ARG, "conv1x1_algo_count: count_out is NULL");
-    if (int rc = check_shape(m, cin, cout)) return rc;
-    int dev = 0;
-    IRN_HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_mu);
-    hipblasLtHandle_t handle;
-    if (int rc = get_handle(dev, &handle)) return rc;
-    Plan *p = nullptr;
-    if (int rc = get_plan(handle, dev, m, cin, cout, has_bias != 0, has_residual != 0, relu != 0, workspace_bytes, &p)) return rc;
-    *count_out = p->n_algos;
-    return IRN_OK;
+    return irn::algo_count(m, cin, cout, has_bias, has_residual, relu, workspace_bytes, count_out, 0, "conv1x1");
+}
+
+int irn_gemm16_algo_count(int64_t m, int k, int cout, int has_bias, int has_residual, int relu, size_t workspace_bytes, int *count_out) {
+    return irn::algo_count(m, k, cout, has_bias, has_residual, relu, workspace_bytes, count_out, 1, "gemm16");
 }
 
 int irn_conv1x1_nhwc(const float *x_dev, const float *w_dev, const float *bias_dev, const float *residual_dev, float *out_dev,
                      int64_t m, int cin, int cout, int relu, int algo_rank, void *workspace_dev, size_t workspace_bytes,
                      void *stream) {
-    using namespace irn;
-    if (!x_dev || !w_dev || !out_dev) return fail(IRN_ERR_ARG, "conv1x1: x, w and out must not be NULL");
-    if (int rc = check_shape(m, cin, cout)) return rc;
-    if (workspace_bytes && !workspace_dev) return fail(IRN_ERR_ARG, "conv1x1: workspace_bytes > 0 with a NULL workspace");
-    int dev = 0;
-    IRN_HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_mu);      // the descriptor's bias pointer is per call: one enqueue at a time
-    hipblasLtHandle_t handle;
-    if (int rc = get_handle(dev, &handle)) return rc;
-    Plan *p = nullptr;
-    if (int rc = get_plan(handle, dev, m, cin, cout, bias_dev != nullptr, residual_dev != nullptr, relu != 0, workspace_bytes, &p)) return rc;
-    if (algo_rank < 0 || algo_rank >= p->n_algos)
-        return fail(IRN_ERR_ARG, "conv1x1: algo_rank %d outside hipBLASLt's list of %d for m=%lld cin=%d cout=%d", algo_rank, p->n_algos,
-                    (long long)m, cin, cout);
-    if (bias_dev) IRN_LT_TRY(hipblasLtMatmulDescSetAttribute(p->desc, HIPBLASLT_MATMUL_DESC_BIAS_POINTER, &bias_dev, sizeof bias_dev));
-    const float alpha = 1.0f, beta = residual_dev ? 1.0f : 0.0f;
-    const float *c = residual_dev ? residual_dev : out_dev;
-    IRN_LT_TRY(hipblasLtMatmul(handle, p->desc, &alpha, w_dev, p->a, x_dev, p->b, &beta, c, p->c, out_dev, p->d, &p->algo[algo_rank].algo,
-                               workspace_dev, workspace_bytes, (hipStream_t)stream));
-    return IRN_OK;
-}
-
-// The split-precision form: a16 = [x_hi | x_hi | x_lo'] fp16 [m, k] (irn_split16, k = 3 cin), b16 = [w_hi | w_lo | w_hi 2^-11]
-// fp16 [cout, k]; one fp16 MFMA GEMM with fp32 accumulation, the same epilogue.
-int irn_gemm16_algo_count(int64_t m, int k, int cout, int has_bias, int has_residual, int relu, size_t workspace_bytes, int *count_out) {
-    using namespace irn;
-    if (!count_out) return fail(IRN_ERR_ARG, "gemm16_algo_count: count_out is NULL");
-    if (int rc = check_shape(m, k, cout)) return rc;
-    int dev = 0;
-    IRN_HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_mu);
-    hipblasLtHandle_t handle;
-    if (int rc = get_handle(dev, &handle)) return rc;
-    Plan *p = nullptr;
-    if (int rc = get_plan(handle, dev, m, k, cout, has_bias != 0, has_residual != 0, relu != 0, workspace_bytes, &p, 1)) return rc;
-    *count_out = p->n_algos;
-    return IRN_OK;
+    return irn::run_1x1(x_dev, w_dev, bias_dev, residual_dev, out_dev, m, cin, cout, relu, 1.0f, algo_rank, workspace_dev, workspace_bytes,
+                        stream, 0, "conv1x1");
 }
 
 int irn_gemm16_nhwc(const void *a16_dev, const void *b16_dev, const float *bias_dev, const float *residual_dev, float *out_dev,
                     int64_t m, int k, int cout, int relu, float alpha, int algo_rank, void *workspace_dev, size_t workspace_bytes,
                     void *stream) {
-    using namespace irn;
-    if (!a16_dev || !b16_dev || !out_dev) return fail(IRN_ERR_ARG, "gemm16: a, b and out must not be NULL");
-    if (int rc = check_shape(m, k, cout)) return rc;
-    if (k & 7) return fail(IRN_ERR_ARG, "gemm16: k = %d must be a multiple of 8 (16-byte rows)", k);
-    if (workspace_bytes && !workspace_dev) return fail(IRN_ERR_ARG, "gemm16: workspace_bytes > 0 with a NULL workspace");
-    int dev = 0;
-    IRN_HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_mu);
-    hipblasLtHandle_t handle;
-    if (int rc = get_handle(dev, &handle)) return rc;
-    Plan *p = nullptr;
-    if (int rc = get_plan(handle, dev, m, k, cout, bias_dev != nullptr, residual_dev != nullptr, relu != 0, workspace_bytes, &p, 1)) return rc;
-    if (algo_rank < 0 || algo_rank >= p->n_algos)
-        return fail(IRN_ERR_ARG, "gemm16: algo_rank %d outside hipBLASLt's list of %d for m=%lld k=%d cout=%d", algo_rank, p->n_algos,
-                    (long long)m, k, cout);
-    if (bias_dev) IRN_LT_TRY(hipblasLtMatmulDescSetAttribute(p->desc, HIPBLASLT_MATMUL_DESC_BIAS_POINTER, &bias_dev, sizeof bias_dev));
-    const float beta = residual_dev ? 1.0f : 0.0f;
-    const float *c = residual_dev ? residual_dev : out_dev;
-    IRN_LT_TRY(hipblasLtMatmul(handle, p->desc, &alpha, b16_dev, p->a, a16_dev, p->b, &beta, c, p->c, out_dev, p->d, &p->algo[algo_rank].algo,
-                               workspace_dev, workspace_bytes, (hipStream_t)stream));
-    return IRN_OK;
+    return irn::run_1x1(a16_dev, b16_dev, bias_dev, residual_dev, out_dev, m, k, cout, relu, alpha, algo_rank, workspace_dev,
+                        workspace_bytes, stream, 1, "gemm16");
 }
 
 // 3x3 / pad 1 / stride 1 convolution on the zero-bordered split operand (irn_split16_pad), one call.
@@ -235,16 +225,12 @@ int irn_conv3x3_split_gemm(const void *a16_dev, const void *w16_dev, float *out_
     if (int rc = check_shape(m, k, cout)) return rc;
     if (k1 & 7) return fail(IRN_ERR_ARG, "conv3x3_split_gemm: cin = %d must be a multiple of 8", cin);
     if (workspace_bytes && !workspace_dev) return fail(IRN_ERR_ARG, "conv3x3_split_gemm: workspace_bytes > 0 with a NULL workspace");
-    int dev = 0;
-    IRN_HIP_TRY(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lk(g_mu);
-    hipblasLtHandle_t handle;
-    if (int rc = get_handle(dev, &handle)) return rc;
+    Session s;
+    if (int rc = s.open()) return rc;
     const int64_t ldx = row_fused ? k1 : 0;
     Plan *first = nullptr, *rest = nullptr;          // beta = 0 for the first GEMM, 1 (C = D = out) for the others
-    if (int rc = get_plan(handle, dev, m, k, cout, false, false, false, workspace_bytes, &first, 1, ldx)) return rc;
-    if (int rc = get_plan(handle, dev, m, k, cout, false, true, false, workspace_bytes, &rest, 1, ldx)) return rc;
-    if (int rc = get_plan(handle, dev, m, k, cout, false, false, false, workspace_bytes, &first, 1, ldx)) return rc;      // (the cache may have been emptied by the call above)
+    if (int rc = get_plan(s, m, k, cout, false, false, false, workspace_bytes, &first, 1, ldx)) return rc;
+    if (int rc = get_plan(s, m, k, cout, false, true, false, workspace_bytes, &rest, 1, ldx)) return rc;
     const int r0 = algo_rank >= 0 && algo_rank < first->n_algos ? algo_rank : 0, r1 = algo_rank >= 0 && algo_rank < rest->n_algos ? algo_rank : 0;
     const char *a = (const char *)a16_dev, *wt = (const char *)w16_dev;
     const size_t row_bytes = (size_t)k1 * 2u, w_bytes = (size_t)cout * k * 2u;
@@ -253,7 +239,7 @@ int irn_conv3x3_split_gemm(const void *a16_dev, const void *w16_dev, float *out_
         const int64_t off = (int64_t)(ky - 1) * (w + 2) + (kx - 1);
         const float beta = t ? 1.0f : 0.0f;
         Plan *p = t ? rest : first;
-        IRN_LT_TRY(hipblasLtMatmul(handle, p->desc, &alpha, wt + t * w_bytes, p->a, a + off * (int64_t)row_bytes, p->b, &beta, out_dev, p->c,
+        IRN_LT_TRY(hipblasLtMatmul(s.handle, p->desc, &alpha, wt + t * w_bytes, p->a, a + off * (int64_t)row_bytes, p->b, &beta, out_dev, p->c,
                                    out_dev, p->d, &p->algo[t ? r1 : r0].algo, workspace_dev, workspace_bytes, (hipStream_t)stream));
     }
     return IRN_OK;

@@ -224,16 +224,17 @@ class FrozenBatchNorm(nn.BatchNorm2d):
         return F.batch_norm(x, self.running_mean, self.running_var, self.weight, self.bias,
                             False, 0.0, self.eps)
 
+    def _fold64(self):
+        """(scale, shift) float64 [C] with forward(x) = x * scale + shift."""
+        w, b, mean, var = (t.detach().double() for t in (self.weight, self.bias, self.running_mean, self.running_var))
+        scale = w / torch.sqrt(var + self.eps)
+        return scale, b - mean * scale
+
     def folded(self):
-        """(scale, shift) fp32 [C] with forward(x) = x * scale + shift, folded in double precision; cached until a
-        parameter or statistic is written or moved."""
-        src = (self.weight, self.bias, self.running_mean, self.running_var)
-        key = tuple((t.data_ptr(), _version(t)) for t in src)
+        """`_fold64` rounded to fp32; cached until a parameter or statistic is written or moved."""
+        key = tuple((t.data_ptr(), _version(t)) for t in (self.weight, self.bias, self.running_mean, self.running_var))
         if self._folded is None or self._folded[0] != key:
-            with torch.no_grad():
-                w, b, mean, var = (t.detach().double() for t in src)
-                scale = w / torch.sqrt(var + self.eps)
-                shift = b - mean * scale
+            scale, shift = self._fold64()
             self._folded = (key, scale.float().contiguous(), shift.float().contiguous())
         return self._folded[1], self._folded[2]
 
@@ -310,18 +311,19 @@ class Bottleneck(nn.Module):
     def gemm_params(self):
         """The unit's 1x1 convolutions as GEMM operands: weights [cout, cin] with their batch norm's scale folded in
         (double precision, rounded once), the shifts as biases; for a projection unit the shortcut's shift rides in
-        conv3's bias (the shortcut GEMM has none).  Cached until a parameter or statistic is written or moved."""
+        conv3's bias (the shortcut GEMM has none).  Cached until a parameter or statistic is written or moved, or a switch
+        that decides which operands exist changes.  bn2 is not in here: `_forward_gemm` reads `bn2.folded()` where it uses it."""
+        from .. import gemm
         convs = [self.conv1, self.conv3] + ([] if self.downsample is None else [self.downsample[0]])
-        w2 = self.conv2.weight
         bns = [self.bn1, self.bn3] + ([] if self.downsample is None else [self.downsample[1]])
-        src = [c.weight for c in convs] + [w2] + [t for b in bns for t in (b.weight, b.bias, b.running_mean, b.running_var)]
-        key = tuple((t.data_ptr(), _version(t)) for t in src)
+        src = [c.weight for c in convs] + [self.conv2.weight] + [t for b in bns for t in (b.weight, b.bias, b.running_mean, b.running_var)]
+        key = (tuple((t.data_ptr(), _version(t)) for t in src), SPLIT_GEMM, SPLIT_MIN_PLANES, SPLIT_MIN_PLANES_3X3, SPLIT_MIN_INPUT,
+               gemm.CONV3X3_ROW_FUSED)
         if self._gemm is None or self._gemm[0] != key:
             with torch.no_grad():
                 folded, folded64 = [], []
                 for c, b in zip(convs, bns):
-                    scale = b.weight.detach().double() / torch.sqrt(b.running_var.detach().double() + b.eps)
-                    shift = b.bias.detach().double() - b.running_mean.detach().double() * scale
+                    scale, shift = b._fold64()
                     folded64.append(c.weight.detach().double() * scale.view(-1, 1, 1, 1))
                     folded.append((folded64[-1].float().contiguous(), shift))
                 p = {"w1": folded[0][0].flatten(1), "b1": folded[0][1].float().contiguous(), "w3": folded[1][0].flatten(1)}
@@ -334,22 +336,19 @@ class Bottleneck(nn.Module):
                     p["wd"] = folded[2][0].contiguous(memory_format=torch.channels_last)   # [cout, cin, 1, 1]: also MIOpen's operand when strided
                     p["b3"] = (folded[1][1] + folded[2][1]).float().contiguous()
                 if SPLIT_GEMM and self.conv1.weight.is_cuda:
-                    # fp16 hi/lo operands of the split-precision GEMMs, from the weights folded in double precision; bn2's
-                    # constants ride in the split pass that feeds conv3
-                    from .. import ops
+                    # fp16 hi/lo operands of the split-precision GEMMs, from the weights folded in double precision
                     planes, cin = self.conv3.weight.shape[1], self.conv1.weight.shape[1]
                     couts = self.conv1.weight.shape[0] + (self.downsample[0].weight.shape[0] if self.downsample is not None and tuple(self.downsample[0].stride) == (1, 1) else 0)
                     if planes >= SPLIT_MIN_PLANES:
-                        p["w3_16"], p["a3"] = ops.split_weight(folded64[1].flatten(1))
-                        p["s2"], p["t2"] = self.bn2.folded()
+                        p["w3_16"], p["a3"] = gemm.split_weight(folded64[1].flatten(1))
                         c2 = self.conv2
                         if (planes >= SPLIT_MIN_PLANES_3X3 and planes % 8 == 0 and tuple(c2.kernel_size) == (3, 3) and tuple(c2.stride) == (1, 1)
                                 and tuple(c2.padding) == (1, 1) and tuple(c2.dilation) == (1, 1) and c2.groups == 1):
-                            p["w2_16"], p["a2"] = ops.split_weight_3x3(c2.weight.detach().double())
+                            p["w2_16"], p["a2"] = gemm.split_weight_3x3(c2.weight.detach().double())
                     if cin * couts >= SPLIT_MIN_INPUT and cin % 8 == 0:
-                        p["w1_16"], p["a1"] = ops.split_weight(folded64[0].flatten(1))
+                        p["w1_16"], p["a1"] = gemm.split_weight(folded64[0].flatten(1))
                         if self.downsample is not None and tuple(self.downsample[0].stride) == (1, 1):
-                            p["wd_16"], p["ad"] = ops.split_weight(folded64[2].flatten(1))
+                            p["wd_16"], p["ad"] = gemm.split_weight(folded64[2].flatten(1))
             self._gemm = (key, p)
         return self._gemm[1]
 
@@ -396,12 +395,12 @@ class Bottleneck(nn.Module):
                 sc = ops.conv1x1_nhwc(x, p["wd"].reshape(p["wd"].shape[0], -1))
         res = x if ds is None else sc
         if y_pad is not None:
-            y3 = ops.split16_pad(y_pad, y_shape, p["s2"], p["t2"], relu=True, in_padded=True)
+            y3 = ops.split16_pad(y_pad, y_shape, *self.bn2.folded(), relu=True, in_padded=True)
             return ops.gemm16_nhwc(y3, p["w3_16"], (y_shape[0], p["w3"].shape[0], y_shape[2], y_shape[3]), p["b3"], residual=res, relu=True,
                                    alpha=p["a3"], out=sc)
         if "w3_16" in p and y.shape[1] % 8 == 0:
             # bn2 + ReLU + split in one pass over the 3x3 convolution's output, then ONE fp16 GEMM with the unit's whole tail
-            y3 = ops.split16(y, p["s2"], p["t2"], relu=True)
+            y3 = ops.split16(y, *self.bn2.folded(), relu=True)
             return ops.gemm16_nhwc(y3, p["w3_16"], (y.shape[0], p["w3"].shape[0], y.shape[2], y.shape[3]), p["b3"], residual=res, relu=True,
                                    alpha=p["a3"], out=sc)
         y = self.bn2.apply_(y, relu=True)

@@ -1,4 +1,6 @@
-"""Host-side wrappers of the label epilogue and instance front-end kernels in libirn_hip.so.
+"""Host-side wrappers of the kernels in libirn_hip.so outside the walk: label epilogue, CAM merge, the trunk's elementwise
+passes (bn_act_, stem_pool, upsample_bilinear), image resizing and the instance front end.  The hipBLASLt convolutions of the
+trunk live in `irn_amd.gemm`; their functions are reachable from here too.
 
 Reference functions mirrored (names kept where the reference has one):
     find_centroids_with_refinement(displacement, iterations=300)   step/make_ins_seg_labels.py:18-56
@@ -11,21 +13,13 @@ Reference functions mirrored (names kept where the reference has one):
 GPU tensors in, GPU tensors out; no CPU fallback.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import torch
 
-from ._lib import check, i32_array, lib, ptr_array
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _need_cuda(t, what):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda):
-        raise ValueError("%s must be a GPU tensor: the HIP path has no CPU fallback" % what)
+from ._lib import _need_cuda, _need_vec, _stream, check, i32_array, lib, ptr_array
+from .gemm import (conv1x1_algo_count, conv1x1_nhwc, conv3x3_split, gemm16_algo_count, gemm16_nhwc, gemm_ranks, gemm_ranks16,  # noqa: F401
+                   gemm_ranks3x3, split16, split16_pad, split_overflowed, split_weight, split_weight_3x3)
 
 
 def label_epilogue(rws, out_sizes, bg_thres, keys=None, want_labels=True, want_argmax=False, want_rw_up=False, packed=False):
@@ -129,8 +123,7 @@ def bn_act_(x, scale, shift, residual=None, relu=True, residual_affine=None):
             raise ValueError("bn_act_: residual_affine without a residual")
         consts += [("residual scale", residual_affine[0]), ("residual shift", residual_affine[1])]
     for name, t in consts:
-        if t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n_ch:
-            raise ValueError("bn_act_: %s must be a contiguous fp32 [%d] tensor on %s" % (name, n_ch, x.device))
+        _need_vec(t, "bn_act_: " + name, n_ch, x.device)
     if residual is not None and (residual.shape != x.shape or residual.dtype != torch.float32 or residual.device != x.device
                                  or not (residual.is_contiguous(memory_format=torch.channels_last) if nhwc else residual.is_contiguous())):
         raise ValueError("bn_act_: residual must match x (shape %s, fp32, same memory format, same device)" % (tuple(x.shape),))
@@ -159,351 +152,6 @@ def bn_act_(x, scale, shift, residual=None, relu=True, residual_affine=None):
     return x
 
 
-_GEMM_WS = {}          # (device index, stream) -> workspace tensor of the fused 1x1 convolutions (stream-ordered use)
-_GEMM_NALGOS = {}      # problems with a non-zero table rank -> length of hipBLASLt's heuristic list in this process
-_GEMM_RANK_WARNED = False
-_GEMM_RANKS = None     # (m, cin, cout, bias, residual, relu) -> rank in hipBLASLt's heuristic list, measured once per device
-
-
-def gemm_ranks():
-    """The shipped table `irn_amd/data/gemm/<device>-hip<version>.json` (written by tools/conv1x1_tune.py on a GPU box):
-    for the problems listed, which entry of hipBLASLt's heuristic list was fastest.  Problems not listed use entry 0.  The
-    table is data, not a timing: every process picks the same kernel for the same problem."""
-    global _GEMM_RANKS
-    if _GEMM_RANKS is None:
-        ranks = {}
-        try:
-            import json
-            import os
-            from .step import _common
-            path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "gemm", _common.miopen_cache_key() + ".json")
-            if os.path.exists(path) and os.environ.get("IRN_GEMM_TABLE", "1") != "0":
-                ranks = {tuple(int(v) for v in k.split(",")): int(r) for k, r in json.load(open(path))["ranks"].items()}
-        except Exception:
-            ranks = {}
-        _GEMM_RANKS = ranks
-    return _GEMM_RANKS
-
-
-def conv1x1_nhwc(x, weight, bias=None, residual=None, relu=False, out=None, algo_rank=None):
-    """1x1 convolution (stride 1) of a channels-last activation with bias, residual add and ReLU in the GEMM's epilogue
-    (irn_conv1x1_nhwc; reference net/resnet50.py:34-54 with FixedBatchNorm folded into `weight` / `bias`).
-    x: GPU fp32 [N, cin, H, W] in torch.channels_last; weight: GPU fp32 [cout, cin] (or [cout, cin, 1, 1]) contiguous;
-    bias: GPU fp32 [cout] or None; residual: like the result, or None; out: a channels-last [N, cout, H, W] tensor to write
-    (may be `residual`), else a fresh one.  -> act(conv(x, weight) + bias (+ residual))."""
-    _need_cuda(x, "x")
-    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
-        raise ValueError("conv1x1_nhwc: x must be a channels-last fp32 [N, C, H, W] tensor, got %s %s %s" % (x.dtype, tuple(x.shape), x.stride()))
-    n, cin, h, w_ = (int(v) for v in x.shape)
-    cout = int(weight.shape[0])
-    if weight.dtype != torch.float32 or weight.device != x.device or not weight.is_contiguous() or weight.numel() != cout * cin:
-        raise ValueError("conv1x1_nhwc: weight must be a contiguous fp32 [%d-out, %d] tensor on %s" % (cout, cin, x.device))
-    if bias is not None and (bias.dtype != torch.float32 or bias.device != x.device or not bias.is_contiguous() or bias.numel() != cout):
-        raise ValueError("conv1x1_nhwc: bias must be a contiguous fp32 [%d] tensor on %s" % (cout, x.device))
-    shape = (n, cout, h, w_)
-    for name, t in (("residual", residual), ("out", out)):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != x.device
-                              or not t.is_contiguous(memory_format=torch.channels_last)):
-            raise ValueError("conv1x1_nhwc: %s must be a channels-last fp32 %s tensor on %s" % (name, shape, x.device))
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-    m = n * h * w_
-    if m == 0:
-        return out
-    # one workspace per (device, stream): GEMMs enqueued on different streams may overlap on the device
-    dev = (x.device.index if x.device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(x.device).cuda_stream)
-    ws = _GEMM_WS.get(dev)
-    if ws is None:
-        ws = _GEMM_WS[dev] = torch.empty(int(lib.irn_conv1x1_workspace_bytes()), dtype=torch.uint8, device=x.device)
-    if algo_rank is None:
-        prob = (m, cin, cout, int(bias is not None), int(residual is not None), int(bool(relu)))
-        algo_rank = gemm_ranks().get(prob, 0)
-        if algo_rank:
-            # the table is keyed by architecture / CU count / HIP version only: another hipBLASLt build or workspace size may
-            # offer a shorter list — then the first pick, with one warning, instead of an error in the middle of a forward
-            n_algos = _GEMM_NALGOS.get(prob)
-            if n_algos is None:
-                with torch.cuda.device(x.device):
-                    n_algos = _GEMM_NALGOS[prob] = conv1x1_algo_count(*prob)
-            if algo_rank >= n_algos:
-                global _GEMM_RANK_WARNED
-                if not _GEMM_RANK_WARNED:
-                    _GEMM_RANK_WARNED = True
-                    import warnings
-                    warnings.warn("irn_amd: the shipped GEMM rank table names entry %d for the 1x1 convolution m=%d cin=%d cout=%d but "
-                                  "hipBLASLt offers %d here (another library build?): using its first pick for such problems; "
-                                  "tools/conv1x1_tune.py rewrites the table" % (algo_rank, m, cin, cout, n_algos), RuntimeWarning)
-                algo_rank = 0
-    with torch.cuda.device(x.device):
-        check(lib.irn_conv1x1_nhwc(x.data_ptr(), weight.data_ptr(), None if bias is None else bias.data_ptr(),
-                                   None if residual is None else residual.data_ptr(), out.data_ptr(), m, cin, cout,
-                                   1 if relu else 0, int(algo_rank), ws.data_ptr(), ws.numel(), _stream()))
-    return out
-
-
-# ---- split-precision 1x1 convolutions (round 6): fp16 hi/lo operands, fp32 accumulation ----
-_SPLIT_FLAGS = {}      # device index -> uint32 [1] device tensor: bit 0 = an activation left fp16's range in irn_split16
-
-
-def _split_flag(device):
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    f = _SPLIT_FLAGS.get(idx)
-    if f is None:
-        f = _SPLIT_FLAGS[idx] = torch.zeros(1, dtype=torch.int32, device=device)
-    return f
-
-
-def split_overflowed(reset=True):
-    """Did any activation handed to `split16` since the last call exceed fp16's range (|x| > 65504) or hold a NaN, on any
-    device of this process?  Reads the device flags (synchronises).  The steps check it at the end of every step and raise:
-    such a network needs IRN_SPLIT_GEMM=0 (trained ResNet-50 activations stay below a few hundred)."""
-    bad = False
-    for f in _SPLIT_FLAGS.values():
-        if int(f.item()) != 0:
-            bad = True
-            if reset:
-                f.zero_()
-    return bad
-
-
-def split16(x, scale=None, shift=None, relu=False):
-    """fp32 channels-last activation [N, C, H, W] -> fp16 [N*H*W, 3C] = [hi | hi | lo'] per pixel (irn_split16), the A operand
-    of `gemm16_nhwc`; with `scale` / `shift` (fp32 [C]) the inference batch norm (+ ReLU) of the convolution that produced
-    `x` is applied on the way (reference net/resnet50.py:40-42) and `x` is never written back."""
-    _need_cuda(x, "x")
-    if x.dtype != torch.float32 or x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
-        raise ValueError("split16: x must be a channels-last fp32 [N, C, H, W] tensor, got %s %s %s" % (x.dtype, tuple(x.shape), x.stride()))
-    n, c, h, w_ = (int(v) for v in x.shape)
-    if c % 8:
-        raise ValueError("split16: %d channels; a multiple of 8 is needed" % c)
-    m = n * h * w_
-    out = torch.empty((m, 3 * c), dtype=torch.float16, device=x.device)
-    if m == 0:
-        return out
-    for name, t in (("scale", scale), ("shift", shift)):
-        if t is not None and (t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous() or t.numel() != c):
-            raise ValueError("split16: %s must be a contiguous fp32 [%d] tensor on %s" % (name, c, x.device))
-    with torch.cuda.device(x.device):
-        per = max(1, (2 ** 31 - 1) // c)
-        for i in range(0, m, per):                       # at most 2^31 - 1 elements per call
-            rows = min(per, m - i)
-            check(lib.irn_split16(x.data_ptr() + 4 * i * c, None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr(),
-                                  1 if relu else 0, out.data_ptr() + 2 * i * 3 * c, rows, c, _split_flag(x.device).data_ptr(), _stream()))
-    return out
-
-
-def gemm16_algo_count(m, k, cout, bias, residual, relu):
-    """How many kernels hipBLASLt's heuristic offers for the split-precision problem (tools/gemm16_tune.py times each once)."""
-    n = C.c_int(0)
-    check(lib.irn_gemm16_algo_count(int(m), int(k), int(cout), int(bool(bias)), int(bool(residual)), int(bool(relu)),
-                                    int(lib.irn_conv1x1_workspace_bytes()), C.byref(n)))
-    return n.value
-
-
-_GEMM_RANKS16 = None
-
-
-def gemm_ranks16():
-    """`ranks16` of the shipped table (gemm_ranks): (m, k, cout, bias, residual, relu) -> entry of hipBLASLt's list for the fp16
-    operand problems, measured once per device by tools/gemm16_tune.py; unlisted problems use entry 0."""
-    global _GEMM_RANKS16
-    if _GEMM_RANKS16 is None:
-        ranks = {}
-        try:
-            import json
-            import os
-            from .step import _common
-            path = os.path.join(_common.gemm_table_root(), _common.miopen_cache_key() + ".json")
-            if os.path.exists(path) and os.environ.get("IRN_GEMM_TABLE", "1") != "0":
-                ranks = {tuple(int(v) for v in k.split(",")): int(r) for k, r in json.load(open(path)).get("ranks16", {}).items()}
-        except Exception:
-            ranks = {}
-        _GEMM_RANKS16 = ranks
-    return _GEMM_RANKS16
-
-
-_GEMM_RANKS3X3 = None
-
-
-def gemm_ranks3x3():
-    """`ranks3x3` of the shipped table: (rows of the bordered operand, cin, cout) -> entry of hipBLASLt's list for the row-fused 3x3
-    split convolution (irn_conv3x3_split_gemm), measured by tools/gemm16_tune.py; unlisted problems use entry 0."""
-    global _GEMM_RANKS3X3
-    if _GEMM_RANKS3X3 is None:
-        ranks = {}
-        try:
-            import json
-            import os
-            from .step import _common
-            path = os.path.join(_common.gemm_table_root(), _common.miopen_cache_key() + ".json")
-            if os.path.exists(path) and os.environ.get("IRN_GEMM_TABLE", "1") != "0":
-                ranks = {tuple(int(v) for v in k.split(",")): int(r) for k, r in json.load(open(path)).get("ranks3x3", {}).items()}
-        except Exception:
-            ranks = {}
-        _GEMM_RANKS3X3 = ranks
-    return _GEMM_RANKS3X3
-
-
-def gemm16_nhwc(a16, b16, shape, bias=None, residual=None, relu=False, alpha=1.0, out=None, algo_rank=None):
-    """act(alpha * a16 . b16^T + bias (+ residual)) as a channels-last fp32 [N, cout, H, W] tensor of `shape` (irn_gemm16_nhwc):
-    a16 fp16 [N*H*W, k] from `split16`, b16 fp16 [cout, k] = [w_hi | w_lo | w_hi 2^-11] of the weight scaled by 1 / alpha."""
-    _need_cuda(a16, "a16")
-    n, cout, h, w_ = (int(v) for v in shape)
-    m, k = int(a16.shape[0]), int(a16.shape[1])
-    if a16.dtype != torch.float16 or not a16.is_contiguous() or m != n * h * w_:
-        raise ValueError("gemm16_nhwc: a16 must be a contiguous fp16 [%d, k] matrix" % (n * h * w_))
-    if b16.dtype != torch.float16 or b16.device != a16.device or not b16.is_contiguous() or tuple(b16.shape) != (cout, k):
-        raise ValueError("gemm16_nhwc: b16 must be a contiguous fp16 [%d, %d] matrix on %s" % (cout, k, a16.device))
-    if bias is not None and (bias.dtype != torch.float32 or bias.device != a16.device or not bias.is_contiguous() or bias.numel() != cout):
-        raise ValueError("gemm16_nhwc: bias must be a contiguous fp32 [%d] tensor on %s" % (cout, a16.device))
-    for name, t in (("residual", residual), ("out", out)):
-        if t is not None and (tuple(t.shape) != (n, cout, h, w_) or t.dtype != torch.float32 or t.device != a16.device
-                              or not t.is_contiguous(memory_format=torch.channels_last)):
-            raise ValueError("gemm16_nhwc: %s must be a channels-last fp32 %s tensor on %s" % (name, (n, cout, h, w_), a16.device))
-    if out is None:
-        out = torch.empty((n, cout, h, w_), dtype=torch.float32, device=a16.device, memory_format=torch.channels_last)
-    if m == 0:
-        return out
-    dev = (a16.device.index if a16.device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(a16.device).cuda_stream)
-    ws = _GEMM_WS.get(dev)
-    if ws is None:
-        ws = _GEMM_WS[dev] = torch.empty(int(lib.irn_conv1x1_workspace_bytes()), dtype=torch.uint8, device=a16.device)
-    if algo_rank is None:
-        prob = (m, k, cout, int(bias is not None), int(residual is not None), int(bool(relu)))
-        algo_rank = gemm_ranks16().get(prob, 0)
-        if algo_rank:
-            n_algos = _GEMM_NALGOS.get(("f16",) + prob)
-            if n_algos is None:
-                with torch.cuda.device(a16.device):
-                    n_algos = _GEMM_NALGOS[("f16",) + prob] = gemm16_algo_count(*prob)
-            if algo_rank >= n_algos:          # another hipBLASLt build than the one the table was measured with
-                algo_rank = 0
-    with torch.cuda.device(a16.device):
-        check(lib.irn_gemm16_nhwc(a16.data_ptr(), b16.data_ptr(), None if bias is None else bias.data_ptr(),
-                                  None if residual is None else residual.data_ptr(), out.data_ptr(), m, k, cout,
-                                  1 if relu else 0, float(alpha), int(algo_rank), ws.data_ptr(), ws.numel(), _stream()))
-    return out
-
-
-def split_weight(w64, p=None):
-    """Weight [cout, cin] (float64, batch norm folded in) -> (b16 fp16 [cout, 3 cin] = [w_hi | w_lo | w_hi 2^-11] of w 2^p, alpha =
-    2^-p): p puts the largest |w 2^p| into [2^13, 2^14), so that w_lo = fp16(w 2^p - w_hi) <= 8 stays a normal fp16 number for
-    every weight above 2^-17 of the largest (smaller ones contribute below the fp32 rounding of the sum).  `p` given: the
-    exponent of a larger tensor this one is a slice of (the taps of a 3x3 weight share one)."""
-    import math
-    w64 = w64.detach().double()
-    if p is None:
-        top = float(w64.abs().max())
-        p = 13 - int(math.floor(math.log2(top))) if top > 0 else 0
-    ws = w64 * (2.0 ** p)
-    hi = ws.to(torch.float16)
-    lo = (ws - hi.double()).to(torch.float16)
-    hi_s = (hi.double() * 2.0 ** -11).to(torch.float16)
-    return torch.cat([hi, lo, hi_s], dim=1).contiguous(), 2.0 ** -p
-
-
-# three GEMMs over 9 cin (row-fused) instead of nine over 3 cin: IRN_CONV3X3_ROW_FUSED=0 keeps the nine
-CONV3X3_ROW_FUSED = os.environ.get("IRN_CONV3X3_ROW_FUSED", "1") != "0"
-
-
-def split_weight_3x3(w64):
-    """3x3 weight [cout, cin, 3, 3] (float64) -> (fp16 [9, cout, 3 cin]: one `split_weight` operand per tap (ky, kx) in raster
-    order, one common exponent, alpha)."""
-    import math
-    w64 = w64.detach().double()
-    top = float(w64.abs().max())
-    p = 13 - int(math.floor(math.log2(top))) if top > 0 else 0
-    taps = [split_weight(w64[:, :, ky, kx], p)[0] for ky in range(3) for kx in range(3)]
-    if CONV3X3_ROW_FUSED:      # [3, cout, 9 cin]: the three taps of a kernel row side by side (irn_conv3x3_split_gemm row_fused)
-        return torch.stack([torch.cat(taps[3 * ky:3 * ky + 3], dim=1) for ky in range(3)]).contiguous(), 2.0 ** -p
-    return torch.stack(taps).contiguous(), 2.0 ** -p
-
-
-def split16_pad(x, shape, scale=None, shift=None, relu=False, in_padded=False, out=None):
-    """`split16` between a dense map and its zero-bordered form (irn_split16_pad).  shape = (n, c, h, w) of the DENSE map.
-    in_padded: `x` is the bordered fp32 form [n (h+2)(w+2), c] (a `conv3x3_split` result), the result is the dense fp16
-    [n h w, 3c]; `out` given (a bordered fp16 buffer's interior view, borders already zero): `x` is a dense channels-last fp32
-    tensor and the split goes into the bordered form, zero border rows included."""
-    n, c, h, w_ = (int(v) for v in shape)
-    _need_cuda(x, "x")
-    if c % 8:
-        raise ValueError("split16_pad: %d channels; a multiple of 8 is needed" % c)
-    if in_padded:
-        if x.dtype != torch.float32 or not x.is_contiguous() or x.numel() != n * (h + 2) * (w_ + 2) * c:
-            raise ValueError("split16_pad: x must be the contiguous bordered fp32 form of a %s map" % (shape,))
-    elif x.dtype != torch.float32 or tuple(x.shape) != (n, c, h, w_) or not x.is_contiguous(memory_format=torch.channels_last):
-        raise ValueError("split16_pad: x must be a channels-last fp32 %s tensor" % (shape,))
-    out_padded = out is not None
-    if out is None:
-        out = torch.empty((n * h * w_, 3 * c), dtype=torch.float16, device=x.device)
-    elif out.dtype != torch.float16 or not out.is_contiguous() or out.numel() < n * (h + 2) * (w_ + 2) * 3 * c:
-        raise ValueError("split16_pad: out must be a contiguous fp16 buffer of the bordered form (its border rows are written too)")
-    if n * h * w_ == 0:
-        return out
-    with torch.cuda.device(x.device):
-        check(lib.irn_split16_pad(x.data_ptr(), None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr(),
-                                  1 if relu else 0, out.data_ptr(), n, h, w_, c, 1 if in_padded else 0, 1 if out_padded else 0,
-                                  _split_flag(x.device).data_ptr(), _stream()))
-    return out
-
-
-_ROW_FUSED_REFUSED = False
-
-
-def conv3x3_split(x, w16, alpha, algo_rank=None):
-    """3x3 / stride 1 / pad 1 convolution (no bias) of a channels-last fp32 activation [N, C, H, W] in the split-precision form,
-    WITHOUT materialising an im2col operand: the activation is split once into a zero-bordered fp16 matrix [N (H+2)(W+2), 3C]
-    (irn_split16_pad writes the borders too); there tap (ky, kx) is the same matrix shifted by (ky-1)(W+2) + (kx-1) rows, so the
-    convolution is nine fp16 GEMMs accumulating in fp32 in a fixed order (irn_conv3x3_split_gemm, one call).  w16 =
-    `split_weight_3x3` fp16 [9, cout, 3C].  -> the result in the bordered fp32 form [N (H+2)(W+2), cout] (border rows hold
-    garbage; `split16_pad(..., in_padded=True)` reads the interior).  Reference: conv2 of Bottleneck.forward, net/resnet50.py:40."""
-    _need_cuda(x, "x")
-    n, c, h, w_ = (int(v) for v in x.shape)
-    cout = int(w16.shape[1])
-    fused = int(w16.shape[0]) == 3
-    if tuple(w16.shape) not in ((9, cout, 3 * c), (3, cout, 9 * c)) or w16.dtype != torch.float16 or not w16.is_contiguous() or w16.device != x.device:
-        raise ValueError("conv3x3_split: w16 must be a contiguous fp16 [9, cout, %d] or [3, cout, %d] tensor on %s" % (3 * c, 9 * c, x.device))
-    m_pad, guard = n * (h + 2) * (w_ + 2), w_ + 3
-    a_buf = torch.empty((m_pad + 2 * guard, 3 * c), dtype=torch.float16, device=x.device)        # guard rows: valid memory, any content
-    out = torch.empty((m_pad, cout), dtype=torch.float32, device=x.device)
-    if m_pad == 0:
-        return out
-    split16_pad(x, (n, c, h, w_), out=a_buf[guard:])
-    dev = (x.device.index if x.device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(x.device).cuda_stream)
-    ws = _GEMM_WS.get(dev)
-    if ws is None:
-        ws = _GEMM_WS[dev] = torch.empty(int(lib.irn_conv1x1_workspace_bytes()), dtype=torch.uint8, device=x.device)
-    rank = algo_rank
-    if rank is None:
-        rank = gemm_ranks3x3().get((m_pad, c, cout), 0) if fused else gemm_ranks16().get((m_pad, 3 * c, cout, 0, 1, 0), 0)
-    global _ROW_FUSED_REFUSED
-    with torch.cuda.device(x.device):
-        if fused and not _ROW_FUSED_REFUSED:
-            rc = lib.irn_conv3x3_split_gemm(a_buf[guard:].data_ptr(), w16.data_ptr(), out.data_ptr(), n, h, w_, c, cout, float(alpha), 1, int(rank),
-                                            ws.data_ptr(), ws.numel(), _stream())
-            if rc == 0:
-                return out
-            # this hipBLASLt build does not take an operand with overlapping rows: the nine-GEMM form computes the same sums
-            _ROW_FUSED_REFUSED = True
-            import warnings
-            warnings.warn("irn_amd: hipBLASLt refused the row-fused 3x3 operand (%s); using nine GEMMs per 3x3 convolution (~7 %% slower "
-                          "backbones)" % lib.irn_last_error().decode(errors="replace"), RuntimeWarning)
-        if fused:                                   # [3, cout, 9c] -> [9, cout, 3c]: the same taps, one per GEMM
-            w16 = w16.view(3, cout, 3, 3 * c).permute(0, 2, 1, 3).reshape(9, cout, 3 * c).contiguous()
-            rank = 0
-        check(lib.irn_conv3x3_split_gemm(a_buf[guard:].data_ptr(), w16.data_ptr(), out.data_ptr(), n, h, w_, c, cout, float(alpha), 0, int(rank),
-                                         ws.data_ptr(), ws.numel(), _stream()))
-    return out
-
-
-def conv1x1_algo_count(m, cin, cout, bias, residual, relu):
-    """How many kernels hipBLASLt's heuristic offers for the problem (tools/conv1x1_tune.py times each of them once)."""
-    n = C.c_int(0)
-    check(lib.irn_conv1x1_algo_count(int(m), int(cin), int(cout), int(bool(bias)), int(bool(residual)), int(bool(relu)),
-                                     int(lib.irn_conv1x1_workspace_bytes()), C.byref(n)))
-    return n.value
-
-
 def _need_f32_contig(t, what, min_dim):
     _need_cuda(t, what)
     if t.dtype != torch.float32 or not t.is_contiguous() or t.dim() < min_dim:
@@ -515,9 +163,8 @@ def stem_pool(x, scale, shift):
     net/resnet50.py:94-97).  x: GPU fp32 [N, C, H, W] (conv1's output, left untouched) -> [N, C, (H-1)//2+1, (W-1)//2+1]."""
     _need_f32_contig(x, "stem_pool: x", 4)
     n, c, h, w = (int(v) for v in x.shape)
-    for name, t in (("scale", scale), ("shift", shift)):
-        if t.device != x.device or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != c:
-            raise ValueError("stem_pool: %s must be a contiguous fp32 [%d] tensor on %s" % (name, c, x.device))
+    _need_vec(scale, "stem_pool: scale", c, x.device)
+    _need_vec(shift, "stem_pool: shift", c, x.device)
     out = torch.empty((n, c, (h - 1) // 2 + 1 if h else 0, (w - 1) // 2 + 1 if w else 0), dtype=torch.float32, device=x.device)
     if out.numel():
         with torch.cuda.device(x.device):

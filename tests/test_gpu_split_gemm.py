@@ -108,13 +108,13 @@ def test_conv3x3_as_nine_accumulating_split_gemms(n, c, cout, h, w, fused, monke
     exact 3x3 / pad 1 convolution, at the accuracy of MIOpen's fp32 convolution; the bordered result read back through the
     batch-norm + ReLU + split pass equals the dense one; same bits on every call, also after other shapes used the buffers."""
     import torch.nn.functional as F
-    from irn_amd import ops
+    from irn_amd import gemm, ops
     dev = _dev()
     g = torch.Generator().manual_seed(n * 100 + c + h)
     x = torch.relu(torch.randn(n, c, h, w, generator=g)) * 2.0
     wt = torch.randn(cout, c, 3, 3, generator=g) / (9 * c) ** 0.5
     want = F.conv2d(x.double(), wt.double(), None, 1, 1)
-    monkeypatch.setattr(ops, "CONV3X3_ROW_FUSED", fused)
+    monkeypatch.setattr(gemm, "CONV3X3_ROW_FUSED", fused)
     w16, alpha = ops.split_weight_3x3(wt.double().to(dev))
     assert w16.shape == ((3, cout, 9 * c) if fused else (9, cout, 3 * c))
     xd = _cl(x.to(dev))
@@ -139,7 +139,7 @@ def test_conv3x3_as_nine_accumulating_split_gemms(n, c, cout, h, w, fused, monke
     assert torch.equal(interior(again), first)
     if fused:
         # a hipBLASLt build that refuses the overlapping-row operand: the same call falls back to nine GEMMs on the same taps
-        monkeypatch.setattr(ops, "_ROW_FUSED_REFUSED", True)
+        monkeypatch.setattr(gemm, "_ROW_FUSED_REFUSED", True)
         nine = interior(ops.conv3x3_split(xd, w16, alpha))
         assert float((nine - first).abs().max()) <= 2e-6 * max(1.0, scale)
     assert not ops.split_overflowed()
@@ -166,14 +166,12 @@ def test_bottleneck_split_path_vs_composed_modules_and_fp32_gemm_path(monkeypatc
             monkeypatch.setattr(r50, "SPLIT_MIN_PLANES", 64)
             monkeypatch.setattr(r50, "SPLIT_MIN_INPUT", 1 << 20)
             monkeypatch.setattr(r50, "SPLIT_MIN_ROWS_3X3", 1)             # the 512-plane units take the nine-GEMM 3x3 here too
-            unit._gemm = None
             y_split = unit(_cl(x))
             p = unit.gemm_params()
             assert ("w2_16" in p) == (planes >= r50.SPLIT_MIN_PLANES_3X3)
             assert "w3_16" in p and (("w1_16" in p) == (c_in * (planes + (4 * planes if project else 0)) >= 1 << 20))
             assert torch.equal(y_split, unit(_cl(x)))
             monkeypatch.setattr(r50, "SPLIT_GEMM", False)
-            unit._gemm = None
             y_f32 = unit(_cl(x))
             assert "w3_16" not in unit.gemm_params()
             y_ref = unit.double()(x.double())                      # NCHW, fp64: the composed modules

@@ -688,6 +688,91 @@ def test_missing_shipped_data_warns_once_and_names_the_remedy(monkeypatch, tmp_p
     assert "worker 3/8" in line and "NOT SHIPPED" in line and "reproducible" in line
 
 
+def test_rank_table_is_read_once_and_a_malformed_one_raises_with_its_path(monkeypatch, tmp_path):
+    """irn_amd/gemm.py: the three rank dicts come from ONE read of `<gemm_table_root>/<key>.json`; no file or IRN_GEMM_TABLE=0 mean
+    empty tables; a file that is there but is not JSON, or holds a key or a rank that is no integer, raises and names the file (a
+    shipped table that silently does nothing costs ~10 % and nobody sees it)."""
+    import json
+    from irn_amd import gemm, ops
+    from irn_amd.step import _common
+    monkeypatch.setattr(_common, "gemm_table_root", lambda: str(tmp_path))
+    monkeypatch.setattr(_common, "miopen_cache_key", lambda: "gfx999-cu1-hip0.0")
+    monkeypatch.delenv("IRN_GEMM_TABLE", raising=False)
+    path = tmp_path / "gfx999-cu1-hip0.0.json"
+    monkeypatch.setattr(gemm, "_TABLE", None)
+    assert gemm.gemm_ranks() == {} and gemm.gemm_ranks16() == {} and gemm.gemm_ranks3x3() == {}          # no file
+    path.write_text(json.dumps({"ranks": {"4096,256,64,1,0,1": 3}, "ranks16": {"4096,768,64,1,0,1": 2}, "ranks3x3": {"1156,128,128": 5}}))
+    assert gemm.gemm_ranks() == {}                                                                       # ... and not looked for again
+    monkeypatch.setattr(gemm, "_TABLE", None)
+    opened = []
+    real_load = json.load
+    monkeypatch.setattr(json, "load", lambda fh: opened.append(fh.name) or real_load(fh))
+    assert ops.gemm_ranks() == {(4096, 256, 64, 1, 0, 1): 3} and ops.gemm_ranks16() == {(4096, 768, 64, 1, 0, 1): 2}
+    assert ops.gemm_ranks3x3() == {(1156, 128, 128): 5} and opened == [str(path)]
+    monkeypatch.setattr(gemm, "_TABLE", None)
+    monkeypatch.setenv("IRN_GEMM_TABLE", "0")
+    assert gemm.gemm_ranks() == {} and gemm.gemm_ranks3x3() == {} and opened == [str(path)]
+    monkeypatch.delenv("IRN_GEMM_TABLE")
+    for text in ("{\"ranks\": {", "[1, 2]", json.dumps({"ranks": {"4096,256,sixty-four,1,0,1": 3}}), json.dumps({"ranks": {"4096,256,64,1,0,1": 3}, "ranks16": {"8,8,8,0,0,0": 1.5}}),
+                 json.dumps({"ranks3x3": {"1156,128,128": "5"}}), json.dumps({"ranks": [3]})):
+        path.write_text(text)
+        for accessor in (gemm.gemm_ranks, gemm.gemm_ranks16, gemm.gemm_ranks3x3):
+            monkeypatch.setattr(gemm, "_TABLE", None)
+            with pytest.raises(ValueError) as e:
+                accessor()
+            assert str(path) in str(e.value) and "malformed" in str(e.value), text
+    monkeypatch.setattr(gemm, "_TABLE", None)           # (the next reader of this process loads the real one)
+
+
+def test_gemm_params_fold_is_the_composed_definition_and_follows_bn2_and_the_switches(monkeypatch):
+    """Bottleneck.gemm_params (reference net/resnet50.py:34-54 with FixedBatchNorm folded in): w * (gamma / sqrt(var + eps)) in
+    float64, rounded to fp32 once; b3 = shift3 + shift_d for a projection unit; bn2's constants are read where they are used, so
+    writing bn2 alone changes them; the SPLIT_* switches are part of the cache key."""
+    from irn_amd.net import resnet50 as r50
+    torch.manual_seed(5)
+    for project in (False, True):
+        unit = r50.Bottleneck(64 if project else 128, 32, stride=1, project=project).eval()
+        bns = [m for m in unit.modules() if isinstance(m, r50.FrozenBatchNorm)]
+        with torch.no_grad():
+            for m in bns:
+                m.weight.uniform_(0.5, 1.5)
+                m.bias.normal_(0, 0.2)
+                m.running_mean.normal_(0, 0.2)
+                m.running_var.uniform_(0.5, 2.0)
+
+        def fold(conv, bn):
+            scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+            return conv.weight.detach().double() * scale.view(-1, 1, 1, 1), bn.bias.detach().double() - bn.running_mean.detach().double() * scale
+        p = unit.gemm_params()
+        w1, t1 = fold(unit.conv1, unit.bn1)
+        w3, t3 = fold(unit.conv3, unit.bn3)
+        assert torch.equal(p["w1"], w1.float().flatten(1)) and torch.equal(p["b1"], t1.float())
+        assert torch.equal(p["w3"], w3.float().flatten(1)) and p["w1"].dtype == torch.float32 and p["b3"].dtype == torch.float32
+        if project:
+            wd, td = fold(unit.downsample[0], unit.downsample[1])
+            assert torch.equal(p["wd"], wd.float()) and torch.equal(p["b3"], (t3 + td).float())
+        else:
+            assert "wd" not in p and torch.equal(p["b3"], t3.float())
+        assert "s2" not in p and "t2" not in p and unit.gemm_params() is p                    # cached; bn2 is not in it
+        scale2 = lambda: (unit.bn2.weight.detach().double() / torch.sqrt(unit.bn2.running_var.detach().double() + unit.bn2.eps)).float()
+        s2, t2 = (t.clone() for t in unit.bn2.folded())
+        assert torch.equal(s2, scale2())
+        with torch.no_grad():
+            unit.bn2.running_var.mul_(4.0)                                                      # bn2 ALONE, in place
+        s2b, t2b = unit.bn2.folded()                                                            # what _forward_gemm hands to the split pass
+        assert not torch.equal(s2b, s2) and torch.equal(s2b, scale2())
+        assert not torch.equal(t2b, t2) and unit.gemm_params() is p                             # ... and nothing else was rebuilt
+        key = unit._gemm[0]
+        monkeypatch.setattr(r50, "SPLIT_GEMM", not r50.SPLIT_GEMM)
+        p2 = unit.gemm_params()
+        assert unit._gemm[0] != key and p2 is not p and torch.equal(p2["w1"], p["w1"])
+        monkeypatch.setattr(r50, "SPLIT_GEMM", not r50.SPLIT_GEMM)
+        for name in ("SPLIT_MIN_PLANES", "SPLIT_MIN_PLANES_3X3", "SPLIT_MIN_INPUT"):
+            before = unit.gemm_params() and unit._gemm[0]
+            monkeypatch.setattr(r50, name, getattr(r50, name) + 8)
+            assert unit.gemm_params() is not None and unit._gemm[0] != before, name
+
+
 def test_edge_store_keys_and_cap(tmp_path):
     """step/_common.EdgeStore: the boundary / displacement maps one label step leaves for the other are keyed by network,
     forward geometry and image FILE; another checkpoint, another image under the same name (new mtime / size) or another
@@ -859,12 +944,12 @@ def test_instance_step_pipeline_order(monkeypatch):
 
 
 def test_split_weight_operands_reconstruct_the_weight_to_22_bits_and_the_split_product_is_fp32_grade():
-    """The host half of the split-precision convolutions (irn_amd/ops.py split_weight[_3x3]; reference net/resnet50.py:34-54 with
+    """The host half of the split-precision convolutions (irn_amd/gemm.py split_weight[_3x3]; reference net/resnet50.py:34-54 with
     FixedBatchNorm folded in): [w_hi | w_lo | w_hi 2^-11] of w 2^p reconstructs w to 2^-22 of the layer's largest weight, every
     entry stays inside fp16's range, the taps of a 3x3 weight share one exponent in both operand layouts — and the product the GPU
     forms with them, emulated here in numpy (fp16 operands, exact products, wide accumulation), is as close to the exact one as a
     correctly rounded fp32 dot product."""
-    from irn_amd import ops
+    from irn_amd import gemm, ops
     g = torch.Generator().manual_seed(4)
     for cout, cin, spread in ((64, 256, 1.0), (512, 128, 1e-3), (8, 16, 30.0)):
         w = torch.randn(cout, cin, generator=g).double() * spread * torch.rand(cout, 1, generator=g).double()
@@ -887,11 +972,11 @@ def test_split_weight_operands_reconstruct_the_weight_to_22_bits_and_the_split_p
         assert float((got - want).abs().max()) <= 4e-7 * scale and float((got - want).abs().max()) <= 2.0 * float((f32 - want).abs().max()) + 1e-7 * scale
     w3 = torch.randn(16, 8, 3, 3, generator=g).double() * 0.1
     for fused, shape in ((False, (9, 16, 24)), (True, (3, 16, 72))):
-        ops.CONV3X3_ROW_FUSED, saved = fused, ops.CONV3X3_ROW_FUSED
+        gemm.CONV3X3_ROW_FUSED, saved = fused, gemm.CONV3X3_ROW_FUSED
         try:
             t16, a3 = ops.split_weight_3x3(w3)
         finally:
-            ops.CONV3X3_ROW_FUSED = saved
+            gemm.CONV3X3_ROW_FUSED = saved
         assert tuple(t16.shape) == shape
         taps = t16.view(3, 16, 3, 24).permute(0, 2, 1, 3).reshape(9, 16, 24) if fused else t16
         for t in range(9):

@@ -486,6 +486,36 @@ int irn_mask_overlap(const uint8_t *masks_dev, int n, const uint8_t *inst_dev, i
                      int64_t *inter_dev, int64_t *area_pred_dev, int64_t *area_gt_dev, int64_t *bad_dev,
                      void *stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * COCO mask encoding  (replaces the pycococreatortools / pycocotools arithmetic behind
+ *                      step/make_cocoann.py:38-46: per mask a run-length code, an area and a box)
+ * masks dev uint8 [n][h][w], row-major, nonzero = in the mask (what make_ins_seg_labels writes and
+ * irn_mask_overlap takes).  The code is pycocotools' rleEncode: pixels in COLUMN-major order
+ * (j = x*h + y); counts[0] is the length of the leading run of zeros (0 when pixel (0,0) is set),
+ * then runs of ones and zeros alternate and the counts of a mask sum to h*w (an empty mask is the
+ * single count h*w, a full one [0, h*w]).  area = number of nonzero pixels; bbox = [x0, y0, width,
+ * height] of the nonzero pixels, [0,0,0,0] for an empty mask (= rleArea, rleToBbox).
+ * The number of counts depends on the data, so the work is two calls on the same inputs and scratch:
+ *
+ * irn_mask_rle_count: n_runs dev int32 [n] (counts of every mask), area dev int64 [n], bbox dev
+ *   int32 [n][4]; all three are written, not added into.  Nothing synchronises: the caller reads
+ *   n_runs (one transfer for the whole call), forms offsets = exclusive scan of n_runs and sizes
+ *   counts.
+ * irn_mask_rle_emit: offsets dev int64 [n+1]; counts dev uint32 [offsets[n]] receives the finished
+ *   run lengths of every mask, mask i at offsets[i].  A count that would fall outside
+ *   [offsets[i], offsets[i+1]) is not written.  Nothing synchronises.  Must follow _count on the
+ *   same stream with the scratch untouched in between.
+ * scratch: irn_mask_rle_scratch_bytes(n, h, w) bytes of caller-owned device memory (0 = bad
+ *   argument, or n == 0).
+ * n == 0 is valid (every array may then be NULL).  1 <= h, w and h*w < 2^31 - 1.  Integer
+ * arithmetic with one writer per output word: bit-reproducible.
+ * ------------------------------------------------------------------------------------------- */
+size_t irn_mask_rle_scratch_bytes(int n, int h, int w);
+int irn_mask_rle_count(const uint8_t *masks_dev, int n, int h, int w, int32_t *n_runs_dev, int64_t *area_dev,
+                       int32_t *bbox_dev, void *scratch_dev, void *stream);
+int irn_mask_rle_emit(const uint8_t *masks_dev, int n, int h, int w, const int64_t *offsets_dev,
+                      uint32_t *counts_dev, void *scratch_dev, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

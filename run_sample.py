@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """CLI boundary — same flags and step order as reference run_sample.py:8-137, for the steps this repository
-implements: the label-generation steps (make_cam, cam_to_ir_label, make_ins_seg, make_sem_seg) and the evaluation
-steps that score them (eval_cam, eval_ins_seg, eval_sem_seg).
+implements: the label-generation steps (make_cam, cam_to_ir_label, make_ins_seg, make_sem_seg), the evaluation
+steps that score them (eval_cam, eval_ins_seg, eval_sem_seg) and the COCO export of the instance labels (make_cocoann,
+step/make_cocoann.py; not in the reference's run_sample.py, which leaves it to be run by hand).
 
 The training steps of the reference (train_cam, train_irn) are outside the hot-path scope; their
 `--*_pass` flags are accepted so existing command lines keep working, and asking for one of them
@@ -92,12 +93,15 @@ def build_parser():
     p.add_argument("--ir_label_out_dir", default="result/ir_label", type=str)
     p.add_argument("--sem_seg_out_dir", default="result/sem_seg", type=str)
     p.add_argument("--ins_seg_out_dir", default="result/ins_seg", type=str)
+    p.add_argument("--cocoann_out", default="voc2012_train_custom.json", type=str,
+                   help="make_cocoann: the COCO annotation file it writes (the reference hard-codes this name, step/make_cocoann.py:48)")
     p.add_argument("--edge_out_dir", default=None, type=str,
                    help="verification aid (not in the reference): also write every image's boundary / displacement maps "
                         "(<name>.npy = {'edge' [1,h,w], 'dp' [2,h,w]}) as the label steps used them")
     for name, default in (("train_cam_pass", False), ("make_cam_pass", True), ("eval_cam_pass", False),
                           ("cam_to_ir_label_pass", False), ("train_irn_pass", False), ("make_ins_seg_pass", True),
-                          ("eval_ins_seg_pass", False), ("make_sem_seg_pass", True), ("eval_sem_seg_pass", False)):
+                          ("eval_ins_seg_pass", False), ("make_cocoann_pass", False), ("make_sem_seg_pass", True),
+                          ("eval_sem_seg_pass", False)):
         p.add_argument("--" + name, default=default, type=_flag)
     return p
 
@@ -142,6 +146,10 @@ def main(argv=None):
         from irn_amd.step import eval_ins_seg
         timer = pyutils.Timer("step.eval_ins_seg:")
         results["eval_ins_seg"] = eval_ins_seg.run(args)
+    if args.make_cocoann_pass is True:
+        from irn_amd.step import make_cocoann
+        timer = pyutils.Timer("step.make_cocoann:")
+        results["make_cocoann"] = make_cocoann.run(args)
     if args.make_sem_seg_pass is True:
         from irn_amd.step import make_sem_seg_labels
         timer = pyutils.Timer("step.make_sem_seg_labels:")

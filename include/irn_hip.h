@@ -411,6 +411,39 @@ int irn_detect_instance_batch_emit(int n_images, const float *const *rw_up_dev, 
                                    const double *min_area, float *const *score_dev, int32_t *const *channel_dev,
                                    uint8_t *const *mask_dev, void *scratch_dev, void *stream);
 
+/* Detections as COCO run lengths, straight from the labelled map: what step/make_ins_seg_labels.py:82-105 detects, in
+ * the form step/make_cocoann.py:38-46 exports, with no dense mask in between.  The masks of one image are disjoint, so
+ * after irn_detect_instance_batch_count the scratch describes all of them as ONE int32 map of detection ids; every
+ * detection's run lengths (the "COCO mask encoding" convention below: column-major, a leading zero-run that may be 0,
+ * no trailing zero count when the last pixel is set), area and box are read off that map.
+ * The outputs are batch-wide arrays over G = sum(n_det) detections, image i's at [g0_i, g0_i + n_det[i]) with g0 the
+ * exclusive prefix of n_det, in detect_instance's order.  n_det: host int32 [n_images], as read from n_det_dev.
+ *
+ * irn_detect_instance_batch_rle_count: after _batch_count with the same inputs and scratch.  score dev fp32 [G] and
+ *   channel dev int32 [G] as irn_detect_instance_batch_emit gives them (area < min_area -> score 0); area dev int32
+ *   [G]; n_runs dev int32 [G]; bbox dev int32 [G][4] = [x0, y0, width, height].  Nothing synchronises: the caller
+ *   reads the five arrays with one transfer and sizes counts.
+ * irn_detect_instance_batch_rle_emit: after _rle_count on the same stream with rle_scratch untouched.  runs: host
+ *   int64 [n_images], the sum of n_runs over each image's detections.  counts dev uint32 [sum(runs)] receives the run
+ *   lengths of every detection back to back in batch order (detection g at the exclusive prefix of n_runs).  A key that
+ *   would fall outside an image's share of the workspace is not written.  Nothing synchronises.
+ * scratch: the one _batch_count used.  rle_scratch: irn_detect_instance_batch_rle_scratch_bytes.  ws:
+ *   irn_detect_instance_batch_rle_sort_bytes(sum(runs), G) bytes (0 = bad argument, or nothing to sort).
+ * n_images == 0 is valid (nothing is done); n_images < 0, a null pointer, h*w above 2^30 (so every h*w >= 2^31 - 1)
+ * and n_det outside [0, h*w] give IRN_ERR_ARG before any device is touched.  Integer arithmetic apart from the score
+ * maximum; the atomics are integer sums, minima and maxima and the run lengths come out of a sort of distinct keys:
+ * bit-reproducible, and independent of the batch an image is part of. */
+size_t irn_detect_instance_batch_rle_scratch_bytes(int n_images, const int32_t *h, const int32_t *w, const int32_t *n_det);
+int irn_detect_instance_batch_rle_count(int n_images, const float *const *rw_up_dev, const int32_t *const *argmax_dev,
+                                        const int32_t *n_channels, const int32_t *h, const int32_t *w,
+                                        const int32_t *n_det, const double *min_area, float *score_dev,
+                                        int32_t *channel_dev, int32_t *area_dev, int32_t *n_runs_dev, int32_t *bbox_dev,
+                                        void *scratch_dev, void *rle_scratch_dev, void *stream);
+size_t irn_detect_instance_batch_rle_sort_bytes(int64_t total_runs, int total_det);
+int irn_detect_instance_batch_rle_emit(int n_images, const int32_t *h, const int32_t *w, const int32_t *n_det,
+                                       const int64_t *runs, uint32_t *counts_dev, void *rle_scratch_dev, void *ws,
+                                       size_t ws_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Dense CRF  (replaces misc/imutils.py:156-170 crf_inference_label over pydensecrf, and
  *             step/cam_to_ir_label.py:22-39)

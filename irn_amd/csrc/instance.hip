@@ -9,6 +9,9 @@
 // multiply-add, float32 rounding after each +=, round-half-even at the end.
 #include "kernels.hpp"
 
+#include <climits>
+#include <rocprim/rocprim.hpp>
+
 namespace irn {
 namespace {
 
@@ -833,6 +836,354 @@ extern "C" int irn_detect_instance_batch_emit(int n_images, const float *const *
     IRN_LAUNCH_CHECK("det_stats_kernel");
     hipLaunchKernelGGL(det_final_kernel, dim3(cdiv(max_det, 256), n_images), dim3(256), 0, stream, jd);
     IRN_LAUNCH_CHECK("det_final_kernel");
+    return scratch_release(stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Detections as COCO run lengths, straight from the labelled map (step/make_ins_seg_labels.py:82-105 followed by the
+// encoding of step/make_cocoann.py:38-46) — no dense mask plane anywhere.
+//
+// After irn_detect_instance_batch_count and det_order_kernel the detection of pixel p is newid[prov[parent[p]]]: ONE
+// int32 map per image holds every mask.  In pycocotools' column-major order (j = x*h + y) a pixel whose id differs from
+// its predecessor's is an EVENT: it ends a run of ones of the predecessor's detection and starts one of its own (the
+// background, id -1, has no runs).  The events of one detection, ordered by j, alternate start / end, their positions are
+// distinct, and with the map's end (j = h*w) appended as a last position the run lengths are the differences of
+// neighbouring positions, the first taken from 0: the leading zero-run (0 when the detection owns pixel (0,0)), then ones
+// and zeros in turn, and the last difference is the trailing zero-run or — when the detection owns the last pixel — the
+// run of ones that reaches the end.  So n_runs = events + 1, always.
+//
+//   count:  det_order_kernel     final ids and channels (shared with the dense path)
+//           rle_init_kernel      box and run counters of every detection
+//           rle_map_kernel       the id map; area, maximum score and box per detection (integer atomics)
+//           rle_events_kernel    <false>: events per detection (integer atomic adds)
+//           rle_final_kernel     score, area, bbox, n_runs of every detection
+//   emit:   rle_events_kernel    <true>: every event appends the key (batch-wide detection index << 32 | j) to its image's
+//                                segment; every detection adds the key of the map's end
+//           rocprim radix sort   ONE sort of the batch's keys: detections ascending, positions ascending inside each
+//           rle_runs_kernel      counts[t] = position of key t - position of key t-1 (0 across a detection's start)
+//
+// Where a key lands before the sort depends on the order the atomics arrive in; the keys are distinct, so the sorted
+// array does not, and everything else is an integer sum, minimum or maximum: the output is bit-reproducible and the
+// same whatever batch an image is part of.  Nothing is sized per thread and per detection: a noisy map with tens of
+// thousands of fragments costs two keys per fragment pixel run, like any other.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+struct RleJob {
+    int *idmap;                       // [npx] detection of every pixel, -1 = background
+    int *x0, *x1, *y0, *y1, *runs;    // [n_det] box corners (inclusive) and number of run lengths
+    int32_t *area_out, *n_runs_out, *bbox_out;   // the image's slice of the batch's outputs (count)
+    unsigned long long *keys;         // the image's key segment (emit)
+    unsigned *cursor;                 // keys appended so far, after the n_det map-end keys (emit)
+    int room;                         // keys of the image = sum of its n_runs (emit)
+    int g0;                           // index of the image's first detection in the batch
+    int h, w, n_det;
+};
+
+__global__ __launch_bounds__(256) void rle_init_kernel(const RleJob *__restrict__ jobs) {
+    const RleJob R = jobs[blockIdx.y];
+    const int d = blockIdx.x * 256 + threadIdx.x;
+    if (d >= R.n_det) return;
+    R.x0[d] = R.y0[d] = INT_MAX;
+    R.x1[d] = R.y1[d] = -1;
+    R.runs[d] = 1;                    // the map's end closes the last run
+}
+
+// det_stats_kernel without the mask byte: the id map instead, and the box next to area and score.
+__global__ __launch_bounds__(256) void rle_map_kernel(const DetJob *__restrict__ jobs, const RleJob *__restrict__ rjobs) {
+    const DetJob J = jobs[blockIdx.y];
+    if (J.n_det < 1) return;
+    const RleJob R = rjobs[blockIdx.y];
+    const int npx = J.h * J.w;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    const int c = p < npx ? J.cls[p] : 0;
+    const bool fg = c > 0;
+    const int y = p / J.w, x = p - y * J.w;
+    int d = -1, bits = 0;
+    if (fg) {
+        d = J.newid[J.prov[J.parent[p]]];
+        const float sc = J.rw_up[(long)(c - 1) * npx + p];
+        bits = sc > 0.f ? __float_as_int(sc) : 0;
+    }
+    if (p < npx) R.idmap[p] = d;
+    const unsigned long long act = __ballot(fg);
+    if (act == 0) return;
+    const int d0 = __shfl(d, __ffsll((long long)act) - 1);
+    if (__all(!fg || d == d0)) {       // the usual case: one detection under the wave's 64 pixels, one set of atomics
+        int mx = bits, xa = fg ? x : INT_MAX, xb = fg ? x : -1, ya = fg ? y : INT_MAX, yb = fg ? y : -1;
+        for (int sft = 32; sft > 0; sft >>= 1) {
+            mx = max(mx, __shfl_xor(mx, sft));
+            xa = min(xa, __shfl_xor(xa, sft)), xb = max(xb, __shfl_xor(xb, sft));
+            ya = min(ya, __shfl_xor(ya, sft)), yb = max(yb, __shfl_xor(yb, sft));
+        }
+        if ((threadIdx.x & 63) == 0) {
+            atomicAdd(J.area + d0, __popcll(act));
+            if (mx > 0) atomicMax(J.score_bits + d0, mx);
+            atomicMin(R.x0 + d0, xa), atomicMax(R.x1 + d0, xb);
+            atomicMin(R.y0 + d0, ya), atomicMax(R.y1 + d0, yb);
+        }
+    } else if (fg) {
+        atomicAdd(J.area + d, 1);
+        if (bits > 0) atomicMax(J.score_bits + d, bits);
+        atomicMin(R.x0 + d, x), atomicMax(R.x1 + d, x);
+        atomicMin(R.y0 + d, y), atomicMax(R.y1 + d, y);
+    }
+}
+
+// one atomic add for the wave when all of its adders share a target (a component's upper edge), one each otherwise
+__device__ __forceinline__ void add_one_per_lane(int *counter, bool on, int target) {
+    const unsigned long long m = __ballot(on);
+    if (m == 0) return;
+    const int first = __ffsll((long long)m) - 1;
+    const int t0 = __shfl(target, first);
+    if (__all(!on || target == t0)) {
+        if ((int)(threadIdx.x & 63) == first) atomicAdd(counter + t0, __popcll(m));
+    } else if (on) {
+        atomicAdd(counter + target, 1);
+    }
+}
+
+// Pixel p = (y, x) follows (y-1, x) in column-major order, or the last pixel of column x-1; the first pixel follows the
+// background.  Row-major threads: the map is read as whole rows, twice.
+template <bool EMIT>
+__global__ __launch_bounds__(256) void rle_events_kernel(const RleJob *__restrict__ jobs) {
+    const RleJob R = jobs[blockIdx.y];
+    if (R.n_det < 1) return;
+    const int npx = R.h * R.w;
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    int a = -1, b = -1, j = 0;
+    if (p < npx) {
+        const int y = p / R.w, x = p - y * R.w;
+        b = R.idmap[p];
+        a = y > 0 ? R.idmap[p - R.w] : (x > 0 ? R.idmap[(R.h - 1) * R.w + x - 1] : -1);
+        j = x * R.h + y;
+    }
+    const bool ends = a != b && a >= 0, starts = a != b && b >= 0;
+    if (!EMIT) {
+        add_one_per_lane(R.runs, ends, a);
+        add_one_per_lane(R.runs, starts, b);
+        return;
+    }
+    if (p < R.n_det && p < R.room) R.keys[p] = ((unsigned long long)(R.g0 + p) << 32) | (unsigned)npx;   // the map's end
+    const unsigned long long me = __ballot(ends), ms = __ballot(starts);
+    const int total = __popcll(me) + __popcll(ms);
+    if (total == 0) return;
+    const int lane = threadIdx.x & 63;
+    const unsigned long long below = lane ? ~0ull >> (64 - lane) : 0ull;
+    unsigned base = 0;
+    if (lane == 0) base = atomicAdd(R.cursor, (unsigned)total);
+    base = (unsigned)__shfl((int)base, 0);
+    long long slot = (long long)R.n_det + base + __popcll(me & below) + __popcll(ms & below);
+    if (ends) {
+        if (slot < R.room) R.keys[slot] = ((unsigned long long)(R.g0 + a) << 32) | (unsigned)j;
+        ++slot;
+    }
+    if (starts && slot < R.room) R.keys[slot] = ((unsigned long long)(R.g0 + b) << 32) | (unsigned)j;
+}
+
+__global__ __launch_bounds__(256) void rle_final_kernel(const DetJob *__restrict__ jobs, const RleJob *__restrict__ rjobs) {
+    const DetJob J = jobs[blockIdx.y];
+    const int d = blockIdx.x * 256 + threadIdx.x;
+    if (d >= J.n_det) return;
+    const RleJob R = rjobs[blockIdx.y];
+    const int area = J.area[d];
+    J.score[d] = ((double)area < J.min_area) ? 0.f : __int_as_float(J.score_bits[d]);   // det_final_kernel's rule
+    R.area_out[d] = area;
+    R.n_runs_out[d] = R.runs[d];
+    const int x0 = R.x0[d], y0 = R.y0[d];
+    int32_t *b = R.bbox_out + 4 * (long)d;
+    b[0] = x0, b[1] = y0, b[2] = R.x1[d] - x0 + 1, b[3] = R.y1[d] - y0 + 1;   // every detection has a pixel
+}
+
+__global__ __launch_bounds__(256) void rle_runs_kernel(const unsigned long long *__restrict__ keys, long long n,
+                                                       uint32_t *__restrict__ counts) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n) return;
+    const unsigned long long k = keys[t];
+    unsigned prev = 0;
+    if (t > 0) {
+        const unsigned long long q = keys[t - 1];
+        if ((q >> 32) == (k >> 32)) prev = (unsigned)q;
+    }
+    counts[t] = (unsigned)k - prev;
+}
+
+// scratch of the rle entries: [cursor int32 x n_images], then per image [idmap npx] and [x0 x1 y0 y1 runs] x n_det int32
+// (each block 256-byte aligned)
+size_t rle_image_bytes(int h, int w, int n_det) {
+    return round_up(4 * (size_t)h * w, 256) + 5 * round_up(4 * (size_t)n_det, 256);
+}
+
+bool rle_shapes_ok(int n_images, const int32_t *h, const int32_t *w, const int32_t *n_det, long long *total_det) {
+    if (n_images < 0 || (n_images > 0 && (!h || !w || !n_det))) return false;
+    long long g = 0;
+    for (int i = 0; i < n_images; ++i) {
+        if (h[i] < 1 || w[i] < 1 || (long long)h[i] * w[i] > (1LL << 30)) return false;   // as irn_detect_instance_batch_count
+        if (n_det[i] < 0 || n_det[i] > (long long)h[i] * w[i]) return false;
+        g += n_det[i];
+    }
+    if (g > INT_MAX) return false;
+    *total_det = g;
+    return true;
+}
+
+void rle_carve(std::vector<RleJob> &jobs, void *scratch, int n_images, const int32_t *h, const int32_t *w,
+               const int32_t *n_det) {
+    jobs.assign(n_images, RleJob{});
+    char *s = (char *)scratch + round_up(4 * (size_t)n_images, 256);
+    int g = 0;
+    for (int i = 0; i < n_images; ++i) {
+        RleJob &R = jobs[i];
+        const size_t a = round_up(4 * (size_t)n_det[i], 256);
+        R.idmap = (int *)s;
+        char *t = s + round_up(4 * (size_t)h[i] * w[i], 256);
+        R.x0 = (int *)t, R.x1 = (int *)(t + a), R.y0 = (int *)(t + 2 * a), R.y1 = (int *)(t + 3 * a), R.runs = (int *)(t + 4 * a);
+        R.cursor = (unsigned *)scratch + i;
+        R.g0 = g;
+        R.h = h[i], R.w = w[i], R.n_det = n_det[i];
+        g += n_det[i];
+        s += rle_image_bytes(h[i], w[i], n_det[i]);
+    }
+}
+
+// the sort looks at the position's 32 bits and at as many bits above them as the batch's detection indices need
+unsigned rle_key_bits(int total_det) {
+    unsigned bits = 33;
+    while (bits < 64 && ((long long)total_det - 1) >> (bits - 32)) ++bits;
+    return bits;
+}
+
+}  // namespace
+
+extern "C" size_t irn_detect_instance_batch_rle_scratch_bytes(int n_images, const int32_t *h, const int32_t *w,
+                                                              const int32_t *n_det) {
+    long long g = 0;
+    if (!rle_shapes_ok(n_images, h, w, n_det, &g)) {
+        fail(IRN_ERR_ARG, "irn_detect_instance_batch_rle_scratch_bytes: bad argument (n_images >= 0, 1 <= h*w <= 2^30, "
+                          "0 <= n_det <= h*w, no null pointer)");
+        return 0;
+    }
+    if (n_images == 0) return 0;
+    size_t total = round_up(4 * (size_t)n_images, 256);
+    for (int i = 0; i < n_images; ++i) total += rle_image_bytes(h[i], w[i], n_det[i]);
+    return total;
+}
+
+extern "C" int irn_detect_instance_batch_rle_count(int n_images, const float *const *rw_up_dev,
+                                                   const int32_t *const *argmax_dev, const int32_t *n_channels,
+                                                   const int32_t *h, const int32_t *w, const int32_t *n_det,
+                                                   const double *min_area, float *score_dev, int32_t *channel_dev,
+                                                   int32_t *area_dev, int32_t *n_runs_dev, int32_t *bbox_dev,
+                                                   void *scratch_dev, void *rle_scratch_dev, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const char *who = "irn_detect_instance_batch_rle_count";
+    long long g = 0;
+    if (!rle_shapes_ok(n_images, h, w, n_det, &g))
+        return fail(IRN_ERR_ARG, "%s: bad argument (n_images >= 0, 1 <= h*w <= 2^30 < 2^31 - 1, 0 <= n_det <= h*w, no null pointer)", who);
+    if (n_images == 0) return IRN_OK;
+    if (!min_area || !rle_scratch_dev) return fail(IRN_ERR_ARG, "%s: null argument", who);
+    std::vector<DetJob> jobs;
+    int max_n = 0;
+    int rc = det_fill_jobs(who, n_images, rw_up_dev, argmax_dev, n_channels, h, w, scratch_dev, jobs, &max_n);
+    if (rc) return rc;
+    if (g == 0) return IRN_OK;
+    if (!score_dev || !channel_dev || !area_dev || !n_runs_dev || !bbox_dev) return fail(IRN_ERR_ARG, "%s: null output", who);
+    std::vector<RleJob> rjobs;
+    rle_carve(rjobs, rle_scratch_dev, n_images, h, w, n_det);
+    int max_det = 0;
+    for (int i = 0; i < n_images; ++i) {
+        DetJob &J = jobs[i];
+        RleJob &R = rjobs[i];
+        J.n_det = n_det[i];
+        J.min_area = min_area[i];
+        J.score = score_dev + R.g0;
+        J.channel = channel_dev + R.g0;
+        R.area_out = area_dev + R.g0;
+        R.n_runs_out = n_runs_dev + R.g0;
+        R.bbox_out = bbox_dev + 4 * (size_t)R.g0;
+        max_det = std::max(max_det, J.n_det);
+    }
+    // both job tables in ONE upload (a scratch slot is released once)
+    const size_t det_bytes = round_up(sizeof(DetJob) * n_images, 16);
+    std::vector<char> blob(det_bytes + sizeof(RleJob) * n_images);
+    memcpy(blob.data(), jobs.data(), sizeof(DetJob) * n_images);
+    memcpy(blob.data() + det_bytes, rjobs.data(), sizeof(RleJob) * n_images);
+    char *bd = nullptr;
+    rc = scratch_upload(blob.data(), blob.size(), (void **)&bd, stream);
+    if (rc) return rc;
+    const DetJob *jd = (const DetJob *)bd;
+    const RleJob *rd = (const RleJob *)(bd + det_bytes);
+    const dim3 per_det(cdiv(max_det, 256), n_images), per_px(cdiv(max_n, 256), n_images);
+    hipLaunchKernelGGL(det_order_kernel, per_det, dim3(256), 0, stream, jd);
+    IRN_LAUNCH_CHECK("det_order_kernel");
+    hipLaunchKernelGGL(rle_init_kernel, per_det, dim3(256), 0, stream, rd);
+    IRN_LAUNCH_CHECK("rle_init_kernel");
+    hipLaunchKernelGGL(rle_map_kernel, per_px, dim3(256), 0, stream, jd, rd);
+    IRN_LAUNCH_CHECK("rle_map_kernel");
+    hipLaunchKernelGGL(rle_events_kernel<false>, per_px, dim3(256), 0, stream, rd);
+    IRN_LAUNCH_CHECK("rle_events_kernel<count>");
+    hipLaunchKernelGGL(rle_final_kernel, per_det, dim3(256), 0, stream, jd, rd);
+    IRN_LAUNCH_CHECK("rle_final_kernel");
+    return scratch_release(stream);
+}
+
+extern "C" size_t irn_detect_instance_batch_rle_sort_bytes(int64_t total_runs, int total_det) {
+    if (total_runs < 0 || total_runs >= (long long)UINT_MAX || total_det < 0 || total_det > total_runs) {
+        fail(IRN_ERR_ARG, "irn_detect_instance_batch_rle_sort_bytes: bad argument (0 <= total_det <= total_runs < 2^32 - 1)");
+        return 0;
+    }
+    if (total_runs == 0) return 0;
+    size_t tmp = 0;
+    (void)rocprim::radix_sort_keys(nullptr, tmp, (unsigned long long *)nullptr, (unsigned long long *)nullptr,
+                                   (unsigned)total_runs, 0u, rle_key_bits(total_det), (hipStream_t)0);
+    return 2 * round_up(8 * (size_t)total_runs, 256) + round_up(tmp, 256);
+}
+
+extern "C" int irn_detect_instance_batch_rle_emit(int n_images, const int32_t *h, const int32_t *w, const int32_t *n_det,
+                                                  const int64_t *runs, uint32_t *counts_dev, void *rle_scratch_dev,
+                                                  void *ws, size_t ws_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const char *who = "irn_detect_instance_batch_rle_emit";
+    long long g = 0;
+    if (!rle_shapes_ok(n_images, h, w, n_det, &g))
+        return fail(IRN_ERR_ARG, "%s: bad argument (n_images >= 0, 1 <= h*w <= 2^30 < 2^31 - 1, 0 <= n_det <= h*w, no null pointer)", who);
+    if (n_images == 0) return IRN_OK;
+    if (!runs) return fail(IRN_ERR_ARG, "%s: null runs", who);
+    long long total = 0;
+    int max_n = 0;
+    for (int i = 0; i < n_images; ++i) {
+        // every detection has at least its first event and the map's end; a map of npx pixels has at most 2*npx events
+        if (runs[i] < 2LL * n_det[i] || runs[i] > 2LL * h[i] * w[i] + n_det[i])
+            return fail(IRN_ERR_ARG, "%s: image %d: %lld runs for %d detections", who, i, (long long)runs[i], n_det[i]);
+        total += runs[i];
+        if (n_det[i] > 0) max_n = std::max(max_n, h[i] * w[i]);
+    }
+    if (total >= (long long)UINT_MAX) return fail(IRN_ERR_ARG, "%s: %lld runs in one batch", who, total);
+    if (total == 0) return IRN_OK;
+    if (!counts_dev || !rle_scratch_dev || !ws) return fail(IRN_ERR_ARG, "%s: null argument", who);
+    const size_t need = irn_detect_instance_batch_rle_sort_bytes(total, (int)g);
+    if (ws_bytes < need) return fail(IRN_ERR_ARG, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, need);
+    const size_t kb = round_up(8 * (size_t)total, 256);
+    unsigned long long *keys_in = (unsigned long long *)ws, *keys_out = (unsigned long long *)((char *)ws + kb);
+    void *tmp = (char *)ws + 2 * kb;
+    size_t tmp_bytes = need - 2 * kb;
+    std::vector<RleJob> rjobs;
+    rle_carve(rjobs, rle_scratch_dev, n_images, h, w, n_det);
+    long long at = 0;
+    for (int i = 0; i < n_images; ++i) {
+        rjobs[i].keys = keys_in + at;
+        rjobs[i].room = (int)std::min<long long>(runs[i], INT_MAX);
+        at += runs[i];
+    }
+    RleJob *rd = nullptr;
+    int rc = scratch_upload(rjobs.data(), sizeof(RleJob) * n_images, (void **)&rd, stream);
+    if (rc) return rc;
+    IRN_HIP_TRY(hipMemsetAsync(rle_scratch_dev, 0, sizeof(int) * n_images, stream));       // the cursors
+    hipLaunchKernelGGL(rle_events_kernel<true>, dim3(cdiv(max_n, 256), n_images), dim3(256), 0, stream, rd);
+    IRN_LAUNCH_CHECK("rle_events_kernel<emit>");
+    IRN_HIP_TRY(rocprim::radix_sort_keys(tmp, tmp_bytes, keys_in, keys_out, (unsigned)total, 0u, rle_key_bits((int)g), stream));
+    hipLaunchKernelGGL(rle_runs_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, keys_out, total, counts_dev);
+    IRN_LAUNCH_CHECK("rle_runs_kernel");
     return scratch_release(stream);
 }
 

@@ -12,6 +12,7 @@ Reference functions mirrored (names kept where the reference has one):
     msf_pack(img, scales)       = voc12/dataloader.py:191-201 (rescale, normalise, CHW, flip pair)
 GPU tensors in, GPU tensors out; no CPU fallback.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -442,16 +443,14 @@ def _copy_stream(dev):
     return _COPY_STREAMS[key]
 
 
-def detect_instance_batch(rw_ups, argmaxes, class_ids, n_channels, max_fragment_sizes, timings=None, deferred=False):
-    """detect_instance for a batch of images with two host round trips in total (the per-image form has three per
-    image): one 4-byte-per-image transfer of the detection counts, one packed transfer of every image's
-    {score, channel, masks} (irn_detect_instance_batch_count / _emit).  Arguments are lists (one entry per image) of
-    what `detect_instance` takes.  Returns a list with, per image, the reference's numpy dict or — for an image without
-    any foreground pixel — the ValueError `detect_instance` would raise.  With `deferred=True` the packed transfer is
-    left in flight on a copy stream and a `PendingDetections` is returned: call its `result()` after the next batch has
-    been enqueued and the 2 MB of masks per image cross PCIe under that batch's kernels."""
-    import time
-    t_start = time.perf_counter()
+class _DetCount(collections.namedtuple("_DetCount", "n dev hs ws cs_a hs_a ws_a sc_p am_p keep scratch nds")):
+    """What the emit entries take after the labelling half of a batched detection: sizes (lists and int32 arrays), the input
+    pointer arrays (`keep` holds the converted inputs alive), the detect scratch and the detection counts."""
+
+
+def _detect_batch_count(rw_ups, argmaxes, n_channels):
+    """The labelling half of a batched detection (irn_detect_instance_batch_count) and its one read-back, the detection
+    counts.  -> _DetCount"""
     n = len(rw_ups)
     dev = rw_ups[0].device
     scs, ams, hs, ws = [], [], [], []
@@ -472,6 +471,23 @@ def detect_instance_batch(rw_ups, argmaxes, class_ids, n_channels, max_fragment_
         check(lib.irn_detect_instance_batch_count(n, sc_p, am_p, cs_a, hs_a, ws_a, n_det_dev.data_ptr(),
                                                   scratch.data_ptr(), _stream()))
         nds = [int(v) for v in n_det_dev.cpu().tolist()]                       # host round trip 1
+    return _DetCount(n, dev, hs, ws, cs_a, hs_a, ws_a, sc_p, am_p, (scs, ams), scratch, nds)
+
+
+def detect_instance_batch(rw_ups, argmaxes, class_ids, n_channels, max_fragment_sizes, timings=None, deferred=False):
+    """detect_instance for a batch of images with two host round trips in total (the per-image form has three per
+    image): one 4-byte-per-image transfer of the detection counts, one packed transfer of every image's
+    {score, channel, masks} (irn_detect_instance_batch_count / _emit).  Arguments are lists (one entry per image) of
+    what `detect_instance` takes.  Returns a list with, per image, the reference's numpy dict or — for an image without
+    any foreground pixel — the ValueError `detect_instance` would raise.  With `deferred=True` the packed transfer is
+    left in flight on a copy stream and a `PendingDetections` is returned: call its `result()` after the next batch has
+    been enqueued and the 2 MB of masks per image cross PCIe under that batch's kernels."""
+    import time
+    t_start = time.perf_counter()
+    dc = _detect_batch_count(rw_ups, argmaxes, n_channels)
+    n, dev, hs, ws, nds, scratch = dc.n, dc.dev, dc.hs, dc.ws, dc.nds, dc.scratch
+    cs_a, hs_a, ws_a, sc_p, am_p = dc.cs_a, dc.hs_a, dc.ws_a, dc.sc_p, dc.am_p
+    with torch.cuda.device(dev):
         t_count = time.perf_counter()
         if timings is not None:          # seconds: labelling + count transfer
             timings["count"] = timings.get("count", 0.0) + t_count - t_start
@@ -515,6 +531,121 @@ def detect_instance_batch(rw_ups, argmaxes, class_ids, n_channels, max_fragment_
     if timings is not None:
         timings["bytes"] = timings.get("bytes", 0) + total
     pending = PendingDetections(n, host, done, nds, offs, hs, ws, class_ids, timings, t_count)
+    return pending if deferred else pending.result()
+
+
+class PendingRleDetections:
+    """`detect_instance_rle_batch(..., deferred=True)`: the run lengths of a batch may still be crossing to the host on the
+    copy stream; `result()` waits for them and returns the list `detect_instance_rle_batch` returns."""
+
+    def __init__(self, n, head, host, done, nds, hs, ws, class_ids, timings, t_emit):
+        self._n, self._head, self._host, self._done, self._nds = n, head, host, done, nds
+        self._hs, self._ws, self._class_ids, self._timings, self._t_emit = hs, ws, class_ids, timings, t_emit
+        self._out = None
+
+    def result(self):
+        if self._out is not None:
+            return self._out
+        import time
+        nothing = "detect_instance: no foreground pixel in any channel"
+        if self._host is None:                      # no foreground pixel in any image of the batch
+            self._out = [ValueError(nothing) for _ in range(self._n)]
+            return self._out
+        self._done.synchronize()                                                   # host round trip 3
+        t_done = time.perf_counter()
+        score, chan, area, n_runs, bbox = self._head
+        counts = self._host.numpy().view(np.uint32)
+        out, g, at = [], 0, 0
+        for i in range(self._n):
+            nd = self._nds[i]
+            if nd == 0:
+                out.append(ValueError(nothing))
+                continue
+            offsets = np.zeros(nd + 1, np.int64)
+            np.cumsum(n_runs[g:g + nd], out=offsets[1:])
+            total = int(offsets[nd])
+            out.append({"score": score[g:g + nd], "class": np.asarray(self._class_ids[i])[chan[g:g + nd]],
+                        "size": (self._hs[i], self._ws[i]), "counts": counts[at:at + total], "offsets": offsets,
+                        "area": area[g:g + nd].astype(np.int64), "bbox": bbox[g:g + nd]})
+            g += nd
+            at += total
+        if self._timings is not None:
+            self._timings["emit_d2h"] = self._timings.get("emit_d2h", 0.0) + t_done - self._t_emit
+            self._timings["unpack"] = self._timings.get("unpack", 0.0) + time.perf_counter() - t_done
+        self._out = out
+        return out
+
+
+def detect_instance_rle_batch(rw_ups, argmaxes, class_ids, n_channels, max_fragment_sizes, timings=None, deferred=False):
+    """`detect_instance_batch` with every mask as its COCO run-length code instead of a dense plane
+    (irn_detect_instance_batch_rle_count / _emit): same arguments, same detections in the same order.  Returns per image
+    {"score" f32 [N], "class" i64 [N], "size" (H, W), "counts" u32 [total], "offsets" i64 [N+1], "area" i64 [N], "bbox"
+    i32 [N,4]} — detection d's run lengths are counts[offsets[d]:offsets[d+1]], exactly what
+    `mask_rle(detect_instance_batch(...)["mask"])` gives — or the ValueError of an image without a foreground pixel.
+    No [N,H,W] block exists on either side of PCIe.  Three host round trips per batch, one more than the dense form: the
+    detection counts; then score, channel, area, n_runs and bbox of every detection (32 bytes each — the added read-back:
+    the number of run lengths depends on the data and sizes the last transfer); then the run lengths.  `deferred=True`
+    leaves that last transfer in flight on the copy stream and returns a `PendingRleDetections`.  `timings["bytes"]`
+    counts the device-to-host bytes of all three."""
+    import time
+    t_start = time.perf_counter()
+    dc = _detect_batch_count(rw_ups, argmaxes, n_channels)
+    n, dev, hs, ws, nds, scratch = dc.n, dc.dev, dc.hs, dc.ws, dc.nds, dc.scratch
+    cs_a, hs_a, ws_a, sc_p, am_p = dc.cs_a, dc.hs_a, dc.ws_a, dc.sc_p, dc.am_p
+    t_count = time.perf_counter()
+    if timings is not None:
+        timings["count"] = timings.get("count", 0.0) + t_count - t_start
+    G = sum(nds)
+    if G == 0:
+        pending = PendingRleDetections(n, None, None, None, nds, hs, ws, class_ids, timings, t_count)
+        return pending if deferred else pending.result()
+    nd_a = i32_array(nds)
+    with torch.cuda.device(dev):
+        rle_scratch = _cached("det_rle_scratch", dev, lib.irn_detect_instance_batch_rle_scratch_bytes(n, hs_a, ws_a, nd_a),
+                              torch.uint8)
+        # score fp32 [G] | channel int32 [G] | area int32 [G] | n_runs int32 [G] | bbox int32 [G][4]
+        head_dev = _cached("det_rle_head", dev, 32 * G, torch.uint8)
+        base = head_dev.data_ptr()
+        check(lib.irn_detect_instance_batch_rle_count(
+            n, sc_p, am_p, cs_a, hs_a, ws_a, nd_a, (C.c_double * n)(*[float(v) for v in max_fragment_sizes]),
+            base, base + 4 * G, base + 8 * G, base + 12 * G, base + 16 * G, scratch.data_ptr(), rle_scratch.data_ptr(),
+            _stream()))
+        head_host = torch.empty(32 * G, dtype=torch.uint8, pin_memory=True)
+        head_host.copy_(head_dev[:32 * G], non_blocking=True)
+        torch.cuda.current_stream().synchronize()                                  # host round trip 2
+        raw = head_host.numpy()
+        head = (raw[:4 * G].view(np.float32), raw[4 * G:8 * G].view(np.int32), raw[8 * G:12 * G].view(np.int32),
+                raw[12 * G:16 * G].view(np.int32), raw[16 * G:].view(np.int32).reshape(G, 4))
+        runs, g = [], 0
+        for nd in nds:
+            runs.append(int(head[3][g:g + nd].sum(dtype=np.int64)))
+            g += nd
+        total = sum(runs)
+        ws_bytes = lib.irn_detect_instance_batch_rle_sort_bytes(total, G)
+        if ws_bytes == 0:
+            check(1)
+        sort_ws = _cached("det_rle_sort", dev, ws_bytes, torch.uint8)
+        counts_dev = (torch.empty(4 * total, dtype=torch.uint8, device=dev) if deferred
+                      else _cached("det_rle_counts", dev, 4 * total, torch.uint8))
+        check(lib.irn_detect_instance_batch_rle_emit(n, hs_a, ws_a, nd_a, (C.c_int64 * n)(*runs), counts_dev.data_ptr(),
+                                                     rle_scratch.data_ptr(), sort_ws.data_ptr(), ws_bytes, _stream()))
+        host = torch.empty(4 * total, dtype=torch.uint8, pin_memory=True)
+        done = torch.cuda.Event()
+        if deferred:
+            side, cur = _copy_stream(dev), torch.cuda.current_stream()
+            emitted = torch.cuda.Event()
+            emitted.record(cur)
+            side.wait_event(emitted)
+            with torch.cuda.stream(side):
+                host.copy_(counts_dev[:4 * total], non_blocking=True)
+                done.record(side)
+            counts_dev.record_stream(side)
+        else:
+            host.copy_(counts_dev[:4 * total], non_blocking=True)
+            done.record(torch.cuda.current_stream())
+    if timings is not None:
+        timings["bytes"] = timings.get("bytes", 0) + 4 * n + 32 * G + 4 * total
+    pending = PendingRleDetections(n, head, host, done, nds, hs, ws, class_ids, timings, t_count)
     return pending if deferred else pending.result()
 
 

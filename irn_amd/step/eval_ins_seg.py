@@ -1,7 +1,8 @@
 """Instance-segmentation evaluation step — drop-in for reference step/eval_ins_seg.py (`run(args)`).
 
 Reads  args.voc12_root (ImageSets/Segmentation/<args.chainer_eval_set>.txt, SegmentationObject/<id>.png,
-       SegmentationClass/<id>.png), args.ins_seg_out_dir/<id>.npy ({'score', 'mask', 'class'} of make_ins_seg_labels)
+       SegmentationClass/<id>.png), args.ins_seg_out_dir/<id>.npy ({'score', 'mask', 'class'} of make_ins_seg_labels), or —
+       when that file does not exist — <id>.rle.npz (its --ins_seg_format rle), decoded to masks on the host
 Prints 0.5iou: {'ap': ..., 'map': ...} as the reference does; returns the dict.
 
 Per image the device counts |mask & instance|, |mask| and |instance| for every predicted mask and GT instance
@@ -19,13 +20,29 @@ from ..voc12 import eval_data
 from . import _eval
 
 
+def load_rle(path):
+    """An <id>.rle.npz of make_ins_seg_labels as the {'score', 'mask', 'class'} dict of its <id>.npy."""
+    with np.load(path, allow_pickle=False) as z:
+        h, w = (int(v) for v in z["size"])
+        counts, offsets = z["counts"], z["offsets"]
+        if len(offsets) != len(z["class"]) + 1:
+            raise ValueError("%d offsets for %d classes" % (len(offsets), len(z["class"])))
+        masks = [ops.rle_decode(counts[offsets[i]:offsets[i + 1]], h, w) for i in range(len(offsets) - 1)]
+        return {"score": z["score"], "class": z["class"], "mask": np.stack(masks) if masks else np.zeros((0, h, w), bool)}
+
+
 def run(args):
     ids = eval_data.seg_ids(args.voc12_root, args.chainer_eval_set)
     dev = _eval.device()
 
     def load(id):
         inst_map, inst_class = eval_data.instance_label(args.voc12_root, id)
-        det = np.load(os.path.join(args.ins_seg_out_dir, id + ".npy"), allow_pickle=True).item()
+        path = os.path.join(args.ins_seg_out_dir, id + ".npy")
+        rle_path = os.path.join(args.ins_seg_out_dir, id + ".rle.npz")
+        if not os.path.exists(path) and os.path.exists(rle_path):
+            det = load_rle(rle_path)
+        else:
+            det = np.load(path, allow_pickle=True).item()
         cls, score = np.asarray(det["class"]).reshape(-1), np.asarray(det["score"]).reshape(-1)
         mask = np.asarray(det["mask"])
         if mask.size == 0 and len(cls) == 0:

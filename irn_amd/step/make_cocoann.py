@@ -1,7 +1,8 @@
 """COCO export of the instance pseudo-labels — counterpart of reference step/make_cocoann.py (`run(args)`).
 
 Reads  args.infer_list (image names, in list order), args.voc12_root/JPEGImages/<name>.jpg (header only: the size),
-       args.ins_seg_out_dir/<name>.npy ({'score', 'mask', 'class'} of make_ins_seg_labels)
+       args.ins_seg_out_dir/<name>.npy ({'score', 'mask', 'class'} of make_ins_seg_labels), or — when that file does not
+       exist — <name>.rle.npz (its --ins_seg_format rle: the masks as run lengths, with area and bbox)
 Writes args.cocoann_out: {"images", "annotations", "categories", "type": "instances"}, what a Mask R-CNN trainer reads.
 Prints and returns {"images", "annotations", "skipped_low_score", "without_detections"}.
 
@@ -9,7 +10,8 @@ Per image the kept masks go to the device once and come back as run lengths, are
 irn_amd/csrc/cocomask.hip); COCO's string form of the run lengths is made on the host.  A detection with score < 1e-5 is
 skipped before the upload (step/make_cocoann.py:39).  make_ins_seg_labels writes no file for an image without
 detections: such an image keeps its image entry, gets no annotation, and is counted.  A mask whose shape is not the
-JPEG's (height, width) is an error that names the image.
+JPEG's (height, width) is an error that names the image.  An .rle.npz record already holds what the annotations need:
+`rle_record_annotations` builds them on the host, with no upload and no kernel.
 
 Image entries carry id, file_name, width and height.  pycococreatortools also writes date_captured (the wall clock),
 license, coco_url and flickr_url; they are left out so that the same inputs always give the same file.
@@ -45,6 +47,59 @@ def categories():
     return [{"supercategory": "none", "id": i + 1, "name": name} for i, name in enumerate(CATEGORIES)]
 
 
+def annotation(ann_id, img_id, cls, area, bbox, height, width, counts):
+    return {"id": ann_id, "image_id": img_id, "category_id": int(cls) + 1, "iscrowd": 0, "area": int(area),
+            "bbox": [float(v) for v in bbox], "segmentation": {"size": [height, width], "counts": ops.rle_to_string(counts)},
+            "width": width, "height": height}
+
+
+def rle_record_kept(rec, height, width, name=None):
+    """One <name>.rle.npz record (a mapping with the arrays `ops.detect_instance_rle_batch` returns), checked against a
+    JPEG of height x width.  -> {"class" int64 [K], "counts" int64 [total], "offsets" int64 [K+1], "area" int64 [K], "bbox"
+    int32 [K,4]} of the K detections that stay (score >= MIN_SCORE), "low" (the number dropped) and "n" (all of them).
+    Needs no device.  Errors name the image when `name` is given."""
+    cls, score = np.asarray(rec["class"]).reshape(-1).astype(np.int64), np.asarray(rec["score"]).reshape(-1)
+    counts, offsets = np.asarray(rec["counts"]).reshape(-1).astype(np.int64), np.asarray(rec["offsets"]).reshape(-1).astype(np.int64)
+    area, bbox = np.asarray(rec["area"]).reshape(-1).astype(np.int64), np.asarray(rec["bbox"]).reshape(-1, 4).astype(np.int32)
+    size = tuple(int(v) for v in np.asarray(rec["size"]).reshape(-1))
+    n = len(cls)
+    who = "%s: " % name if name else ""
+    if not (len(score) == n and len(offsets) == n + 1 and len(area) == n and len(bbox) == n):
+        raise ValueError("%s%d classes, %d scores, %d offsets, %d areas, %d boxes" % (who, n, len(score), len(offsets),
+                                                                                       len(area), len(bbox)))
+    if size != (height, width):
+        raise ValueError("%srun lengths of size %s do not match the %dx%d (height x width) JPEG" % (who, size, height, width))
+    if offsets[0] != 0 or (np.diff(offsets) < 1).any() or offsets[n] != len(counts):
+        raise ValueError("%soffsets do not partition the %d run lengths" % (who, len(counts)))
+    if n and (cls.min() < 0 or cls.max() >= len(CATEGORIES)):
+        raise ValueError("%sclass outside 0..%d" % (who, len(CATEGORIES) - 1))
+    keep = np.flatnonzero(~(score < MIN_SCORE))
+    parts = [counts[offsets[i]:offsets[i + 1]] for i in keep]
+    for i, c in zip(keep, parts):
+        if int(c.sum()) != height * width:
+            raise ValueError("%sthe run lengths of detection %d sum to %d, the image has %d pixels"
+                             % (who, i, int(c.sum()), height * width))
+    kept_offsets = np.zeros(len(keep) + 1, np.int64)
+    np.cumsum([len(c) for c in parts], out=kept_offsets[1:])
+    return {"class": cls[keep], "counts": np.concatenate(parts) if parts else np.zeros(0, np.int64), "offsets": kept_offsets,
+            "area": area[keep], "bbox": bbox[keep], "low": n - len(keep), "n": n}
+
+
+def annotations(kept, img_id, height, width, first_id):
+    """The annotation dicts of one image from per-detection class, area, bbox and run lengths (counts / offsets) — from the
+    device's encoder for dense masks, from `rle_record_kept` for a stored record."""
+    cls, counts, offsets = kept["class"], kept["counts"], kept["offsets"]
+    return [annotation(first_id + i, img_id, cls[i], kept["area"][i], kept["bbox"][i], height, width,
+                       counts[offsets[i]:offsets[i + 1]]) for i in range(len(cls))]
+
+
+def rle_record_annotations(rec, img_id, height, width, first_id, name=None):
+    """The annotations of one <name>.rle.npz record for a JPEG of height x width: exactly what the dense masks of the same
+    detections give.  Needs no device.  -> (annotations with ids first_id, first_id + 1, ..., number of detections dropped)."""
+    kept = rle_record_kept(rec, height, width, name)
+    return annotations(kept, img_id, height, width, first_id), kept["low"]
+
+
 def run(args):
     names = [dataloader.decode_int_filename(v) for v in dataloader.load_img_name_list(args.infer_list)]
     dev = _eval.device()
@@ -55,6 +110,13 @@ def run(args):
         path = os.path.join(args.ins_seg_out_dir, name + ".npy")
         mask, cls, low = np.zeros((0, height, width), bool), np.zeros(0, np.int64), 0
         found = os.path.exists(path)
+        rle_path = os.path.join(args.ins_seg_out_dir, name + ".rle.npz")
+        if not found and os.path.exists(rle_path):
+            with np.load(rle_path, allow_pickle=False) as z:
+                kept = rle_record_kept(z, height, width)               # (the loader names the image of an error)
+            return {"rle": np.int64(1), "class": kept["class"], "counts": kept["counts"], "offsets": kept["offsets"],
+                    "area": kept["area"], "bbox": kept["bbox"], "size": np.int64([height, width]),
+                    "low": np.int64(kept["low"]), "found": np.int64(kept["n"] > 0)}
         if found:
             det = np.load(path, allow_pickle=True).item()
             cls, score = np.asarray(det["class"]).reshape(-1).astype(np.int64), np.asarray(det["score"]).reshape(-1)
@@ -72,7 +134,7 @@ def run(args):
                 low = int(len(cls) - keep.sum())
                 mask, cls = m[keep], cls[keep]
         return {"mask": np.ascontiguousarray(mask), "class": cls, "size": np.int64([height, width]),
-                "low": np.int64(low), "found": np.int64(found)}
+                "low": np.int64(low), "found": np.int64(found), "rle": np.int64(0)}
 
     out = {"images": [], "annotations": [], "categories": categories(), "type": "instances"}
     stats = {"images": 0, "annotations": 0, "skipped_low_score": 0, "without_detections": 0}
@@ -87,13 +149,12 @@ def run(args):
                 stats["without_detections"] += 1
             if len(cls) == 0:
                 continue
-            counts, offsets, area, bbox = ops.mask_rle(it["mask"].to(dev, non_blocking=True))
-            for i in range(len(cls)):
-                out["annotations"].append({
-                    "id": len(out["annotations"]) + 1, "image_id": img_id, "category_id": int(cls[i]) + 1, "iscrowd": 0,
-                    "area": int(area[i]), "bbox": [float(v) for v in bbox[i]],
-                    "segmentation": {"size": [height, width], "counts": ops.rle_to_string(counts[offsets[i]:offsets[i + 1]])},
-                    "width": width, "height": height})
+            if int(it["rle"]):          # an .rle.npz record holds what the encoder would compute: no upload, no kernel
+                kept = {k: it[k].numpy() for k in ("class", "counts", "offsets", "area", "bbox")}
+            else:
+                counts, offsets, area, bbox = ops.mask_rle(it["mask"].to(dev, non_blocking=True))
+                kept = {"class": cls, "counts": counts, "offsets": offsets, "area": area, "bbox": bbox}
+            out["annotations"] += annotations(kept, img_id, height, width, len(out["annotations"]) + 1)
     stats["images"], stats["annotations"] = len(out["images"]), len(out["annotations"])
     with open(args.cocoann_out, "w") as f:
         json.dump(out, f)

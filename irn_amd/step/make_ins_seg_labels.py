@@ -4,6 +4,10 @@ Reads  args.irn_network, args.irn_weights_name, args.infer_list, args.voc12_root
        args.beta, args.exp_times, args.ins_seg_bg_thres, args.num_workers
 Writes args.ins_seg_out_dir/<name>.npy = {'score': float[N], 'mask': bool[N,H,W], 'class': int64[N]}
        (schema consumed by step/make_cocoann.py:34-38 and step/eval_ins_seg.py)
+       or, with args.ins_seg_format == "rle" (not in the reference), args.ins_seg_out_dir/<name>.rle.npz = {'score' f32[N],
+       'class' i64[N], 'size' i64[2] = (H, W), 'counts' u32[total], 'offsets' i64[N+1], 'area' i64[N], 'bbox' i32[N,4]}:
+       detection d's mask as its COCO run lengths counts[offsets[d]:offsets[d+1]] (`ops.detect_instance_rle_batch`; plain
+       arrays, no pickle).  No dense mask is allocated, filled or copied in that mode.
 
 Per image (step/make_ins_seg_labels.py:119-152): EdgeDisplacement forward -> edge, dp; centroid
 refinement, clustering, per-instance CAM split, random walk, label epilogue and the per-mask
@@ -34,9 +38,9 @@ def instance_front(items):
     return ops.cluster_centroids_batch(ops.find_centroids_batch(dps), dps, k_on_device=True)
 
 
-def instance_back(walker, items, front, beta, exp_times, bg_thres, deferred=False):
+def instance_back(walker, items, front, beta, exp_times, bg_thres, deferred=False, fmt="npy", timings=None):
     """Second half: reads the K of `instance_front` (the first host round trip of the batch), then the per-instance CAM split +
-    random walk, the label epilogue and the detections."""
+    random walk, the label epilogue and the detections — with dense masks (`fmt` "npy") or as run lengths ("rle")."""
     cmaps, k_dev = front
     ks = [int(k) for k in k_dev.cpu().tolist()]
     rws = walker([it["edge"] for it in items], [it["cam"] for it in items], beta=beta, exp_times=exp_times,
@@ -48,8 +52,9 @@ def instance_back(walker, items, front, beta, exp_times, bg_thres, deferred=Fals
                                 want_rw_up=True)
     n_ch = [it["cam"].shape[0] * k for it, k in zip(items, ks)]
     class_ids = [np.repeat(np.asarray(torch.as_tensor(it["keys"]).cpu()), k) for it, k in zip(items, ks)]
-    return ops.detect_instance_batch(ep["rw_up"], ep["argmax"], class_ids, n_ch,
-                                     [it["size"][0] * it["size"][1] * 0.01 for it in items], deferred=deferred)
+    detect = {"npy": ops.detect_instance_batch, "rle": ops.detect_instance_rle_batch}[fmt]
+    return detect(ep["rw_up"], ep["argmax"], class_ids, n_ch, [it["size"][0] * it["size"][1] * 0.01 for it in items],
+                  timings=timings, deferred=deferred)
 
 
 def instance_labels_batch(walker, items, beta, exp_times, bg_thres, deferred=False):
@@ -72,12 +77,30 @@ def instance_labels(walker, edge, dp, cams, keys, size, beta, exp_times, bg_thre
     return det
 
 
+def ins_seg_format(args):
+    fmt = getattr(args, "ins_seg_format", "npy")
+    if fmt not in ("npy", "rle"):
+        raise ValueError("ins_seg_format must be npy or rle, got %r" % (fmt,))
+    return fmt
+
+
+def save_rle(path, det):
+    """One image's run-length detections as <name>.rle.npz: the arrays of `ops.detect_instance_rle_batch`, size as int64[2]."""
+    with open(path, "wb") as f:            # an open file: np.savez would append ".npz" to a name
+        np.savez(f, score=det["score"], size=np.asarray(det["size"], np.int64), counts=det["counts"],
+                 offsets=det["offsets"], area=det["area"], bbox=det["bbox"], **{"class": det["class"]})
+
+
 def _write(names, pending, args, writer):
+    rle = ins_seg_format(args) == "rle"
     for name, det in zip(names, pending.result()):
         if isinstance(det, Exception):
             warnings.warn("%s: %s — no file written" % (name, det))
             continue
-        writer.submit(np.save, os.path.join(args.ins_seg_out_dir, name + ".npy"), det)
+        if rle:
+            writer.submit(save_rle, os.path.join(args.ins_seg_out_dir, name + ".rle.npz"), det)
+        else:
+            writer.submit(np.save, os.path.join(args.ins_seg_out_dir, name + ".npy"), det)
 
 
 def _flush(model, walker, pend, args, writer, state):
@@ -92,8 +115,12 @@ def _flush(model, walker, pend, args, writer, state):
     done = None
     if state.get("front") is not None:
         items, front = state["front"]
+        extra = {"fmt": "rle"} if ins_seg_format(args) == "rle" else {}        # the default call is the one it always was
+        if getattr(args, "detect_timings", None) is not None:                   # a caller's dict for the detection calls' `timings`
+            extra["timings"] = args.detect_timings
         done = ([it["name"] for it in items],
-                instance_back(walker, items, front, float(args.beta), int(args.exp_times), float(args.ins_seg_bg_thres), deferred=True))
+                instance_back(walker, items, front, float(args.beta), int(args.exp_times), float(args.ins_seg_bg_thres), deferred=True,
+                              **extra))
         state["front"] = None
     if pend:
         make_sem_seg_labels.edges_for(model, pend, int(getattr(args, "irn_batch", 0) or 8),

@@ -93,6 +93,10 @@ def build_parser():
     p.add_argument("--ir_label_out_dir", default="result/ir_label", type=str)
     p.add_argument("--sem_seg_out_dir", default="result/sem_seg", type=str)
     p.add_argument("--ins_seg_out_dir", default="result/ins_seg", type=str)
+    p.add_argument("--ins_seg_format", default="npy", choices=("npy", "rle"),
+                   help="make_ins_seg_labels: npy = the reference's <name>.npy with dense masks; rle (not in the reference) = "
+                        "<name>.rle.npz with every mask as its COCO run lengths, encoded on the GPU — make_cocoann and "
+                        "eval_ins_seg read either")
     p.add_argument("--cocoann_out", default="voc2012_train_custom.json", type=str,
                    help="make_cocoann: the COCO annotation file it writes (the reference hard-codes this name, step/make_cocoann.py:48)")
     p.add_argument("--edge_out_dir", default=None, type=str,

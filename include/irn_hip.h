@@ -82,6 +82,37 @@ int irn_pair_displacement(const float *disp_dev, int batch, int channels, int hp
 int irn_pair_displacement_backward(const float *grad_out_dev, int batch, int channels, int hp, int wp, int radius,
                                    float *grad_disp_dev, void *stream);
 
+/* Fused affinity / displacement loss of IRNet training (replaces, for the training step, the chain
+ * net/resnet50_irn.py:198-213 + step/train_irn.py:58-64 + voc12/dataloader.py:80-106 without writing any
+ * [batch, |S|, N] tensor).  edge: dev fp32 [batch, hp, wp], already through the sigmoid; dp: dev fp32
+ * [batch, 2, hp, wp]; label: dev uint8 [batch, hp, wp], 0 = background, 1..20 = a class, >= 21 = ignore.
+ * Geometry as irn_edge_to_affinity / irn_pair_displacement: with rf = radius-1, source cell (y, rf+x), y < hp-rf,
+ * x < wp-2rf, pairs with (y+dy_d, rf+x+dx_d).  With a, b the labels of the two cells: valid = a<21 && b<21,
+ * bg = valid && a==b==0, fg = valid && a==b>0, neg = valid && a!=b; aff = 1 - max of edge over path(d);
+ * pd_c = dp_c[src] - dp_c[dst]:
+ *   sums[0] = sum bg * -log(aff+1e-5)        sums[1] = sum fg * -log(aff+1e-5)     sums[2] = sum neg * -log(1+1e-5-aff)
+ *   sums[3] = sum_c sum fg * |pd_c - (dy_d, dx_d)_c|                              sums[4] = sum_c sum bg * |pd_c|
+ *   counts[0..2] = sum bg, sum fg, sum neg (exact)
+ * sums (dev fp64 [5]) and counts (dev int64 [3]) are device memory.  Per-element arithmetic is fp32, accumulation
+ * fp64 through per-workgroup partials in the workspace that a second kernel adds in a fixed order: no float atomics,
+ * the forward is bit-reproducible.
+ * The backward recomputes everything from the three maps.  coef: dev fp32 [5], the upstream gradients of the five
+ * sums (read on the device, nothing synchronises).  With g_aff = -(c0*bg + c1*fg)/(aff+1e-5) + c2*neg/(1+1e-5-aff),
+ * -g_aff goes to the first path cell that attains the maximum (the rule of irn_edge_to_affinity_backward), and
+ * g_c = c3*fg*sgn(pd_c - dst_c) + c4*bg*sgn(pd_c), sgn(0) = 0, is added at the source cell and subtracted at the
+ * destination.  grad_edge [batch, hp, wp] and grad_dp [batch, 2, hp, wp] are fully written (zero where nothing
+ * lands).  The gradients are gathered with float atomics (LDS, then one global atomic per touched cell of a tile):
+ * reproducible to rounding, NOT bit for bit.
+ * ws: irn_aff_loss_workspace_bytes(batch, hp, wp, radius) bytes of device memory (0 = bad geometry); the backward
+ * checks it like the forward and leaves it untouched.  Null pointers, batch outside [1, 65535], radius outside
+ * [2, IRN_MAX_RADIUS] (the path table's range), hp <= rf or wp <= 2 rf give IRN_ERR_ARG, a workspace that is too
+ * small IRN_ERR_STATE, all before any device is touched. */
+size_t irn_aff_loss_workspace_bytes(int batch, int hp, int wp, int radius);
+int irn_aff_loss_forward(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp, int radius,
+                         double *sums, int64_t *counts, void *ws, size_t ws_bytes, void *stream);
+int irn_aff_loss_backward(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp, int radius,
+                          const float *coef, float *grad_edge, float *grad_dp, void *ws, size_t ws_bytes, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Random-walk context  (replaces misc/indexing.py:141-165 `propagate_to_edge` and everything it
  * calls: PathIndex :148, edge_to_affinity :151, affinity_sparse2dense :154, to_transition_matrix

@@ -35,6 +35,9 @@ _SIGS = {
     "irn_edge_to_affinity_backward": (i32, [vp, vp, i32, i32, i32, i32, vp, vp]),
     "irn_pair_displacement": (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
     "irn_pair_displacement_backward": (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
+    "irn_aff_loss_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "irn_aff_loss_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "irn_aff_loss_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "irn_walk_create": (i32, [i32, C.POINTER(vp)]),
     "irn_walk_destroy": (i32, [vp]),
     "irn_walk_configure": (i32, [vp, i32, pi32, pi32, pi32, C.POINTER(sz)]),

@@ -1,5 +1,7 @@
 """Image helpers the hot path needs (API mirror of the corresponding reference misc/imutils.py
-functions; the augmentation / colouring helpers of that file are training-side and out of scope).
+functions; the colouring helpers of that file are out of scope).  The augmentations of the training step
+(`random_scale`, `random_lr_flip`, `random_crop`, `top_left_crop`) take their random source as an argument, a
+`numpy.random.Generator` or a `random.Random`, instead of the reference's global `random` module: a seed fixes a run.
 """
 import numpy as np
 from PIL import Image
@@ -17,6 +19,59 @@ def pil_rescale(img, scale, order):
     """misc/imutils.py:19-22."""
     h, w = img.shape[:2]
     return pil_resize(img, (int(np.round(h * scale)), int(np.round(w * scale))), order)
+
+
+def _uniform(rng):
+    return float(rng.random())
+
+
+def _below(rng, n):
+    """An integer in [0, n) from either kind of random source."""
+    return int(rng.integers(n)) if hasattr(rng, "integers") else rng.randrange(n)
+
+
+def random_scale(pair, scale_range, order, rng):
+    """misc/imutils.py:36-43 for an (image, label) pair: one scale drawn uniformly from `scale_range`, each member
+    rescaled with its own `order` (3 for the image, 0 for the label)."""
+    scale = scale_range[0] + _uniform(rng) * (scale_range[1] - scale_range[0])
+    return tuple(pil_rescale(m, scale, o) for m, o in zip(pair, order))
+
+
+def random_lr_flip(pair, rng):
+    """misc/imutils.py:45-53: with probability 1/2 every member is mirrored left-right."""
+    return tuple(np.fliplr(m) for m in pair) if _below(rng, 2) else tuple(pair)
+
+
+def _crop_box(size, cropsize, rng):
+    """misc/imutils.py:55-78: where an h x w image lands in a cropsize^2 container, per axis: a random window of the image
+    where it is larger, a random offset inside the container where it is smaller.  Returns (container top, left, image top,
+    left, rows, cols).  The horizontal position is drawn first, as in the reference."""
+    h, w = size
+    left = _below(rng, abs(w - cropsize) + 1)
+    top = _below(rng, abs(h - cropsize) + 1)
+    c_left, i_left = (0, left) if w > cropsize else (left, 0)
+    c_top, i_top = (0, top) if h > cropsize else (top, 0)
+    return c_top, c_left, i_top, i_left, min(cropsize, h), min(cropsize, w)
+
+
+def random_crop(pair, cropsize, fill, rng):
+    """misc/imutils.py:80-101: the same random box for every member; what the image does not cover holds the member's
+    fill value ((0, 255) for an image and its label)."""
+    c_top, c_left, i_top, i_left, rows, cols = _crop_box(pair[0].shape[:2], cropsize, rng)
+    out = []
+    for m, f in zip(pair, fill):
+        cont = np.full((cropsize, cropsize) + m.shape[2:], f, m.dtype)
+        cont[c_top:c_top + rows, c_left:c_left + cols] = m[i_top:i_top + rows, i_left:i_left + cols]
+        out.append(cont)
+    return tuple(out)
+
+
+def top_left_crop(img, cropsize, fill):
+    """misc/imutils.py:103-117: the image's top-left cropsize^2 corner in a container of `fill`."""
+    rows, cols = min(cropsize, img.shape[0]), min(cropsize, img.shape[1])
+    cont = np.full((cropsize, cropsize) + img.shape[2:], fill, img.dtype)
+    cont[:rows, :cols] = img[:rows, :cols]
+    return cont
 
 
 def HWC_to_CHW(img):

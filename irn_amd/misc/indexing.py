@@ -9,6 +9,8 @@ Same names, argument meaning and return shapes as the reference:
     to_transition_matrix(affinity_dense, beta, times)    misc/indexing.py:132-139
     propagate_to_edge(x, edge, radius, beta, exp_times)  misc/indexing.py:141-165
 
+and the operators of the training seam (`pair_displacement`, `affinity_displacement_sums`: net/resnet50_irn.py:177-213)
+
 plus the batched form the steps and bench use (``RandomWalk``).  Tensors must live on the GPU; there
 is no CPU implementation here (the CPU restatement is test infrastructure under ``oracle/``).
 """
@@ -193,6 +195,65 @@ def pair_displacement(disp, radius):
     if disp.dim() != 4:
         raise ValueError("pair_displacement: [B, C, Hp, Wp] expected")
     return _PairDisplacement.apply(disp.contiguous().float(), radius)
+
+
+class _AffinityDisplacementSums(torch.autograd.Function):
+    """irn_aff_loss_forward with irn_aff_loss_backward as its vector-Jacobian product.  Saves the three maps and nothing
+    else: the backward recomputes path maxima, pair classes and signs from them."""
+
+    @staticmethod
+    def forward(ctx, edge, dp, label, radius):
+        b, hp, wp = label.shape
+        need = lib.irn_aff_loss_workspace_bytes(b, hp, wp, radius)
+        if need == 0:
+            raise ValueError("affinity_displacement_sums: batch %d, grid %dx%d, radius %d is not a shape the kernel takes"
+                             % (b, hp, wp, radius))
+        ws = torch.empty(need, dtype=torch.uint8, device=edge.device)
+        sums = torch.empty(5, dtype=torch.float64, device=edge.device)
+        counts = torch.empty(3, dtype=torch.int64, device=edge.device)
+        with torch.cuda.device(edge.device):
+            check(lib.irn_aff_loss_forward(edge.data_ptr(), dp.data_ptr(), label.data_ptr(), b, hp, wp, radius,
+                                           sums.data_ptr(), counts.data_ptr(), ws.data_ptr(), need, _stream()))
+        ctx.save_for_backward(edge, dp, label)
+        ctx.geom = (radius, ws)
+        ctx.mark_non_differentiable(counts)
+        return sums, counts
+
+    @staticmethod
+    def backward(ctx, grad_sums, _grad_counts):
+        edge, dp, label = ctx.saved_tensors
+        radius, ws = ctx.geom
+        b, hp, wp = label.shape
+        coef = grad_sums.to(torch.float32).contiguous()          # stays on the device: nothing synchronises
+        grad_edge = torch.empty_like(edge)
+        grad_dp = torch.empty_like(dp)
+        with torch.cuda.device(edge.device):
+            check(lib.irn_aff_loss_backward(edge.data_ptr(), dp.data_ptr(), label.data_ptr(), b, hp, wp, radius,
+                                            coef.data_ptr(), grad_edge.data_ptr(), grad_dp.data_ptr(), ws.data_ptr(),
+                                            ws.numel(), _stream()))
+        return grad_edge, grad_dp, None, None
+
+
+def affinity_displacement_sums(edge, dp, label, radius):
+    """The five sums and three counts that the IRNet training losses are formed from (reference
+    net/resnet50_irn.py:198-213 + step/train_irn.py:58-64 + voc12/dataloader.py:80-106), in one pass over the three maps:
+    no [B, |S|, N] tensor is written, forward or backward (include/irn_hip.h, irn_aff_loss_forward).
+
+    ``edge``: GPU float [B, Hp, Wp] (or [B, 1, Hp, Wp]), already through the sigmoid; ``dp``: GPU float [B, 2, Hp, Wp];
+    ``label``: GPU uint8 [B, Hp, Wp], 0 background, 1..20 a class, >= 21 ignore.  Returns ``(sums, counts)``: fp64 [5]
+    (bg / fg positive-affinity loss, negative-affinity loss, fg / bg displacement loss) and int64 [3] (bg, fg, neg
+    pairs), both on the device.  Differentiable w.r.t. ``edge`` and ``dp``."""
+    _need_cuda(edge, "edge")
+    _need_cuda(dp, "dp")
+    _need_cuda(label, "label")
+    if label.dtype != torch.uint8 or label.dim() != 3:
+        raise ValueError("affinity_displacement_sums: label must be uint8 [B, Hp, Wp]")
+    b, hp, wp = label.shape
+    if edge.numel() != b * hp * wp or tuple(dp.shape) != (b, 2, hp, wp):
+        raise ValueError("affinity_displacement_sums: edge %s and dp %s do not fit label %s"
+                         % (tuple(edge.shape), tuple(dp.shape), tuple(label.shape)))
+    return _AffinityDisplacementSums.apply(edge.reshape(b, hp, wp).contiguous().float(), dp.contiguous().float(),
+                                           label.contiguous(), int(radius))
 
 
 def affinity_sparse2dense(affinity_sparse, ind_from, ind_to, n_vertices):

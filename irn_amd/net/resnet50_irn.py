@@ -2,9 +2,10 @@
 PyTorch-ROCm.  API mirror of reference net/resnet50_irn.py:7-133 (``Net``) and :216-234
 (``EdgeDisplacement``); attribute names reproduce the reference's state-dict keys.
 
-``AffinityDisplacementLoss`` (net/resnet50_irn.py:144-213) is mirrored as the training SEAM only (SURVEY.md §8f
-rank 4): its two gather operators run as differentiable HIP ops (``irn_amd.misc.indexing.edge_to_affinity``,
-``pair_displacement``); the training loop, optimiser and datasets around it are out of scope.
+``AffinityDisplacementLoss`` (net/resnet50_irn.py:144-213): its two gather operators run as differentiable HIP ops
+(``irn_amd.misc.indexing.edge_to_affinity``, ``pair_displacement``) in ``forward``, the composed path; ``fused_losses``
+is what ``irn_amd.step.train_irn`` trains on: the four scalar losses from one fused pass over the boundary,
+displacement and label maps (``indexing.affinity_displacement_sums``).
 """
 import torch
 import torch.nn as nn
@@ -201,3 +202,17 @@ class AffinityDisplacementLoss(Net):
         neg_aff_loss = (-1) * torch.log(1. + 1e-5 - aff)
         pair_disp = self.to_pair_displacement(dp_out)
         return pos_aff_loss, neg_aff_loss, self.to_displacement_loss(pair_disp), torch.abs(pair_disp)
+
+    def fused_losses(self, x, label):
+        """The four scalar losses of a training step (reference step/train_irn.py:58-64: positive affinity, negative
+        affinity, foreground displacement, background displacement) from the images ``x`` and the reduced IR label maps
+        ``label`` (uint8 [B, Hp, Wp]) — `forward(x, True)` followed by the masked sums, without any [B, |S|, N] tensor."""
+        from ..misc import indexing
+        edge_out, dp_out = Net.forward(self, x)
+        s, n = indexing.affinity_displacement_sums(torch.sigmoid(edge_out), dp_out, label, self.path_index.radius)
+        n = n.to(torch.float64)
+        pos_aff_loss = s[0] / (n[0] + 1e-5) / 2 + s[1] / (n[1] + 1e-5) / 2
+        neg_aff_loss = s[2] / (n[2] + 1e-5)
+        dp_fg_loss = s[3] / (2 * n[1] + 1e-5)
+        dp_bg_loss = s[4] / (2 * n[0] + 1e-5)
+        return pos_aff_loss, neg_aff_loss, dp_fg_loss, dp_bg_loss

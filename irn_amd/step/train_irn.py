@@ -1,0 +1,128 @@
+"""IRNet training (reference step/train_irn.py), single GPU, single process.
+
+Reads  args.train_list, args.infer_list, args.voc12_root, args.ir_label_out_dir (the PNGs of cam_to_ir_label),
+       args.irn_crop_size, args.irn_batch_size, args.irn_num_epoches, args.irn_learning_rate, args.irn_weight_decay,
+       args.num_workers, args.seed, args.irn_init_weights
+Writes args.irn_weights_name: the state dict the label steps load (EdgeDisplacement through net.weights.load_checkpoint)
+
+The reference's loop with two differences.  The loss is `AffinityDisplacementLoss.fused_losses`: one HIP pass from the
+boundary, displacement and reduced label maps to the five sums (irn_amd/csrc/aff_loss.hip), so the loader sends one
+uint8 map per image instead of three [|S|, N] float tensors and no [B, |S|, N] tensor exists on the device.  And there is
+no nn.DataParallel: one device.  Initial weights: `--irn_init_weights` (a state dict, loaded non-strictly: an ImageNet
+trunk, or an earlier checkpoint), else the seeded random state of net.weights; nothing is downloaded.
+"""
+import os
+
+import torch
+from torch.utils.data import DataLoader
+
+from ..misc import indexing, pyutils, torchutils
+from ..net import weights
+from ..net.resnet50_irn import AffinityDisplacementLoss
+from ..voc12 import dataloader
+
+MAX_LOADER_WORKERS = 8
+
+
+def build_model(args, path_index):
+    model = AffinityDisplacementLoss(path_index)
+    init = getattr(args, "irn_init_weights", None)
+    if init:
+        state = torch.load(init, map_location="cpu", weights_only=True)
+    else:
+        state = weights.random_irn_state()
+    model.load_state_dict(state, strict=False)
+    return model
+
+
+def _loader(dataset, args, shuffle, seed):
+    gen = torch.Generator().manual_seed(seed)
+    return DataLoader(dataset, batch_size=args.irn_batch_size, shuffle=shuffle, drop_last=True, pin_memory=True,
+                      num_workers=max(0, min(int(args.num_workers), MAX_LOADER_WORKERS)), generator=gen)
+
+
+def train_step(model, optimizer, img, label):
+    """One optimisation step on a batch already on the device; returns the four losses as a device tensor [4]."""
+    parts = model.fused_losses(img, label)
+    pos_aff_loss, neg_aff_loss, dp_fg_loss, dp_bg_loss = parts
+    total_loss = (pos_aff_loss + neg_aff_loss) / 2 + (dp_fg_loss + dp_bg_loss) / 2
+    optimizer.zero_grad()
+    total_loss.backward()
+    optimizer.step()
+    return torch.stack([p.detach() for p in parts])
+
+
+def displacement_mean(model, loader, device):
+    """Mean over the batches of `loader` of the per-batch channel means of the displacement field (step/train_irn.py:97-107)."""
+    means = []
+    with torch.no_grad():
+        for pack in loader:
+            _, dp = model(pack["img"].to(device, non_blocking=True), False)
+            means.append(torch.mean(dp, dim=(0, 2, 3)))
+    if not means:
+        raise RuntimeError("train_irn: infer_list holds fewer images than one batch of %d" % loader.batch_size)
+    return torch.mean(torch.stack(means), dim=0)
+
+
+def run(args):
+    """Returns {'first_losses': [4 floats], 'steps': int}: the losses of the first step and the steps taken."""
+    device = torch.device("cuda", torch.cuda.current_device())
+    seed = int(getattr(args, "seed", 0))
+    torch.manual_seed(seed)
+    grid = args.irn_crop_size // 4
+    path_index = indexing.PathIndex(radius=10, default_size=(grid, grid))
+    model = build_model(args, path_index)
+
+    train_dataset = dataloader.VOC12AffinityDataset(args.train_list, label_dir=args.ir_label_out_dir,
+                                                    voc12_root=args.voc12_root, hor_flip=True,
+                                                    crop_size=args.irn_crop_size, crop_method="random",
+                                                    rescale=(0.5, 1.5), seed=seed)
+    max_step = (len(train_dataset) // args.irn_batch_size) * args.irn_num_epoches
+    if max_step == 0:
+        raise RuntimeError("train_irn: train_list holds fewer images than one batch of %d" % args.irn_batch_size)
+
+    edge_params, dp_params = model.trainable_parameters()
+    optimizer = torchutils.PolyOptimizer([
+        {"params": edge_params, "lr": 1 * args.irn_learning_rate, "weight_decay": args.irn_weight_decay},
+        {"params": dp_params, "lr": 10 * args.irn_learning_rate, "weight_decay": args.irn_weight_decay},
+    ], lr=args.irn_learning_rate, weight_decay=args.irn_weight_decay, max_step=max_step)
+
+    model = model.to(device)
+    model.train()
+    timer = pyutils.Timer()
+    first, pending = None, []
+    for ep in range(args.irn_num_epoches):
+        print("Epoch %d/%d" % (ep + 1, args.irn_num_epoches))
+        train_dataset.set_epoch(ep)
+        for it, pack in enumerate(_loader(train_dataset, args, True, seed + ep)):
+            img = pack["img"].to(device, non_blocking=True)
+            label = pack["label"].to(device, non_blocking=True)
+            pending.append(train_step(model, optimizer, img, label))
+            if first is None:
+                first = [float(v) for v in pending[0].cpu()]
+            if (optimizer.global_step - 1) % 50 == 0:
+                timer.update_progress(optimizer.global_step / max_step)
+                mean = torch.stack(pending).mean(0).cpu()          # the one read-back per 50 steps
+                pending = []
+                print("step:%5d/%5d" % (optimizer.global_step - 1, max_step),
+                      "loss:%.4f %.4f %.4f %.4f" % tuple(float(v) for v in mean),
+                      "imps:%.1f" % ((it + 1) * args.irn_batch_size / timer.get_stage_elapsed()),
+                      "lr: %.4f" % (optimizer.param_groups[0]["lr"]),
+                      "etc:%s" % (timer.str_estimated_complete()), flush=True)
+        timer.reset_stage()
+
+    infer_dataset = dataloader.VOC12ImageDataset(args.infer_list, voc12_root=args.voc12_root, crop_size=args.irn_crop_size)
+    model.eval()
+    # the mean is that of the raw field: in eval mode `mean_shift` subtracts whatever the initial weights carried (zeros in
+    # the reference, which always starts from a fresh module; an earlier checkpoint or the seeded random state do not)
+    model.mean_shift.running_mean.zero_()
+    print("Analyzing displacements mean ... ", end="")
+    model.mean_shift.running_mean = displacement_mean(model, _loader(infer_dataset, args, False, seed), device)
+    print("done.")
+
+    out_dir = os.path.dirname(args.irn_weights_name)
+    if out_dir:
+        os.makedirs(out_dir, exist_ok=True)
+    torch.save(model.to("cpu").state_dict(), args.irn_weights_name)      # (on the host: the aliased entries stay one storage)
+    torch.cuda.empty_cache()
+    return {"first_losses": first, "steps": optimizer.global_step}

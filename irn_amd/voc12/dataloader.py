@@ -6,8 +6,12 @@ voc12/dataloader.py pieces the label-generation steps use:
 
 JPEGs are decoded with PIL (the reference's imageio call decodes through PIL as well).  The
 image-level labels come from ``cls_labels.npy`` ({int id -> float32[20]}); pass ``cls_labels=`` or
-keep the file next to the image lists as the reference does.  Training datasets / augmentation of
-that file are out of scope.
+keep the file next to the image lists as the reference does.
+
+The two datasets of the IRNet training step are here as well: ``VOC12ImageDataset`` (:109-156, the top-left crops of
+the displacement-mean pass) and ``VOC12AffinityDataset`` (:207-273), which hands over the reduced IR label map instead
+of the reference's three [|S|, N] float tensors: the fused loss classifies the pairs on the GPU from that map.
+Nothing here touches the GPU, so the datasets are safe in loader worker processes.
 """
 import os
 
@@ -101,3 +105,69 @@ class VOC12ClassificationDatasetMSF(Dataset):
             ms = ms[0]
         return {"name": name_str, "img": ms, "size": (img.shape[0], img.shape[1]),
                 "label": torch.from_numpy(self.label_list[idx])}
+
+
+class VOC12ImageDataset(Dataset):
+    """item -> {'name': str, 'img': float32 [3, crop, crop]}: the normalised image, top-left cropped with zeros around
+    it (voc12/dataloader.py:109-156 as step/train_irn.py:87-90 configures it)."""
+
+    def __init__(self, img_name_list_path, voc12_root, crop_size, img_normal=TorchvisionNormalize()):
+        self.img_name_list = load_img_name_list(img_name_list_path)
+        self.voc12_root = voc12_root
+        self.crop_size = crop_size
+        self.img_normal = img_normal
+
+    def __len__(self):
+        return len(self.img_name_list)
+
+    def __getitem__(self, idx):
+        name_str = decode_int_filename(self.img_name_list[idx])
+        img = np.asarray(Image.open(get_img_path(name_str, self.voc12_root)).convert("RGB"))
+        img = imutils.top_left_crop(self.img_normal(img), self.crop_size, 0)
+        return {"name": name_str, "img": np.ascontiguousarray(imutils.HWC_to_CHW(img))}
+
+
+class VOC12AffinityDataset(Dataset):
+    """item -> {'name': str, 'img': float32 [3, crop, crop], 'label': uint8 [crop/4, crop/4]} (voc12/dataloader.py:207-273):
+    image and IR label (``label_dir/<name>.png``) rescaled together by a factor from ``rescale`` (bicubic / nearest), the
+    image normalised, both mirrored with probability 1/2 and cropped by one random box (fill 0 / 255), the label then
+    reduced by ``pil_rescale(label, 0.25, 0)``.  The draws of item ``idx`` come from a generator seeded with
+    (seed, epoch, idx): a run is fixed by its seed whatever the number of loader workers; call ``set_epoch`` before each
+    pass."""
+
+    def __init__(self, img_name_list_path, label_dir, crop_size, voc12_root, rescale=None,
+                 img_normal=TorchvisionNormalize(), hor_flip=False, crop_method="random", seed=0):
+        self.img_name_list = load_img_name_list(img_name_list_path)
+        self.voc12_root = voc12_root
+        self.label_dir = label_dir
+        self.crop_size = crop_size
+        self.rescale = rescale
+        self.img_normal = img_normal
+        self.hor_flip = hor_flip
+        self.crop_method = crop_method
+        self.seed = int(seed)
+        self.epoch = 0
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        return len(self.img_name_list)
+
+    def __getitem__(self, idx):
+        name_str = decode_int_filename(self.img_name_list[idx])
+        rng = np.random.default_rng([self.seed, self.epoch, int(idx)])
+        img = np.asarray(Image.open(get_img_path(name_str, self.voc12_root)).convert("RGB"))
+        label = np.asarray(Image.open(os.path.join(self.label_dir, name_str + ".png")))
+        if self.rescale:
+            img, label = imutils.random_scale((img, label), self.rescale, (3, 0), rng)
+        if self.img_normal:
+            img = self.img_normal(img)
+        if self.hor_flip:
+            img, label = imutils.random_lr_flip((img, label), rng)
+        if self.crop_method == "random":
+            img, label = imutils.random_crop((img, label), self.crop_size, (0, 255), rng)
+        else:
+            img, label = imutils.top_left_crop(img, self.crop_size, 0), imutils.top_left_crop(label, self.crop_size, 255)
+        reduced = imutils.pil_rescale(np.ascontiguousarray(label), 0.25, 0)
+        return {"name": name_str, "img": np.ascontiguousarray(imutils.HWC_to_CHW(img)), "label": np.array(reduced)}       # (a copy: PIL hands out read-only memory)

@@ -118,7 +118,9 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     for name in OUT_OF_SCOPE:
         if getattr(args, name):
-            raise SystemExit("--%s: this step is not part of the MI355X hot-path build; run it with the reference" % name)
+            raise SystemExit("--train_irn_pass: IRNet training is run by `python run_train.py --train_irn_pass True`, not from here"
+                             if name == "train_irn_pass" else
+                             "--%s: this step is not part of the MI355X hot-path build; run it with the reference" % name)
     for d in (args.cam_out_dir, args.sem_seg_out_dir, args.ins_seg_out_dir) + ((args.ir_label_out_dir,) if args.cam_to_ir_label_pass else ()):
         os.makedirs(d, exist_ok=True)
     if args.split_gemm is not None:

@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""Fused against composed IRNet training loss on the GPU: milliseconds per forward + backward, peak allocated bytes, and
+the images/s of the whole training step on synthetic files.  Prints one JSON line.
+
+    python tools/aff_loss_bench.py [--batch 32] [--grid 128] [--radius 10] [--iters 20] [--step_images 64]
+
+fused    = indexing.affinity_displacement_sums + the four losses + backward to the edge / displacement maps
+composed = edge_to_affinity, pair_displacement, the logarithms and absolute values of AffinityDisplacementLoss.forward,
+           float masks uploaded from the host as the reference's loader builds them, masked torch.sum, backward
+Times are device events around `iters` iterations after a warm-up, the two paths alternating; the step figure is the
+wall clock of `train_irn.run` (one epoch, crop 4*grid) over the images it trained on, loader and checkpoint included.
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", default=32, type=int)
+    ap.add_argument("--grid", default=128, type=int)
+    ap.add_argument("--radius", default=10, type=int)
+    ap.add_argument("--iters", default=20, type=int)
+    ap.add_argument("--step_images", default=64, type=int, help="0 skips the training-step measurement")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "aff_loss_bench needs a GPU"
+    import _aff_loss_ref as R
+    from irn_amd.misc import indexing
+    dev = torch.device("cuda", 0)
+    b, g, r = args.batch, args.grid, args.radius
+    edge, dp, label = R.make_inputs(r, b, g, g, seed=1)
+    pi = indexing.PathIndex(r, (g, g))
+    e = torch.from_numpy(edge).to(dev).requires_grad_(True)
+    d = torch.from_numpy(dp).to(dev).requires_grad_(True)
+    lab = torch.from_numpy(label).to(dev)
+    masks = [torch.from_numpy(m.astype(np.float32)).pin_memory() for m in R.batch_pair_labels(label, pi)]
+    target = torch.as_tensor(pi.search_dst, dtype=torch.float32, device=dev).t()[None, :, :, None]
+
+    def fused():
+        sums, counts = indexing.affinity_displacement_sums(e, d, lab, r)
+        R.total_loss(sums, counts).backward()
+
+    def composed():
+        bg, fg, neg = (m.to(dev, non_blocking=True) for m in masks)
+        aff = indexing.edge_to_affinity(e.reshape(b, -1), radius=r, size=(g, g))
+        pos_l = (-1) * torch.log(aff + 1e-5)
+        neg_l = (-1) * torch.log(1. + 1e-5 - aff)
+        pd = indexing.pair_displacement(d, r)
+        sums = torch.stack([torch.sum(bg * pos_l), torch.sum(fg * pos_l), torch.sum(neg * neg_l),
+                            torch.sum(torch.abs(pd - target) * fg[:, None]), torch.sum(torch.abs(pd) * bg[:, None])])
+        R.total_loss(sums, torch.stack([bg.sum(), fg.sum(), neg.sum()])).backward()
+
+    out = {"batch": b, "grid": g, "radius": r, "iters": args.iters}
+    paths = (("fused", fused), ("composed", composed))
+    for name, fn in paths:                                   # warm-up, and the peak of one iteration of each
+        e.grad = d.grad = None
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        out[name + "_peak_bytes"] = int(torch.cuda.max_memory_allocated() - base)
+        fn()
+    ms = {name: [] for name, _ in paths}
+    for _ in range(args.iters):
+        for name, fn in paths:
+            e.grad = d.grad = None
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            fn()
+            t1.record()
+            torch.cuda.synchronize()
+            ms[name].append(t0.elapsed_time(t1))
+    for name in ms:
+        out[name + "_ms"] = round(float(np.median(ms[name])), 3)
+        out[name + "_ms_min_max"] = [round(min(ms[name]), 3), round(max(ms[name]), 3)]
+
+    if args.step_images:
+        from irn_amd.step import train_irn
+        with tempfile.TemporaryDirectory() as root:
+            lst, label_dir = R.write_voc(root, args.step_images, h=375, w=500)
+            a = argparse.Namespace(train_list=lst, infer_list=lst, voc12_root=root, ir_label_out_dir=label_dir,
+                                   irn_crop_size=4 * g, irn_batch_size=b, irn_num_epoches=1, irn_learning_rate=0.1,
+                                   irn_weight_decay=1e-4, num_workers=8, seed=0, irn_init_weights=None,
+                                   irn_weights_name=os.path.join(root, "irn.pth"))
+            t = time.perf_counter()
+            res = train_irn.run(a)
+            torch.cuda.synchronize()
+            out["step_images_per_s"] = round(res["steps"] * b / (time.perf_counter() - t), 2)
+            out["step_images"] = res["steps"] * b
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

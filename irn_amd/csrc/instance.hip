@@ -95,30 +95,27 @@ __device__ __forceinline__ void uf_union(int *parent, int a, int b) {
     }
 }
 
-__global__ __launch_bounds__(256) void ccl_init_kernel(const uint8_t *__restrict__ mask, int *__restrict__ parent,
-                                                       long total, int npx) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    parent[i] = mask[i] ? (int)(i % npx) : -1;
-}
-
-__global__ __launch_bounds__(256) void ccl_merge_kernel(int *__restrict__ parent_all, int h, int w, long total) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int npx = h * w;
-    const int img = (int)(i / npx), p = (int)(i - (long)img * npx);
-    int *parent = parent_all + (long)img * npx;
+// The passes over a forest are written once, for every job type with the members parent, h and w (grid.y = image).
+// Merge: every pixel of the mask (parent >= 0) is joined with its left and its upper neighbour.
+template <class Job>
+__global__ __launch_bounds__(256) void forest_merge_kernel(const Job *__restrict__ jobs) {
+    const Job J = jobs[blockIdx.y];
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= J.h * J.w) return;
+    int *parent = J.parent;
     if (parent[p] < 0) return;
-    const int y = p / w, x = p - y * w;
+    const int y = p / J.w, x = p - y * J.w;
     if (x > 0 && parent[p - 1] >= 0) uf_union(parent, p, p - 1);
-    if (y > 0 && parent[p - w] >= 0) uf_union(parent, p, p - w);
+    if (y > 0 && parent[p - J.w] >= 0) uf_union(parent, p, p - J.w);
 }
 
-__global__ __launch_bounds__(256) void ccl_flatten_kernel(int *__restrict__ parent_all, int npx, long total) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const int img = (int)(i / npx), p = (int)(i - (long)img * npx);
-    int *parent = parent_all + (long)img * npx;
+// Flatten: every pixel points at its root.
+template <class Job>
+__global__ __launch_bounds__(256) void forest_flatten_kernel(const Job *__restrict__ jobs) {
+    const Job J = jobs[blockIdx.y];
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= J.h * J.w) return;
+    int *parent = J.parent;
     if (parent[p] < 0) return;
     // roots never change in this pass (all unions are done), so plain chasing is race-free
     int r = p;
@@ -126,39 +123,61 @@ __global__ __launch_bounds__(256) void ccl_flatten_kernel(int *__restrict__ pare
     parent[p] = r;   // may shortcut another thread's chase; every value it can read still leads to r
 }
 
-// One workgroup per image: rank[root] = 1 + #roots before it (raster order); n_labels[img] = #roots.
-__global__ __launch_bounds__(1024) void ccl_rank_kernel(const int *__restrict__ parent_all, int *__restrict__ rank_all,
-                                                        int *__restrict__ n_labels, int npx) {
-    __shared__ int sums[1024];
-    const int img = blockIdx.x;
-    const int *parent = parent_all + (long)img * npx;
-    int *rank = rank_all + (long)img * npx;
-    const int chunk = (npx + 1023) / 1024;
-    const int lo = min(npx, (int)threadIdx.x * chunk), hi = min(npx, lo + chunk);
-    int cnt = 0;
-    for (int p = lo; p < hi; ++p) cnt += (parent[p] == p);
+// Exclusive prefix of `cnt` over the 1024 threads of a workgroup (Hillis-Steele in LDS); the workgroup's total is left in
+// sums[1023], visible to every thread.
+__device__ __forceinline__ int block_scan_1024(int cnt, int *sums) {
     sums[threadIdx.x] = cnt;
     __syncthreads();
-    for (int s = 1; s < 1024; s <<= 1) {   // Hillis-Steele inclusive scan
+    for (int s = 1; s < 1024; s <<= 1) {
         const int v = threadIdx.x >= s ? sums[threadIdx.x - s] : 0;
         __syncthreads();
         sums[threadIdx.x] += v;
         __syncthreads();
     }
-    int run = sums[threadIdx.x] - cnt;     // exclusive prefix
-    for (int p = lo; p < hi; ++p)
-        if (parent[p] == p) rank[p] = ++run;
-    if (threadIdx.x == 1023 && n_labels) n_labels[img] = sums[1023];
+    return sums[threadIdx.x] - cnt;
 }
 
-__global__ __launch_bounds__(256) void ccl_relabel_kernel(const int *__restrict__ parent_all,
-                                                          const int *__restrict__ rank_all,
-                                                          int32_t *__restrict__ labels, int npx, long total) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
-    const long base = (i / npx) * npx;
-    const int r = parent_all[i];
-    labels[i] = r < 0 ? 0 : rank_all[base + r];
+// One workgroup of 1024 threads per image, each with a chunk of consecutive pixels: rank[root] = 1 + number of roots
+// before it in raster order (skimage numbering).  The number of roots is left in sums[1023].
+__device__ __forceinline__ void rank_roots(const int *parent, int *rank, int npx, int *sums) {
+    const int chunk = (npx + 1023) / 1024;
+    const int lo = min(npx, (int)threadIdx.x * chunk), hi = min(npx, lo + chunk);
+    int cnt = 0;
+    for (int p = lo; p < hi; ++p) cnt += (parent[p] == p);
+    int run = block_scan_1024(cnt, sums);
+    for (int p = lo; p < hi; ++p)
+        if (parent[p] == p) rank[p] = ++run;
+}
+
+// irn_label4: one job per image of the [n,h,w] stack
+struct CclJob {
+    const uint8_t *mask;   // [h,w]
+    int *parent, *rank;    // [npx] each; rank is separate from `labels`: relabel overwrites roots other pixels still need
+    int32_t *labels;       // [h,w] out
+    int32_t *n_labels;     // -> the image's component count, or null
+    int h, w;
+};
+
+__global__ __launch_bounds__(256) void ccl_init_kernel(const CclJob *__restrict__ jobs) {
+    const CclJob J = jobs[blockIdx.y];
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= J.h * J.w) return;
+    J.parent[p] = J.mask[p] ? p : -1;
+}
+
+__global__ __launch_bounds__(1024) void ccl_rank_kernel(const CclJob *__restrict__ jobs) {
+    __shared__ int sums[1024];
+    const CclJob J = jobs[blockIdx.x];
+    rank_roots(J.parent, J.rank, J.h * J.w, sums);
+    if (threadIdx.x == 1023 && J.n_labels) *J.n_labels = sums[1023];
+}
+
+__global__ __launch_bounds__(256) void ccl_relabel_kernel(const CclJob *__restrict__ jobs) {
+    const CclJob J = jobs[blockIdx.y];
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= J.h * J.w) return;
+    const int r = J.parent[p];
+    J.labels[p] = r < 0 ? 0 : J.rank[r];
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -190,49 +209,10 @@ __global__ __launch_bounds__(256) void cluster_init_kernel(const ClusterJob *__r
     J.present[p] = 0;
 }
 
-__global__ __launch_bounds__(256) void cluster_merge_kernel(const ClusterJob *__restrict__ jobs) {
-    const ClusterJob J = jobs[blockIdx.y];
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= J.h * J.w) return;
-    int *parent = J.parent;
-    if (parent[p] < 0) return;
-    const int y = p / J.w, x = p - y * J.w;
-    if (x > 0 && parent[p - 1] >= 0) uf_union(parent, p, p - 1);
-    if (y > 0 && parent[p - J.w] >= 0) uf_union(parent, p, p - J.w);
-}
-
-__global__ __launch_bounds__(256) void cluster_flatten_kernel(const ClusterJob *__restrict__ jobs) {
-    const ClusterJob J = jobs[blockIdx.y];
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= J.h * J.w) return;
-    int *parent = J.parent;
-    if (parent[p] < 0) return;
-    int r = p;
-    while (parent[r] != r) r = parent[r];      // all unions are done: roots are final
-    parent[p] = r;
-}
-
-// one workgroup per image: rank[root] = 1 + number of roots before it in raster order (skimage numbering)
 __global__ __launch_bounds__(1024) void cluster_rank_kernel(const ClusterJob *__restrict__ jobs) {
     __shared__ int sums[1024];
     const ClusterJob J = jobs[blockIdx.x];
-    const int npx = J.h * J.w;
-    const int *parent = J.parent;
-    const int chunk = (npx + 1023) / 1024;
-    const int lo = min(npx, (int)threadIdx.x * chunk), hi = min(npx, lo + chunk);
-    int cnt = 0;
-    for (int p = lo; p < hi; ++p) cnt += (parent[p] == p);
-    sums[threadIdx.x] = cnt;
-    __syncthreads();
-    for (int s = 1; s < 1024; s <<= 1) {
-        const int v = threadIdx.x >= s ? sums[threadIdx.x - s] : 0;
-        __syncthreads();
-        sums[threadIdx.x] += v;
-        __syncthreads();
-    }
-    int run = sums[threadIdx.x] - cnt;
-    for (int p = lo; p < hi; ++p)
-        if (parent[p] == p) J.rank[p] = ++run;
+    rank_roots(J.parent, J.rank, J.h * J.w, sums);
 }
 
 // picked[p] = label at centroid(p) (+1, as the reference adds before compress_range); mark presence
@@ -259,15 +239,7 @@ __global__ __launch_bounds__(1024) void cluster_compress_kernel(const ClusterJob
     const int lo = min(n_vals, (int)threadIdx.x * chunk), hi = min(n_vals, lo + chunk);
     int cnt = 0;
     for (int v = lo; v < hi; ++v) cnt += present[v] != 0;
-    sums[threadIdx.x] = cnt;
-    __syncthreads();
-    for (int s = 1; s < 1024; s <<= 1) {
-        const int t = threadIdx.x >= s ? sums[threadIdx.x - s] : 0;
-        __syncthreads();
-        sums[threadIdx.x] += t;
-        __syncthreads();
-    }
-    int run = sums[threadIdx.x] - cnt;
+    int run = block_scan_1024(cnt, sums);
     for (int v = lo; v < hi; ++v) present[v] = present[v] ? run++ : -1;   // now: new id of value v
     if (threadIdx.x == 1023) *J.k_out = sums[1023];
 }
@@ -298,6 +270,18 @@ struct DetJob {
     int32_t *channel;           // [n_det]      (emit)
     uint8_t *mask;              // [n_det,h,w]  (emit)
     double min_area;
+    int h, w, n_det;
+};
+
+// what the run-length entries keep per image next to its DetJob (see "Detections as COCO run lengths" below)
+struct RleJob {
+    int *idmap;                       // [npx] detection of every pixel, -1 = background
+    int *x0, *x1, *y0, *y1, *runs;    // [n_det] box corners (inclusive) and number of run lengths
+    int32_t *area_out, *n_runs_out, *bbox_out;   // the image's slice of the batch's outputs (count)
+    unsigned long long *keys;         // the image's key segment (emit)
+    unsigned *cursor;                 // keys appended so far, after the n_det map-end keys (emit)
+    int room;                         // keys of the image = sum of its n_runs (emit)
+    int g0;                           // index of the image's first detection in the batch
     int h, w, n_det;
 };
 
@@ -440,17 +424,6 @@ __global__ __launch_bounds__(256) void det_border_kernel(const DetJob *__restric
     }
 }
 
-__global__ __launch_bounds__(256) void det_flatten_kernel(const DetJob *__restrict__ jobs) {
-    const DetJob J = jobs[blockIdx.y];
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    if (p >= J.h * J.w) return;
-    int *parent = J.parent;
-    if (parent[p] < 0) return;
-    int r = p;
-    while (parent[r] != r) r = parent[r];
-    parent[p] = r;
-}
-
 // Every root (= first raster pixel of its component) claims a provisional id and records its sort key
 // channel * npx + pixel: detections are ordered channel ascending, then by first pixel (skimage's
 // label order inside a channel).
@@ -511,10 +484,12 @@ __global__ __launch_bounds__(256) void det_zero_masks_kernel(const DetJob *__res
     }
 }
 
-// Pixel p belongs to detection newid[prov[root(p)]]: its mask byte, and area / max score per detection.  Scores are
-// compared as int bit patterns: the reference takes max(score * mask), which is >= 0 whatever the scores are, and so
-// is a maximum that starts from +0.
-__global__ __launch_bounds__(256) void det_stats_kernel(const DetJob *__restrict__ jobs) {
+// Pixel p belongs to detection newid[prov[root(p)]]; area / max score per detection.  Scores are compared as int bit
+// patterns: the reference takes max(score * mask), which is >= 0 whatever the scores are, and so is a maximum that
+// starts from +0.  The dense form (RLE = false, rjobs unused) sets the pixel's byte in its detection's mask plane; the
+// run-length form stores the id (-1 = background) in the image's id map and keeps the box next to area and score.
+template <bool RLE>
+__global__ __launch_bounds__(256) void det_stats_kernel(const DetJob *__restrict__ jobs, const RleJob *__restrict__ rjobs) {
     const DetJob J = jobs[blockIdx.y];
     if (J.n_det < 1) return;
     const int npx = J.h * J.w;
@@ -524,53 +499,55 @@ __global__ __launch_bounds__(256) void det_stats_kernel(const DetJob *__restrict
     int d = -1, bits = 0;
     if (fg) {
         d = J.newid[J.prov[J.parent[p]]];
-        J.mask[(long)d * npx + p] = 1;
+        if (!RLE) J.mask[(long)d * npx + p] = 1;
         const float sc = J.rw_up[(long)(c - 1) * npx + p];
         bits = sc > 0.f ? __float_as_int(sc) : 0;
     }
-    // A wave's 64 consecutive pixels nearly always lie in ONE detection: one pair of atomics per wave then
+    const RleJob R = RLE ? rjobs[blockIdx.y] : RleJob{};
+    const int y = p / J.w, x = p - y * J.w;
+    if (RLE && p < npx) R.idmap[p] = d;
+    // A wave's 64 consecutive pixels nearly always lie in ONE detection: one set of atomics per wave then
     // (per-pixel atomics onto a handful of addresses took 1.4 ms per 512^2 image — 80 % of the whole step).
     const unsigned long long act = __ballot(fg);
     if (act == 0) return;
     const int d0 = __shfl(d, __ffsll((long long)act) - 1);
     if (__all(!fg || d == d0)) {
-        int mx = bits;
-        for (int sft = 32; sft > 0; sft >>= 1) mx = max(mx, __shfl_xor(mx, sft));
+        int mx = bits, xa = fg ? x : INT_MAX, xb = fg ? x : -1, ya = fg ? y : INT_MAX, yb = fg ? y : -1;
+        for (int sft = 32; sft > 0; sft >>= 1) {
+            mx = max(mx, __shfl_xor(mx, sft));
+            if (RLE) {
+                xa = min(xa, __shfl_xor(xa, sft)), xb = max(xb, __shfl_xor(xb, sft));
+                ya = min(ya, __shfl_xor(ya, sft)), yb = max(yb, __shfl_xor(yb, sft));
+            }
+        }
         if ((threadIdx.x & 63) == 0) {
             atomicAdd(J.area + d0, __popcll(act));
             if (mx > 0) atomicMax(J.score_bits + d0, mx);
+            if (RLE) {
+                atomicMin(R.x0 + d0, xa), atomicMax(R.x1 + d0, xb);
+                atomicMin(R.y0 + d0, ya), atomicMax(R.y1 + d0, yb);
+            }
         }
     } else if (fg) {
         atomicAdd(J.area + d, 1);
         if (bits > 0) atomicMax(J.score_bits + d, bits);
+        if (RLE) {
+            atomicMin(R.x0 + d, x), atomicMax(R.x1 + d, x);
+            atomicMin(R.y0 + d, y), atomicMax(R.y1 + d, y);
+        }
     }
+}
+
+// a detection below the area threshold keeps its place and scores 0; statistics are kept by FINAL id
+__device__ __forceinline__ float final_score(int area, double min_area, int bits) {
+    return ((double)area < min_area) ? 0.f : __int_as_float(bits);
 }
 
 __global__ __launch_bounds__(256) void det_final_kernel(const DetJob *__restrict__ jobs) {
     const DetJob J = jobs[blockIdx.y];
     const int d = blockIdx.x * 256 + threadIdx.x;
     if (d >= J.n_det) return;
-    J.score[d] = ((double)J.area[d] < J.min_area) ? 0.f : __int_as_float(J.score_bits[d]);   // statistics are kept by FINAL id
-}
-
-int run_label4(const uint8_t *mask, int n, int h, int w, int32_t *labels, int32_t *n_labels, void *scratch,
-               hipStream_t stream) {
-    const int npx = h * w;
-    const long total = (long)n * npx;
-    int *parent = (int *)scratch;
-    int *rank = parent + total;   // separate from `labels`: relabel overwrites roots other pixels still need
-    const int nb = (int)((total + 255) / 256);
-    hipLaunchKernelGGL(ccl_init_kernel, dim3(nb), dim3(256), 0, stream, mask, parent, total, npx);
-    IRN_LAUNCH_CHECK("ccl_init_kernel");
-    hipLaunchKernelGGL(ccl_merge_kernel, dim3(nb), dim3(256), 0, stream, parent, h, w, total);
-    IRN_LAUNCH_CHECK("ccl_merge_kernel");
-    hipLaunchKernelGGL(ccl_flatten_kernel, dim3(nb), dim3(256), 0, stream, parent, npx, total);
-    IRN_LAUNCH_CHECK("ccl_flatten_kernel");
-    hipLaunchKernelGGL(ccl_rank_kernel, dim3(n), dim3(1024), 0, stream, parent, rank, n_labels, npx);
-    IRN_LAUNCH_CHECK("ccl_rank_kernel");
-    hipLaunchKernelGGL(ccl_relabel_kernel, dim3(nb), dim3(256), 0, stream, parent, rank, labels, npx, total);
-    IRN_LAUNCH_CHECK("ccl_relabel_kernel");
-    return IRN_OK;
+    J.score[d] = final_score(J.area[d], J.min_area, J.score_bits[d]);
 }
 
 }  // namespace
@@ -618,7 +595,29 @@ extern "C" int irn_label4(const uint8_t *mask_dev, int n, int h, int w, int32_t 
     if (!mask_dev || !labels_dev || !scratch_dev || n < 1 || h < 1 || w < 1)
         return fail(IRN_ERR_ARG, "irn_label4: bad argument");
     if ((long)h * w > (1L << 30)) return fail(IRN_ERR_ARG, "irn_label4: image too large");
-    return run_label4(mask_dev, n, h, w, labels_dev, n_labels_dev, scratch_dev, stream);
+    if (n > 65535) return fail(IRN_ERR_ARG, "irn_label4: at most 65535 images per call");   // grid.y = image
+    const int npx = h * w;
+    int *parent = (int *)scratch_dev, *rank = parent + (size_t)n * npx;
+    std::vector<CclJob> jobs(n);
+    for (int i = 0; i < n; ++i) {
+        const size_t at = (size_t)i * npx;
+        jobs[i] = CclJob{mask_dev + at, parent + at, rank + at, labels_dev + at, n_labels_dev ? n_labels_dev + i : nullptr, h, w};
+    }
+    CclJob *jd = nullptr;
+    int rc = scratch_upload(jobs.data(), sizeof(CclJob) * n, (void **)&jd, stream);
+    if (rc) return rc;
+    const dim3 px(cdiv(npx, 256), n);
+    hipLaunchKernelGGL(ccl_init_kernel, px, dim3(256), 0, stream, jd);
+    IRN_LAUNCH_CHECK("ccl_init_kernel");
+    hipLaunchKernelGGL(forest_merge_kernel<CclJob>, px, dim3(256), 0, stream, jd);
+    IRN_LAUNCH_CHECK("forest_merge_kernel<ccl>");
+    hipLaunchKernelGGL(forest_flatten_kernel<CclJob>, px, dim3(256), 0, stream, jd);
+    IRN_LAUNCH_CHECK("forest_flatten_kernel<ccl>");
+    hipLaunchKernelGGL(ccl_rank_kernel, dim3(n), dim3(1024), 0, stream, jd);
+    IRN_LAUNCH_CHECK("ccl_rank_kernel");
+    hipLaunchKernelGGL(ccl_relabel_kernel, px, dim3(256), 0, stream, jd);
+    IRN_LAUNCH_CHECK("ccl_relabel_kernel");
+    return scratch_release(stream);
 }
 
 // scratch of one image in irn_cluster_centroids[_batch]:
@@ -673,10 +672,10 @@ extern "C" int irn_cluster_centroids_batch(int n_images, const int32_t *const *c
     const dim3 px(cdiv(max_n, 256), n_images);
     hipLaunchKernelGGL(cluster_init_kernel, px, dim3(256), 0, stream, jd, thres);
     IRN_LAUNCH_CHECK("cluster_init_kernel");
-    hipLaunchKernelGGL(cluster_merge_kernel, px, dim3(256), 0, stream, jd);
-    IRN_LAUNCH_CHECK("cluster_merge_kernel");
-    hipLaunchKernelGGL(cluster_flatten_kernel, px, dim3(256), 0, stream, jd);
-    IRN_LAUNCH_CHECK("cluster_flatten_kernel");
+    hipLaunchKernelGGL(forest_merge_kernel<ClusterJob>, px, dim3(256), 0, stream, jd);
+    IRN_LAUNCH_CHECK("forest_merge_kernel<cluster>");
+    hipLaunchKernelGGL(forest_flatten_kernel<ClusterJob>, px, dim3(256), 0, stream, jd);
+    IRN_LAUNCH_CHECK("forest_flatten_kernel<cluster>");
     hipLaunchKernelGGL(cluster_rank_kernel, dim3(n_images), dim3(1024), 0, stream, jd);
     IRN_LAUNCH_CHECK("cluster_rank_kernel");
     hipLaunchKernelGGL(cluster_pick_kernel, px, dim3(256), 0, stream, jd);
@@ -788,8 +787,8 @@ extern "C" int irn_detect_instance_batch_count(int n_images, const float *const 
         hipLaunchKernelGGL(det_border_kernel, dim3(cdiv(max_border, 256), n_images), dim3(256), 0, stream, jd);
         IRN_LAUNCH_CHECK("det_border_kernel");
     }
-    hipLaunchKernelGGL(det_flatten_kernel, px, dim3(256), 0, stream, jd);
-    IRN_LAUNCH_CHECK("det_flatten_kernel");
+    hipLaunchKernelGGL(forest_flatten_kernel<DetJob>, px, dim3(256), 0, stream, jd);
+    IRN_LAUNCH_CHECK("forest_flatten_kernel<det>");
     hipLaunchKernelGGL(det_roots_kernel, px, dim3(256), 0, stream, jd);
     IRN_LAUNCH_CHECK("det_roots_kernel");
     return scratch_release(stream);
@@ -832,8 +831,8 @@ extern "C" int irn_detect_instance_batch_emit(int n_images, const float *const *
     IRN_LAUNCH_CHECK("det_zero_masks_kernel");
     hipLaunchKernelGGL(det_order_kernel, dim3(cdiv(max_det, 256), n_images), dim3(256), 0, stream, jd);
     IRN_LAUNCH_CHECK("det_order_kernel");
-    hipLaunchKernelGGL(det_stats_kernel, dim3(cdiv(max_n, 256), n_images), dim3(256), 0, stream, jd);
-    IRN_LAUNCH_CHECK("det_stats_kernel");
+    hipLaunchKernelGGL(det_stats_kernel<false>, dim3(cdiv(max_n, 256), n_images), dim3(256), 0, stream, jd, (const RleJob *)nullptr);
+    IRN_LAUNCH_CHECK("det_stats_kernel<dense>");
     hipLaunchKernelGGL(det_final_kernel, dim3(cdiv(max_det, 256), n_images), dim3(256), 0, stream, jd);
     IRN_LAUNCH_CHECK("det_final_kernel");
     return scratch_release(stream);
@@ -854,7 +853,7 @@ extern "C" int irn_detect_instance_batch_emit(int n_images, const float *const *
 //
 //   count:  det_order_kernel     final ids and channels (shared with the dense path)
 //           rle_init_kernel      box and run counters of every detection
-//           rle_map_kernel       the id map; area, maximum score and box per detection (integer atomics)
+//           det_stats_kernel     <true>: the id map; area, maximum score and box per detection (integer atomics)
 //           rle_events_kernel    <false>: events per detection (integer atomic adds)
 //           rle_final_kernel     score, area, bbox, n_runs of every detection
 //   emit:   rle_events_kernel    <true>: every event appends the key (batch-wide detection index << 32 | j) to its image's
@@ -869,17 +868,6 @@ extern "C" int irn_detect_instance_batch_emit(int n_images, const float *const *
 // ---------------------------------------------------------------------------------------------
 namespace {
 
-struct RleJob {
-    int *idmap;                       // [npx] detection of every pixel, -1 = background
-    int *x0, *x1, *y0, *y1, *runs;    // [n_det] box corners (inclusive) and number of run lengths
-    int32_t *area_out, *n_runs_out, *bbox_out;   // the image's slice of the batch's outputs (count)
-    unsigned long long *keys;         // the image's key segment (emit)
-    unsigned *cursor;                 // keys appended so far, after the n_det map-end keys (emit)
-    int room;                         // keys of the image = sum of its n_runs (emit)
-    int g0;                           // index of the image's first detection in the batch
-    int h, w, n_det;
-};
-
 __global__ __launch_bounds__(256) void rle_init_kernel(const RleJob *__restrict__ jobs) {
     const RleJob R = jobs[blockIdx.y];
     const int d = blockIdx.x * 256 + threadIdx.x;
@@ -887,47 +875,6 @@ __global__ __launch_bounds__(256) void rle_init_kernel(const RleJob *__restrict_
     R.x0[d] = R.y0[d] = INT_MAX;
     R.x1[d] = R.y1[d] = -1;
     R.runs[d] = 1;                    // the map's end closes the last run
-}
-
-// det_stats_kernel without the mask byte: the id map instead, and the box next to area and score.
-__global__ __launch_bounds__(256) void rle_map_kernel(const DetJob *__restrict__ jobs, const RleJob *__restrict__ rjobs) {
-    const DetJob J = jobs[blockIdx.y];
-    if (J.n_det < 1) return;
-    const RleJob R = rjobs[blockIdx.y];
-    const int npx = J.h * J.w;
-    const int p = blockIdx.x * 256 + threadIdx.x;
-    const int c = p < npx ? J.cls[p] : 0;
-    const bool fg = c > 0;
-    const int y = p / J.w, x = p - y * J.w;
-    int d = -1, bits = 0;
-    if (fg) {
-        d = J.newid[J.prov[J.parent[p]]];
-        const float sc = J.rw_up[(long)(c - 1) * npx + p];
-        bits = sc > 0.f ? __float_as_int(sc) : 0;
-    }
-    if (p < npx) R.idmap[p] = d;
-    const unsigned long long act = __ballot(fg);
-    if (act == 0) return;
-    const int d0 = __shfl(d, __ffsll((long long)act) - 1);
-    if (__all(!fg || d == d0)) {       // the usual case: one detection under the wave's 64 pixels, one set of atomics
-        int mx = bits, xa = fg ? x : INT_MAX, xb = fg ? x : -1, ya = fg ? y : INT_MAX, yb = fg ? y : -1;
-        for (int sft = 32; sft > 0; sft >>= 1) {
-            mx = max(mx, __shfl_xor(mx, sft));
-            xa = min(xa, __shfl_xor(xa, sft)), xb = max(xb, __shfl_xor(xb, sft));
-            ya = min(ya, __shfl_xor(ya, sft)), yb = max(yb, __shfl_xor(yb, sft));
-        }
-        if ((threadIdx.x & 63) == 0) {
-            atomicAdd(J.area + d0, __popcll(act));
-            if (mx > 0) atomicMax(J.score_bits + d0, mx);
-            atomicMin(R.x0 + d0, xa), atomicMax(R.x1 + d0, xb);
-            atomicMin(R.y0 + d0, ya), atomicMax(R.y1 + d0, yb);
-        }
-    } else if (fg) {
-        atomicAdd(J.area + d, 1);
-        if (bits > 0) atomicMax(J.score_bits + d, bits);
-        atomicMin(R.x0 + d, x), atomicMax(R.x1 + d, x);
-        atomicMin(R.y0 + d, y), atomicMax(R.y1 + d, y);
-    }
 }
 
 // one atomic add for the wave when all of its adders share a target (a component's upper edge), one each otherwise
@@ -987,7 +934,7 @@ __global__ __launch_bounds__(256) void rle_final_kernel(const DetJob *__restrict
     if (d >= J.n_det) return;
     const RleJob R = rjobs[blockIdx.y];
     const int area = J.area[d];
-    J.score[d] = ((double)area < J.min_area) ? 0.f : __int_as_float(J.score_bits[d]);   // det_final_kernel's rule
+    J.score[d] = final_score(area, J.min_area, J.score_bits[d]);
     R.area_out[d] = area;
     R.n_runs_out[d] = R.runs[d];
     const int x0 = R.x0[d], y0 = R.y0[d];
@@ -1118,8 +1065,8 @@ extern "C" int irn_detect_instance_batch_rle_count(int n_images, const float *co
     IRN_LAUNCH_CHECK("det_order_kernel");
     hipLaunchKernelGGL(rle_init_kernel, per_det, dim3(256), 0, stream, rd);
     IRN_LAUNCH_CHECK("rle_init_kernel");
-    hipLaunchKernelGGL(rle_map_kernel, per_px, dim3(256), 0, stream, jd, rd);
-    IRN_LAUNCH_CHECK("rle_map_kernel");
+    hipLaunchKernelGGL(det_stats_kernel<true>, per_px, dim3(256), 0, stream, jd, rd);
+    IRN_LAUNCH_CHECK("det_stats_kernel<rle>");
     hipLaunchKernelGGL(rle_events_kernel<false>, per_px, dim3(256), 0, stream, rd);
     IRN_LAUNCH_CHECK("rle_events_kernel<count>");
     hipLaunchKernelGGL(rle_final_kernel, per_det, dim3(256), 0, stream, jd, rd);

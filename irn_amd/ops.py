@@ -395,42 +395,55 @@ def detect_instance(rw_up, argmax, class_ids, n_channels, max_fragment_size=0):
     return {"score": score, "mask": mask, "class": class_ids[chan]}
 
 
-class PendingDetections:
-    """Detections of a batch whose packed transfer to the host may still be in flight (`detect_instance_batch(...,
-    deferred=True)`): `result()` waits for it and returns the list `detect_instance_batch` returns.  The transfer runs on
-    a copy stream of its own, so the caller can enqueue the next batch's kernels before collecting this one."""
+_NOTHING = "detect_instance: no foreground pixel in any channel"
 
-    def __init__(self, n, host, done, nds, offs, hs, ws, class_ids, timings, t_emit):
-        self._n, self._host, self._done, self._nds, self._offs = n, host, done, nds, offs
-        self._hs, self._ws, self._class_ids, self._timings, self._t_emit = hs, ws, class_ids, timings, t_emit
+
+class _PendingBatch:
+    """Results of a batched detection whose last transfer to the host may still be in flight: `result()` waits for it once
+    and returns the list the blocking call returns, an image without any detection holding its ValueError.  `host` is None
+    when no image of the batch has one.  A subclass's `_unpack()` yields the results of the images that have detections,
+    in order."""
+
+    def __init__(self, nds, host, done, timings, t_emit):
+        self._nds, self._host, self._done, self._timings, self._t_emit = nds, host, done, timings, t_emit
         self._out = None
 
     def result(self):
         if self._out is not None:
             return self._out
         import time
-        out = []
-        if self._host is None:                      # no foreground pixel in any image of the batch
-            out = [ValueError("detect_instance: no foreground pixel in any channel") for _ in range(self._n)]
-        else:
-            self._done.synchronize()                                               # host round trip 2
-            t_done = time.perf_counter()
-            raw = self._host.numpy()
-            for i in range(self._n):
-                nd = self._nds[i]
-                if nd == 0:
-                    out.append(ValueError("detect_instance: no foreground pixel in any channel"))
-                    continue
-                o_sc, o_ch, o_mk = self._offs[i]
-                score = raw[o_sc:o_sc + 4 * nd].view(np.float32)
-                chan = raw[o_ch:o_ch + 4 * nd].view(np.int32)
-                mask = raw[o_mk:o_mk + nd * self._hs[i] * self._ws[i]].view(np.bool_).reshape(nd, self._hs[i], self._ws[i])
-                out.append({"score": score, "mask": mask, "class": np.asarray(self._class_ids[i])[chan]})
-            if self._timings is not None:            # seconds: emit + packed transfer (as far as the caller waited for it), unpacking
-                self._timings["emit_d2h"] = self._timings.get("emit_d2h", 0.0) + t_done - self._t_emit
-                self._timings["unpack"] = self._timings.get("unpack", 0.0) + time.perf_counter() - t_done
-        self._out = out
-        return out
+        if self._host is None:
+            self._out = [ValueError(_NOTHING) for _ in self._nds]
+            return self._out
+        self._done.synchronize()                                                   # the batch's last host round trip
+        t_done = time.perf_counter()
+        found = self._unpack()
+        self._out = [next(found) if nd else ValueError(_NOTHING) for nd in self._nds]
+        if self._timings is not None:            # seconds: emit + transfer (as far as the caller waited for it), unpacking
+            self._timings["emit_d2h"] = self._timings.get("emit_d2h", 0.0) + t_done - self._t_emit
+            self._timings["unpack"] = self._timings.get("unpack", 0.0) + time.perf_counter() - t_done
+        return self._out
+
+
+class PendingDetections(_PendingBatch):
+    """Detections of a batch whose packed transfer to the host may still be in flight (`detect_instance_batch(...,
+    deferred=True)`): `result()` waits for it and returns the list `detect_instance_batch` returns.  The transfer runs on
+    a copy stream of its own, so the caller can enqueue the next batch's kernels before collecting this one."""
+
+    def __init__(self, nds, host, done, timings, t_emit, offs, hs, ws, class_ids):
+        super().__init__(nds, host, done, timings, t_emit)
+        self._offs, self._hs, self._ws, self._class_ids = offs, hs, ws, class_ids
+
+    def _unpack(self):
+        raw = self._host.numpy()
+        for i, nd in enumerate(self._nds):
+            if nd == 0:
+                continue
+            o_sc, o_ch, o_mk = self._offs[i]
+            score = raw[o_sc:o_sc + 4 * nd].view(np.float32)
+            chan = raw[o_ch:o_ch + 4 * nd].view(np.int32)
+            mask = raw[o_mk:o_mk + nd * self._hs[i] * self._ws[i]].view(np.bool_).reshape(nd, self._hs[i], self._ws[i])
+            yield {"score": score, "mask": mask, "class": np.asarray(self._class_ids[i])[chan]}
 
 
 _COPY_STREAMS = {}
@@ -441,6 +454,25 @@ def _copy_stream(dev):
     if key not in _COPY_STREAMS:
         _COPY_STREAMS[key] = torch.cuda.Stream(device=dev)
     return _COPY_STREAMS[key]
+
+
+def read_back(src, host, side):
+    """Start the copy of the device bytes `src` into the head of the page-locked buffer `host` and return the event that
+    marks its end.  The copy runs on the current stream or, with `side`, on the device's copy stream behind everything
+    enqueued so far: it then crosses PCIe under the kernels the caller enqueues next, and the allocator hands `src`'s block
+    out again only behind it."""
+    done = torch.cuda.Event()
+    stream = torch.cuda.current_stream(src.device)
+    if side:
+        ready = torch.cuda.Event()
+        ready.record(stream)
+        stream = _copy_stream(src.device)
+        stream.wait_event(ready)
+        src.record_stream(stream)
+    with torch.cuda.stream(stream):
+        host[:src.numel()].copy_(src, non_blocking=True)
+        done.record(stream)
+    return done
 
 
 class _DetCount(collections.namedtuple("_DetCount", "n dev hs ws cs_a hs_a ws_a sc_p am_p keep scratch nds")):
@@ -485,95 +517,65 @@ def detect_instance_batch(rw_ups, argmaxes, class_ids, n_channels, max_fragment_
     import time
     t_start = time.perf_counter()
     dc = _detect_batch_count(rw_ups, argmaxes, n_channels)
-    n, dev, hs, ws, nds, scratch = dc.n, dc.dev, dc.hs, dc.ws, dc.nds, dc.scratch
-    cs_a, hs_a, ws_a, sc_p, am_p = dc.cs_a, dc.hs_a, dc.ws_a, dc.sc_p, dc.am_p
-    with torch.cuda.device(dev):
-        t_count = time.perf_counter()
-        if timings is not None:          # seconds: labelling + count transfer
-            timings["count"] = timings.get("count", 0.0) + t_count - t_start
-        # packed output: per image [score fp32 x nd | channel int32 x nd | pad to 16 | masks uint8 nd x h x w | pad to 16]
-        offs, total = [], 0
-        for i in range(n):
-            head = (8 * nds[i] + 15) // 16 * 16
-            offs.append((total, total + 4 * nds[i], total + head))
-            total += head + (nds[i] * hs[i] * ws[i] + 15) // 16 * 16
-        if total == 0:
-            pending = PendingDetections(n, None, None, nds, offs, hs, ws, class_ids, timings, t_count)
-            return pending if deferred else pending.result()
-        # the device-side staging buffer: the cached one when the call waits for its transfer, one of the batch's own
-        # when the transfer is left in flight (the next batch must not write into it)
-        packed = (torch.empty(total + 16, dtype=torch.uint8, device=dev) if deferred
-                  else _cached("det_out_b", dev, total + 16, torch.uint8))
-        base = (packed.data_ptr() + 15) // 16 * 16
-        shift = base - packed.data_ptr()
-        live = [nd > 0 for nd in nds]
-        check(lib.irn_detect_instance_batch_emit(
-            n, sc_p, am_p, cs_a, hs_a, ws_a, i32_array(nds), (C.c_double * n)(*[float(v) for v in max_fragment_sizes]),
-            ptr_array([base + o[0] if l else None for o, l in zip(offs, live)]),
-            ptr_array([base + o[1] if l else None for o, l in zip(offs, live)]),
-            ptr_array([base + o[2] if l else None for o, l in zip(offs, live)]), scratch.data_ptr(), _stream()))
-        # a page-locked buffer of its own for every batch: the detections are handed out as VIEWS of it (no second copy of
-        # 2 MB of masks per image) and it goes back to torch's caching host allocator when the last of them is dropped
-        host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
-        done = torch.cuda.Event()
-        if deferred:
-            side, cur = _copy_stream(dev), torch.cuda.current_stream()
-            emitted = torch.cuda.Event()
-            emitted.record(cur)
-            side.wait_event(emitted)
-            with torch.cuda.stream(side):
-                host.copy_(packed[shift:shift + total], non_blocking=True)
-                done.record(side)
-            packed.record_stream(side)               # the allocator may hand the block out again only behind the copy
-        else:
-            host.copy_(packed[shift:shift + total], non_blocking=True)
-            done.record(torch.cuda.current_stream())
-    if timings is not None:
-        timings["bytes"] = timings.get("bytes", 0) + total
-    pending = PendingDetections(n, host, done, nds, offs, hs, ws, class_ids, timings, t_count)
+    n, nds = dc.n, dc.nds
+    t_count = time.perf_counter()
+    if timings is not None:          # seconds: labelling + count transfer
+        timings["count"] = timings.get("count", 0.0) + t_count - t_start
+    # packed output: per image [score fp32 x nd | channel int32 x nd | pad to 16 | masks uint8 nd x h x w | pad to 16]
+    offs, total = [], 0
+    for i in range(n):
+        head = (8 * nds[i] + 15) // 16 * 16
+        offs.append((total, total + 4 * nds[i], total + head))
+        total += head + (nds[i] * dc.hs[i] * dc.ws[i] + 15) // 16 * 16
+    host = done = None
+    if total:
+        with torch.cuda.device(dc.dev):
+            # the device-side staging buffer: the cached one when the call waits for its transfer, one of the batch's own
+            # when the transfer is left in flight (the next batch must not write into it)
+            packed = (torch.empty(total + 16, dtype=torch.uint8, device=dc.dev) if deferred
+                      else _cached("det_out_b", dc.dev, total + 16, torch.uint8))
+            base = (packed.data_ptr() + 15) // 16 * 16
+            shift = base - packed.data_ptr()
+            live = [nd > 0 for nd in nds]
+            check(lib.irn_detect_instance_batch_emit(
+                n, dc.sc_p, dc.am_p, dc.cs_a, dc.hs_a, dc.ws_a, i32_array(nds),
+                (C.c_double * n)(*[float(v) for v in max_fragment_sizes]),
+                ptr_array([base + o[0] if l else None for o, l in zip(offs, live)]),
+                ptr_array([base + o[1] if l else None for o, l in zip(offs, live)]),
+                ptr_array([base + o[2] if l else None for o, l in zip(offs, live)]), dc.scratch.data_ptr(), _stream()))
+            # a page-locked buffer of its own for every batch: the detections are handed out as VIEWS of it (no second copy
+            # of 2 MB of masks per image) and it goes back to torch's caching host allocator when the last of them is dropped
+            host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            done = read_back(packed[shift:shift + total], host, side=deferred)
+        if timings is not None:
+            timings["bytes"] = timings.get("bytes", 0) + total
+    pending = PendingDetections(nds, host, done, timings, t_count, offs, dc.hs, dc.ws, class_ids)
     return pending if deferred else pending.result()
 
 
-class PendingRleDetections:
+class PendingRleDetections(_PendingBatch):
     """`detect_instance_rle_batch(..., deferred=True)`: the run lengths of a batch may still be crossing to the host on the
     copy stream; `result()` waits for them and returns the list `detect_instance_rle_batch` returns."""
 
-    def __init__(self, n, head, host, done, nds, hs, ws, class_ids, timings, t_emit):
-        self._n, self._head, self._host, self._done, self._nds = n, head, host, done, nds
-        self._hs, self._ws, self._class_ids, self._timings, self._t_emit = hs, ws, class_ids, timings, t_emit
-        self._out = None
+    def __init__(self, nds, host, done, timings, t_emit, head, hs, ws, class_ids):
+        super().__init__(nds, host, done, timings, t_emit)
+        self._head, self._hs, self._ws, self._class_ids = head, hs, ws, class_ids
 
-    def result(self):
-        if self._out is not None:
-            return self._out
-        import time
-        nothing = "detect_instance: no foreground pixel in any channel"
-        if self._host is None:                      # no foreground pixel in any image of the batch
-            self._out = [ValueError(nothing) for _ in range(self._n)]
-            return self._out
-        self._done.synchronize()                                                   # host round trip 3
-        t_done = time.perf_counter()
+    def _unpack(self):
         score, chan, area, n_runs, bbox = self._head
         counts = self._host.numpy().view(np.uint32)
-        out, g, at = [], 0, 0
-        for i in range(self._n):
-            nd = self._nds[i]
+        g, at = 0, 0
+        for i, nd in enumerate(self._nds):
             if nd == 0:
-                out.append(ValueError(nothing))
                 continue
             offsets = np.zeros(nd + 1, np.int64)
             np.cumsum(n_runs[g:g + nd], out=offsets[1:])
             total = int(offsets[nd])
-            out.append({"score": score[g:g + nd], "class": np.asarray(self._class_ids[i])[chan[g:g + nd]],
-                        "size": (self._hs[i], self._ws[i]), "counts": counts[at:at + total], "offsets": offsets,
-                        "area": area[g:g + nd].astype(np.int64), "bbox": bbox[g:g + nd]})
+            yield {"score": score[g:g + nd], "class": np.asarray(self._class_ids[i])[chan[g:g + nd]],
+                   "size": (self._hs[i], self._ws[i]), "counts": counts[at:at + total], "offsets": offsets,
+                   "area": area[g:g + nd].astype(np.int64), "bbox": bbox[g:g + nd]}
             g += nd
             at += total
-        if self._timings is not None:
-            self._timings["emit_d2h"] = self._timings.get("emit_d2h", 0.0) + t_done - self._t_emit
-            self._timings["unpack"] = self._timings.get("unpack", 0.0) + time.perf_counter() - t_done
-        self._out = out
-        return out
 
 
 def detect_instance_rle_batch(rw_ups, argmaxes, class_ids, n_channels, max_fragment_sizes, timings=None, deferred=False):
@@ -590,29 +592,27 @@ def detect_instance_rle_batch(rw_ups, argmaxes, class_ids, n_channels, max_fragm
     import time
     t_start = time.perf_counter()
     dc = _detect_batch_count(rw_ups, argmaxes, n_channels)
-    n, dev, hs, ws, nds, scratch = dc.n, dc.dev, dc.hs, dc.ws, dc.nds, dc.scratch
-    cs_a, hs_a, ws_a, sc_p, am_p = dc.cs_a, dc.hs_a, dc.ws_a, dc.sc_p, dc.am_p
+    n, dev, nds = dc.n, dc.dev, dc.nds
     t_count = time.perf_counter()
     if timings is not None:
         timings["count"] = timings.get("count", 0.0) + t_count - t_start
     G = sum(nds)
     if G == 0:
-        pending = PendingRleDetections(n, None, None, None, nds, hs, ws, class_ids, timings, t_count)
+        pending = PendingRleDetections(nds, None, None, timings, t_count, None, dc.hs, dc.ws, class_ids)
         return pending if deferred else pending.result()
     nd_a = i32_array(nds)
     with torch.cuda.device(dev):
-        rle_scratch = _cached("det_rle_scratch", dev, lib.irn_detect_instance_batch_rle_scratch_bytes(n, hs_a, ws_a, nd_a),
+        rle_scratch = _cached("det_rle_scratch", dev, lib.irn_detect_instance_batch_rle_scratch_bytes(n, dc.hs_a, dc.ws_a, nd_a),
                               torch.uint8)
         # score fp32 [G] | channel int32 [G] | area int32 [G] | n_runs int32 [G] | bbox int32 [G][4]
         head_dev = _cached("det_rle_head", dev, 32 * G, torch.uint8)
         base = head_dev.data_ptr()
         check(lib.irn_detect_instance_batch_rle_count(
-            n, sc_p, am_p, cs_a, hs_a, ws_a, nd_a, (C.c_double * n)(*[float(v) for v in max_fragment_sizes]),
-            base, base + 4 * G, base + 8 * G, base + 12 * G, base + 16 * G, scratch.data_ptr(), rle_scratch.data_ptr(),
+            n, dc.sc_p, dc.am_p, dc.cs_a, dc.hs_a, dc.ws_a, nd_a, (C.c_double * n)(*[float(v) for v in max_fragment_sizes]),
+            base, base + 4 * G, base + 8 * G, base + 12 * G, base + 16 * G, dc.scratch.data_ptr(), rle_scratch.data_ptr(),
             _stream()))
         head_host = torch.empty(32 * G, dtype=torch.uint8, pin_memory=True)
-        head_host.copy_(head_dev[:32 * G], non_blocking=True)
-        torch.cuda.current_stream().synchronize()                                  # host round trip 2
+        read_back(head_dev[:32 * G], head_host, side=False).synchronize()          # host round trip 2
         raw = head_host.numpy()
         head = (raw[:4 * G].view(np.float32), raw[4 * G:8 * G].view(np.int32), raw[8 * G:12 * G].view(np.int32),
                 raw[12 * G:16 * G].view(np.int32), raw[16 * G:].view(np.int32).reshape(G, 4))
@@ -627,25 +627,13 @@ def detect_instance_rle_batch(rw_ups, argmaxes, class_ids, n_channels, max_fragm
         sort_ws = _cached("det_rle_sort", dev, ws_bytes, torch.uint8)
         counts_dev = (torch.empty(4 * total, dtype=torch.uint8, device=dev) if deferred
                       else _cached("det_rle_counts", dev, 4 * total, torch.uint8))
-        check(lib.irn_detect_instance_batch_rle_emit(n, hs_a, ws_a, nd_a, (C.c_int64 * n)(*runs), counts_dev.data_ptr(),
+        check(lib.irn_detect_instance_batch_rle_emit(n, dc.hs_a, dc.ws_a, nd_a, (C.c_int64 * n)(*runs), counts_dev.data_ptr(),
                                                      rle_scratch.data_ptr(), sort_ws.data_ptr(), ws_bytes, _stream()))
         host = torch.empty(4 * total, dtype=torch.uint8, pin_memory=True)
-        done = torch.cuda.Event()
-        if deferred:
-            side, cur = _copy_stream(dev), torch.cuda.current_stream()
-            emitted = torch.cuda.Event()
-            emitted.record(cur)
-            side.wait_event(emitted)
-            with torch.cuda.stream(side):
-                host.copy_(counts_dev[:4 * total], non_blocking=True)
-                done.record(side)
-            counts_dev.record_stream(side)
-        else:
-            host.copy_(counts_dev[:4 * total], non_blocking=True)
-            done.record(torch.cuda.current_stream())
+        done = read_back(counts_dev[:4 * total], host, side=deferred)
     if timings is not None:
         timings["bytes"] = timings.get("bytes", 0) + 4 * n + 32 * G + 4 * total
-    pending = PendingRleDetections(n, head, host, done, nds, hs, ws, class_ids, timings, t_count)
+    pending = PendingRleDetections(nds, host, done, timings, t_count, head, dc.hs, dc.ws, class_ids)
     return pending if deferred else pending.result()
 
 

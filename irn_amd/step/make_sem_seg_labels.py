@@ -113,16 +113,8 @@ def _start_copy(batch):
     """The batch's label maps (views of one device buffer) leave for the host as ONE copy into page-locked memory on the
     copy stream, behind everything enqueued so far; `_collect` waits for it when the next batch is already queued."""
     flat = batch["flat"]
-    staging = _common.PINNED.take(flat.numel())
-    ready = torch.cuda.Event()
-    ready.record()
-    cs = ops._copy_stream(flat.device)
-    cs.wait_event(ready)
-    with torch.cuda.stream(cs):
-        staging[:flat.numel()].copy_(flat, non_blocking=True)
-        done = torch.cuda.Event()
-        done.record(cs)
-    batch["staging"], batch["done"] = staging, done
+    batch["staging"] = _common.PINNED.take(flat.numel())
+    batch["done"] = ops.read_back(flat, batch["staging"], side=True)
 
 
 def _enqueue(model, walker, pend, args):

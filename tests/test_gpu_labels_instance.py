@@ -102,6 +102,55 @@ def test_label4_vs_oracle_random_masks():
     assert int(counts[0]) == 1 and np.array_equal(labels[0].cpu().numpy(), O.label4(m[0]))
 
 
+def _noise_dp(h, w, seed):
+    """A displacement field of noise: many roots of the weak mask and many clusters, unlike the smooth synthetic fields."""
+    return (np.random.RandomState(seed).randn(2, h, w) * 2.0).astype(np.float32)
+
+
+def test_label4_job_table_vs_oracle_noise_masks():
+    """irn_label4 with one job per image: a stack of three weak masks of noise fields (1221 pixels each: chunks of two
+    pixels and a run of empty tail threads in the ranking), a wide strip, and a call without the count output."""
+    from irn_amd import ops
+    from irn_amd._lib import _stream, check, lib
+
+    def weak(h, w, seed):
+        dp = _noise_dp(h, w, seed)
+        return np.sqrt(dp[1] ** 2 + dp[0] ** 2) < 2.5
+
+    for m in (np.stack([weak(33, 37, s) for s in (12, 21, 22)]), weak(5, 300, 13)[None]):
+        refs = [O.label4(mi) for mi in m]
+        assert all(r.max() >= 3 for r in refs)
+        labels, counts = ops.label4(torch.from_numpy(m).to(_dev()))
+        for i, ref in enumerate(refs):
+            assert np.array_equal(labels[i].cpu().numpy(), ref), (m.shape, i)
+            assert int(counts[i]) == ref.max(), (m.shape, i)
+    # n_labels_dev == NULL: labels only
+    n, h, w = m.shape
+    md = torch.from_numpy(m).to(_dev()).to(torch.uint8).contiguous()
+    labels = torch.empty((n, h, w), dtype=torch.int32, device=_dev())
+    scratch = torch.empty(lib.irn_ccl_scratch_bytes(n, h, w), dtype=torch.uint8, device=_dev())
+    check(lib.irn_label4(md.data_ptr(), n, h, w, labels.data_ptr(), None, scratch.data_ptr(), _stream()))
+    assert np.array_equal(labels[0].cpu().numpy(), refs[0])
+
+
+def test_cluster_front_end_on_noise_fields_vs_oracle():
+    """find_centroids_batch / cluster_centroids_batch pinned on the oracle directly, one ragged batch of noise fields at the
+    sizes where the ranking's scan changes shape: fewer pixels than threads, exactly 1024, chunks of two with empty tail
+    threads, a wide strip, several hundred roots."""
+    from irn_amd import ops
+    dps = [_noise_dp(h, w, s) for h, w, s in ((7, 9, 6), (32, 32, 11), (33, 37, 12), (5, 300, 13), (64, 80, 14))]
+    dev_dps = [torch.from_numpy(d).to(_dev()) for d in dps]
+    cens = ops.find_centroids_batch(dev_dps)
+    cmaps, ks = ops.cluster_centroids_batch(cens, dev_dps)
+    for i, dp in enumerate(dps):
+        ref_cen = O.find_centroids_with_refinement(dp)
+        assert np.array_equal(cens[i].cpu().numpy(), ref_cen), i
+        ref_oh = O.cluster_centroids(ref_cen, dp)
+        assert ks[i] >= 3, (i, ks[i])
+        oh = cmaps[i][None] == torch.arange(ks[i], device=_dev(), dtype=torch.int32)[:, None, None]
+        assert oh.shape == ref_oh.shape and np.array_equal(oh.cpu().numpy(), ref_oh.astype(bool)), i
+
+
 @pytest.mark.parametrize("name", ["a", "b", "c"])
 def test_instance_labels_end_to_end_vs_reference(golden, name):
     from irn_amd.misc import indexing

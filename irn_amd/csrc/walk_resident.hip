@@ -21,7 +21,7 @@
 //     0-3 add them pairwise in fp32, add the centre term and multiply by 1/deg in fp64, apply the recurrence of the
 //     schedule (below) and store y_{t+1}[c] (numerics: tests/test_precision_model.py).  Channels are
 //     independent chains: with C >= 2 the poll of the next step flies during the arithmetic of this one.
-//   * the step loop (walk_resident_steps.inc) exists once per wave ROLE since round 4: the polling waves' copy never
+//   * the step loop (`step_loop` in resident_kernel) exists once per wave role since round 4: the polling waves' copy never
 //     stores, the combining waves' copy holds no poll registers; a wave branches into its copy once per job and the
 //     barriers of the two copies match one for one (LESSONS.md 31).  Radius 5, single-channel jobs: the polling waves
 //     take half of the combine.
@@ -59,42 +59,19 @@ typedef const double IRN_GLOBAL *gcd_t;
 typedef float IRN_GLOBAL *gf_t;
 typedef float f4a __attribute__((ext_vector_type(4)));
 
-#ifndef IRN_R10_COMBINER_UNSPLIT
-#define IRN_R10_COMBINER_UNSPLIT 1 // radius 10, two channels: the combining waves (no poll to issue) run the arithmetic as ONE pipeline
-#endif
-#ifndef IRN_R5_SHARED_COMBINE
-#define IRN_R5_SHARED_COMBINE 1    // radius 5, single-channel jobs: the polling waves take half of the combine (walk_resident_steps.inc)
-#endif
-#ifndef IRN_PROF_COMBINE
-#define IRN_PROF_COMBINE 0     // diagnostic builds only (tools/combine_profile.py): 1 / 2 move the PROF stamps into the combine phase
-#endif
-#ifndef IRN_PS_LDS_BYTES
-#define IRN_PS_LDS_BYTES (96 * 1024)       // LDS spent on the recurrence's private terms: 48 channels at radius 10, 12 at radius 5
-#endif
 constexpr int kSlabH = 8, kSlabW = 32;     // 64 lanes x 4 px
 constexpr int kWaves = 8;                  // 512 threads
+constexpr int kPsLdsBytes = 96 * 1024;     // LDS spent on the recurrence's private terms: 48 channels at radius 10, 12 at radius 5
 
 template <int R>
 struct RCfg;
 template <>
 struct RCfg<10> {
     static constexpr int Q = 8, SL_Y = 1, SL_X = 1;
-    static constexpr bool PREFETCH_ROWS = true;     // read the next neighbour row's window ahead of this row's FMAs
-#ifndef IRN_R10_ROLE_SPLIT
-#define IRN_R10_ROLE_SPLIT 1
-#endif
-    static constexpr bool ROLE_SPLIT = IRN_R10_ROLE_SPLIT != 0;     // one copy of the step loop per wave role (see the step loop)
 };
 template <>
 struct RCfg<5> {
     static constexpr int Q = 2, SL_Y = 2, SL_X = 2;
-    static constexpr bool PREFETCH_ROWS = true;     // fits since the fp32 chains freed the fp64 accumulators (250 VGPRs)
-#ifndef IRN_R5_ROLE_SPLIT
-#define IRN_R5_ROLE_SPLIT 1
-#endif
-    // split, this instantiation spills six loop-invariant registers that the polling waves reload once per step (their
-    // staging addresses) — and is still 3.6 % faster (profiles/r04_s11_role_split_radius5_ab.txt)
-    static constexpr bool ROLE_SPLIT = IRN_R5_ROLE_SPLIT != 0;
 };
 
 // The neighbour disc (dy,dx) != (0,0), dx^2 + dy^2 < R^2, in raster order: the union of the
@@ -147,7 +124,7 @@ struct Geom {
     static constexpr int INVD_BYTES = SLABS * 4 * 64 * 8;           // [slab][row][column] fp64
     // {y_{t-1}, s_t} of the tile's own pixels for the first CAPC channels of a job (the rest go through the workspace)
     static constexpr int TPX = TH * TW;
-    static constexpr int CAPC = IRN_PS_LDS_BYTES / (TPX * 8);
+    static constexpr int CAPC = kPsLdsBytes / (TPX * 8);
     static constexpr int PS_OFF = XS_BYTES + PART_BYTES + INVD_BYTES + 16;
     static constexpr int LDS_BYTES = PS_OFF + CAPC * TPX * 8;
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget of one compute unit");
@@ -304,19 +281,13 @@ __device__ __forceinline__ void fma_window(const float (&wr)[Geom<R>::NS][4], co
 // The window of row r+1 is read BEFORE the FMAs of row r (two windows live).  Isolated in
 // tools/arith_probe.hip the phase is LDS-bound: the window reads alone take 0.44 us per step, reads
 // then FMAs row after row 0.78 us (no overlap at all: every wave of the CU is in the same phase), this
-// order 0.62 us; reading every window of the part first 0.70 us.
+// order 0.62 us; reading every window of the part first 0.70 us.  (Radius 5 has had the registers for the second
+// window since the fp32 chains freed the fp64 accumulators: 250 VGPRs.)
 template <int R, int QI, int HALF>
 __device__ __forceinline__ void partial_sums(const float (&wr)[Geom<R>::NS][4], const float *xrow, float (&pf)[4]) {
     constexpr int NR = kRowList<R, QI, HALF>.n;
     if constexpr (HALF != 1) pf[0] = pf[1] = pf[2] = pf[3] = 0.f;
-    if constexpr (NR > 0 && !RCfg<R>::PREFETCH_ROWS) {
-        // row after row
-        static_for<NR>([&](auto ir) __attribute__((always_inline)) {
-            float w1[kMaxWin * 4];
-            load_window<R, QI, kRowList<R, QI, HALF>.dy[decltype(ir)::value]>(w1, xrow);
-            fma_window<R, QI, kRowList<R, QI, HALF>.dy[decltype(ir)::value]>(wr, w1, pf);
-        });
-    } else if constexpr (NR > 0) {
+    if constexpr (NR > 0) {
         float w[2][kMaxWin * 4];
         load_window<R, QI, kRowList<R, QI, HALF>.dy[0]>(w[0], xrow);
         static_for<NR>([&](auto ir) __attribute__((always_inline)) {
@@ -326,6 +297,20 @@ __device__ __forceinline__ void partial_sums(const float (&wr)[Geom<R>::NS][4], 
             fma_window<R, QI, kRowList<R, QI, HALF>.dy[r]>(wr, w[r & 1], pf);
             __builtin_amdgcn_sched_barrier(0);
         });
+    }
+}
+
+// partial_sums of wave part `qi`, one of the parts that a copy of the step loop can hold (resident_kernel: at radius 10 the
+// polling waves are parts 4-7 and the combining waves parts 0-3; radius 5 has parts 0 and 1 in either role, so its last
+// two labels are never taken).  Each part is its own instruction stream.
+template <int R, bool POLLS, int HALF>
+__device__ __forceinline__ void wave_part(int qi, const float (&wr)[Geom<R>::NS][4], const float *xrow, float (&pf)[4]) {
+    constexpr int Q = Geom<R>::Q, Q0 = R == 10 && POLLS ? 4 : 0;
+    switch (qi) {
+        case Q0: partial_sums<R, Q0 % Q, HALF>(wr, xrow, pf); break;
+        case Q0 + 1: partial_sums<R, (Q0 + 1) % Q, HALF>(wr, xrow, pf); break;
+        case Q0 + 2: partial_sums<R, (Q0 + 2) % Q, HALF>(wr, xrow, pf); break;
+        default: partial_sums<R, (Q0 + 3) % Q, HALF>(wr, xrow, pf); break;
     }
 }
 
@@ -587,31 +572,318 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         int t = t_first, c = 0;
         bool fresh = true;             // first step of the job: its input has been there since before the launch
         bool polled = false;           // the poll of the current step is already in flight
-        // One copy of the step loop per wave ROLE (round 4): the polling waves' copy has no stores and the
-        // combining waves' copy no poll registers, so no wait — and no register-allocation accident — of one role can land on
+        // One copy of the step loop per wave role (round 4), POLLS = true: the polling waves' copy (waves 4-7: poll, stage,
+        // arithmetic; never store), false: the combining waves' copy (waves 0-3: arithmetic, combine, store; no poll
+        // registers).  So no wait — and no register-allocation accident — of one role can land on
         // the other; at radius 10 each copy's arithmetic switch holds only its own four parts, so the code does not grow.  Measured
         // (profiles/r04_s10_role_split_ab.txt): default workload +4.2 %, COCO shape +6.1 %; steps 2.12 / 1.49 / 1.38 ->
         // 1.94 / 1.40 / 1.29 us at 1 / 2 / 3 channels; radius 5 (r04_s11): 66 398 -> 68 815 images/s, steps 1.88 / 1.54 -> 1.79 / 1.41 us.
-        if constexpr (RCfg<R>::ROLE_SPLIT) {
-            auto step_loop = [&](auto role_tag) __attribute__((always_inline)) -> bool {
-                constexpr int ROLE = decltype(role_tag)::value;
-                const bool poller_ = ROLE == 1;
-#define IRN_STEP_ABORT return true
-#include "walk_resident_steps.inc"
-#undef IRN_STEP_ABORT
-                return false;
-            };
-            if (poller) {
-                if (step_loop(std::integral_constant<int, 1>{})) return;
-            } else {
-                if (step_loop(std::integral_constant<int, 2>{})) return;
+        // (Split, the radius-5 instantiation spills six loop-invariant registers that the polling waves reload once per step
+        // — their staging addresses — and is still 3.6 % faster: profiles/r04_s11_role_split_radius5_ab.txt.)
+        // Returns true when the job was abandoned (bounded poll): the workgroup then leaves the kernel.
+        auto step_loop = [&](auto polls_tag) __attribute__((always_inline)) -> bool {
+            constexpr bool POLLS = decltype(polls_tag)::value;
+#pragma unroll 1
+            for (int k = 0; k < n_steps; ++k) {
+                const __amdgpu_buffer_rsrc_t src = state_rsrc(t), dst = state_rsrc(t + 1);
+                const bool last = (t + 1 == t_total);
+                const unsigned want = (unsigned)(t + 1);
+                const float ck = cheb ? coef[t + 1] : 0.f;       // coefficient of y_{t+1} in the series (scalar load)
+                const bool rec2 = cheb && t > 0;                 // y_{t+1} = 2 T y_t - y_{t-1}; the first step is y_1 = T y_0
+                float *xsb = xs + (k & 1) * (LH * LW);
+                long long *pslot = nullptr;   // diagnostic time stamps of round 0 for two workgroups
+                if (PROF && prof && round == 0 && tid == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x / 2) && k < 248)
+                    pslot = prof + ((blockIdx.x == 0 ? 0 : 256) + k) * 4;
+                if (PROF && pslot) pslot[0] = wall_clock64();
+
+                // ---- [A] poll + stage x_t[c] of the tile and its halo (polling waves) ----
+                // All tiles of an image run in lock step, so nothing is ready right after our own stores:
+                // an unprefetched poll (C = 1) goes out `poll_delay` behind them so that it samples memory
+                // just after the neighbours' stores have landed.  Polling early is worse than useless
+                // (delay 0: 4.3 us per sweep, delay 20: 2.6 — early loads pull stale lines that the
+                // stores must then displace, and a miss costs a whole ~0.85 us round trip).
+                if (POLLS) {
+                    unsigned pend = vmask;
+                    if (!polled) {
+                        if (!fresh) nap(job_delay);
+                        issue(src, c * ch_bytes);
+                    }
+                    if (timeout_ticks < 0 && k > 0) {       // test hook (option inject_timeout): give up at the first hand-off
+                        if (lane == 0 && atomicCAS(err, 0u, 1u) == 0u) {
+                            err[1] = (unsigned)je.x;
+                            err[2] = (unsigned)t;
+                            err[3] = blockIdx.x;
+                        }
+                        *abort_flag = 1;
+                        pend = 0;
+                    }
+                    long long t_start = 0;
+                    for (;;) {
+#pragma unroll
+                        for (int kk = 0; kk < NK; ++kk) {
+                            if (((pend >> (2 * kk)) & 1u) && va[kk].y == want) {
+                                xsb[btab[kk] & 0xfff] = __uint_as_float(va[kk].x);
+                                pend &= ~(1u << (2 * kk));
+                            }
+                            if (((pend >> (2 * kk)) & 2u) && va[kk].w == want) {
+                                xsb[(btab[kk] & 0xfff) + 1] = __uint_as_float(va[kk].z);
+                                pend &= ~(2u << (2 * kk));
+                            }
+                        }
+                        if (!__builtin_amdgcn_ballot_w64(pend != 0)) break;
+                        issue(src, c * ch_bytes);
+                        const long long now = wall_clock64();
+                        if (t_start == 0) t_start = now;
+                        else if (now - t_start > timeout_ticks ||
+                                 __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+                            if (lane == 0 && atomicCAS(err, 0u, 1u) == 0u) {
+                                err[1] = (unsigned)je.x;
+                                err[2] = (unsigned)t;
+                                err[3] = blockIdx.x;
+                            }
+                            *abort_flag = 1;
+                            break;
+                        }
+                    }
+                }
+                __syncthreads();
+                if (*abort_flag) return true;
+                if (PROF && pslot) pslot[1] = wall_clock64();
+
+                // ---- [B] prefetch: the next step's poll is issued as soon as its input can be there ----
+                // chain cn was stored C-1 steps ago: long ago for C >= 3 (issue before the arithmetic), at the
+                // end of the previous step for C = 2 (issue behind the arithmetic, ~1 us after the stores)
+                int tn = t, cn = c + 1;
+                if (cn == C) {
+                    cn = 0;
+                    ++tn;
+                }
+                polled = C >= 2 && k + 1 < n_steps;
+                if (polled && POLLS && C >= 3) issue(state_rsrc(tn), cn * ch_bytes);
+
+                // ---- [C] partial sums -> LDS -> fp64 combine -> store ----
+                {
+                    const float *xrow = xsb + (ly + H) * LW + lx + HP;
+                    float acc[4];
+                    // the two-channel schedule at radius 10 splits the arithmetic in two so that the polling waves can issue
+                    // the poll in between (~0.7 us behind the stores it waits for); each half starts with a window read that
+                    // nothing overlaps (0.10 us).  The combining waves issue no poll: theirs stays one pipeline.  (Issuing the
+                    // poll from INSIDE an unsplit pipeline in the polling waves costs 12 spilled registers whose reloads share
+                    // vmcnt with the poll: -10 % / -23 %, profiles/r04_s14_mid_issue_ab.txt)
+                    constexpr bool UNSPLIT = R == 10 && !POLLS;
+                    if constexpr (UNSPLIT) {
+                        wave_part<R, POLLS, 2>(qi, wr, xrow, acc);
+                    } else if (R == 10 && C == 2) {
+                        wave_part<R, POLLS, 0>(qi, wr, xrow, acc);
+                        // C = 2: the next step's chain was stored at the end of the previous step; half-way through
+                        // the arithmetic (~0.7 us behind those stores) its poll goes out and flies under the rest
+                        if (polled && POLLS) issue(state_rsrc(tn), cn * ch_bytes);
+                        wave_part<R, POLLS, 1>(qi, wr, xrow, acc);
+                    } else {
+                        wave_part<R, POLLS, 2>(qi, wr, xrow, acc);
+                        if (polled && POLLS && C == 2) issue(state_rsrc(tn), cn * ch_bytes);   // radius 5
+                    }
+                    // the wave's four chains leave as ONE 16-byte LDS write; [buffer][wave][lane][j] fp32
+                    float *partf = reinterpret_cast<float *>(part);
+                    int wl = lane;                         // opaque: the LDS address is rebuilt per step instead of living in a register
+                    asm volatile("" : "+v"(wl));
+                    *reinterpret_cast<f4a *>(partf + (k & 1) * (kWaves * 256) + wv * 256 + wl * 4) = f4a{acc[0], acc[1], acc[2], acc[3]};
+                    __syncthreads();
+                    if (PROF && pslot) pslot[2] = wall_clock64();
+                    // One pixel per combining thread, consecutive threads = consecutive pixels of a tile row (their
+                    // partial sums are contiguous in LDS).  Neighbouring lanes then swap results and the even lane
+                    // stores BOTH granules with one 16-byte store (8-byte sc1 stores are the expensive form, lesson 10;
+                    // folding two pixels per thread instead doubled the combine's latency chain: 0.21 -> 0.40 us).
+                    if constexpr (R == 10) {
+                    auto combine10 = [&](auto lds_tag) __attribute__((always_inline)) {
+                        constexpr bool PS_LDS = decltype(lds_tag)::value;
+                        const int i = tid;                    // G::SLABS * 256 == 256: one pixel per combining thread
+                        const int s2 = i >> 8, prow = (i >> 5) & 7, x = i & 31;
+                        const int py = (s2 / G::C::SL_X) * kSlabH + prow;
+                        const int px = (s2 % G::C::SL_X) * kSlabW + x;
+                        const float *pr = partf + (k & 1) * (kWaves * 256) + (s2 * Q) * 256 + (prow * 8 + (x >> 2)) * 4 + (x & 3);
+                        const int yy = ty0 + py, xx = tx0 + px;
+                        const bool inimg = yy < h && xx < w;
+                        const unsigned o = (unsigned)(yy * w + xx);
+                        // {y_{t-1}, s_t} of this pixel: LDS for the first CAPC channels (read together with the partial sums),
+                        // else the workspace (asked for first: an L2 round trip that the LDS reads below cover)
+                        f2a pv{0.f, 0.f};
+                        if constexpr (PS_LDS) pv = psl[c * G::TPX + i];
+                        else if (inimg) pv = __builtin_bit_cast(f2a, __builtin_amdgcn_raw_buffer_load_b64(prs, (int)o * 8, c * ch_bytes, 0));
+                        // the Q fp32 chains of the pixel: pairwise in fp32 (as close to the exact operator as adding them in
+                        // fp64: the model of tests/test_precision_model.py gives the same 1.5e-6 after 256 sweeps), then centre
+                        // term and normalisation in fp64.  A chain of Q dependent fp64 conversions + additions was most of the
+                        // combine's latency.
+                        float ps[Q];
+#pragma unroll
+                        for (int q = 0; q < Q; ++q) ps[q] = pr[q * 256];
+                        const float centre = xsb[(py + H) * LW + px + HP];
+                        const double inv = invd[i];
+#pragma unroll
+                        for (int span = 1; span < Q; span *= 2)
+#pragma unroll
+                            for (int q = 0; q + span < Q; q += 2 * span) ps[q] = ps[q] + ps[q + span];
+                        const double m = ((double)centre + (double)ps[0]) * inv;
+                        const float res = rec2 ? (float)(2.0 * m - (double)pv.x) : (float)m;
+                        float outv = res;
+                        if (cheb) {
+                            outv = fmaf(ck, res, pv.y);
+                            const f2a nv{centre, outv};
+                            if constexpr (PS_LDS) psl[c * G::TPX + i] = nv;
+                            else if (inimg && !last)
+                                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, nv), prs, (int)o * 8, c * ch_bytes, 0);
+                        }
+                        // neighbour lane's result through a DPP quad permute (lanes 2n <-> 2n+1) instead of an LDS round trip
+                        const float other = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(res), 0xB1, 0xF, 0xF, true));
+                        if (inimg) {
+                            if (last) ((gf_t)I.out)[(unsigned)c * n + o] = outv;
+                            else if ((x & 1) == 0 && xx + 1 < w) {
+                                if (plain_st) st_granule2<0>(dst, (int)o * 8, c * ch_bytes, want + 1, res, other);
+                                else st_granule2(dst, (int)o * 8, c * ch_bytes, want + 1, res, other);
+                            } else if ((x & 1) == 0) {
+                                if (plain_st) st_granule<0>(dst, (int)o * 8, c * ch_bytes, want + 1, res);
+                                else st_granule(dst, (int)o * 8, c * ch_bytes, want + 1, res);
+                            }
+                        }
+                    };
+                    static_assert(R != 10 || G::SLABS * 256 == 256, "one pixel per combining thread at radius 10");
+                    if (!POLLS) {
+                        if (!cheb || c < G::CAPC) combine10(std::true_type{});
+                        else combine10(std::false_type{});
+                    }
+                    } else {
+                        // radius 5 (1024 pixels per tile, 4 per combining thread): a pixel PAIR per thread and iteration
+                        // (0.41 vs 0.75 us for four single pixels); the sums of all iterations are formed before the
+                        // first store so that their LDS reads overlap
+                        constexpr int NIT = G::SLABS * 128 / 256;
+                        // Three phases, each over all iterations: every read is issued before the first dependent operation,
+                        // every write comes last (written iteration by iteration, the LDS write of one iteration's recurrence
+                        // terms kept the next iteration's reads behind it — one array to the compiler — and the phase took
+                        // 0.8 us instead of 0.46).  Two copies of the body, chosen per step: recurrence terms in LDS (the
+                        // common case, no branches inside) or in the workspace (channels beyond CAPC).
+                        // `it_lo .. it_hi` = which of the NIT pixel pairs of a thread this call handles, `tb` = the thread's index among
+                        // the 256 combining threads of the call (single-channel jobs: the polling waves take the second pair, below)
+                        auto combine5 = [&](auto lds_tag, auto lo_tag, auto hi_tag, int tb) __attribute__((always_inline)) {
+                            constexpr bool PS_LDS = decltype(lds_tag)::value;
+                            constexpr int IT_LO = decltype(lo_tag)::value, IT_HI = decltype(hi_tag)::value;
+                            float pa[NIT][Q], pb[NIT][Q], ce0[NIT], ce1[NIT];
+                            double iv0[NIT], iv1[NIT];
+                            f4a pv[NIT];
+#pragma unroll
+                            for (int it = IT_LO; it < IT_HI; ++it) {
+                                const int i = tb + it * 256;
+                                const int s2 = i >> 7, prow = (i >> 4) & 7, x = (i & 15) * 2;
+                                const int py = (s2 / G::C::SL_X) * kSlabH + prow;
+                                const int px = (s2 % G::C::SL_X) * kSlabW + x;
+                                const int ii = s2 * 256 + prow * 32 + x;
+                                if constexpr (PS_LDS) {
+                                    pv[it] = *reinterpret_cast<const f4a *>(psl + c * G::TPX + ii);
+                                } else {
+                                    const int yy = ty0 + py, xx = tx0 + px;
+                                    const bool in0 = yy < h && xx < w, in1 = in0 && xx + 1 < w;
+                                    const unsigned o = (unsigned)(yy * w + xx);
+                                    pv[it] = f4a{0.f, 0.f, 0.f, 0.f};
+                                    if (in1) pv[it] = __builtin_bit_cast(f4a, __builtin_amdgcn_raw_buffer_load_b128(prs, (int)o * 8, c * ch_bytes, 0));
+                                    else if (in0) {
+                                        const f2a p2 = __builtin_bit_cast(f2a, __builtin_amdgcn_raw_buffer_load_b64(prs, (int)o * 8, c * ch_bytes, 0));
+                                        pv[it].x = p2.x;
+                                        pv[it].y = p2.y;
+                                    }
+                                }
+                                const float *pr = partf + (k & 1) * (kWaves * 256) + (s2 * Q) * 256 + (prow * 8 + (x >> 2)) * 4 + (x & 3);
+                                const float *xc = xsb + (py + H) * LW + px + HP;
+#pragma unroll
+                                for (int q = 0; q < Q; ++q) {
+                                    pa[it][q] = pr[q * 256];
+                                    pb[it][q] = pr[q * 256 + 1];
+                                }
+                                ce0[it] = xc[0];
+                                ce1[it] = xc[1];
+                                iv0[it] = invd[ii];
+                                iv1[it] = invd[ii + 1];
+                            }
+                            __builtin_amdgcn_sched_barrier(0);
+                            float r0v[NIT], r1v[NIT], s0v[NIT], s1v[NIT];
+#pragma unroll
+                            for (int it = IT_LO; it < IT_HI; ++it) {
+                                float ps0 = pa[it][0], ps1 = pb[it][0];
+#pragma unroll
+                                for (int q = 1; q < Q; ++q) {
+                                    ps0 += pa[it][q];
+                                    ps1 += pb[it][q];
+                                }
+                                const double m0 = ((double)ce0[it] + (double)ps0) * iv0[it], m1 = ((double)ce1[it] + (double)ps1) * iv1[it];
+                                r0v[it] = rec2 ? (float)(2.0 * m0 - (double)pv[it].x) : (float)m0;
+                                r1v[it] = rec2 ? (float)(2.0 * m1 - (double)pv[it].z) : (float)m1;
+                                s0v[it] = fmaf(ck, r0v[it], pv[it].y);
+                                s1v[it] = fmaf(ck, r1v[it], pv[it].w);
+                            }
+                            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                            for (int it = IT_LO; it < IT_HI; ++it) {
+                                const int i = tb + it * 256;
+                                const int s2 = i >> 7, prow = (i >> 4) & 7, x = (i & 15) * 2;
+                                const int ii = s2 * 256 + prow * 32 + x;
+                                const int yy = ty0 + (s2 / G::C::SL_X) * kSlabH + prow;
+                                const int xx = tx0 + (s2 % G::C::SL_X) * kSlabW + x;
+                                const bool in0 = yy < h && xx < w, in1 = in0 && xx + 1 < w;
+                                const unsigned o = (unsigned)(yy * w + xx);
+                                if (cheb) {
+                                    const f4a nv{ce0[it], s0v[it], ce1[it], s1v[it]};
+                                    if constexpr (PS_LDS) {
+                                        *reinterpret_cast<f4a *>(psl + c * G::TPX + ii) = nv;
+                                    } else if (!last) {
+                                        if (in1) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, nv), prs, (int)o * 8, c * ch_bytes, 0);
+                                        else if (in0) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2v, f2a{ce0[it], s0v[it]}), prs, (int)o * 8, c * ch_bytes, 0);
+                                    }
+                                }
+                                const float r0 = r0v[it], r1 = r1v[it];
+                                if (in0) {
+                                    if (last) {         // the series sum is the result (plain powers: the state itself)
+                                        ((gf_t)I.out)[(unsigned)c * n + o] = cheb ? s0v[it] : r0;
+                                        if (in1) ((gf_t)I.out)[(unsigned)c * n + o + 1] = cheb ? s1v[it] : r1;
+                                    } else if (in1) {
+                                        if (plain_st) st_granule2<0>(dst, (int)o * 8, c * ch_bytes, want + 1, r0, r1);
+                                        else st_granule2(dst, (int)o * 8, c * ch_bytes, want + 1, r0, r1);
+                                    } else {
+                                        if (plain_st) st_granule<0>(dst, (int)o * 8, c * ch_bytes, want + 1, r0);
+                                        else st_granule(dst, (int)o * 8, c * ch_bytes, want + 1, r0);
+                                    }
+                                }
+                            }
+                        };
+                        using I0 = std::integral_constant<int, 0>;
+                        using I1 = std::integral_constant<int, 1>;
+                        using IN = std::integral_constant<int, NIT>;
+                        // Single-channel jobs: nothing is in flight for the polling waves during the combine
+                        // (their next poll goes out behind the barrier that follows these stores), so they take the second pixel
+                        // pair of every thread: 512 threads x 1 pair instead of 256 x 2, and the phase is one chain long, not two.
+                        // (With >= 2 channels a polling wave holds a prefetched poll; stores of its own would put the write-through
+                        // acknowledge in front of it, LESSONS.md 3 — there waves 0-3 combine alone as before.)
+                        constexpr bool SHARE = R == 5 && NIT == 2;
+                        if (SHARE && C == 1) {
+                            if (POLLS) combine5(std::true_type{}, I1{}, IN{}, tid - 256);
+                            else combine5(std::true_type{}, I0{}, I1{}, tid);
+                        } else if (!POLLS) {
+                            if (!cheb || c < G::CAPC) combine5(std::true_type{}, I0{}, IN{}, tid);
+                            else combine5(std::false_type{}, I0{}, IN{}, tid);
+                        }
+                    }
+                }
+                fresh = false;
+                // C = 1: the next poll is timed from our own stores, so every wave has to start its delay
+                // behind them (the waves that do not combine would otherwise poll ~0.2 us early)
+                if (C == 1) __syncthreads();
+                if (PROF && pslot) pslot[3] = wall_clock64();
+                t = tn;
+                c = cn;
             }
+            return false;
+        };
+        if (poller) {
+            if (step_loop(std::true_type{})) return;
         } else {
-            constexpr int ROLE = 0;
-            const bool poller_ = poller;
-#define IRN_STEP_ABORT return
-#include "walk_resident_steps.inc"
-#undef IRN_STEP_ABORT
+            if (step_loop(std::false_type{})) return;
         }
         // a walk cut into several launches (test hook): the LDS-held terms go back to the workspace for the next one
         if (c_lds > 0 && t_first + t_count < t_total) {

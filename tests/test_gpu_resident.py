@@ -171,6 +171,40 @@ def test_full_size_256_sweeps_vs_fp64_oracle_and_streaming_kernel():
     blocked.close()
 
 
+TOL_KERNELS = 2e-6     # the resident kernel against another kernel at the same schedule: the bound of the test above
+
+
+@pytest.mark.parametrize("r,shapes", [
+    (10, [(16, 40, 50), (16, 40, 2)]),      # 4 tiles of 8 x 32; Geom<10>::CAPC = 48: channels 48 and 49
+    (5, [(20, 70, 14), (20, 70, 1)]),       # 4 tiles of 16 x 64; Geom<5>::CAPC = 12: channels 12 and 13
+])
+def test_recurrence_terms_beyond_the_lds_capacity_go_through_the_workspace(r, shapes):
+    """The recurrence's private terms {y_{t-1}, s_t} live in LDS for the first CAPC channels of a job and in the
+    workspace for the rest.  With the recurrence ON (fewer steps than sweeps) the workspace-held terms are loaded and
+    stored by the combine every step, and at a launch boundary the LDS-held ones are written back and reloaded: a walk
+    cut into launches of 5 steps must equal the one-launch walk bit for bit, and both agree with the generic kernel."""
+    n_sw = 256
+    edges, cams = _inputs(shapes, 700)
+    one = _walker(r)
+    assert one.steps(n_sw) < n_sw
+    a = [o.clone() for o in one(edges, cams, beta=10, n_sweeps=n_sw)]
+    one.check()
+    five = _walker(r, sweeps_per_launch=5)
+    b = five(edges, cams, beta=10, n_sweeps=n_sw)
+    five.check()
+    for i in range(len(shapes)):
+        assert torch.equal(a[i], b[i]), (r, shapes[i])
+    gen = _walker(r, variant=0)
+    assert gen.steps(n_sw) == one.steps(n_sw)
+    g = gen(edges, cams, beta=10, n_sweeps=n_sw)
+    gen.check()
+    for i in range(len(shapes)):
+        d = (a[i] - g[i]).abs().max().item()
+        assert d <= TOL_KERNELS, (r, shapes[i], d)
+    for wkr in (one, five, gen):
+        wkr.close()
+
+
 def test_falls_back_when_an_image_does_not_fit_a_round():
     """A 264x264 radius-10 image has 33x9 = 297 tiles > 256 workgroups: the run must still be right
     (streaming sweeps take over) — and so must a narrow image (w < radius)."""

@@ -43,6 +43,68 @@ def test_restatement_pair_classes():
     lab[:, 6:] = 9
     bg, fg, neg = R.pair_labels(lab, pi)
     assert neg.any() and fg.any() and not bg.any() and not (neg & fg).any()
+    # the ignore threshold: 1..20 are classes, 21..255 take no part.  20 | 21 side by side: 20 pairs with 20 as fg, 21 with nothing
+    lab[:] = 20
+    lab[:, 6:] = 21
+    bg, fg, neg = R.pair_labels(lab, pi)
+    flat = lab.reshape(-1)
+    a, b = np.broadcast_to(flat[pi.src_indices][None], bg.shape), flat[pi.dst_indices]
+    assert not bg.any() and not neg.any() and fg.any()
+    assert np.array_equal(fg, (a == 20) & (b == 20)) and (a == 21).any() and ((a == 20) & (b == 21)).any()
+    # 254 behaves as 255: beside background and a class, both maps give the same three masks
+    lab[:] = 0
+    lab[2:, 3:9] = 20
+    lab[:, 5:7] = 254
+    with_254 = R.pair_labels(lab, pi)
+    lab[lab == 254] = 255
+    with_255 = R.pair_labels(lab, pi)
+    assert all(np.array_equal(p, q) for p, q in zip(with_254, with_255))
+    assert all(m.any() for m in with_254) and not (with_254[0] | with_254[1] | with_254[2]).all()
+    # and the first class is a class: 0 | 1 is a negative pair, 1 | 1 a foreground pair
+    lab[:] = 0
+    lab[:, 6:] = 1
+    bg, fg, neg = R.pair_labels(lab, pi)
+    assert bg.any() and fg.any() and neg.any()
+
+
+@pytest.mark.parametrize("shape", tuple(R.DEGENERATE_SEED), ids=lambda s: "r%d_b%d_%dx%d" % s)
+def test_degenerate_inputs_provoke_what_they_are_for(shape):
+    """The second input family at every shape of DEGENERATE_SEED with its seed: all three pair classes, tied path maxima,
+    both edge saturations, residuals of exactly 0 for fg and bg pairs; and the helpers the GPU tests build their per-cell
+    bounds from agree with each other on it."""
+    radius, batch, hp, wp = shape
+    edge, dp, label = R.make_degenerate_inputs(radius, batch, hp, wp, R.DEGENERATE_SEED[shape])
+    assert edge.dtype == np.float32 and dp.dtype == np.float32 and label.dtype == np.uint8
+    assert set(np.unique(edge)) == {0.0, 0.25, 0.5, 0.75, 1.0}
+    assert set(np.unique(dp)) <= {-2.0, -1.0, 0.0, 1.0, 2.0} and set(np.unique(label)) <= {0, 1, 20, 21, 254, 255}
+    ref = R.reference(edge, dp, label, radius, fp32_constants=True)
+    tied, fg_zero, bg_zero = R.degeneracy(edge, dp, label, radius)
+    assert (ref["counts"] > 0).all() and (ref["sums"] > 0).all()
+    assert tied > 0 and fg_zero > 0 and bg_zero > 0
+    # the gradient of the total loss is the gradient under its coefficients (fp64 on both sides: 1e-12 is ~4000 ulps of
+    # slack for the different order of the products), and no cell's exceeds the sum of its |addends|
+    coef = R.total_loss_coefficients(ref["counts"])
+    by_coef = R.reference(edge, dp, label, radius, fp32_constants=True, coef=coef)
+    assert np.allclose(by_coef["grad_edge"], ref["grad_edge"], rtol=1e-12, atol=0)
+    assert np.allclose(by_coef["grad_dp"], ref["grad_dp"], rtol=1e-12, atol=0)
+    mag_e, mag_d = R.addend_magnitudes(edge, dp, label, radius, coef, fp32_constants=True)
+    assert (np.abs(ref["grad_edge"]) <= mag_e * (1 + 1e-12)).all() and (np.abs(ref["grad_dp"]) <= mag_d * (1 + 1e-12)).all()
+    assert (mag_e > 0).any() and (mag_e == 0).any() and (mag_d > 0).any()
+    # the fp32 constants touch the logarithms only: counts and displacement sums are the same numbers
+    exact = R.reference(edge, dp, label, radius)
+    assert np.array_equal(exact["sums"][[3, 4]], ref["sums"][[3, 4]]) and np.array_equal(exact["counts"], ref["counts"])
+
+
+def test_restatement_constants_at_their_fp32_values():
+    """One unequal pair over a path of zeros: -log(1 + 1e-5 - 1) with the constant exact and at its fp32 value."""
+    edge = np.zeros((1, 2, 3), np.float32)
+    label = np.asarray([[[255, 1, 2], [255, 255, 255]]], np.uint8)       # radius 2: one 1x1 source rectangle, the cell (0, 1)
+    dp = np.zeros((1, 2, 2, 3), np.float32)
+    exact, fp32 = R.reference(edge, dp, label, 2), R.reference(edge, dp, label, 2, fp32_constants=True)
+    assert exact["counts"].tolist() == [0, 0, 1] and fp32["counts"].tolist() == [0, 0, 1]
+    assert exact["sums"][2] == pytest.approx(-np.log(1e-5), rel=1e-9)
+    assert fp32["sums"][2] == -np.log(float(np.float32(1.00001) - np.float32(1.0)))
+    assert abs(fp32["sums"][2] - exact["sums"][2]) > 1e-3                # log(1.00136e-5 / 1e-5) = 1.36e-3
 
 
 def test_c_entries_refuse_bad_arguments_before_any_device():

@@ -242,6 +242,43 @@ def test_edge_to_affinity_is_differentiable_like_the_reference(golden, r):
         assert (err <= bound).all(), (rr, float((err / bound).max()))
 
 
+@pytest.mark.parametrize("r,hp,wp", [(3, 11, 37), (5, 13, 41), (10, 19, 52)], ids=lambda v: str(v))
+def test_edge_to_affinity_backward_routes_tied_maxima_like_the_reference(r, hp, wp):
+    """The tie rule of irn_edge_to_affinity_backward: the gradient of a path whose maximum several cells attain goes to the
+    first of them in path order (max_pool2d's rule; the oracle's `np.argmax`).  Smooth edge fields never tie; here the edge
+    takes five values only (a sigmoid saturated in fp32 gives exact 0 and 1), so most paths tie, then one value, so all do.
+    Two images, sources a cell or two over one 8x32 tile."""
+    from irn_amd.misc import indexing
+    rng = np.random.RandomState(40 + r)
+    e_np = rng.choice(np.asarray([0, 0.25, 0.5, 0.75, 1.0], np.float32), (2, hp, wp))
+    n_src = (hp - r + 1) * (wp - 2 * (r - 1))
+    g_np = rng.randn(2, len(O.search_paths_dst(r)[1]), n_src).astype(np.float32)
+
+    def backward(edge_np, gout):
+        e = torch.from_numpy(edge_np).to(_dev()).requires_grad_(True)
+        a = indexing.edge_to_affinity(e[:, None], radius=r, size=(hp, wp))
+        assert tuple(a.shape) == gout.shape
+        (a * torch.from_numpy(gout).to(_dev())).sum().backward()
+        return e.grad.cpu().numpy()
+
+    eps = float(np.finfo(np.float32).eps)
+    want = O.edge_to_affinity_backward(e_np, g_np, r)
+    bound = 64 * eps * np.abs(O.edge_to_affinity_backward(e_np, np.abs(g_np), r)) + 1e-7     # the per-cell bound of the test above
+    err = np.abs(backward(e_np, g_np) - want)
+    print("\nradius %d quantised edge: worst error / bound %.3f" % (r, float((err / bound).max())))
+    assert (err <= bound).all(), ("quantised edge", float((err / bound).max()), int((err > bound).sum()))
+    # constant edge, positive upstream gradient: nothing cancels, so the cells that receive a gradient are the oracle's exactly
+    const, g_pos = np.full_like(e_np, 0.5), np.abs(g_np) + 1.0
+    want = O.edge_to_affinity_backward(const, g_pos, r)
+    got = backward(const, g_pos)
+    print("radius %d constant edge: cells with a gradient %d (oracle %d), differing %d"
+          % (r, int((got != 0).sum()), int((want != 0).sum()), int(((got != 0) != (want != 0)).sum())))
+    assert (want != 0).any() and not (want != 0).all()
+    assert np.array_equal(got != 0, want != 0), "the gradient of a tied path lands on other cells than its first"
+    err = np.abs(got - want)
+    assert (err <= 64 * eps * np.abs(want) + 1e-7).all(), ("constant edge", float(err.max()))
+
+
 @pytest.mark.parametrize("r", [3, 5, 10])
 def test_pair_displacement_forward_backward_vs_reference_autograd(golden, r):
     """irn_pair_displacement / _backward (training seam, net/resnet50_irn.py:177-193) against the reference run

@@ -103,6 +103,12 @@ int irn_pair_displacement_backward(const float *grad_out_dev, int batch, int cha
  * destination.  grad_edge [batch, hp, wp] and grad_dp [batch, 2, hp, wp] are fully written (zero where nothing
  * lands).  The gradients are gathered with float atomics (LDS, then one global atomic per touched cell of a tile):
  * reproducible to rounding, NOT bit for bit.
+ * irn_aff_loss_backward_ordered takes the same arguments and means the same, as a gather: a workgroup owns a tile of
+ * output cells and every thread adds what reaches its cell in the path table's order (direction ascending, path cell
+ * ascending; for grad_dp per direction the cell as source, then as destination).  No atomics of any kind: identical bits
+ * for identical inputs, and an image's gradients do not depend on the images it is batched with.  Every cell of grad_edge
+ * and grad_dp is written exactly once with a plain store, nothing is cleared first.  It differs from
+ * irn_aff_loss_backward by the order of the additions only, and costs more (it re-walks a path for each of its cells).
  * ws: irn_aff_loss_workspace_bytes(batch, hp, wp, radius) bytes of device memory (0 = bad geometry); the backward
  * checks it like the forward and leaves it untouched.  Null pointers, batch outside [1, 65535], radius outside
  * [2, IRN_MAX_RADIUS] (the path table's range), hp <= rf or wp <= 2 rf give IRN_ERR_ARG, a workspace that is too
@@ -112,6 +118,9 @@ int irn_aff_loss_forward(const float *edge, const float *dp, const uint8_t *labe
                          double *sums, int64_t *counts, void *ws, size_t ws_bytes, void *stream);
 int irn_aff_loss_backward(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp, int radius,
                           const float *coef, float *grad_edge, float *grad_dp, void *ws, size_t ws_bytes, void *stream);
+int irn_aff_loss_backward_ordered(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
+                                  int radius, const float *coef, float *grad_edge, float *grad_dp, void *ws, size_t ws_bytes,
+                                  void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Random-walk context  (replaces misc/indexing.py:141-165 `propagate_to_edge` and everything it
@@ -371,6 +380,15 @@ int irn_stem_pool(const float *x_dev, const float *scale_dev, const float *shift
  *   x dev fp32 [n_planes, h, w] -> out dev fp32 [n_planes, h * f, w * f] (16-byte aligned) */
 int irn_upsample_bilinear(const float *x_dev, int64_t n_planes, int h, int w, int factor, int relu, float *out_dev,
                           void *stream);
+/* Its exact adjoint: grad_in[y, x] = sum over the outputs (yo, xo) of grad_out[yo, xo] * (out[yo, xo] > 0, with relu) * the
+ * weight the forward gave input (y, x) in output (yo, xo) — the same fp32 source index and weights, second tap clamped to
+ * the last row / column.  A gather: one thread per input cell, output rows ascending and columns ascending within a row,
+ * fp32 accumulation, one plain store per cell.  No atomics: identical bits for identical inputs (ATen's
+ * upsample_bilinear2d_backward scatters with atomics).
+ *   grad_out dev fp32 [n_planes, h * f, w * f]; out: the forward's output (needed with relu = 1, else may be null)
+ *   -> grad_in dev fp32 [n_planes, h, w], fully written */
+int irn_upsample_bilinear_backward(const float *grad_out_dev, const float *out_dev, int64_t n_planes, int h, int w, int factor,
+                                   int relu, float *grad_in_dev, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Instance front-end

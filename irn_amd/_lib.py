@@ -38,6 +38,7 @@ _SIGS = {
     "irn_aff_loss_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "irn_aff_loss_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "irn_aff_loss_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "irn_aff_loss_backward_ordered": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "irn_walk_create": (i32, [i32, C.POINTER(vp)]),
     "irn_walk_destroy": (i32, [vp]),
     "irn_walk_configure": (i32, [vp, i32, pi32, pi32, pi32, C.POINTER(sz)]),
@@ -72,6 +73,7 @@ _SIGS = {
     "irn_gemm16_nhwc": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, f32, i32, vp, sz, vp]),
     "irn_stem_pool": (i32, [vp, vp, vp, i64, i32, i32, i32, vp, vp]),
     "irn_upsample_bilinear": (i32, [vp, i64, i32, i32, i32, i32, vp, vp]),
+    "irn_upsample_bilinear_backward": (i32, [vp, vp, i64, i32, i32, i32, i32, vp, vp]),
     "irn_find_centroids": (i32, [vp, i32, i32, i32, vp, vp]),
     "irn_cluster_scratch_bytes": (sz, [i32, i32]),
     "irn_cluster_centroids": (i32, [vp, vp, i32, i32, f32, vp, C.POINTER(i32), vp, vp]),

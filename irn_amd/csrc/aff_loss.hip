@@ -14,6 +14,9 @@
 // Backward: gradients of a workgroup meet in LDS tiles (ds_add_f32) and are flushed with one global float atomic per
 // touched cell, like affinity_backward_kernel: the order of those additions is not fixed, so the gradients are
 // reproducible to rounding only, not bit for bit.
+// Ordered backward (irn_aff_loss_backward_ordered): the same gradients as a gather.  One workgroup owns a tile of OUTPUT
+// cells, stages the maps with a halo of radius - 1 on all four sides, and every thread adds what reaches its own cell in
+// the path table's order in a register: no atomic, one plain store per cell, identical bits for identical inputs.
 #include "path_unroll.hpp"
 
 namespace irn {
@@ -271,6 +274,106 @@ __global__ __launch_bounds__(256) void aff_loss_backward_kernel(const float *__r
     }
 }
 
+// Stage rows [ty0, ty0+LH), cols [tx0, tx0+LW) of the grid, ty0 / tx0 possibly negative (the halo above and to the left of
+// an output tile).  Cells outside the grid carry label 255 and are never a source or a destination.
+__device__ __forceinline__ void stage_around(const float *__restrict__ edge, const float *__restrict__ dp,
+                                             const unsigned char *__restrict__ label, int hp, int wp, int ty0, int tx0,
+                                             int LH, int LW, float *t_edge, float *t_dp0, float *t_dp1,
+                                             unsigned char *t_lab) {
+    const long plane = (long)hp * wp;
+    for (int i = threadIdx.x; i < LH * LW; i += 256) {
+        const int ly = i / LW, lx = i - ly * LW;
+        const int gy = ty0 + ly, gx = tx0 + lx;
+        float e = 1.0f, d0 = 0.f, d1 = 0.f;
+        unsigned char l = 255;
+        if (gy >= 0 && gy < hp && gx >= 0 && gx < wp) {
+            const long g = (long)gy * wp + gx;
+            e = edge[g];
+            d0 = dp[g];
+            d1 = dp[plane + g];
+            l = label[g];
+        }
+        t_edge[i] = e;
+        t_dp0[i] = d0;
+        t_dp1[i] = d1;
+        t_lab[i] = l;
+    }
+}
+
+// Ordered backward: the gather form of aff_loss_backward_kernel.  A thread owns the output cell c and walks the path table
+// in its own order (direction d ascending, path cell k ascending).  Table cell (d, k) names the one source s = c - cell(k)
+// whose path (s, d) has c as its k-th cell; it contributes iff s is a source, the pair (s, s + dir(d)) is counted, and c
+// is the FIRST cell of that path attaining its maximum: every earlier cell < edge[c], every later one <= edge[c] (the
+// strict `>` of the scatter).  The path cells of (s, d) lie within radius - 1 of c in both axes, hence the halo.  The
+// displacement gradient of c: per direction, c as the source of (c, d), then c as the destination of (c - dir(d), d).
+// (d, k) is wave-uniform, so the table is read with scalar loads; the walk of a candidate ends at its first refusal.
+__global__ __launch_bounds__(256) void aff_loss_backward_ordered_kernel(
+    const float *__restrict__ edge, const float *__restrict__ dp, const unsigned char *__restrict__ label, int hp, int wp,
+    int radius, int n_dirs, const int *__restrict__ dir_start, const int *__restrict__ cell_dy,
+    const int *__restrict__ cell_dx, const int *__restrict__ dir_dy, const int *__restrict__ dir_dx,
+    const float *__restrict__ coef, float *__restrict__ grad_edge, float *__restrict__ grad_dp) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int halo = radius - 1;
+    const int LW = AFF_TW + 2 * halo, LH = AFF_TH + 2 * halo, cells = LH * LW;
+    float *t_edge = lds, *t_dp0 = lds + cells, *t_dp1 = lds + 2 * cells;
+    unsigned char *t_lab = reinterpret_cast<unsigned char *>(lds + 3 * cells);
+    const int tiles_x = (wp + AFF_TW - 1) / AFF_TW;
+    const int ty0 = ((int)blockIdx.x / tiles_x) * AFF_TH, tx0 = ((int)blockIdx.x % tiles_x) * AFF_TW;
+    const long img = (long)blockIdx.y * hp * wp;
+    stage_around(edge + img, dp + 2 * img, label + img, hp, wp, ty0 - halo, tx0 - halo, LH, LW, t_edge, t_dp0, t_dp1, t_lab);
+    __syncthreads();
+
+    const int ly = threadIdx.x / AFF_TW, lx = threadIdx.x % AFF_TW;
+    const int cy = ty0 + ly, cx = tx0 + lx;
+    if (cy >= hp || cx >= wp) return;
+    const int ctr = (ly + halo) * LW + lx + halo;
+    // the source rectangle: rows [0, sy1), columns [sx0, sx1)
+    const int sy1 = hp - halo, sx0 = halo, sx1 = wp - halo;
+    const float c_bgp = coef[0], c_fgp = coef[1], c_neg = coef[2], c_fg = coef[3], c_bg = coef[4];
+    const float ec = t_edge[ctr], aff = 1.0f - ec;
+    // what c receives as the first maximum of a path, by the kind of pair
+    const float e_bg = c_bgp / (aff + 1e-5f), e_fg = c_fgp / (aff + 1e-5f), e_neg = -c_neg / (1.00001f - aff);
+    const int lc = t_lab[ctr];
+    const float q0 = t_dp0[ctr], q1 = t_dp1[ctr];
+    const bool c_is_src = cy < sy1 && cx >= sx0 && cx < sx1 && lc < kIgnoreFrom;
+    float acc_e = 0.f, acc0 = 0.f, acc1 = 0.f;
+    for (int d = 0; d < n_dirs; ++d) {
+        const int dy = dir_dy[d], dx = dir_dx[d];
+        const int o = dy * LW + dx;
+        const float fy = (float)dy, fx = (float)dx;
+        if (c_is_src && (int)t_lab[ctr + o] == lc) {           // c the source of (c, d): + g
+            const float p0 = q0 - t_dp0[ctr + o], p1 = q1 - t_dp1[ctr + o];
+            acc0 += lc > 0 ? c_fg * sgn(p0 - fy) : c_bg * sgn(p0);
+            acc1 += lc > 0 ? c_fg * sgn(p1 - fx) : c_bg * sgn(p1);
+        }
+        if (lc < kIgnoreFrom && cy - dy >= 0 && cy - dy < sy1 && cx - dx >= sx0 && cx - dx < sx1 && (int)t_lab[ctr - o] == lc) {
+            // c the destination of (c - dir, d): - g, chosen by the source's label (equal to c's)
+            const float p0 = t_dp0[ctr - o] - q0, p1 = t_dp1[ctr - o] - q1;
+            acc0 -= lc > 0 ? c_fg * sgn(p0 - fy) : c_bg * sgn(p0);
+            acc1 -= lc > 0 ? c_fg * sgn(p1 - fx) : c_bg * sgn(p1);
+        }
+        const int k0 = dir_start[d], k1 = dir_start[d + 1];
+        for (int k = k0; k < k1; ++k) {
+            const int ky = cell_dy[k], kx = cell_dx[k];
+            const int sy = cy - ky, sx = cx - kx;
+            if (sy < 0 || sy >= sy1 || sx < sx0 || sx >= sx1) continue;
+            const int s = ctr - (ky * LW + kx);
+            const int a = t_lab[s], b = t_lab[s + o];
+            if (a >= kIgnoreFrom || b >= kIgnoreFrom) continue;
+            bool first = true;
+            for (int j = k0; j < k1 && first; ++j) {
+                const float v = t_edge[s + cell_dy[j] * LW + cell_dx[j]];
+                first = j < k ? v < ec : (j == k || v <= ec);
+            }
+            if (first) acc_e += a != b ? e_neg : (a == 0 ? e_bg : e_fg);
+        }
+    }
+    const long g = (long)cy * wp + cx, plane = (long)hp * wp;
+    grad_edge[img + g] = acc_e;
+    grad_dp[2 * img + g] = acc0;
+    grad_dp[2 * img + plane + g] = acc1;
+}
+
 int n_tiles(int hp, int wp, int radius) {
     const int rf = radius - 1;
     return cdiv(hp - rf, AFF_TH) * cdiv(wp - 2 * rf, AFF_TW);
@@ -347,5 +450,24 @@ extern "C" int irn_aff_loss_backward(const float *edge, const float *dp, const u
                        lds_bytes((AFF_TH + rf) * (AFF_TW + 2 * rf), true), stream, edge, dp, label, hp, wp, radius, tab->n_dirs,
                        tab->dir_start, tab->cell_dy, tab->cell_dx, tab->dir_dy, tab->dir_dx, coef, grad_edge, grad_dp);
     IRN_LAUNCH_CHECK("aff_loss_backward_kernel");
+    return IRN_OK;
+}
+
+extern "C" int irn_aff_loss_backward_ordered(const float *edge, const float *dp, const uint8_t *label, int batch, int hp,
+                                             int wp, int radius, const float *coef, float *grad_edge, float *grad_dp,
+                                             void *ws, size_t ws_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (int rc = check_args("irn_aff_loss_backward_ordered", edge && dp && label && coef && grad_edge && grad_dp, batch, hp,
+                            wp, radius, ws, ws_bytes))
+        return rc;
+    const DeviceTable *tab = nullptr;
+    if (int rc = get_device_table(radius, 0, &tab)) return rc;
+    const int rf = radius - 1;
+    // tiles of output cells over the whole grid: every cell of both gradients is stored once, nothing is cleared first
+    hipLaunchKernelGGL(aff_loss_backward_ordered_kernel, dim3(cdiv(hp, AFF_TH) * cdiv(wp, AFF_TW), batch), dim3(256),
+                       lds_bytes((AFF_TH + 2 * rf) * (AFF_TW + 2 * rf), false), stream, edge, dp, label, hp, wp, radius,
+                       tab->n_dirs, tab->dir_start, tab->cell_dy, tab->cell_dx, tab->dir_dy, tab->dir_dx, coef, grad_edge,
+                       grad_dp);
+    IRN_LAUNCH_CHECK("aff_loss_backward_ordered_kernel");
     return IRN_OK;
 }

@@ -352,6 +352,54 @@ int launch_upsample(const float *x, float *out, unsigned n_planes, int h, int w,
     return IRN_OK;
 }
 
+// The forward's source rows / columns and weights of output index `o` (the same fp32 expressions as upsample_kernel):
+// taps i0 and i1 = i0 + 1 (clamped to the last index `n - 1`) with weights 1 - l and l.  Returns the weight with which input
+// index `i` enters output `o`: both taps where the clamp folds them onto one index.
+__device__ __forceinline__ float upsample_weight(int o, int i, int n, float rscale) {
+    float s = rscale * ((float)o + 0.5f) - 0.5f;
+    s = s < 0.f ? 0.f : s;
+    const int i0 = (int)s;
+    const int i1 = i0 + (i0 < n - 1 ? 1 : 0);
+    const float l = s - (float)i0;
+    return (i0 == i ? 1.f - l : 0.f) + (i1 == i ? l : 0.f);
+}
+
+// Backward of upsample_kernel, as a gather: one thread owns the input cell (y, x) and adds, rows ascending and columns
+// ascending within a row, grad_out (masked by out > 0 behind the ReLU) times the weight the forward gave the cell; one store.
+// Which outputs touch input index i: those whose first tap i0 is i - 1 or i.  In exact arithmetic i0 = floor((o + 0.5) / f
+// - 0.5) lies in [i - 1, i] for f*i - f/2 - 0.5 <= o < f*i + 3f/2 - 0.5 (the clamp at 0 only moves outputs onto i = 0 that
+// the range already holds; the clamp of the second tap adds none).  The loop runs over that range widened by one output on
+// each side, which covers the rounding of the fp32 mapping, and takes the weights from the forward's own expressions:
+// an output outside the true support weighs exactly 0 and is skipped.
+template <bool RELU>
+__global__ __launch_bounds__(256) void upsample_backward_kernel(const float *__restrict__ grad_out, const float *__restrict__ out,
+                                                                float *__restrict__ grad_in, int h, int w, int ho, int wo,
+                                                                int factor, float rscale) {
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
+    const unsigned plane = blockIdx.z;
+    if (x >= w || y >= h) return;
+    const int below = factor / 2 + 2, above = (3 * factor + 1) / 2 + 1;
+    const int yo0 = max(0, factor * y - below), yo1 = min(ho, factor * y + above);
+    const int xo0 = max(0, factor * x - below), xo1 = min(wo, factor * x + above);
+    const float *g = grad_out + (size_t)plane * ho * wo;
+    const float *o = RELU ? out + (size_t)plane * ho * wo : nullptr;
+    float acc = 0.f;
+    for (int yo = yo0; yo < yo1; ++yo) {
+        const float wy = upsample_weight(yo, y, h, rscale);
+        if (wy == 0.f) continue;
+        for (int xo = xo0; xo < xo1; ++xo) {
+            const float wx = upsample_weight(xo, x, w, rscale);
+            if (wx == 0.f) continue;
+            const size_t at = (size_t)yo * wo + xo;
+            float v = g[at];
+            if (RELU) v = o[at] > 0.f ? v : 0.f;
+            acc += v * (wy * wx);
+        }
+    }
+    grad_in[((size_t)plane * h + y) * w + x] = acc;
+}
+
 }  // namespace
 }  // namespace irn
 
@@ -397,6 +445,34 @@ extern "C" int irn_upsample_bilinear(const float *x_dev, int64_t n_planes, int h
         else if (wo % 2 == 0) rc = launch_upsample<2>(xs, os, np, h, w, ho, wo, rscale, relu, (hipStream_t)stream);
         else rc = launch_upsample<1>(xs, os, np, h, w, ho, wo, rscale, relu, (hipStream_t)stream);
         if (rc != IRN_OK) return rc;
+    }
+    return IRN_OK;
+}
+
+extern "C" int irn_upsample_bilinear_backward(const float *grad_out_dev, const float *out_dev, int64_t n_planes, int h, int w,
+                                              int factor, int relu, float *grad_in_dev, void *stream) {
+    using namespace irn;
+    if (!grad_out_dev || !grad_in_dev) return fail(IRN_ERR_ARG, "irn_upsample_bilinear_backward: null pointer");
+    if (relu && !out_dev) return fail(IRN_ERR_ARG, "irn_upsample_bilinear_backward: the ReLU mask needs the forward's output");
+    if (n_planes < 0 || h <= 0 || w <= 0 || factor < 1 || factor > 64)
+        return fail(IRN_ERR_ARG, "irn_upsample_bilinear_backward: non-positive size or factor outside 1..64");
+    if (n_planes == 0) return IRN_OK;
+    const int ho = h * factor, wo = w * factor;
+    if (cdiv(ho, 4) > 65535) return fail(IRN_ERR_ARG, "irn_upsample_bilinear_backward: %d output rows; at most 262140", ho);
+    const float rscale = (float)(1.0 / (double)factor);
+    for (int64_t p0 = 0; p0 < n_planes; p0 += 65535) {
+        const unsigned np = (unsigned)((n_planes - p0) < 65535 ? (n_planes - p0) : 65535);
+        const float *gs = grad_out_dev + (size_t)p0 * ho * wo;
+        const float *os = out_dev ? out_dev + (size_t)p0 * ho * wo : nullptr;
+        float *gi = grad_in_dev + (size_t)p0 * h * w;
+        const dim3 grid((unsigned)cdiv(w, 64), (unsigned)cdiv(h, 4), np);
+        if (relu)
+            hipLaunchKernelGGL(upsample_backward_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, gs, os, gi, h, w, ho, wo,
+                               factor, rscale);
+        else
+            hipLaunchKernelGGL(upsample_backward_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, gs, os, gi, h, w, ho, wo,
+                               factor, rscale);
+        IRN_LAUNCH_CHECK("upsample_backward_kernel");
     }
     return IRN_OK;
 }

@@ -198,11 +198,12 @@ def pair_displacement(disp, radius):
 
 
 class _AffinityDisplacementSums(torch.autograd.Function):
-    """irn_aff_loss_forward with irn_aff_loss_backward as its vector-Jacobian product.  Saves the three maps and nothing
-    else: the backward recomputes path maxima, pair classes and signs from them."""
+    """irn_aff_loss_forward with irn_aff_loss_backward (or, `ordered`, irn_aff_loss_backward_ordered: no atomics, the same
+    bits every time) as its vector-Jacobian product.  Saves the three maps and nothing else: the backward recomputes path
+    maxima, pair classes and signs from them."""
 
     @staticmethod
-    def forward(ctx, edge, dp, label, radius):
+    def forward(ctx, edge, dp, label, radius, ordered=False):
         b, hp, wp = label.shape
         need = lib.irn_aff_loss_workspace_bytes(b, hp, wp, radius)
         if need == 0:
@@ -215,26 +216,26 @@ class _AffinityDisplacementSums(torch.autograd.Function):
             check(lib.irn_aff_loss_forward(edge.data_ptr(), dp.data_ptr(), label.data_ptr(), b, hp, wp, radius,
                                            sums.data_ptr(), counts.data_ptr(), ws.data_ptr(), need, _stream()))
         ctx.save_for_backward(edge, dp, label)
-        ctx.geom = (radius, ws)
+        ctx.geom = (radius, ws, bool(ordered))
         ctx.mark_non_differentiable(counts)
         return sums, counts
 
     @staticmethod
     def backward(ctx, grad_sums, _grad_counts):
         edge, dp, label = ctx.saved_tensors
-        radius, ws = ctx.geom
+        radius, ws, ordered = ctx.geom
         b, hp, wp = label.shape
         coef = grad_sums.to(torch.float32).contiguous()          # stays on the device: nothing synchronises
         grad_edge = torch.empty_like(edge)
         grad_dp = torch.empty_like(dp)
+        backward = lib.irn_aff_loss_backward_ordered if ordered else lib.irn_aff_loss_backward
         with torch.cuda.device(edge.device):
-            check(lib.irn_aff_loss_backward(edge.data_ptr(), dp.data_ptr(), label.data_ptr(), b, hp, wp, radius,
-                                            coef.data_ptr(), grad_edge.data_ptr(), grad_dp.data_ptr(), ws.data_ptr(),
-                                            ws.numel(), _stream()))
-        return grad_edge, grad_dp, None, None
+            check(backward(edge.data_ptr(), dp.data_ptr(), label.data_ptr(), b, hp, wp, radius, coef.data_ptr(),
+                           grad_edge.data_ptr(), grad_dp.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+        return grad_edge, grad_dp, None, None, None
 
 
-def affinity_displacement_sums(edge, dp, label, radius):
+def affinity_displacement_sums(edge, dp, label, radius, ordered=False):
     """The five sums and three counts that the IRNet training losses are formed from (reference
     net/resnet50_irn.py:198-213 + step/train_irn.py:58-64 + voc12/dataloader.py:80-106), in one pass over the three maps:
     no [B, |S|, N] tensor is written, forward or backward (include/irn_hip.h, irn_aff_loss_forward).
@@ -242,7 +243,9 @@ def affinity_displacement_sums(edge, dp, label, radius):
     ``edge``: GPU float [B, Hp, Wp] (or [B, 1, Hp, Wp]), already through the sigmoid; ``dp``: GPU float [B, 2, Hp, Wp];
     ``label``: GPU uint8 [B, Hp, Wp], 0 background, 1..20 a class, >= 21 ignore.  Returns ``(sums, counts)``: fp64 [5]
     (bg / fg positive-affinity loss, negative-affinity loss, fg / bg displacement loss) and int64 [3] (bg, fg, neg
-    pairs), both on the device.  Differentiable w.r.t. ``edge`` and ``dp``."""
+    pairs), both on the device.  Differentiable w.r.t. ``edge`` and ``dp``.  ``ordered``: the backward is the gather
+    (irn_aff_loss_backward_ordered) — bit-identical gradients for identical inputs, whatever an image is batched with —
+    instead of the faster scatter with float atomics, whose gradients are reproducible to rounding only."""
     _need_cuda(edge, "edge")
     _need_cuda(dp, "dp")
     _need_cuda(label, "label")
@@ -253,7 +256,7 @@ def affinity_displacement_sums(edge, dp, label, radius):
         raise ValueError("affinity_displacement_sums: edge %s and dp %s do not fit label %s"
                          % (tuple(edge.shape), tuple(dp.shape), tuple(label.shape)))
     return _AffinityDisplacementSums.apply(edge.reshape(b, hp, wp).contiguous().float(), dp.contiguous().float(),
-                                           label.contiguous(), int(radius))
+                                           label.contiguous(), int(radius), bool(ordered))
 
 
 def affinity_sparse2dense(affinity_sparse, ind_from, ind_to, n_vertices):

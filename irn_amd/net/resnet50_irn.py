@@ -27,7 +27,15 @@ def _head(c_in, c_out, groups, up=0, tail=()):
 class _Head(nn.Sequential):
     """A head's module list with the reference's state-dict keys (net/resnet50_irn.py:21-97).  On the inference path
     (GPU, autograd off) `Upsample -> ReLU` is one pass of a hand-written kernel (`ops.upsample_bilinear`): ATen's generic
-    bilinear kernel took 4 % of the end-to-end time for writing 0.5 GB per batch."""
+    bilinear kernel took 4 % of the end-to-end time for writing 0.5 GB per batch.  Under autograd in the reproducible mode
+    (training: `step/train_irn`) the same kernel runs as a differentiable operator, because its backward is a gather: the
+    backward of `nn.Upsample` on the GPU scatters with float atomics and gives other bits from run to run."""
+
+    @staticmethod
+    def _ordered_backward(x):
+        # the training case has a condition of its own: `_r50._fused` stays the inference path's gate
+        return (_r50.DETERMINISTIC is True and torch.is_grad_enabled() and x.is_cuda and x.dtype == torch.float32
+                and x.is_contiguous())
 
     def forward(self, x):
         mods = list(self)
@@ -43,7 +51,8 @@ class _Head(nn.Sequential):
             i = 1
         while i < len(mods):
             m = mods[i]
-            if (isinstance(m, nn.Upsample) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU) and _r50._fused(x)
+            if (isinstance(m, nn.Upsample) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+                    and (_r50._fused(x) or self._ordered_backward(x))
                     and m.mode == "bilinear" and not m.align_corners and float(m.scale_factor) == int(m.scale_factor)):
                 from .. import ops
                 x = ops.upsample_bilinear(x, int(m.scale_factor), relu=True)
@@ -209,7 +218,9 @@ class AffinityDisplacementLoss(Net):
         ``label`` (uint8 [B, Hp, Wp]) — `forward(x, True)` followed by the masked sums, without any [B, |S|, N] tensor."""
         from ..misc import indexing
         edge_out, dp_out = Net.forward(self, x)
-        s, n = indexing.affinity_displacement_sums(torch.sigmoid(edge_out), dp_out, label, self.path_index.radius)
+        # reproducible mode: the gather backward, the same bits every time; otherwise the faster scatter with float atomics
+        s, n = indexing.affinity_displacement_sums(torch.sigmoid(edge_out), dp_out, label, self.path_index.radius,
+                                                   ordered=_r50.DETERMINISTIC is True)
         n = n.to(torch.float64)
         pos_aff_loss = s[0] / (n[0] + 1e-5) / 2 + s[1] / (n[1] + 1e-5) / 2
         neg_aff_loss = s[2] / (n[2] + 1e-5)

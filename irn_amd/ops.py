@@ -173,13 +173,52 @@ def stem_pool(x, scale, shift):
     return out
 
 
+def _upsample_bilinear_backward(grad_out, out, factor, relu):
+    """irn_upsample_bilinear_backward: the exact adjoint as a gather (no atomics, bit-reproducible).  grad_out: GPU fp32
+    [..., h*factor, w*factor]; out: the forward's output (the ReLU mask) or None -> [..., h, w]."""
+    ho, wo = int(grad_out.shape[-2]), int(grad_out.shape[-1])
+    h, w = ho // factor, wo // factor
+    grad_in = torch.empty(tuple(grad_out.shape[:-2]) + (h, w), dtype=torch.float32, device=grad_out.device)
+    if grad_in.numel():
+        with torch.cuda.device(grad_out.device):
+            check(lib.irn_upsample_bilinear_backward(grad_out.data_ptr(), out.data_ptr() if relu else None, grad_out.numel() // (ho * wo),
+                                                     h, w, factor, 1 if relu else 0, grad_in.data_ptr(), _stream()))
+    return grad_in
+
+
+class _UpsampleBilinear(torch.autograd.Function):
+    """irn_upsample_bilinear with irn_upsample_bilinear_backward as its vector-Jacobian product; behind a ReLU the output is
+    saved for the mask."""
+
+    @staticmethod
+    def forward(ctx, x, factor, relu):
+        out = _upsample_bilinear_forward(x, factor, relu)
+        ctx.factor, ctx.relu = factor, relu
+        if relu:
+            ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        out = ctx.saved_tensors[0] if ctx.relu else None
+        return _upsample_bilinear_backward(grad_out.contiguous().float(), out, ctx.factor, ctx.relu), None, None
+
+
 def upsample_bilinear(x, factor, relu=False):
     """nn.Upsample(scale_factor=factor, mode='bilinear', align_corners=False) (+ ReLU) of the IRNet heads in one pass
-    (irn_upsample_bilinear; reference net/resnet50_irn.py:36-48, :72-84).  x: GPU fp32 [..., h, w] -> [..., h*factor, w*factor]."""
+    (irn_upsample_bilinear; reference net/resnet50_irn.py:36-48, :72-84).  x: GPU fp32 [..., h, w] -> [..., h*factor, w*factor].
+    Differentiable w.r.t. ``x``: under autograd the same forward runs inside an autograd function whose backward is a gather
+    without atomics (irn_upsample_bilinear_backward)."""
     _need_f32_contig(x, "upsample_bilinear: x", 2)
     if int(factor) != factor or not 1 <= factor <= 64:
         raise ValueError("upsample_bilinear: integer factor in 1..64 expected, got %r" % (factor,))
     factor = int(factor)
+    if x.requires_grad and torch.is_grad_enabled():
+        return _UpsampleBilinear.apply(x, factor, bool(relu))
+    return _upsample_bilinear_forward(x, factor, relu)
+
+
+def _upsample_bilinear_forward(x, factor, relu):
     h, w = int(x.shape[-2]), int(x.shape[-1])
     out = torch.empty(tuple(x.shape[:-2]) + (h * factor, w * factor), dtype=torch.float32, device=x.device)
     if out.numel():

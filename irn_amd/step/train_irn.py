@@ -8,7 +8,10 @@ Writes args.irn_weights_name: the state dict the label steps load (EdgeDisplacem
 The reference's loop with two differences.  The loss is `AffinityDisplacementLoss.fused_losses`: one HIP pass from the
 boundary, displacement and reduced label maps to the five sums (irn_amd/csrc/aff_loss.hip), so the loader sends one
 uint8 map per image instead of three [|S|, N] float tensors and no [B, |S|, N] tensor exists on the device.  And there is
-no nn.DataParallel: one device.  Initial weights: `--irn_init_weights` (a state dict, loaded non-strictly: an ImageNet
+no nn.DataParallel: one device.  In the reproducible mode (IRN_DETERMINISTIC, default 1; run_train.py --deterministic) the step
+sets the process's mode before its first convolution like the label steps, the loss back-propagates through its ordered
+gather and the heads' `Upsample -> ReLU` through `ops.upsample_bilinear`: no float atomic takes part in a gradient.
+`--deterministic 0` keeps the faster scatter kernels, whose gradients are reproducible to rounding only.  Initial weights: `--irn_init_weights` (a state dict, loaded non-strictly: an ImageNet
 trunk, or an earlier checkpoint), else the seeded random state of net.weights; nothing is downloaded.
 """
 import os
@@ -66,6 +69,19 @@ def displacement_mean(model, loader, device):
 
 def run(args):
     """Returns {'first_losses': [4 floats], 'steps': int}: the losses of the first step and the steps taken."""
+    from ..net import resnet50 as _r50
+    from . import _common
+    # this IS the caller's process: its own torch.backends.cudnn.deterministic and the trunk's mode are put back on return
+    saved = (torch.backends.cudnn.deterministic, _r50.DETERMINISTIC)
+    try:
+        # before the model is built or a convolution runs: MIOpen keeps the solver it resolved for a problem
+        _common.apply_deterministic_setting()
+        return _run(args)
+    finally:
+        torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
+
+
+def _run(args):
     device = torch.device("cuda", torch.cuda.current_device())
     seed = int(getattr(args, "seed", 0))
     torch.manual_seed(seed)

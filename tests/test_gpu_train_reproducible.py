@@ -1,0 +1,102 @@
+"""The reproducible training step on the GPU (`train_irn` in the mode IRN_DETERMINISTIC=1): with the ordered backward of the
+fused loss and the gather backward of the heads' upsampling inside the model, two identical steps give identical gradient
+bits, and three fresh processes — the loader with and without workers — write the same checkpoint."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _aff_loss_ref as R  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _dev():
+    return torch.device("cuda", 0)
+
+
+@pytest.fixture()
+def reproducible_mode(monkeypatch):
+    """The process's mode as `train_irn.run` establishes it, put back afterwards."""
+    from irn_amd.net import resnet50 as _r50
+    from irn_amd.step import _common
+    saved = (torch.backends.cudnn.deterministic, _r50.DETERMINISTIC)
+    monkeypatch.setenv("IRN_DETERMINISTIC", "1")
+    _common.apply_deterministic_setting()
+    yield
+    torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
+
+
+def test_two_steps_on_the_same_state_give_the_same_gradient_bits(reproducible_mode):
+    import copy
+    from irn_amd.misc import indexing, torchutils
+    from irn_amd.net import weights
+    from irn_amd.net.resnet50_irn import AffinityDisplacementLoss
+    from irn_amd.step import train_irn
+    model = AffinityDisplacementLoss(indexing.PathIndex(10, (24, 24)))
+    model.load_state_dict(weights.random_irn_state(), strict=False)
+    model = model.to(_dev()).train()
+    state = copy.deepcopy(model.state_dict())
+    g = torch.Generator().manual_seed(5)
+    img = torch.randn(2, 3, 96, 96, generator=g).to(_dev())
+    label = torch.from_numpy(R.make_inputs(10, 2, 24, 24, seed=12)[2]).to(_dev())
+    heads = [(k, p) for k, p in model.named_parameters() if k.startswith(("fc_edge", "fc_dp"))]
+    assert len(heads) >= 30
+
+    def step():
+        model.load_state_dict(state)
+        edge_params, dp_params = model.trainable_parameters()
+        opt = torchutils.PolyOptimizer([{"params": edge_params, "lr": 0.1, "weight_decay": 1e-4},
+                                        {"params": dp_params, "lr": 1.0, "weight_decay": 1e-4}], lr=0.1, weight_decay=1e-4, max_step=4)
+        losses = train_irn.train_step(model, opt, img, label)
+        return losses.clone(), {k: p.grad.clone() for k, p in heads}
+
+    l1, g1 = step()
+    l2, g2 = step()
+    assert torch.isfinite(l1).all() and torch.equal(l1, l2)
+    assert all(torch.isfinite(v).all() for v in g1.values()) and any(v.abs().max() > 0 for v in g1.values())
+    differing = [k for k in g1 if not torch.equal(g1[k], g2[k])]
+    assert not differing, "head parameters whose .grad differs between two identical steps: %s" % differing
+
+
+CHILD = """
+import json, sys
+import run_train
+res = run_train.main(sys.argv[2:])["train_irn"]
+json.dump(res, open(sys.argv[1], "w"))
+"""
+
+
+def test_three_processes_write_the_same_checkpoint(tmp_path):
+    """`run_train.py --train_irn_pass True` in three fresh processes — the same seed twice with no loader workers, once with
+    two — writes the same state dict, tensor for tensor, and reports the same first-step losses."""
+    root = str(tmp_path)
+    lst, label_dir = R.write_voc(root, 4)                      # four 120x140 images; crop 96 -> grid 24x24; batch 2 -> 2 steps
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    env.pop("IRN_DETERMINISTIC", None)                         # the default mode is the reproducible one
+    runs = []
+    for tag, workers in (("a", 0), ("b", 0), ("c", 2)):
+        out = os.path.join(root, "sess_" + tag, "res50_irn.pth")
+        argv = ["--voc12_root", root, "--train_list", lst, "--infer_list", lst, "--ir_label_out_dir", label_dir,
+                "--irn_crop_size", "96", "--irn_batch_size", "2", "--irn_num_epoches", "1", "--num_workers", str(workers),
+                "--irn_weights_name", out, "--log_name", os.path.join(root, "log_" + tag), "--train_irn_pass", "True", "--seed", "4"]
+        done = subprocess.run([sys.executable, "-c", CHILD, out + ".json"] + argv, cwd=ROOT, env=env, timeout=300,
+                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert done.returncode == 0, "run %s failed:\n%s" % (tag, done.stdout[-3000:])      # stop at the first failure
+        res = json.load(open(out + ".json"))
+        assert res["steps"] == 2
+        runs.append((tag, res["first_losses"], torch.load(out, map_location="cpu", weights_only=True)))
+    tag0, losses0, state0 = runs[0]
+    assert "mean_shift.running_mean" in state0 and np.isfinite(losses0).all()
+    for tag, losses, state in runs[1:]:
+        print("\nfirst-step losses %s: %s / %s: %s" % (tag0, losses0, tag, losses))
+        assert losses == losses0, "first-step losses of runs %s and %s differ" % (tag0, tag)
+        assert list(state) == list(state0)
+        differing = [k for k in state0 if not torch.equal(state[k], state0[k])]
+        assert not differing, "runs %s and %s differ in %s" % (tag0, tag, differing)

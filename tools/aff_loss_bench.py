@@ -4,7 +4,10 @@ the images/s of the whole training step on synthetic files.  Prints one JSON lin
 
     python tools/aff_loss_bench.py [--batch 32] [--grid 128] [--radius 10] [--iters 20] [--step_images 64]
 
-fused    = indexing.affinity_displacement_sums + the four losses + backward to the edge / displacement maps
+fused    = indexing.affinity_displacement_sums + the four losses + backward to the edge / displacement maps (the scatter
+           with float atomics, `--deterministic 0`)
+fused_ordered = the same with `ordered=True`: the backward is the gather without atomics (the reproducible mode)
+backward_atomic / backward_ordered = the two backward entries alone (irn_aff_loss_backward / _ordered), same inputs
 composed = edge_to_affinity, pair_displacement, the logarithms and absolute values of AffinityDisplacementLoss.forward,
            float masks uploaded from the host as the reference's loader builds them, masked torch.sum, backward
 Times are device events around `iters` iterations after a warm-up, the two paths alternating; the step figure is the
@@ -50,6 +53,21 @@ def main():
         sums, counts = indexing.affinity_displacement_sums(e, d, lab, r)
         R.total_loss(sums, counts).backward()
 
+    def fused_ordered():
+        sums, counts = indexing.affinity_displacement_sums(e, d, lab, r, ordered=True)
+        R.total_loss(sums, counts).backward()
+
+    from irn_amd._lib import _stream, check, lib
+    with torch.no_grad():
+        sums, counts = indexing.affinity_displacement_sums(e, d, lab, r)
+    coef = torch.as_tensor(R.total_loss_coefficients(counts.cpu().numpy()), dtype=torch.float32, device=dev)
+    ws = torch.empty(lib.irn_aff_loss_workspace_bytes(b, g, g, r), dtype=torch.uint8, device=dev)
+    ge, gd = torch.empty_like(e), torch.empty_like(d)
+
+    def backward_entry(entry):
+        return lambda: check(entry(e.data_ptr(), d.data_ptr(), lab.data_ptr(), b, g, g, r, coef.data_ptr(), ge.data_ptr(),
+                                   gd.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
+
     def composed():
         bg, fg, neg = (m.to(dev, non_blocking=True) for m in masks)
         aff = indexing.edge_to_affinity(e.reshape(b, -1), radius=r, size=(g, g))
@@ -61,7 +79,9 @@ def main():
         R.total_loss(sums, torch.stack([bg.sum(), fg.sum(), neg.sum()])).backward()
 
     out = {"batch": b, "grid": g, "radius": r, "iters": args.iters}
-    paths = (("fused", fused), ("composed", composed))
+    paths = (("fused", fused), ("fused_ordered", fused_ordered), ("composed", composed),
+             ("backward_atomic", backward_entry(lib.irn_aff_loss_backward)),
+             ("backward_ordered", backward_entry(lib.irn_aff_loss_backward_ordered)))
     for name, fn in paths:                                   # warm-up, and the peak of one iteration of each
         e.grad = d.grad = None
         torch.cuda.synchronize()

@@ -12,7 +12,8 @@
 //     l1 = src - i0;  l0 = 1 - l1
 //     top = fma(v00, lx0, v01*lx1);  bot = fma(v10, lx0, v11*lx1);  out = fma(ly0, top, ly1*bot)
 // followed by an IEEE division by the global maximum; argmax keeps the FIRST maximum
-// (strict > while scanning channels after the background plane).
+// (strict > while scanning channels after the background plane) and, as torch.argmax does, takes a NaN for
+// the maximum: an all-zero map (0 / 0 in every channel) is labelled keys[0] + 1, not background.
 //
 // Roofline: reads C*h*w floats (L2-resident), writes H*W bytes; ~0.3 MB per 512^2 image against
 // 2.7 GB streamed by the walk — not a bottleneck.
@@ -80,8 +81,9 @@ __device__ __forceinline__ float bilerp(const float *__restrict__ plane, int w, 
 // outputs of cell (k, l) are the rows 4k+2 .. 4k+5 (0 .. 5 for k = 0) and the same in x.  Pass 1 evaluates ONE output
 // per cell (a lower bound L of the maximum); pass 2 evaluates all outputs of the cells whose bound reaches L — a handful
 // around the peak — with the same `bilerp` as the argmax pass, so the maximum is the identical float.  (The one-pass
-// form interpolated every output pixel twice: 0.65 ms of a 31.7 ms step.)  The bound carries a few-ulp margin: the
-// rounded fma chain of `bilerp` can exceed max(cell) in the last bit.
+// form interpolated every output pixel twice: 0.65 ms of a 31.7 ms step.)  The bound carries a few-ulp margin as a
+// precaution only: with the x4 weights (multiples of 1/8) every rounded step of `bilerp` is a monotone rounding of a convex
+// combination, so no output has been seen above max(cell) (tests/test_label_cases_cpu.py checks it on every test input).
 __device__ __forceinline__ int cell_lo(int k) { return k == 0 ? 0 : 4 * k + 2; }
 
 template <int PASS>
@@ -168,7 +170,8 @@ __global__ __launch_bounds__(256) void label_argmax_kernel(const LabelJob *__res
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                if (v[q] > best[q]) {
+                // torch.argmax takes a NaN for the maximum and keeps the first one (an all-zero map: 0 / 0 everywhere)
+                if (v[q] > best[q] || (v[q] != v[q] && best[q] == best[q])) {
                     best[q] = v[q];
                     idx[q] = c + 1;
                 }

@@ -156,6 +156,11 @@ class Lattice:
         return out
 
 
+def random_features(n, d, seed=0, spread=12.0):
+    """n points uniform in [0, spread)^d (float32): a few lattice cells per axis, several points per vertex."""
+    return (np.random.RandomState(100 * d + n + seed).rand(n, d) * spread).astype(F32)
+
+
 class DenseKernel:
     """DIAG_KERNEL + NORMALIZE_SYMMETRIC: norm = 1/sqrt(compute(1) + 1e-20), K(Q) = norm * compute(norm * Q)."""
 

@@ -162,6 +162,76 @@ def test_ir_label_vs_restatement():
     assert not empty.any()
 
 
+def _threshold_cams(h, w, k, fg, bg, seed):
+    """CAMs on a floor of 0.01 whose interesting entries sit exactly on, one ulp below and one ulp above each threshold (and
+    at 0.7); pixel p takes scenario p mod 14: one class at the value, or (second half, k > 1) two classes at the same value."""
+    f32 = np.float32
+    vals = [f32(bg), np.nextafter(f32(bg), f32(-1)), np.nextafter(f32(bg), f32(1)),
+            f32(fg), np.nextafter(f32(fg), f32(-1)), np.nextafter(f32(fg), f32(1)), f32(0.7)]
+    rng = np.random.RandomState(seed)
+    cams = np.full((k, h * w), 0.01, f32)
+    for p in range(h * w):
+        s = p % (2 * len(vals))
+        c1 = int(rng.randint(k))
+        cams[c1, p] = vals[s % len(vals)]
+        if s >= len(vals) and k > 1:
+            cams[(c1 + 1 + int(rng.randint(k - 1))) % k, p] = vals[s % len(vals)]
+    return cams.reshape(k, h, w)
+
+
+@pytest.mark.parametrize("k", [1, 3, 20])
+@pytest.mark.parametrize("h,w", [(7, 5), (64, 48)])
+def test_ir_label_seed_and_finish_rules_exact_without_iterations(h, w, k):
+    """With t = 0 the map is a pure function of k_prologue (seeds: strict >, so a CAM equal to the threshold leaves the
+    background and the first of two equal classes wins), the unary softmax and k_finish (argmax, keys, combination): it
+    equals the restatement exactly, no tie allowance."""
+    from irn_amd import ops, synth
+    fg, bg = 0.30, 0.05
+    img = synth.photo(h, w, seed=3)
+    cams = _threshold_cams(h, w, k, fg, bg, seed=h + k)
+    keys = np.sort(np.random.RandomState(k).choice(20, k, replace=False))
+    got = ops.crf_ir_label(torch.from_numpy(img).to(_dev()), torch.from_numpy(cams).to(_dev()), keys, fg, bg, t=0).cpu().numpy()
+    want = R.ir_label(img, cams, keys, fg, bg, t=0)
+    assert np.array_equal(got, want), (h, w, k, int((got != want).sum()))
+    # the rules, spelt out on the scenarios (pixel p: scenario p mod 14)
+    flat, scen = want.reshape(-1), np.arange(h * w) % 14
+    assert (flat[np.isin(scen, (0, 1, 7, 8))] == 0).all()                    # <= bg threshold: background in both seeds
+    assert (flat[np.isin(scen, (2, 3, 4, 9, 10, 11))] == 255).all()          # above bg, not above fg: unsure
+    seed_fg = R.seed_labels(cams, fg).reshape(-1)
+    sure = np.isin(scen, (5, 6, 12, 13))
+    assert (seed_fg[sure] > 0).all() and np.array_equal(flat[sure], (keys + 1)[seed_fg[sure] - 1])
+    assert np.array_equal(seed_fg[sure], np.argmax(cams.reshape(k, -1)[:, sure] > np.float32(fg), axis=0) + 1)   # the first class wins
+
+
+@pytest.mark.parametrize("n", [1, 37, 3072])
+@pytest.mark.parametrize("d", [1, 3, 4])
+def test_lattice_dimensions_1_3_4_vs_restatement(d, n):
+    from irn_amd import ops
+    feat = R.random_features(n, d)
+    lat = R.Lattice(feat)
+    vals = np.random.RandomState(d + n).randn(n, 3)
+    out, keys, nbr = ops.crf_filter(torch.from_numpy(feat).to(_dev()), torch.from_numpy(vals.astype(np.float32)).to(_dev()),
+                                    return_lattice=True)
+    assert keys.shape[0] == lat.m, (d, n, keys.shape[0], lat.m)
+    assert np.array_equal(keys.cpu().numpy(), lat.keys), (d, n)
+    assert np.array_equal(nbr.cpu().numpy(), lat.nbr), (d, n)
+    want = lat.compute(vals.astype(np.float32).astype(np.float64))
+    err = float(np.abs(out.cpu().numpy() - want).max()) / max(float(np.abs(want).max()), 1e-30)
+    assert err <= 1e-5, (d, n, err)
+
+
+@pytest.mark.parametrize("d,spread", [(1, 1.5e6), (4, 1.5e5)])
+def test_lattice_key_outside_the_packed_range_is_refused(d, spread):
+    """21 (d = 1) and 16 (d = 4) bits per key component: features this wide leave the range, and the call must say so rather
+    than return a lattice of aliased keys."""
+    from irn_amd import ops
+    from irn_amd._lib import IrnHipError
+    feat = R.random_features(37, d, spread=spread)
+    assert np.abs(R.Lattice(feat).keys).max() >= 1 << ((21 if d == 1 else 16) - 1)
+    with pytest.raises(IrnHipError, match=r"exceeds \d+ bits per component"):
+        ops.crf_filter(torch.from_numpy(feat).to(_dev()), torch.ones((37, 1), device=_dev()), return_lattice=True)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the step
 # ---------------------------------------------------------------------------------------------------------------------

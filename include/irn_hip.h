@@ -288,6 +288,33 @@ int irn_msf_pack(const uint8_t *img_dev, int h, int w, int n_scales, const int32
                  const float *lut_dev, float *const *out_dev, void *scratch_dev, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Training-input pipeline of the CAM step, batched  (replaces VOC12ClassificationDataset.__getitem__,
+ * voc12/dataloader.py:129-156 as step/train_cam.py:44-46 configures it: random_resize_long misc/imutils.py:25-34 ->
+ * TorchvisionNormalize -> random_lr_flip -> random_crop / top_left_crop -> HWC_to_CHW) for n_images ragged images in
+ * two launches: a horizontal pass over the source rows the crop shows, a vertical pass that writes every cell of
+ * out fp32 [n_images, 3, crop, crop] once (lut[c * 256 + byte] inside an image's box, 0.0f outside; lut as irn_msf_pack).
+ * Bit-exact against the PIL / numpy pipeline: the taps are Pillow's (irn_bicubic_plan), the arithmetic is integer.
+ *
+ * meta: HOST int32 [meta_words] = n_images descriptors of IRN_AUGMENT_DESC_WORDS words followed by the tap tables:
+ *   word 0 h, 1 w                 source size; the image is u8 [h, w, 3] at byte word 10 of pixels_dev
+ *   2 c_top, 3 c_left, 4 rows, 5 cols   the image's box in the crop
+ *   6 r0, 7 n_rows                source rows [r0, r0 + n_rows) go through the horizontal pass into
+ *                                 scratch u8 [n_rows, cols, 3] at byte word 11 of scratch_dev
+ *   8 kx, 9 ky                    weights per entry of the X / Y table
+ *   12 x_table, 13 y_table        word index in meta of a table: lo [n] | count [n] | weights [n, k]; X has `cols`
+ *                                 entries over source columns (a mirrored image lists them reversed), Y has `rows`
+ *                                 entries over the scratch rows (lo counted from r0);  14, 15 unused
+ * Every bound is checked on the host before any HIP call (lo >= 0, lo + count <= extent, box inside the crop, offsets
+ * inside pixels_bytes / scratch_bytes / meta_words, out_elems >= n_images * 3 * crop^2): a bad descriptor is IRN_ERR_ARG
+ * and nothing is launched.  meta is then copied to meta_dev (>= meta_words words) on the stream; it must stay valid until
+ * that copy has run when it is page-locked memory.  n_images == 0 is IRN_OK without a launch.
+ * ------------------------------------------------------------------------------------------- */
+#define IRN_AUGMENT_DESC_WORDS 16
+int irn_augment_batch(int n_images, int crop, const int32_t *meta, size_t meta_words, const uint8_t *pixels_dev,
+                      size_t pixels_bytes, const float *lut_dev, float *out_dev, size_t out_elems, void *scratch_dev,
+                      size_t scratch_bytes, int32_t *meta_dev, size_t meta_dev_words, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Trunk epilogue  (replaces the elementwise tail of reference net/resnet50.py:34-54 Bottleneck.forward —
  * FixedBatchNorm :11-14, `out += residual`, ReLU — and of the stem :94-97, on the inference path)
  *

@@ -1,6 +1,6 @@
 """Image helpers the hot path needs (API mirror of the corresponding reference misc/imutils.py
 functions; the colouring helpers of that file are out of scope).  The augmentations of the training step
-(`random_scale`, `random_lr_flip`, `random_crop`, `top_left_crop`) take their random source as an argument, a
+(`random_resize_long`, `random_scale`, `random_lr_flip`, `random_crop`, `top_left_crop`) take their random source as an argument, a
 `numpy.random.Generator` or a `random.Random`, instead of the reference's global `random` module: a seed fixes a run.
 """
 import numpy as np
@@ -37,8 +37,24 @@ def random_scale(pair, scale_range, order, rng):
     return tuple(pil_rescale(m, scale, o) for m, o in zip(pair, order))
 
 
+def resize_long_size(h, w, target_long):
+    """Size `random_resize_long` resizes an h x w image to for a drawn long side (misc/imutils.py:27-34: the scale is
+    taken from the longer side, then both sides are rounded as `pil_rescale` rounds them)."""
+    scale = target_long / h if w < h else target_long / w
+    return int(np.round(h * scale)), int(np.round(w * scale))
+
+
+def random_resize_long(img, min_long, max_long, rng):
+    """misc/imutils.py:25-34: the long side drawn from min_long..max_long, both ends included (`random.randint`), bicubic."""
+    target_long = min_long + _below(rng, max_long - min_long + 1)
+    h, w = img.shape[:2]
+    return pil_rescale(img, target_long / h if w < h else target_long / w, 3)
+
+
 def random_lr_flip(pair, rng):
-    """misc/imutils.py:45-53: with probability 1/2 every member is mirrored left-right."""
+    """misc/imutils.py:45-53: with probability 1/2 every member is mirrored left-right.  A single array comes back as one."""
+    if isinstance(pair, np.ndarray):
+        return random_lr_flip((pair,), rng)[0]
     return tuple(np.fliplr(m) for m in pair) if _below(rng, 2) else tuple(pair)
 
 
@@ -56,7 +72,9 @@ def _crop_box(size, cropsize, rng):
 
 def random_crop(pair, cropsize, fill, rng):
     """misc/imutils.py:80-101: the same random box for every member; what the image does not cover holds the member's
-    fill value ((0, 255) for an image and its label)."""
+    fill value ((0, 255) for an image and its label).  A single array (with a single fill value) comes back as one."""
+    if isinstance(pair, np.ndarray):
+        return random_crop((pair,), cropsize, (fill,), rng)[0]
     c_top, c_left, i_top, i_left, rows, cols = _crop_box(pair[0].shape[:2], cropsize, rng)
     out = []
     for m, f in zip(pair, fill):

@@ -1,9 +1,10 @@
-"""CAM classifier backbone (inference form), host side on PyTorch-ROCm.
+"""CAM classifier backbone (inference form, and the classifier's training forward), host side on PyTorch-ROCm.
 
 API mirror of reference net/resnet50_cam.py: module attribute names (``resnet50, stage1..4,
 classifier, backbone, newly_added``) reproduce the reference's state-dict keys, aliases included,
 so ``load_state_dict(torch.load('res50_cam.pth'), strict=True)`` (step/make_cam.py:64) works.
 """
+import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
@@ -13,7 +14,8 @@ N_CLASSES = 20
 
 
 class Net(nn.Module):
-    """Classifier form (net/resnet50_cam.py:7-47); only its parameters matter to the hot path."""
+    """Classifier form (net/resnet50_cam.py:7-47): its parameters are what the label steps load; `forward_train` and
+    `trainable_parameters` are what step/train_cam.py trains them with."""
 
     def __init__(self):
         super().__init__()
@@ -34,6 +36,21 @@ class Net(nn.Module):
         f = self.features(x)
         _r50.end_trunk_pass()
         return self.classifier(f.mean(dim=(2, 3), keepdim=True)).flatten(1)
+
+
+    def forward_train(self, x):
+        """[B,3,H,W] -> logits [B,20] with gradients for stages 3-4 and the classifier only (net/resnet50_cam.py:25-37).
+        The reference detaches stage 2's output and no parameter of stages 1-2 ever receives a gradient; here that half
+        runs under `no_grad` instead — the same function and the same gradients, but no activation of it is saved and it
+        takes the inference path (fused batch norm passes).  Stages 3-4 are composed PyTorch ops under autograd."""
+        with torch.no_grad():
+            x = _r50.to_nchw(self.stage2(self.stage1(x)))
+        f = self.stage4(self.stage3(x))
+        return self.classifier(f.mean(dim=(2, 3), keepdim=True)).flatten(1)
+
+    def trainable_parameters(self):
+        """(backbone parameters, newly added parameters): the optimiser's two groups (net/resnet50_cam.py:45-47)."""
+        return list(self.backbone.parameters()), list(self.newly_added.parameters())
 
 
 class CAM(Net):

@@ -10,6 +10,7 @@ Reference functions mirrored (names kept where the reference has one):
     detect_instance(...)        = step/make_ins_seg_labels.py:82-105
     bicubic_resize(img, size)   = misc/imutils.py:8-17 pil_resize(img, size, order=3)
     msf_pack(img, scales)       = voc12/dataloader.py:191-201 (rescale, normalise, CHW, flip pair)
+    augment_batch(images, ...)  = voc12/dataloader.py:129-156 for a batch (resize_long, normalise, mirror, crop, CHW)
 GPU tensors in, GPU tensors out; no CPU fallback.
 """
 import collections
@@ -284,10 +285,7 @@ def msf_pack(img, scales, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225))
     dev = src.device
     h, w = int(src.shape[0]), int(src.shape[1])
     sizes = [(h, w) if s == 1 else rescale_size(h, w, s) for s in scales]
-    key = ("msf_lut", tuple(mean), tuple(std), str(dev))
-    lut = _LUTS.get(key)
-    if lut is None:
-        lut = _LUTS[key] = torch.from_numpy(normalize_lut(mean, std)).to(dev).contiguous()
+    lut = _lut(mean, std, dev)
     outs = [torch.empty((2, 3, hs, ws), dtype=torch.float32, device=dev) for hs, ws in sizes]
     nbytes = max([lib.irn_bicubic_scratch_bytes(h, w, hs, ws, 3) for hs, ws in sizes] + [1])
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
@@ -296,6 +294,127 @@ def msf_pack(img, scales, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225))
                                i32_array([s[1] for s in sizes]), lut.data_ptr(), ptr_array([o.data_ptr() for o in outs]),
                                scratch.data_ptr(), _stream()))
     return outs
+
+
+def _lut(mean, std, dev):
+    key = ("msf_lut", tuple(mean), tuple(std), str(dev))
+    lut = _LUTS.get(key)
+    if lut is None:
+        lut = _LUTS[key] = torch.from_numpy(normalize_lut(mean, std)).to(dev).contiguous()
+    return lut
+
+
+AUGMENT_DESC_WORDS = 16               # IRN_AUGMENT_DESC_WORDS
+AugmentTables = collections.namedtuple("AugmentTables", "meta src_offsets pixels_bytes scratch_bytes")
+_PLANS = {}
+
+
+def _plan(in_size, out_size):
+    """`bicubic_plan`, kept per size pair (read-only: a training epoch meets a few hundred of them again and again)."""
+    key = (int(in_size), int(out_size))
+    if key not in _PLANS:
+        if len(_PLANS) >= 8192:
+            _PLANS.clear()
+        _PLANS[key] = bicubic_plan(*key)
+    return _PLANS[key]
+
+
+def augment_tables(sizes, params, crop):
+    """Host-only: the descriptors and tap tables `irn_augment_batch` takes (include/irn_hip.h), for images of `sizes[i]` =
+    (h, w) and the draws `params[i]` = (hs, ws, flip, box): the image resized to hs x ws (`rescale_size`), mirrored when
+    `flip`, then `box` = (c_top, c_left, i_top, i_left, rows, cols) of `imutils._crop_box` applied to that.  The X table of
+    an image holds, for column j of its box, the full-axis plan row of resized column i_left + j (ws - 1 - (i_left + j) when
+    mirrored); the Y table the rows i_top .. i_top + rows - 1 with `lo` counted from r0, the first source row any of them
+    reads.  -> AugmentTables(meta int32 [words], byte offset of every image in the packed pixel buffer, its size, the
+    scratch size)."""
+    n = len(sizes)
+    crop = int(crop)
+    desc = np.zeros((n, AUGMENT_DESC_WORDS), np.int32)
+    tabs, src_offsets = [], []
+    word, src, mid = n * AUGMENT_DESC_WORDS, 0, 0
+    for i, ((h, w), (hs, ws, flip, box)) in enumerate(zip(sizes, params)):
+        h, w, hs, ws = int(h), int(w), int(hs), int(ws)
+        c_top, c_left, i_top, i_left, rows, cols = (int(v) for v in box)
+        if (min(h, w, hs, ws, rows, cols) < 1 or min(c_top, c_left, i_top, i_left) < 0 or i_top + rows > hs or i_left + cols > ws
+                or c_top + rows > crop or c_left + cols > crop):
+            raise ValueError("augment_tables: image %d: box %s does not fit a %dx%d image in a %d^2 crop" % (i, tuple(box), hs, ws, crop))
+        xlo, xcnt, xk = _plan(w, ws)
+        ylo, ycnt, yk = _plan(h, hs)
+        xs = np.arange(i_left, i_left + cols)
+        if flip:
+            xs = ws - 1 - xs
+        ys = np.arange(i_top, i_top + rows)
+        r0 = int(ylo[ys].min())
+        r1 = int((ylo[ys] + ycnt[ys]).max())
+        xt = np.concatenate([xlo[xs], xcnt[xs], xk[xs].reshape(-1)])
+        yt = np.concatenate([ylo[ys] - r0, ycnt[ys], yk[ys].reshape(-1)])
+        desc[i, :14] = (h, w, c_top, c_left, rows, cols, r0, r1 - r0, xk.shape[1], yk.shape[1], src, mid, word, word + xt.size)
+        tabs += [xt, yt]
+        src_offsets.append(src)
+        word += xt.size + yt.size
+        src += h * w * 3
+        mid += (r1 - r0) * cols * 3
+    if max(src, mid, word) >= 2 ** 31:
+        raise ValueError("augment_tables: the batch's pixels, intermediates or tables exceed 2^31 - 1")
+    meta = np.concatenate([desc.reshape(-1)] + tabs).astype(np.int32, copy=False) if n else np.zeros(0, np.int32)
+    return AugmentTables(meta, src_offsets, src, mid)
+
+
+_AUG_STAGED = {}          # device -> event behind the last upload out of the page-locked staging buffers
+
+
+def augment_batch(images, params, crop, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), device=None, out=None):
+    """The CAM training step's input batch on the GPU (irn_augment_batch): `images` is a list of uint8 [H,W,3] tensors (on the
+    host or the device, ragged), `params[i]` = (hs, ws, flip, box) the draws of image i as `augment_tables` takes them ->
+    GPU fp32 [B,3,crop,crop], bit-identical to resize (PIL bicubic) -> TorchvisionNormalize -> fliplr -> box into zeros -> CHW
+    per image.  Two launches per batch; host images are packed into one page-locked buffer that is reused across calls and
+    cross in one non-blocking copy, the descriptors and tables in a second one.  `out`: a contiguous fp32 [B,3,crop,crop]
+    GPU tensor to write into (every cell is written)."""
+    n = len(images)
+    for im in images:
+        if not (isinstance(im, torch.Tensor) and im.dtype == torch.uint8 and im.dim() == 3 and im.shape[2] == 3):
+            raise ValueError("augment_batch: uint8 [H,W,3] images expected")
+    if device is None:
+        on_dev = [im.device for im in images if im.is_cuda]
+        device = on_dev[0] if on_dev else torch.device("cuda", torch.cuda.current_device())
+    dev = torch.device(device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    crop = int(crop)
+    if out is None:
+        out = torch.empty((n, 3, crop, crop), dtype=torch.float32, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == dev and out.is_contiguous()
+              and tuple(out.shape) == (n, 3, crop, crop)):
+        raise ValueError("augment_batch: out must be a contiguous fp32 [%d,3,%d,%d] tensor on %s" % (n, crop, crop, dev))
+    if n == 0:
+        return out
+    t = augment_tables([im.shape[:2] for im in images], params, crop)
+    words = int(t.meta.size)
+    with torch.cuda.device(dev):
+        lut = _lut(mean, std, dev)
+        pixels = torch.empty(t.pixels_bytes, dtype=torch.uint8, device=dev)
+        scratch = torch.empty(max(t.scratch_bytes, 1), dtype=torch.uint8, device=dev)
+        meta_dev = torch.empty(words, dtype=torch.int32, device=dev)
+        staged = _AUG_STAGED.get(str(dev))
+        if staged is not None:
+            staged.synchronize()                     # the staging buffers are free again once the last call's copies have run
+        meta_host = _cached("aug_meta", "pinned", words, torch.int32)
+        meta_host[:words].copy_(torch.from_numpy(t.meta))
+        if all(not im.is_cuda for im in images):
+            stage = _cached("aug_pixels", "pinned", t.pixels_bytes, torch.uint8)
+            for im, off in zip(images, t.src_offsets):
+                stage[off:off + im.numel()].copy_(im.reshape(-1))
+            pixels.copy_(stage[:t.pixels_bytes], non_blocking=True)
+        else:
+            for im, off in zip(images, t.src_offsets):
+                pixels[off:off + im.numel()].copy_(im.reshape(-1), non_blocking=True)
+        check(lib.irn_augment_batch(n, crop, C.cast(meta_host.data_ptr(), C.POINTER(C.c_int32)), words, pixels.data_ptr(),
+                                    t.pixels_bytes, lut.data_ptr(), out.data_ptr(), out.numel(), scratch.data_ptr(),
+                                    scratch.numel(), meta_dev.data_ptr(), words, _stream()))
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev))
+        _AUG_STAGED[str(dev)] = done
+    return out
 
 
 def find_centroids_with_refinement(displacement, iterations=300):

@@ -11,6 +11,8 @@ keep the file next to the image lists as the reference does.
 The two datasets of the IRNet training step are here as well: ``VOC12ImageDataset`` (:109-156, the top-left crops of
 the displacement-mean pass) and ``VOC12AffinityDataset`` (:207-273), which hands over the reduced IR label map instead
 of the reference's three [|S|, N] float tensors: the fused loss classifies the pairs on the GPU from that map.
+``VOC12ClassificationDataset`` (:158-173) is the CAM training step's: the reference's augmented item, or (``raw=True``) the
+decoded bytes and the augmentation's draws for `irn_amd.ops.augment_batch`.
 Nothing here touches the GPU, so the datasets are safe in loader worker processes.
 """
 import os
@@ -55,6 +57,98 @@ class TorchvisionNormalize:
         for c in range(3):
             out[..., c] = (arr[..., c] / 255. - self.mean[c]) / self.std[c]
         return out
+
+
+class VOC12ClassificationDataset(Dataset):
+    """item -> {'name': str, 'img': float32 [3, crop, crop], 'label': float32[20]} (voc12/dataloader.py:109-173 as
+    step/train_cam.py:44-52 configures it): the long side resized to a length drawn from ``resize_long`` (both ends
+    included), normalised, mirrored with probability 1/2 when ``hor_flip``, then a random ``crop_size`` box
+    (``crop_method="random"``) or the top-left one, zeros around a smaller image.  The draws of item ``idx`` come from a
+    generator seeded with (seed, epoch, idx), in the reference's order — long side, mirror, box (horizontal, vertical): a run
+    is fixed by its seed whatever the number of loader workers; call ``set_epoch`` before each pass.
+
+    ``raw=True`` makes no resize and no float array in the worker: the item is {'name', 'img': uint8 [H,W,3], 'size': (H, W),
+    'label', 'aug': (hs, ws, flip, box)} with the same draws, and `irn_amd.ops.augment_batch` builds the same floats on the
+    GPU for the whole batch (0.4 MB per image cross to the device instead of 3 MB).  Batch such items with
+    `classification_collate`: the images are ragged."""
+
+    def __init__(self, img_name_list_path, voc12_root, resize_long=None, hor_flip=False, crop_size=None, crop_method=None,
+                 cls_labels=None, raw=False, seed=0, img_normal=TorchvisionNormalize()):
+        self.img_name_list = load_img_name_list(img_name_list_path)
+        self.voc12_root = voc12_root
+        self.resize_long = resize_long
+        self.hor_flip = hor_flip
+        self.crop_size = crop_size
+        self.crop_method = crop_method
+        self.raw = raw
+        self.img_normal = img_normal
+        self.seed = int(seed)
+        self.epoch = 0
+        if raw and not crop_size:
+            raise ValueError("VOC12ClassificationDataset: raw items are made for a fixed crop_size")
+        if cls_labels is None:
+            path = os.path.join(os.path.dirname(os.path.abspath(img_name_list_path)), "cls_labels.npy")
+            cls_labels = np.load(path, allow_pickle=True).item()
+        self.label_list = np.array([cls_labels[int(n)] for n in self.img_name_list], np.float32)
+
+    def set_epoch(self, epoch):
+        self.epoch = int(epoch)
+
+    def __len__(self):
+        return len(self.img_name_list)
+
+    def _rng(self, idx):
+        return np.random.default_rng([self.seed, self.epoch, int(idx)])
+
+    def draw(self, idx, size):
+        """(hs, ws, flip, box) of item `idx` for an image of `size` = (h, w): what the item's augmentation draws."""
+        rng = self._rng(idx)
+        hs, ws = int(size[0]), int(size[1])
+        if self.resize_long:
+            lo, hi = self.resize_long
+            hs, ws = imutils.resize_long_size(hs, ws, lo + imutils._below(rng, hi - lo + 1))
+        flip = imutils._below(rng, 2) if self.hor_flip else 0
+        crop = self.crop_size
+        if self.crop_method == "random":
+            box = imutils._crop_box((hs, ws), crop, rng)
+        else:
+            box = (0, 0, 0, 0, min(crop, hs), min(crop, ws))
+        return hs, ws, flip, box
+
+    def __getitem__(self, idx):
+        name_str = decode_int_filename(self.img_name_list[idx])
+        img = np.asarray(Image.open(get_img_path(name_str, self.voc12_root)).convert("RGB"))
+        label = torch.from_numpy(self.label_list[idx])
+        if self.raw:
+            size = (img.shape[0], img.shape[1])
+            return {"name": name_str, "img": torch.from_numpy(np.array(img)), "size": size, "label": label,
+                    "aug": self.draw(idx, size)}
+        rng = self._rng(idx)
+        if self.resize_long:
+            img = imutils.random_resize_long(img, self.resize_long[0], self.resize_long[1], rng)
+        if self.img_normal:
+            img = self.img_normal(img)
+        if self.hor_flip:
+            img = imutils.random_lr_flip(img, rng)
+        if self.crop_size:
+            if self.crop_method == "random":
+                img = imutils.random_crop(img, self.crop_size, 0, rng)
+            else:
+                img = imutils.top_left_crop(img, self.crop_size, 0)
+        return {"name": name_str, "img": np.ascontiguousarray(imutils.HWC_to_CHW(img)), "label": label}
+
+
+def classification_collate(items):
+    """Batch of VOC12ClassificationDataset items: labels stacked; the images stacked too when they are the reference's
+    [3, crop, crop] floats, kept as a list (with 'size' and 'aug') when they are raw and ragged."""
+    out = {"name": [it["name"] for it in items], "label": torch.stack([it["label"] for it in items])}
+    if "aug" in items[0]:
+        out["img"] = [it["img"] for it in items]
+        out["size"] = [it["size"] for it in items]
+        out["aug"] = [it["aug"] for it in items]
+    else:
+        out["img"] = torch.stack([torch.as_tensor(it["img"]) for it in items])
+    return out
 
 
 class VOC12ClassificationDatasetMSF(Dataset):

@@ -4,10 +4,10 @@ implements: the label-generation steps (make_cam, cam_to_ir_label, make_ins_seg,
 steps that score them (eval_cam, eval_ins_seg, eval_sem_seg) and the COCO export of the instance labels (make_cocoann,
 step/make_cocoann.py; not in the reference's run_sample.py, which leaves it to be run by hand).
 
-The training steps of the reference (train_cam, train_irn) are outside the hot-path scope; their
-`--*_pass` flags are accepted so existing command lines keep working, and asking for one of them
+The training steps of the reference have commands of their own (train_cam: run_train_cam.py, train_irn: run_train.py);
+their `--*_pass` flags are accepted here so existing command lines keep working, and asking for one of them
 is an error rather than a silent skip.  Weights are inputs: --cam_weights_name / --irn_weights_name
-must point at checkpoints written by the reference's training steps (or any state dict with the
+must point at checkpoints written by those commands or by the reference's training steps (any state dict with the
 same keys).
 """
 import argparse
@@ -45,12 +45,12 @@ def build_parser():
     p.add_argument("--conf_fg_thres", default=0.30, type=float, help="cam_to_ir_label: CAM score of a confident foreground seed")
     p.add_argument("--conf_bg_thres", default=0.05, type=float, help="cam_to_ir_label: CAM score below which a seed is background")
     # training / evaluation hyper-parameters of the reference (run_sample.py:25-40): accepted so that an existing
-    # command line keeps parsing; the steps that read them are not part of this build
+    # command line keeps parsing; the steps that read them are run by run_train_cam.py (cam_*) and run_train.py (irn_*)
     for name, default, typ in (("cam_crop_size", 512, int), ("cam_batch_size", 16, int), ("cam_num_epoches", 5, int),
                                ("cam_learning_rate", 0.1, float), ("cam_weight_decay", 1e-4, float),
                                ("irn_crop_size", 512, int), ("irn_batch_size", 32, int), ("irn_num_epoches", 3, int),
                                ("irn_learning_rate", 0.1, float), ("irn_weight_decay", 1e-4, float)):
-        p.add_argument("--" + name, default=default, type=typ, help="accepted and ignored (training side of the reference)")
+        p.add_argument("--" + name, default=default, type=typ, help="read by run_train_cam.py / run_train.py; accepted and ignored here")
     p.add_argument("--cam_eval_thres", default=0.15, type=float,
                    help="eval_cam: background score of the CAM argmax (step/eval_cam.py:15)")
     p.add_argument("--cam_eval_thres_sweep", default=[], type=float, nargs="*",
@@ -120,7 +120,7 @@ def main(argv=None):
         if getattr(args, name):
             raise SystemExit("--train_irn_pass: IRNet training is run by `python run_train.py --train_irn_pass True`, not from here"
                              if name == "train_irn_pass" else
-                             "--%s: this step is not part of the MI355X hot-path build; run it with the reference" % name)
+                             "--%s: CAM training is run by `python run_train_cam.py`, not from here" % name)
     for d in (args.cam_out_dir, args.sem_seg_out_dir, args.ins_seg_out_dir) + ((args.ir_label_out_dir,) if args.cam_to_ir_label_pass else ()):
         os.makedirs(d, exist_ok=True)
     if args.split_gemm is not None:

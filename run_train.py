@@ -6,7 +6,7 @@ asked for, so that labels and weights come out of one command:
 
 The flags are run_sample.py's (the `irn_*` hyper-parameters that run_sample.py accepts and ignores are read here) plus
 --seed and --irn_init_weights.  run_sample.py itself keeps refusing the training passes; `--train_cam_pass` is refused
-here as well: CAM training is not part of this repository.
+here as well: CAM training has a command of its own, `python run_train_cam.py` (irn_amd/step/train_cam.py).
 """
 import os
 
@@ -27,7 +27,7 @@ def main(argv=None):
     """Runs cam_to_ir_label and train_irn where their pass flags ask for them; returns {step name: what the step returned}."""
     args = build_parser().parse_args(argv)
     if args.train_cam_pass:
-        raise SystemExit("--train_cam_pass: CAM training is not part of this repository; run it with the reference")
+        raise SystemExit("--train_cam_pass: CAM training is run by `python run_train_cam.py`, not from here")
     if args.deterministic is not None:
         os.environ["IRN_DETERMINISTIC"] = str(int(args.deterministic))
     pyutils.Logger(args.log_name + ".log")

@@ -1,0 +1,192 @@
+"""The CAM training step on the GPU (irn_amd/step/train_cam.py) at small shapes: crop 64, batch 2, long side 48..96, random
+initial weights.  Two identical steps give identical bits and leave stages 1-2 alone; the training forward with its frozen
+half under `no_grad` is as close to fp64 as the reference's detach formulation; two fresh processes, the loader with and
+without workers, write the same checkpoint; the device and the host input pipelines give the same first loss."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _augment_ref as A  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FROZEN = ("resnet50.conv1.", "resnet50.bn1.", "resnet50.layer1.", "resnet50.layer2.")
+
+
+def _dev():
+    return torch.device("cuda", 0)
+
+
+@pytest.fixture()
+def reproducible_mode(monkeypatch):
+    """The process's mode as `train_cam.run` establishes it, put back afterwards."""
+    from irn_amd.net import resnet50 as _r50
+    from irn_amd.step import _common
+    saved = (torch.backends.cudnn.deterministic, _r50.DETERMINISTIC)
+    monkeypatch.setenv("IRN_DETERMINISTIC", "1")
+    _common.apply_deterministic_setting()
+    yield
+    torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
+
+
+@pytest.fixture(scope="module")
+def batch():
+    g = torch.Generator().manual_seed(5)
+    img = torch.randn(2, 3, 64, 64, generator=g)
+    label = torch.zeros(2, 20)
+    label[0, [3, 7]] = 1
+    label[1, 14] = 1
+    return img, label
+
+
+def test_two_steps_on_the_same_state_give_the_same_bits_and_leave_stages_1_2_alone(reproducible_mode, batch):
+    import copy
+    from irn_amd.misc import torchutils
+    from irn_amd.net import weights
+    from irn_amd.net.resnet50_cam import Net
+    from irn_amd.step import train_cam
+    model = Net()
+    model.load_state_dict(weights.random_cam_state(), strict=False)
+    model = model.to(_dev()).train()
+    state = copy.deepcopy(model.state_dict())
+    img, label = (t.to(_dev()) for t in batch)
+    named = dict(model.named_parameters())
+    frozen = [k for k in named if k.startswith(FROZEN)]
+    trained = [k for k in named if not k.startswith(FROZEN)]
+    assert len(frozen) >= 60 and len(trained) >= 80 and "classifier.weight" in trained
+
+    def step():
+        model.load_state_dict(state)
+        backbone, new = model.trainable_parameters()
+        assert len(backbone) + len(new) == len(named) and len(new) == 1
+        opt = torchutils.PolyOptimizer([{"params": backbone, "lr": 0.1, "weight_decay": 1e-4},
+                                        {"params": new, "lr": 1.0, "weight_decay": 1e-4}], lr=0.1, weight_decay=1e-4, max_step=4)
+        loss = train_cam.train_step(model, opt, img, label)
+        return loss.clone(), {k: named[k].grad.clone() for k in trained}
+
+    l1, g1 = step()
+    assert all(named[k].grad is None for k in frozen)
+    assert all(torch.equal(named[k].detach(), state[k]) for k in frozen), "a stage 1-2 parameter moved"
+    assert any(not torch.equal(named[k].detach(), state[k]) for k in trained)
+    l2, g2 = step()
+    assert torch.isfinite(l1) and torch.equal(l1, l2)
+    assert all(torch.isfinite(v).all() for v in g1.values()) and all(v.abs().max() > 0 for v in g1.values())
+    differing = [k for k in g1 if not torch.equal(g1[k], g2[k])]
+    assert not differing, "parameters whose .grad differs between two identical steps: %s" % differing
+
+
+def _rel(a, b):
+    a, b = a.detach().double().cpu(), b.detach().double().cpu()
+    return float((a - b).norm() / b.norm())
+
+
+def _detach_formulation(model, x):
+    """The reference's forward (net/resnet50_cam.py:25-37): autograd on throughout, stage 2's output detached."""
+    y = model.stage2(model.stage1(x)).detach()
+    f = model.stage4(model.stage3(y))
+    return model.classifier(f.mean(dim=(2, 3), keepdim=True)).flatten(1)
+
+
+def test_frozen_half_under_no_grad_is_as_close_to_fp64_as_the_detach_formulation(reproducible_mode, batch):
+    """Yardstick: fp64 on the CPU, composed ops, `.detach()` behind stage 2.  (A) the same formulation in fp32 on the GPU,
+    (B) `Net.forward_train`.  Measure: relative L2 distance from fp64 of the logits and of classifier.weight.grad;
+    err(B) <= 4 * err(A)."""
+    from irn_amd.net import weights
+    from irn_amd.net.resnet50_cam import Net
+    img, label = batch
+    state = weights.random_cam_state()
+
+    def run(forward, dtype, dev):
+        model = Net()
+        model.load_state_dict(state, strict=False)
+        model = model.to(dev, dtype).train()
+        logits = forward(model, img.to(dev, dtype))
+        F.multilabel_soft_margin_loss(logits, label.to(dev, dtype)).backward()
+        return logits, model.classifier.weight.grad
+
+    l64, g64 = run(_detach_formulation, torch.float64, torch.device("cpu"))
+    la, ga = run(_detach_formulation, torch.float32, _dev())
+    lb, gb = run(lambda m, x: m.forward_train(x), torch.float32, _dev())
+    errs = {"logits": (_rel(la, l64), _rel(lb, l64)), "classifier.weight.grad": (_rel(ga, g64), _rel(gb, g64))}
+    for what, (ea, eb) in errs.items():
+        print("\n%s: relative L2 error against fp64: detach formulation (A) %.3e, forward_train (B) %.3e" % (what, ea, eb))
+    for what, (ea, eb) in errs.items():
+        assert eb <= 4 * ea, "%s: forward_train %.3e against %.3e for the detach formulation" % (what, eb, ea)
+
+
+CHILD = """
+import json, sys
+import run_train_cam
+res = run_train_cam.main(sys.argv[2:])["train_cam"]
+json.dump(res, open(sys.argv[1], "w"))
+"""
+
+
+def _argv(root, lst, out, workers, log, augment="device"):
+    return ["--voc12_root", root, "--train_list", lst, "--val_list", lst, "--cam_crop_size", "64", "--cam_batch_size", "2",
+            "--cam_num_epoches", "1", "--cam_resize_long", "48", "96", "--num_workers", str(workers), "--cam_weights_name", out,
+            "--log_name", log, "--seed", "4", "--cam_augment", augment,
+            # the seeded random weights give logits in the hundreds (first loss ~5e2): at the default rate of 0.1, made for
+            # ImageNet weights, the second step is NaN and nothing could be compared; 1e-5 keeps both steps finite
+            "--cam_learning_rate", "1e-5"]
+
+
+def test_two_processes_write_the_same_checkpoint(tmp_path):
+    """`run_train_cam.py` in two fresh processes with the same seed — the loader without workers and with two, the batch
+    built on the device — writes the same state dict, tensor for tensor; the file is a `Net` state dict that `make_cam`'s
+    loader accepts."""
+    from irn_amd.net import weights
+    from irn_amd.net.resnet50_cam import CAM, Net
+    root = str(tmp_path)
+    lst = A.write_voc(root, 4)                                 # four 120x140 images; batch 2 -> 2 steps
+    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
+    env.pop("IRN_DETERMINISTIC", None)                         # the default mode is the reproducible one
+    runs = []
+    for tag, workers in (("a", 0), ("b", 2)):
+        out = os.path.join(root, "sess_" + tag, "res50_cam")
+        argv = _argv(root, lst, out, workers, os.path.join(root, "log_" + tag))
+        done = subprocess.run([sys.executable, "-c", CHILD, out + ".json"] + argv, cwd=ROOT, env=env, timeout=300,
+                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert done.returncode == 0, "run %s failed:\n%s" % (tag, done.stdout[-3000:])      # stop at the first failure
+        res = json.load(open(out + ".json"))
+        assert res["steps"] == 2 and len(res["val_losses"]) == 1 and np.isfinite(res["val_losses"]).all()
+        assert "validating ... loss:" in done.stdout and "step:    0/    2 loss:" in done.stdout
+        runs.append((res, torch.load(out + ".pth", map_location="cpu", weights_only=True), out + ".pth"))
+    (res0, state0, path0), (res1, state1, _) = runs
+    print("\nfirst loss a: %r / b: %r" % (res0["first_loss"], res1["first_loss"]))
+    assert np.isfinite(res0["first_loss"]) and res0["first_loss"] == res1["first_loss"]
+    assert res0["val_losses"] == res1["val_losses"]
+    assert list(state0) == list(state1) == list(Net().state_dict().keys())
+    assert all(torch.isfinite(v).all() for v in state0.values()), "the run diverged"
+    differing = [k for k in state0 if not torch.equal(state0[k], state1[k])]
+    assert not differing, "the two runs differ in %s" % differing
+    cam = weights.load_checkpoint(CAM, path0, strict=True)
+    assert torch.equal(cam.classifier.weight.detach(), state0["classifier.weight"])
+    initial = weights.random_cam_state()
+    assert not torch.equal(state0["classifier.weight"], initial["classifier.weight"])          # it trained
+    assert torch.equal(state0["resnet50.layer2.0.conv1.weight"], initial["resnet50.layer2.0.conv1.weight"])
+
+
+def test_device_and_host_pipelines_give_the_same_first_loss(tmp_path):
+    import struct
+
+    import run_train_cam
+    from irn_amd.step import train_cam
+    root = str(tmp_path)
+    lst = A.write_voc(root, 4)
+    losses = {}
+    for augment in ("host", "device"):
+        args = run_train_cam.build_parser().parse_args(
+            _argv(root, lst, os.path.join(root, "sess_" + augment, "res50_cam"), 0, os.path.join(root, "log"), augment))
+        res = train_cam.run(args)
+        assert res["steps"] == 2 and np.isfinite(res["first_loss"]) and np.isfinite(res["val_losses"]).all()
+        losses[augment] = struct.pack("<d", res["first_loss"])
+        print("\n%s: first loss %r" % (augment, res["first_loss"]))
+    assert losses["host"] == losses["device"]

@@ -315,6 +315,33 @@ int irn_augment_batch(int n_images, int crop, const int32_t *meta, size_t meta_w
                       size_t scratch_bytes, int32_t *meta_dev, size_t meta_dev_words, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Label half of the IRNet step's (image, label) pair, batched  (replaces the label's share of
+ * VOC12AffinityDataset.__getitem__, voc12/dataloader.py:251-267: random_scale with order 0 misc/imutils.py:36-43 ->
+ * random_lr_flip -> random_crop / top_left_crop with fill 255 -> pil_rescale(label, 0.25, 0)) for n_images ragged
+ * u8 [h, w] IR label maps in ONE launch.  out u8 [n_images, crop / reduce, crop / reduce], every cell written once:
+ * cell (y, x) looks at container position (Y, X) = (reduce * y + reduce / 2, reduce * x + reduce / 2), the cell Pillow's
+ * NEAREST reads when it shrinks crop -> crop / reduce; it is 255 outside the image's box and
+ * label[row_table[Y - c_top], col_table[X - c_left]] inside.  reduce == 1 returns the whole cropped label.
+ * The tables are Pillow's NEAREST source indices of the box's rows and columns (irn_amd.ops.nearest_plan: (int) of a
+ * double that starts at 0.5 * in / out and grows by in / out per cell — not floor((x + 0.5) * in / out)); a mirrored
+ * image lists its columns reversed.  Integers only, no atomics: bit-exact and bit-reproducible.
+ *
+ * meta: HOST int32 [meta_words] = n_images descriptors of IRN_AUGMENT_LABEL_DESC_WORDS words followed by the tables:
+ *   word 0 h, 1 w                 source size; the map is u8 [h, w] at byte word 6 of labels_dev
+ *   2 c_top, 3 c_left, 4 rows, 5 cols   the image's box in the crop (the same box irn_augment_batch takes)
+ *   7 row_table, 8 col_table      word index in meta of an index table: `rows` source rows / `cols` source columns;
+ *                                 9 .. 11 unused
+ * As with irn_augment_batch every bound is checked on the host before any HIP call (table entries inside [0, h) / [0, w),
+ * box inside the crop, offsets inside labels_bytes / meta_words, reduce >= 1 and crop % reduce == 0,
+ * out_elems >= n_images * (crop / reduce)^2): a bad descriptor is IRN_ERR_ARG and nothing is launched.  meta is then copied
+ * to meta_dev (>= meta_words words) on the stream; n_images == 0 is IRN_OK without a launch.
+ * ------------------------------------------------------------------------------------------- */
+#define IRN_AUGMENT_LABEL_DESC_WORDS 12
+int irn_augment_label_batch(int n_images, int crop, int reduce, const int32_t *meta, size_t meta_words,
+                            const uint8_t *labels_dev, size_t labels_bytes, uint8_t *out_dev, size_t out_elems,
+                            int32_t *meta_dev, size_t meta_dev_words, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Trunk epilogue  (replaces the elementwise tail of reference net/resnet50.py:34-54 Bottleneck.forward —
  * FixedBatchNorm :11-14, `out += residual`, ReLU — and of the stem :94-97, on the inference path)
  *

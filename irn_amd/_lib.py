@@ -62,6 +62,7 @@ _SIGS = {
     "irn_bicubic_resize_u8": (i32, [vp, i32, i32, i32, i32, i32, vp, vp, vp]),
     "irn_msf_pack": (i32, [vp, i32, i32, i32, pi32, pi32, vp, ppv, vp, vp]),
     "irn_augment_batch": (i32, [i32, i32, pi32, sz, vp, sz, vp, vp, sz, vp, sz, vp, sz, vp]),
+    "irn_augment_label_batch": (i32, [i32, i32, i32, pi32, sz, vp, sz, vp, sz, vp, sz, vp]),
     "irn_bn_act": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i64, i32, vp]),
     "irn_bn_act_nhwc": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i32, vp]),
     "irn_conv1x1_workspace_bytes": (sz, []),

@@ -17,6 +17,17 @@
 //
 // The kernels trust their tables, so the C entry does not: it takes descriptors and tables as HOST arrays, checks every
 // bound before any HIP call, and only then copies them to the caller's device buffer on the stream and launches.
+//
+// The label half of the IRNet step's (image, label) pair (reference voc12/dataloader.py:251-267: Pillow NEAREST rescale,
+// mirror, the image's crop box into a container of 255, pil_rescale(label, 0.25, 0)) is one gather, augment_label_kernel:
+// output cell (y, x) of the [crop / reduce]^2 map looks at container position (reduce * y + reduce / 2, reduce * x +
+// reduce / 2) — what Pillow's NEAREST reads when it shrinks by an integer factor — which is 255 outside the image's box and
+// source cell (row table[Y - c_top], column table[X - c_left]) inside it.  The tables are Pillow's nearest indices of the
+// box's rows and columns (irn_amd.ops.nearest_plan; a mirrored image lists its columns reversed), so the kernel is integers
+// only, has no atomics and writes every cell once.  64 x 4 threads per block, one thread per cell: a wave is 64 cells of
+// one output row, image and row are uniform per wave, so descriptor and row-table reads are one address for all lanes.
+// The whole output at the training shape (32 x 128 x 128) is 512 KB and the launch is latency-bound: byte stores are
+// left as they are, wider ones would buy nothing measurable.
 #include "common.hpp"
 
 #pragma clang fp contract(off)
@@ -91,6 +102,35 @@ __global__ __launch_bounds__(256) void augment_cols_kernel(const uint8_t *__rest
     for (int c = 0; c < 3; ++c) o[c * plane] = lut[c * 256 + clip8(acc[c])];
 }
 
+constexpr int kLabelDesc = IRN_AUGMENT_LABEL_DESC_WORDS;
+enum { L_H, L_W, L_CTOP, L_CLEFT, L_ROWS, L_COLS, L_SRC, L_RTAB, L_CTAB };
+
+// every cell of out u8 [B, grid, grid]: the label of image z under container position (reduce * y + half, reduce * x + half).
+__global__ __launch_bounds__(256) void augment_label_kernel(const uint8_t *__restrict__ labels, uint8_t *__restrict__ out,
+                                                            const int32_t *__restrict__ meta, int grid, int reduce) {
+    const int32_t *d = meta + (size_t)blockIdx.z * kLabelDesc;
+    const int x = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    if (x >= grid || y >= grid) return;
+    const int half = reduce / 2;
+    const int yy = reduce * y + half - d[L_CTOP], xx = reduce * x + half - d[L_CLEFT];
+    uint8_t v = 255;
+    if (yy >= 0 && yy < d[L_ROWS] && xx >= 0 && xx < d[L_COLS])
+        v = labels[d[L_SRC] + (size_t)meta[d[L_RTAB] + yy] * d[L_W] + meta[d[L_CTAB] + xx]];
+    out[((size_t)blockIdx.z * grid + y) * grid + x] = v;
+}
+
+// One index table of image `i` of the label entry: `n` entries at word `off` of meta, each inside [0, extent).
+int check_index_table(const int32_t *meta, size_t meta_words, int n_images, int i, const char *axis, int64_t off, int n, int extent) {
+    if (off < (int64_t)n_images * kLabelDesc || off + n > (int64_t)meta_words)
+        return fail(IRN_ERR_ARG, "irn_augment_label_batch: image %d: %s table at word %lld (+%d) lies outside the %zu words passed", i, axis,
+                    (long long)off, n, meta_words);
+    for (int j = 0; j < n; ++j)
+        if (meta[off + j] < 0 || meta[off + j] >= extent)
+            return fail(IRN_ERR_ARG, "irn_augment_label_batch: image %d: %s entry %d is %d, outside the %d source cells", i, axis, j,
+                        meta[off + j], extent);
+    return IRN_OK;
+}
+
 // One axis table of image `i`: `n` entries at word `off` of meta, `ksize` weights per entry, taps inside [0, extent).
 int check_table(const int32_t *meta, size_t meta_words, int n_images, int i, const char *axis, int64_t off, int n, int ksize,
                 int extent) {
@@ -154,5 +194,42 @@ extern "C" int irn_augment_batch(int n_images, int crop, const int32_t *meta, si
     IRN_LAUNCH_CHECK("augment_rows_kernel");
     augment_cols_kernel<<<dim3(cdiv(crop, 256), crop, n_images), 256, 0, st>>>((const uint8_t *)scratch_dev, out_dev, meta_dev, lut_dev, crop);
     IRN_LAUNCH_CHECK("augment_cols_kernel");
+    return IRN_OK;
+}
+
+extern "C" int irn_augment_label_batch(int n_images, int crop, int reduce, const int32_t *meta, size_t meta_words,
+                                       const uint8_t *labels_dev, size_t labels_bytes, uint8_t *out_dev, size_t out_elems,
+                                       int32_t *meta_dev, size_t meta_dev_words, void *stream) {
+    if (n_images < 0) return fail(IRN_ERR_ARG, "irn_augment_label_batch: n_images must be >= 0 (got %d)", n_images);
+    if (crop < 1 || crop > 65535) return fail(IRN_ERR_ARG, "irn_augment_label_batch: crop must be in 1..65535 (got %d)", crop);
+    if (reduce < 1 || crop % reduce != 0)
+        return fail(IRN_ERR_ARG, "irn_augment_label_batch: reduce must be >= 1 and divide the crop (got %d for crop %d)", reduce, crop);
+    if (n_images == 0) return IRN_OK;
+    if (!meta || !labels_dev || !out_dev || !meta_dev) return fail(IRN_ERR_ARG, "irn_augment_label_batch: null pointer");
+    if (n_images > 65535) return fail(IRN_ERR_ARG, "irn_augment_label_batch: at most 65535 images per call (got %d)", n_images);
+    if (meta_words < (size_t)n_images * kLabelDesc || meta_words > (size_t)INT32_MAX || meta_dev_words < meta_words)
+        return fail(IRN_ERR_ARG, "irn_augment_label_batch: %zu descriptor / table words for %d images, device buffer of %zu", meta_words,
+                    n_images, meta_dev_words);
+    if (labels_bytes > (size_t)INT32_MAX) return fail(IRN_ERR_ARG, "irn_augment_label_batch: the label buffer is addressed with 31 bits");
+    const int grid = crop / reduce;
+    if (out_elems < (size_t)n_images * grid * grid)
+        return fail(IRN_ERR_ARG, "irn_augment_label_batch: output of %zu bytes for [%d, %d, %d]", out_elems, n_images, grid, grid);
+    for (int i = 0; i < n_images; ++i) {
+        const int32_t *d = meta + (size_t)i * kLabelDesc;
+        const int64_t h = d[L_H], w = d[L_W], rows = d[L_ROWS], cols = d[L_COLS];
+        if (h < 1 || w < 1) return fail(IRN_ERR_ARG, "irn_augment_label_batch: image %d: bad size %lldx%lld", i, (long long)h, (long long)w);
+        if (rows < 1 || cols < 1 || d[L_CTOP] < 0 || d[L_CLEFT] < 0 || d[L_CTOP] + rows > crop || d[L_CLEFT] + cols > crop)
+            return fail(IRN_ERR_ARG, "irn_augment_label_batch: image %d: box %lldx%lld at (%d, %d) is not inside the %d^2 crop", i,
+                        (long long)rows, (long long)cols, d[L_CTOP], d[L_CLEFT], crop);
+        if (d[L_SRC] < 0 || (int64_t)d[L_SRC] + h * w > (int64_t)labels_bytes)
+            return fail(IRN_ERR_ARG, "irn_augment_label_batch: image %d: labels at byte %d (+%lld) lie outside the %zu bytes passed", i,
+                        d[L_SRC], (long long)(h * w), labels_bytes);
+        if (int rc = check_index_table(meta, meta_words, n_images, i, "row", d[L_RTAB], (int)rows, (int)h)) return rc;
+        if (int rc = check_index_table(meta, meta_words, n_images, i, "column", d[L_CTAB], (int)cols, (int)w)) return rc;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    IRN_HIP_TRY(hipMemcpyAsync(meta_dev, meta, meta_words * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    augment_label_kernel<<<dim3(cdiv(grid, 64), cdiv(grid, 4), n_images), dim3(64, 4), 0, st>>>(labels_dev, out_dev, meta_dev, grid, reduce);
+    IRN_LAUNCH_CHECK("augment_label_kernel");
     return IRN_OK;
 }

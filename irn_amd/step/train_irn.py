@@ -2,17 +2,23 @@
 
 Reads  args.train_list, args.infer_list, args.voc12_root, args.ir_label_out_dir (the PNGs of cam_to_ir_label),
        args.irn_crop_size, args.irn_batch_size, args.irn_num_epoches, args.irn_learning_rate, args.irn_weight_decay,
-       args.num_workers, args.seed, args.irn_init_weights
+       args.num_workers, args.seed, args.irn_init_weights, args.irn_augment
 Writes args.irn_weights_name: the state dict the label steps load (EdgeDisplacement through net.weights.load_checkpoint)
 
-The reference's loop with two differences.  The loss is `AffinityDisplacementLoss.fused_losses`: one HIP pass from the
-boundary, displacement and reduced label maps to the five sums (irn_amd/csrc/aff_loss.hip), so the loader sends one
-uint8 map per image instead of three [|S|, N] float tensors and no [B, |S|, N] tensor exists on the device.  And there is
-no nn.DataParallel: one device.  In the reproducible mode (IRN_DETERMINISTIC, default 1; run_train.py --deterministic) the step
-sets the process's mode before its first convolution like the label steps, the loss back-propagates through its ordered
-gather and the heads' `Upsample -> ReLU` through `ops.upsample_bilinear`: no float atomic takes part in a gradient.
-`--deterministic 0` keeps the faster scatter kernels, whose gradients are reproducible to rounding only.  Initial weights: `--irn_init_weights` (a state dict, loaded non-strictly: an ImageNet
-trunk, or an earlier checkpoint), else the seeded random state of net.weights; nothing is downloaded.
+The reference's loop with three differences.  The input batch is built on the GPU (`--irn_augment device`, the default):
+the loader workers hand over the decoded image, the IR label map and the augmentation's draws, and `ops.augment_pair_batch`
+rescales, normalises, mirrors and crops the images and gathers the reduced label maps for the whole batch
+(irn_amd/csrc/augment.hip), bit for bit what the PIL / numpy pipeline gives for the same draws — `--irn_augment host` runs
+that pipeline in the workers instead.  The displacement-mean pass follows the same choice.
+The loss is `AffinityDisplacementLoss.fused_losses`: one HIP pass from the boundary, displacement and reduced label maps to
+the five sums (irn_amd/csrc/aff_loss.hip), so the loader sends one uint8 map per image instead of three [|S|, N] float
+tensors and no [B, |S|, N] tensor exists on the device.  And there is no nn.DataParallel: one device.  In the reproducible
+mode (IRN_DETERMINISTIC, default 1; run_train.py --deterministic) the step sets the process's mode before its first
+convolution like the label steps, the loss back-propagates through its ordered gather and the heads' `Upsample -> ReLU`
+through `ops.upsample_bilinear`: no float atomic takes part in a gradient.  `--deterministic 0` keeps the faster scatter
+kernels, whose gradients are reproducible to rounding only.  Initial weights: `--irn_init_weights` (a state dict, loaded
+non-strictly: an ImageNet trunk, or an earlier checkpoint), else the seeded random state of net.weights; nothing is
+downloaded.
 """
 import os
 
@@ -38,10 +44,43 @@ def build_model(args, path_index):
     return model
 
 
+def device_augment(args):
+    return getattr(args, "irn_augment", "device") != "host"
+
+
+def make_datasets(args, seed):
+    """(train, infer) datasets as step/train_irn.py:33-38, 87-90 configures them; raw items when the batch is built on the GPU."""
+    raw = device_augment(args)
+    train = dataloader.VOC12AffinityDataset(args.train_list, label_dir=args.ir_label_out_dir, voc12_root=args.voc12_root,
+                                            hor_flip=True, crop_size=args.irn_crop_size, crop_method="random",
+                                            rescale=(0.5, 1.5), seed=seed, raw=raw)
+    infer = dataloader.VOC12ImageDataset(args.infer_list, voc12_root=args.voc12_root, crop_size=args.irn_crop_size, raw=raw)
+    return train, infer
+
+
 def _loader(dataset, args, shuffle, seed):
     gen = torch.Generator().manual_seed(seed)
-    return DataLoader(dataset, batch_size=args.irn_batch_size, shuffle=shuffle, drop_last=True, pin_memory=True,
-                      num_workers=max(0, min(int(args.num_workers), MAX_LOADER_WORKERS)), generator=gen)
+    raw = getattr(dataset, "raw", False)
+    return DataLoader(dataset, batch_size=args.irn_batch_size, shuffle=shuffle, drop_last=True, pin_memory=not raw,
+                      num_workers=max(0, min(int(args.num_workers), MAX_LOADER_WORKERS)), generator=gen,
+                      collate_fn=dataloader.affinity_collate if raw else None)
+
+
+def device_batch(pack, crop, device):
+    """Loader batch of the training set -> (GPU fp32 [B,3,crop,crop], GPU uint8 [B,crop/4,crop/4]): raw items through
+    `ops.augment_pair_batch`, the host pipeline's arrays as they are."""
+    if "aug" in pack:
+        from .. import ops
+        return ops.augment_pair_batch(pack["img"], pack["label_map"], pack["aug"], crop, reduce=4, device=device)
+    return pack["img"].to(device, non_blocking=True), pack["label"].to(device, non_blocking=True)
+
+
+def device_images(pack, crop, device):
+    """Loader batch of the displacement-mean pass -> GPU fp32 [B,3,crop,crop]."""
+    if "aug" in pack:
+        from .. import ops
+        return ops.augment_batch(pack["img"], pack["aug"], crop, device=device)
+    return pack["img"].to(device, non_blocking=True)
 
 
 def train_step(model, optimizer, img, label):
@@ -60,7 +99,7 @@ def displacement_mean(model, loader, device):
     means = []
     with torch.no_grad():
         for pack in loader:
-            _, dp = model(pack["img"].to(device, non_blocking=True), False)
+            _, dp = model(device_images(pack, loader.dataset.crop_size, device), False)
             means.append(torch.mean(dp, dim=(0, 2, 3)))
     if not means:
         raise RuntimeError("train_irn: infer_list holds fewer images than one batch of %d" % loader.batch_size)
@@ -89,10 +128,7 @@ def _run(args):
     path_index = indexing.PathIndex(radius=10, default_size=(grid, grid))
     model = build_model(args, path_index)
 
-    train_dataset = dataloader.VOC12AffinityDataset(args.train_list, label_dir=args.ir_label_out_dir,
-                                                    voc12_root=args.voc12_root, hor_flip=True,
-                                                    crop_size=args.irn_crop_size, crop_method="random",
-                                                    rescale=(0.5, 1.5), seed=seed)
+    train_dataset, infer_dataset = make_datasets(args, seed)
     max_step = (len(train_dataset) // args.irn_batch_size) * args.irn_num_epoches
     if max_step == 0:
         raise RuntimeError("train_irn: train_list holds fewer images than one batch of %d" % args.irn_batch_size)
@@ -111,8 +147,7 @@ def _run(args):
         print("Epoch %d/%d" % (ep + 1, args.irn_num_epoches))
         train_dataset.set_epoch(ep)
         for it, pack in enumerate(_loader(train_dataset, args, True, seed + ep)):
-            img = pack["img"].to(device, non_blocking=True)
-            label = pack["label"].to(device, non_blocking=True)
+            img, label = device_batch(pack, args.irn_crop_size, device)
             pending.append(train_step(model, optimizer, img, label))
             if first is None:
                 first = [float(v) for v in pending[0].cpu()]
@@ -127,7 +162,6 @@ def _run(args):
                       "etc:%s" % (timer.str_estimated_complete()), flush=True)
         timer.reset_stage()
 
-    infer_dataset = dataloader.VOC12ImageDataset(args.infer_list, voc12_root=args.voc12_root, crop_size=args.irn_crop_size)
     model.eval()
     # the mean is that of the raw field: in eval mode `mean_shift` subtracts whatever the initial weights carried (zeros in
     # the reference, which always starts from a fresh module; an earlier checkpoint or the seeded random state do not)

@@ -11,6 +11,8 @@ keep the file next to the image lists as the reference does.
 The two datasets of the IRNet training step are here as well: ``VOC12ImageDataset`` (:109-156, the top-left crops of
 the displacement-mean pass) and ``VOC12AffinityDataset`` (:207-273), which hands over the reduced IR label map instead
 of the reference's three [|S|, N] float tensors: the fused loss classifies the pairs on the GPU from that map.
+Both have a ``raw=True`` form: the decoded bytes and the augmentation's draws, for `irn_amd.ops.augment_pair_batch` and
+`augment_batch`.
 ``VOC12ClassificationDataset`` (:158-173) is the CAM training step's: the reference's augmented item, or (``raw=True``) the
 decoded bytes and the augmentation's draws for `irn_amd.ops.augment_batch`.
 Nothing here touches the GPU, so the datasets are safe in loader worker processes.
@@ -203,13 +205,18 @@ class VOC12ClassificationDatasetMSF(Dataset):
 
 class VOC12ImageDataset(Dataset):
     """item -> {'name': str, 'img': float32 [3, crop, crop]}: the normalised image, top-left cropped with zeros around
-    it (voc12/dataloader.py:109-156 as step/train_irn.py:87-90 configures it)."""
+    it (voc12/dataloader.py:109-156 as step/train_irn.py:87-90 configures it).
 
-    def __init__(self, img_name_list_path, voc12_root, crop_size, img_normal=TorchvisionNormalize()):
+    ``raw=True`` hands over {'name', 'img': uint8 [H,W,3], 'size': (H, W), 'aug': (H, W, 0, top-left box)} instead: no
+    resize, no mirror, and `irn_amd.ops.augment_batch` builds the same floats on the GPU (its bicubic plan of equal sizes is
+    the identity).  Batch such items with `affinity_collate`."""
+
+    def __init__(self, img_name_list_path, voc12_root, crop_size, img_normal=TorchvisionNormalize(), raw=False):
         self.img_name_list = load_img_name_list(img_name_list_path)
         self.voc12_root = voc12_root
         self.crop_size = crop_size
         self.img_normal = img_normal
+        self.raw = raw
 
     def __len__(self):
         return len(self.img_name_list)
@@ -217,6 +224,10 @@ class VOC12ImageDataset(Dataset):
     def __getitem__(self, idx):
         name_str = decode_int_filename(self.img_name_list[idx])
         img = np.asarray(Image.open(get_img_path(name_str, self.voc12_root)).convert("RGB"))
+        if self.raw:
+            h, w = img.shape[:2]
+            box = (0, 0, 0, 0, min(self.crop_size, h), min(self.crop_size, w))
+            return {"name": name_str, "img": torch.from_numpy(np.array(img)), "size": (h, w), "aug": (h, w, 0, box)}
         img = imutils.top_left_crop(self.img_normal(img), self.crop_size, 0)
         return {"name": name_str, "img": np.ascontiguousarray(imutils.HWC_to_CHW(img))}
 
@@ -227,10 +238,14 @@ class VOC12AffinityDataset(Dataset):
     image normalised, both mirrored with probability 1/2 and cropped by one random box (fill 0 / 255), the label then
     reduced by ``pil_rescale(label, 0.25, 0)``.  The draws of item ``idx`` come from a generator seeded with
     (seed, epoch, idx): a run is fixed by its seed whatever the number of loader workers; call ``set_epoch`` before each
-    pass."""
+    pass.
+
+    ``raw=True`` makes no resize and no float array in the worker: the item is {'name', 'img': uint8 [H,W,3], 'label_map':
+    uint8 [H,W], 'size': (H, W), 'aug': (hs, ws, flip, box)} with the same draws, and `irn_amd.ops.augment_pair_batch` builds
+    the same floats and the same reduced map on the GPU for the whole batch.  Batch such items with `affinity_collate`."""
 
     def __init__(self, img_name_list_path, label_dir, crop_size, voc12_root, rescale=None,
-                 img_normal=TorchvisionNormalize(), hor_flip=False, crop_method="random", seed=0):
+                 img_normal=TorchvisionNormalize(), hor_flip=False, crop_method="random", seed=0, raw=False):
         self.img_name_list = load_img_name_list(img_name_list_path)
         self.voc12_root = voc12_root
         self.label_dir = label_dir
@@ -241,6 +256,7 @@ class VOC12AffinityDataset(Dataset):
         self.crop_method = crop_method
         self.seed = int(seed)
         self.epoch = 0
+        self.raw = raw
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
@@ -248,11 +264,36 @@ class VOC12AffinityDataset(Dataset):
     def __len__(self):
         return len(self.img_name_list)
 
+    def _rng(self, idx):
+        return np.random.default_rng([self.seed, self.epoch, int(idx)])
+
+    def draw(self, idx, size):
+        """(hs, ws, flip, box) of item `idx` for an image of `size` = (h, w): what the item's augmentation draws, in the order
+        of `__getitem__` — scale, mirror, box (horizontal, vertical)."""
+        rng = self._rng(idx)
+        hs, ws = int(size[0]), int(size[1])
+        if self.rescale:
+            scale = self.rescale[0] + imutils._uniform(rng) * (self.rescale[1] - self.rescale[0])
+            hs, ws = int(np.round(hs * scale)), int(np.round(ws * scale))          # as pil_rescale rounds them
+        flip = imutils._below(rng, 2) if self.hor_flip else 0
+        crop = self.crop_size
+        if self.crop_method == "random":
+            box = imutils._crop_box((hs, ws), crop, rng)
+        else:
+            box = (0, 0, 0, 0, min(crop, hs), min(crop, ws))
+        return hs, ws, flip, box
+
     def __getitem__(self, idx):
         name_str = decode_int_filename(self.img_name_list[idx])
-        rng = np.random.default_rng([self.seed, self.epoch, int(idx)])
         img = np.asarray(Image.open(get_img_path(name_str, self.voc12_root)).convert("RGB"))
         label = np.asarray(Image.open(os.path.join(self.label_dir, name_str + ".png")))
+        if self.raw:
+            size = (img.shape[0], img.shape[1])
+            if label.dtype != np.uint8 or label.shape != size:
+                raise ValueError("VOC12AffinityDataset: %s: a %s %s label map for a %dx%d image" % ((name_str, label.dtype, label.shape) + size))
+            return {"name": name_str, "img": torch.from_numpy(np.array(img)), "label_map": torch.from_numpy(np.array(label)),
+                    "size": size, "aug": self.draw(idx, size)}
+        rng = self._rng(idx)
         if self.rescale:
             img, label = imutils.random_scale((img, label), self.rescale, (3, 0), rng)
         if self.img_normal:
@@ -265,3 +306,14 @@ class VOC12AffinityDataset(Dataset):
             img, label = imutils.top_left_crop(img, self.crop_size, 0), imutils.top_left_crop(label, self.crop_size, 255)
         reduced = imutils.pil_rescale(np.ascontiguousarray(label), 0.25, 0)
         return {"name": name_str, "img": np.ascontiguousarray(imutils.HWC_to_CHW(img)), "label": np.array(reduced)}       # (a copy: PIL hands out read-only memory)
+
+
+def affinity_collate(items):
+    """Batch of raw VOC12AffinityDataset / VOC12ImageDataset items: the ragged images (and label maps) stay lists, with
+    'size' and 'aug' beside them; items of the reference's form go through torch's default collate."""
+    if "aug" not in items[0]:
+        return torch.utils.data.default_collate(items)
+    out = {k: [it[k] for it in items] for k in ("name", "img", "size", "aug")}
+    if "label_map" in items[0]:
+        out["label_map"] = [it["label_map"] for it in items]
+    return out

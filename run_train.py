@@ -5,7 +5,7 @@ asked for, so that labels and weights come out of one command:
     python run_train.py --voc12_root VOC2012 --cam_to_ir_label_pass True --train_irn_pass True
 
 The flags are run_sample.py's (the `irn_*` hyper-parameters that run_sample.py accepts and ignores are read here) plus
---seed and --irn_init_weights.  run_sample.py itself keeps refusing the training passes; `--train_cam_pass` is refused
+--seed, --irn_init_weights and --irn_augment.  run_sample.py itself keeps refusing the training passes; `--train_cam_pass` is refused
 here as well: CAM training has a command of its own, `python run_train_cam.py` (irn_amd/step/train_cam.py).
 """
 import os
@@ -20,6 +20,10 @@ def build_parser():
     p.add_argument("--irn_init_weights", default=None, type=str,
                    help="state dict the IRNet starts from, loaded non-strictly (an ImageNet ResNet-50 trunk, an earlier "
                         "checkpoint); unset: seeded random weights.  Nothing is downloaded")
+    p.add_argument("--irn_augment", default="device", choices=("device", "host"),
+                   help="device: the loader hands over bytes, the IR label map and the draws, the (image, label) batch is "
+                        "rescaled / mirrored / cropped on the GPU (bit-identical); host: the PIL / numpy pipeline in the "
+                        "loader workers")
     return p
 
 

@@ -1,0 +1,172 @@
+#!/usr/bin/env python3
+"""The IRNet training step's input pipeline and its step rate on synthetic VOC-size images.  Prints one JSON line per section.
+
+    python tools/train_irn_bench.py [--images 128] [--batch 32] [--crop 512] [--reps 20] [--warmup 3] [--steps 20] [--workers 8]
+
+`augment_pair`: `ops.augment_pair_batch` on batches of `--batch` decoded images and IR label maps held on the host (what the
+step does: staging, one upload, three launches) — the device time between two events around the call and the host time of
+the call, median over `--reps` calls after one warm call per batch; and the same with the inputs already on the device (the
+kernels and the device-side packing alone).  `host_pipeline`: the PIL / numpy augmentation of one decoded pair on one CPU
+thread, median per image.  `step`: images/s of `train_irn`'s own loop (loader with `--workers` processes, batch on the device,
+forward, fused loss, backward, update) over `--steps` steps after `--warmup` of ONE pass over the list (each image is named
+several times) — the model is built, MIOpen's first-use searches have run and the loader's workers have started before the
+clock starts — with `--irn_augment device` and `host` alternating `--rounds` times; the clock stops behind a device
+synchronise.  Needs a GPU: there is no fallback.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from irn_amd import synth  # noqa: E402
+
+
+def write_tree(root, n, repeat=1):
+    """n synthetic VOC-size JPEGs with IR label PNGs (0 / class + 1 / 255 in 16-pixel blocks); the list names each `repeat`
+    times, so that one pass over it is long enough to time without a loader start inside; -> (list file, label dir)."""
+    from PIL import Image
+    os.makedirs(os.path.join(root, "JPEGImages"), exist_ok=True)
+    label_dir = os.path.join(root, "ir_label")
+    os.makedirs(label_dir, exist_ok=True)
+    names = []
+    for i in range(n):
+        name = "2008_%06d" % (i + 1)
+        h, w = synth.voc_image_size(i)
+        Image.fromarray(synth.photo(h, w, seed=i)).save(os.path.join(root, "JPEGImages", name + ".jpg"), quality=90)
+        values = np.asarray([0, 255] + [int(k) + 1 for k in synth.voc_keys(synth.voc_num_classes(i), i)], np.uint8)
+        rng = np.random.RandomState(i)
+        lab = rng.choice(values, (h // 16 + 1, w // 16 + 1)).repeat(16, 0).repeat(16, 1)[:h, :w]
+        Image.fromarray(np.ascontiguousarray(lab)).save(os.path.join(label_dir, name + ".png"))
+        names.append(name)
+    lst = os.path.join(root, "list.txt")
+    with open(lst, "w") as f:
+        f.write("\n".join(names * repeat) + "\n")
+    return lst, label_dir
+
+
+def step_args(root, lst, label_dir, a, augment):
+    import run_train
+    return run_train.build_parser().parse_args([
+        "--voc12_root", root, "--train_list", lst, "--infer_list", lst, "--ir_label_out_dir", label_dir, "--irn_batch_size", str(a.batch),
+        "--irn_crop_size", str(a.crop), "--num_workers", str(a.workers), "--irn_augment", augment, "--irn_num_epoches", "1000000"])
+
+
+def bench_augment(dataset, a, dev):
+    from irn_amd import ops
+    crop = dataset.crop_size
+    batches = []
+    for s in range(0, a.images - a.batch + 1, a.batch):
+        items = [dataset[i] for i in range(s, s + a.batch)]
+        batches.append(([it["img"] for it in items], [it["label_map"] for it in items], [it["aug"] for it in items]))
+    out = {"batch": a.batch, "crop": crop, "reduce": 4,
+           "upload_bytes_per_image": int(np.mean([im.numel() + lb.numel() for b in batches for im, lb in zip(b[0], b[1])])),
+           "host_path_bytes_per_image": 3 * crop * crop * 4 + (crop // 4) ** 2}
+    for where in ("host", "device"):
+        place = (lambda ts: ts) if where == "host" else (lambda ts: [t.to(dev) for t in ts])
+        dev_ms, host_ms = [], []
+        for imgs, labs, params in batches:
+            ops.augment_pair_batch(place(imgs), place(labs), params, crop, device=dev)      # warm: code loaded, buffers grown
+        torch.cuda.synchronize()
+        for r in range(a.reps):
+            imgs, labs, params = batches[r % len(batches)]
+            imgs, labs = place(imgs), place(labs)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            e0.record()
+            ops.augment_pair_batch(imgs, labs, params, crop, device=dev)
+            e1.record()
+            t1 = time.perf_counter()
+            torch.cuda.synchronize()
+            dev_ms.append(e0.elapsed_time(e1))
+            host_ms.append((t1 - t0) * 1e3)
+        out["%s_inputs" % where] = {"device_ms_median": statistics.median(dev_ms), "device_ms_min": min(dev_ms),
+                                    "device_ms_max": max(dev_ms), "host_call_ms_median": statistics.median(host_ms)}
+    return out
+
+
+def bench_host_pipeline(raw, host, n):
+    """The worker's share of a host item beyond the decodes both forms pay: item(raw=False) - item(raw=True)."""
+    t_raw, t_host = [], []
+    for i in range(n):
+        t0 = time.perf_counter()
+        raw[i]
+        t1 = time.perf_counter()
+        host[i]
+        t2 = time.perf_counter()
+        t_raw.append((t1 - t0) * 1e3)
+        t_host.append((t2 - t1) * 1e3)
+    return {"images": n, "decode_only_ms_median": statistics.median(t_raw), "decode_and_augment_ms_median": statistics.median(t_host)}
+
+
+def bench_step(args, a, dev, model, optimizer):
+    from irn_amd.step import train_irn
+    train, _ = train_irn.make_datasets(args, 0)
+    assert len(train) >= (a.warmup + a.steps) * a.batch          # one pass: the loader's start lies in the warm-up
+    done, t0 = 0, None
+    for pack in train_irn._loader(train, args, True, 0):
+        if done == a.warmup:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        img, label = train_irn.device_batch(pack, args.irn_crop_size, dev)
+        train_irn.train_step(model, optimizer, img, label)
+        done += 1
+        if done == a.warmup + a.steps:
+            break
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    return {"augment": args.irn_augment, "workers": a.workers, "steps": a.steps, "seconds": dt, "images_per_s": a.steps * a.batch / dt}
+
+
+def main(argv=None):
+    p = argparse.ArgumentParser()
+    p.add_argument("--images", default=128, type=int)
+    p.add_argument("--batch", default=32, type=int)
+    p.add_argument("--crop", default=512, type=int)
+    p.add_argument("--reps", default=20, type=int)
+    p.add_argument("--warmup", default=3, type=int)
+    p.add_argument("--steps", default=20, type=int)
+    p.add_argument("--workers", default=8, type=int)
+    p.add_argument("--rounds", default=2, type=int, help="device / host pairs of the step section: the spread shows next to the difference")
+    p.add_argument("--skip_step", action="store_true", help="the input pipeline only")
+    a = p.parse_args(argv)
+    if not torch.cuda.is_available():
+        raise SystemExit("train_irn_bench needs a GPU")
+    from irn_amd.misc import indexing, torchutils
+    from irn_amd.net import resnet50 as _r50
+    from irn_amd.step import _common, train_irn
+    dev = torch.device("cuda", torch.cuda.current_device())
+    saved = (torch.backends.cudnn.deterministic, _r50.DETERMINISTIC)
+    with tempfile.TemporaryDirectory() as root:
+        lst, label_dir = write_tree(root, a.images, repeat=-(-(a.warmup + a.steps) * a.batch // a.images))
+        args = step_args(root, lst, label_dir, a, "device")
+        raw, _ = train_irn.make_datasets(args, 0)
+        print(json.dumps({"augment_pair": bench_augment(raw, a, dev)}), flush=True)
+        host, _ = train_irn.make_datasets(step_args(root, lst, label_dir, a, "host"), 0)
+        print(json.dumps({"host_pipeline": bench_host_pipeline(raw, host, min(a.images, 64))}), flush=True)
+        if not a.skip_step:
+            try:
+                _common.apply_deterministic_setting()
+                torch.manual_seed(0)
+                grid = a.crop // 4
+                model = train_irn.build_model(args, indexing.PathIndex(radius=10, default_size=(grid, grid))).to(dev).train()
+                edge, dp = model.trainable_parameters()
+                opt = torchutils.PolyOptimizer([{"params": edge, "lr": 0.01, "weight_decay": 1e-4}, {"params": dp, "lr": 0.1, "weight_decay": 1e-4}],
+                                               lr=0.01, weight_decay=1e-4, max_step=10 ** 9)
+                for augment in ("device", "host") * a.rounds:
+                    print(json.dumps({"step": bench_step(step_args(root, lst, label_dir, a, augment), a, dev, model, opt)}), flush=True)
+            finally:
+                torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
+
+
+if __name__ == "__main__":
+    main()

@@ -363,6 +363,38 @@ int irn_bn_act(float *x_dev, const float *res_dev, const float *scale_dev, const
 int irn_bn_act_nhwc(float *x_dev, const float *res_dev, const float *scale_dev, const float *shift_dev, const float *res_scale_dev,
                     const float *res_shift_dev, int64_t n_pixels, int n_channels, int relu, void *stream);
 
+/* The same tail as a differentiable operator, for the training seam (net/resnet50.py TRAIN_FUSED_TAIL, ops.bn_act): the
+ * reference trains through FixedBatchNorm -> `out += residual` -> ReLU (net/resnet50.py:11-14, :34-54) with autograd's
+ * composed kernels.  All three entries are free of atomics: the same inputs give the same bits.
+ *
+ * irn_bn_fold: weight, bias, mean, var dev fp32 [n_channels] -> scale = weight / sqrt(var + eps), shift = bias - mean * scale,
+ *   dev fp32 [n_channels], every operation in double with its own rounding (no contraction) and ONE rounding to fp32 at the
+ *   end: bit for bit `FrozenBatchNorm._fold64()` followed by `.float()`.  One launch.
+ * irn_bn_act_forward: irn_bn_act out of place — x is left as it is (the weight gradient needs it), out dev fp32 like x, not
+ *   overlapping it, receives act(x * scale[c] + shift[c] (+ r)); same arithmetic, same bits as irn_bn_act.
+ * irn_bn_act_backward: with dz = grad_out where out > 0 or NaN (relu = 1; torch's threshold_backward), else grad_out itself:
+ *       grad_x = dz * scale[c]                                         (written if grad_x_dev != NULL; needs scale_dev)
+ *       grad_res = dz, or dz * res_scale[c] if res_scale_dev != NULL   (written if grad_res_dev != NULL)
+ *       sums[0 * C + c] = sum dz,  sums[1 * C + c] = sum dz * x,  and with res_scale_dev: sums[2 * C + c] = sum dz * res
+ *                                                                      (dev fp64 [2 or 3, C], if sums_dev != NULL; needs x_dev)
+ *   over images and plane, accumulated in double: per thread, then a fixed tree per workgroup, then a channel's workgroup
+ *   partials in ascending order by a second small launch.  From them the caller has grad_weight = (S1 - mean * S0) /
+ *   sqrt(var + eps), grad_bias = S0, and the shortcut's batch norm likewise with S2.  grad_out, out (needed with relu = 1), x,
+ *   res, grad_x, grad_res dev fp32 [n_images, n_channels, plane_elems] contiguous, 16-byte aligned; what is not needed may be
+ *   NULL and is then neither read nor written.  workspace: caller device memory of
+ *   irn_bn_act_backward_workspace_bytes(n_images, n_channels, plane_elems) bytes (0 = bad geometry), needed with sums_dev.
+ *   At most 2^31 - 1 elements per call; enqueued on `stream`, nothing synchronises. */
+int irn_bn_fold(const float *weight_dev, const float *bias_dev, const float *mean_dev, const float *var_dev, double eps,
+                int n_channels, float *scale_dev, float *shift_dev, void *stream);
+int irn_bn_act_forward(const float *x_dev, const float *res_dev, const float *scale_dev, const float *shift_dev,
+                       const float *res_scale_dev, const float *res_shift_dev, float *out_dev, int64_t n_images, int n_channels,
+                       int64_t plane_elems, int relu, void *stream);
+size_t irn_bn_act_backward_workspace_bytes(int64_t n_images, int n_channels, int64_t plane_elems);
+int irn_bn_act_backward(const float *grad_out_dev, const float *out_dev, const float *x_dev, const float *res_dev,
+                        const float *scale_dev, const float *res_scale_dev, float *grad_x_dev, float *grad_res_dev, double *sums_dev,
+                        int64_t n_images, int n_channels, int64_t plane_elems, int relu, void *workspace_dev, size_t workspace_bytes,
+                        void *stream);
+
 /* 1x1 convolution of a channels-last activation with its whole elementwise tail in the GEMM's epilogue (hipBLASLt, fp32
  * compute): conv1 -> bn1 -> ReLU and conv3 -> bn3 -> (+ residual) -> ReLU of Bottleneck.forward, reference
  * net/resnet50.py:34-54 (FixedBatchNorm :11-14 is a constant affine map: its scale is folded into `w` by the caller in

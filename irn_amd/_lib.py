@@ -65,6 +65,10 @@ _SIGS = {
     "irn_augment_label_batch": (i32, [i32, i32, i32, pi32, sz, vp, sz, vp, sz, vp, sz, vp]),
     "irn_bn_act": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i64, i32, vp]),
     "irn_bn_act_nhwc": (i32, [vp, vp, vp, vp, vp, vp, i64, i32, i32, vp]),
+    "irn_bn_fold": (i32, [vp, vp, vp, vp, C.c_double, i32, vp, vp, vp]),
+    "irn_bn_act_forward": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, i32, vp]),
+    "irn_bn_act_backward_workspace_bytes": (sz, [i64, i32, i64]),
+    "irn_bn_act_backward": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i64, i32, vp, sz, vp]),
     "irn_conv1x1_workspace_bytes": (sz, []),
     "irn_conv1x1_algo_count": (i32, [i64, i32, i32, i32, i32, i32, sz, C.POINTER(i32)]),
     "irn_conv1x1_nhwc": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, sz, vp]),

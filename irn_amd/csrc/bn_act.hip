@@ -51,12 +51,13 @@ constexpr int kThreads = 256, kPieces = 4;       // 16-byte pieces per thread, a
 // profiles/r02_s19_epilogue_bench.txt)
 __device__ __forceinline__ f4v load_piece(const float *p, unsigned i) { return reinterpret_cast<const f4v *>(p)[i]; }
 
-// RES: 0 no residual, 1 residual added as it is, 2 residual through its own scale / shift first
+// RES: 0 no residual, 1 residual added as it is, 2 residual through its own scale / shift first.  `out` is `x` itself (the
+// inference pass, in place) or another tensor (irn_bn_act_forward, which keeps x for the backward).
 template <int RES, bool RELU>
-__global__ __launch_bounds__(kThreads) void bn_act_kernel(float *__restrict__ x, const float *__restrict__ res,
-                                                          const float *__restrict__ scale, const float *__restrict__ shift,
-                                                          const float *__restrict__ res_scale, const float *__restrict__ res_shift,
-                                                          unsigned n_pieces, unsigned hw, unsigned n_ch, Div by_hw, Div by_ch) {
+__device__ __forceinline__ void bn_act_pieces(const float *x, float *out, const float *__restrict__ res,
+                                              const float *__restrict__ scale, const float *__restrict__ shift,
+                                              const float *__restrict__ res_scale, const float *__restrict__ res_shift,
+                                              unsigned n_pieces, unsigned hw, unsigned n_ch, Div by_hw, Div by_ch) {
     constexpr bool HAS_RES = RES != 0;
     const unsigned base = blockIdx.x * (unsigned)(kThreads * kPieces) + threadIdx.x;
     f4v v[kPieces], r[kPieces];
@@ -103,13 +104,30 @@ __global__ __launch_bounds__(kThreads) void bn_act_kernel(float *__restrict__ x,
             if (RELU) y = y < 0.f ? 0.f : y;      // NaN stays NaN, like torch.relu
             o[k] = y;
         }
-        reinterpret_cast<f4v *>(x)[p] = o;
+        reinterpret_cast<f4v *>(out)[p] = o;
     }
+}
+
+template <int RES, bool RELU>
+__global__ __launch_bounds__(kThreads) void bn_act_kernel(float *__restrict__ x, const float *__restrict__ res,
+                                                          const float *__restrict__ scale, const float *__restrict__ shift,
+                                                          const float *__restrict__ res_scale, const float *__restrict__ res_shift,
+                                                          unsigned n_pieces, unsigned hw, unsigned n_ch, Div by_hw, Div by_ch) {
+    bn_act_pieces<RES, RELU>(x, x, res, scale, shift, res_scale, res_shift, n_pieces, hw, n_ch, by_hw, by_ch);
+}
+
+template <int RES, bool RELU>
+__global__ __launch_bounds__(kThreads) void bn_act_forward_kernel(const float *__restrict__ x, float *__restrict__ out,
+                                                                  const float *__restrict__ res, const float *__restrict__ scale,
+                                                                  const float *__restrict__ shift, const float *__restrict__ res_scale,
+                                                                  const float *__restrict__ res_shift, unsigned n_pieces, unsigned hw,
+                                                                  unsigned n_ch, Div by_hw, Div by_ch) {
+    bn_act_pieces<RES, RELU>(x, out, res, scale, shift, res_scale, res_shift, n_pieces, hw, n_ch, by_hw, by_ch);
 }
 
 // one element per thread from `first` on: the last numel % 4 elements, and tensors whose planes are shorter than a piece
 template <int RES, bool RELU>
-__global__ void bn_act_tail_kernel(float *__restrict__ x, const float *__restrict__ res, const float *__restrict__ scale,
+__global__ void bn_act_tail_kernel(const float *x, float *out, const float *__restrict__ res, const float *__restrict__ scale,
                                    const float *__restrict__ shift, const float *__restrict__ res_scale,
                                    const float *__restrict__ res_shift, unsigned first, unsigned numel, unsigned hw, unsigned n_ch) {
     const unsigned e = first + blockIdx.x * blockDim.x + threadIdx.x;
@@ -119,7 +137,7 @@ __global__ void bn_act_tail_kernel(float *__restrict__ x, const float *__restric
     if (RES == 1) y += res[e];
     if (RES == 2) y += fmaf(res[e], res_scale[c], res_shift[c]);
     if (RELU) y = y < 0.f ? 0.f : y;
-    x[e] = y;
+    out[e] = y;
 }
 
 // The same pass over a channels-last tensor ([n_pixels, n_ch] in memory, n_ch a multiple of 4): the four elements of a
@@ -177,28 +195,301 @@ int launch_nhwc(float *x, const float *res, const float *scale, const float *shi
     return IRN_OK;
 }
 
+// out == x: the in-place pass; otherwise x is only read
 template <int RES, bool RELU>
-int launch(float *x, const float *res, const float *scale, const float *shift, const float *res_scale, const float *res_shift,
-           unsigned numel, unsigned hw, unsigned n_ch, hipStream_t stream) {
+int launch(const float *x, float *out, const float *res, const float *scale, const float *shift, const float *res_scale,
+           const float *res_shift, unsigned numel, unsigned hw, unsigned n_ch, hipStream_t stream) {
     // planes shorter than a piece (a piece would span more than two of them) go element by element; such maps carry no time
     const unsigned n_pieces = hw >= 4u ? numel / 4u : 0u;
     if (n_pieces) {
         const unsigned blocks = (n_pieces + kThreads * kPieces - 1) / (kThreads * kPieces);
-        hipLaunchKernelGGL((bn_act_kernel<RES, RELU>), dim3(blocks), dim3(kThreads), 0, stream, x, res, scale, shift, res_scale,
-                           res_shift, n_pieces, hw, n_ch, make_div(hw), make_div(n_ch));
+        if (out == x)
+            hipLaunchKernelGGL((bn_act_kernel<RES, RELU>), dim3(blocks), dim3(kThreads), 0, stream, out, res, scale, shift, res_scale,
+                               res_shift, n_pieces, hw, n_ch, make_div(hw), make_div(n_ch));
+        else
+            hipLaunchKernelGGL((bn_act_forward_kernel<RES, RELU>), dim3(blocks), dim3(kThreads), 0, stream, x, out, res, scale, shift,
+                               res_scale, res_shift, n_pieces, hw, n_ch, make_div(hw), make_div(n_ch));
         IRN_LAUNCH_CHECK("bn_act_kernel");
     }
     const unsigned rest = numel - n_pieces * 4u;
     if (rest) {
-        hipLaunchKernelGGL((bn_act_tail_kernel<RES, RELU>), dim3((rest + 63u) / 64u), dim3(64), 0, stream, x, res, scale, shift,
+        hipLaunchKernelGGL((bn_act_tail_kernel<RES, RELU>), dim3((rest + 63u) / 64u), dim3(64), 0, stream, x, out, res, scale, shift,
                            res_scale, res_shift, n_pieces * 4u, numel, hw, n_ch);
         IRN_LAUNCH_CHECK("bn_act_tail_kernel");
     }
     return IRN_OK;
 }
 
+int launch_mode(const float *x, float *out, const float *res, const float *scale, const float *shift, const float *res_scale,
+                const float *res_shift, unsigned numel, unsigned hw, unsigned n_ch, int relu, hipStream_t s) {
+    const int mode = !res ? 0 : (res_scale ? 2 : 1);
+#define IRN_BN_ACT_CASE(RES_MODE)                                                                                       \
+    return relu ? launch<RES_MODE, true>(x, out, res, scale, shift, res_scale, res_shift, numel, hw, n_ch, s)          \
+                : launch<RES_MODE, false>(x, out, res, scale, shift, res_scale, res_shift, numel, hw, n_ch, s)
+    if (mode == 0) IRN_BN_ACT_CASE(0);
+    if (mode == 1) IRN_BN_ACT_CASE(1);
+    IRN_BN_ACT_CASE(2);
+#undef IRN_BN_ACT_CASE
+}
+
+// ------------------------------------------------------------------------------------------------
+// The training seam: the same tail as a differentiable operator (ops.bn_act).  irn_bn_fold makes scale / shift from the
+// layer's parameters in one launch (the optimiser writes them every step), irn_bn_act_forward is the pass above out of
+// place, irn_bn_act_backward is its vector-Jacobian product in one pass over the tensors plus a tiny second launch.
+// ------------------------------------------------------------------------------------------------
+
+// `FrozenBatchNorm._fold64().float()`: every operation a separate IEEE double operation (contraction is off in this file),
+// one rounding to fp32 at the end
+__global__ void bn_fold_kernel(const float *__restrict__ weight, const float *__restrict__ bias, const float *__restrict__ mean,
+                               const float *__restrict__ var, double eps, int n_ch, float *__restrict__ scale,
+                               float *__restrict__ shift) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= n_ch) return;
+    const double s = (double)weight[c] / sqrt((double)var[c] + eps);
+    const double m = (double)mean[c] * s;
+    scale[c] = (float)s;
+    shift[c] = (float)((double)bias[c] - m);
+}
+
+// Backward.  With z = x * scale[c] + shift[c] (+ r) and out = act(z):  dz = grad_out where out > 0 (or NaN), else 0 —
+// torch's threshold_backward — and
+//     grad_x = dz * scale[c],   grad_res = dz  or  dz * res_scale[c],
+//     S0[c] = sum dz,   S1[c] = sum dz * x,   S2[c] = sum dz * res          (over images and plane, in double)
+// from which the caller forms the parameter gradients.  A channel's N planes lie C planes apart, so a workgroup takes ONE
+// channel and a share of its planes — kBwdShare elements: whole planes of consecutive images while a plane is at most a
+// share long, else one kBwdShare-long chunk of one plane — and walks each plane range in 16-byte pieces of the flat tensor
+// (a range's first and last piece may hold neighbours' elements: those go element by element, so no store ever touches
+// an element of another workgroup).  Sums: per thread in double (the product of two floats is exact in double), a fixed
+// shuffle tree per wave, the four waves added in ascending order by thread 0, one partial per (sum, channel, share) in the
+// caller's workspace; bn_act_sums_kernel then adds a channel's partials in ascending share order.  No atomics: the same
+// inputs give the same bits.  Blocks are numbered share-major, so that concurrent blocks read neighbouring planes.
+constexpr int kBwdThreads = 256, kBwdShare = kBwdThreads * 4 * kPieces;      // 4096 elements
+
+struct BwdSplit {
+    unsigned chunks;       // shares per plane (1 when a plane fits a share)
+    unsigned images;       // images per share (1 when chunks > 1)
+    unsigned shares;       // per channel
+};
+
+BwdSplit bwd_split(unsigned n_img, unsigned hw) {
+    BwdSplit sp;
+    sp.chunks = hw > (unsigned)kBwdShare ? (hw + kBwdShare - 1) / kBwdShare : 1u;
+    sp.images = sp.chunks > 1 ? 1u : (unsigned)kBwdShare / hw;                  // hw >= 1
+    sp.shares = sp.chunks > 1 ? n_img * sp.chunks : (n_img + sp.images - 1) / sp.images;
+    return sp;
+}
+
+template <bool RES_BN, bool RELU, bool SUMS>
+__global__ __launch_bounds__(kBwdThreads) void bn_act_backward_kernel(
+    const float *__restrict__ grad_out, const float *__restrict__ out, const float *__restrict__ x, const float *__restrict__ res,
+    const float *__restrict__ scale, const float *__restrict__ res_scale, float *__restrict__ grad_x, float *__restrict__ grad_res,
+    double *__restrict__ partial, unsigned n_img, unsigned hw, unsigned n_ch, BwdSplit sp) {
+    constexpr int NQ = RES_BN ? 3 : 2;
+    const unsigned share = blockIdx.x / n_ch, c = blockIdx.x - share * n_ch;
+    unsigned n0, n1, first = 0, last = hw;                                      // images [n0, n1), plane range [first, last)
+    if (sp.chunks > 1) {
+        n0 = share / sp.chunks;
+        n1 = n0 + 1;
+        first = (share - n0 * sp.chunks) * (unsigned)kBwdShare;
+        last = min(hw, first + (unsigned)kBwdShare);
+    } else {
+        n0 = share * sp.images;
+        n1 = min(n_img, n0 + sp.images);
+    }
+    const float sc = grad_x ? scale[c] : 0.f;
+    const float rsc = RES_BN ? res_scale[c] : 1.f;
+    double acc[NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
+    for (unsigned n = n0; n < n1; ++n) {
+        const unsigned plane0 = (n * n_ch + c) * hw;
+        const unsigned b = plane0 + first, e = plane0 + last;                  // flat element range of this plane, e < 2^31
+        for (unsigned p = (b >> 2) + threadIdx.x; p * 4u < e; p += kBwdThreads) {
+            const unsigned e0 = p * 4u;
+            const bool whole = e0 >= b && e0 + 4u <= e;
+            float g[4], o[4], xv[4], rv[4];
+            if (whole) {
+                const f4v gv = load_piece(grad_out, p);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) g[k] = gv[k];
+                if (RELU) {
+                    const f4v ov = load_piece(out, p);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) o[k] = ov[k];
+                }
+                if (SUMS) {
+                    const f4v v = load_piece(x, p);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) xv[k] = v[k];
+                    if (RES_BN) {
+                        const f4v r = load_piece(res, p);
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) rv[k] = r[k];
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const unsigned i = e0 + k;
+                    const bool in = i >= b && i < e;
+                    g[k] = in ? grad_out[i] : 0.f;                              // an element outside the range adds +0 to every sum
+                    o[k] = (RELU && in) ? out[i] : 1.f;
+                    xv[k] = (SUMS && in) ? x[i] : 0.f;
+                    rv[k] = (SUMS && RES_BN && in) ? res[i] : 0.f;
+                }
+            }
+            float gx[4], gr[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float dz = g[k];
+                if (RELU) dz = o[k] <= 0.f ? 0.f : dz;                          // a NaN output lets the gradient pass, as in torch
+                gx[k] = dz * sc;
+                gr[k] = RES_BN ? dz * rsc : dz;
+                if (SUMS) {
+                    acc[0] += (double)dz;
+                    acc[1] += (double)dz * (double)xv[k];
+                    if (RES_BN) acc[2] += (double)dz * (double)rv[k];
+                }
+            }
+            if (whole) {
+                if (grad_x) reinterpret_cast<f4v *>(grad_x)[p] = f4v{gx[0], gx[1], gx[2], gx[3]};
+                if (grad_res) reinterpret_cast<f4v *>(grad_res)[p] = f4v{gr[0], gr[1], gr[2], gr[3]};
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const unsigned i = e0 + k;
+                    if (i < b || i >= e) continue;
+                    if (grad_x) grad_x[i] = gx[k];
+                    if (grad_res) grad_res[i] = gr[k];
+                }
+            }
+        }
+    }
+    if (!SUMS) return;
+    __shared__ double wave_sum[kBwdThreads / 64][NQ];
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) {
+        double v = acc[q];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+        if ((threadIdx.x & 63) == 0) wave_sum[threadIdx.x >> 6][q] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < NQ) {
+        double v = wave_sum[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < kBwdThreads / 64; ++w) v += wave_sum[w][threadIdx.x];
+        partial[((size_t)threadIdx.x * n_ch + c) * sp.shares + share] = v;
+    }
+}
+
+// sums[q * n_ch + c] = partial[q][c][0] + partial[q][c][1] + ... in that order; one thread per (q, c)
+__global__ void bn_act_sums_kernel(const double *__restrict__ partial, double *__restrict__ sums, unsigned n_rows, unsigned shares) {
+    const unsigned row = blockIdx.x * blockDim.x + threadIdx.x;
+    if (row >= n_rows) return;
+    const double *p = partial + (size_t)row * shares;
+    double v = p[0];
+    for (unsigned s = 1; s < shares; ++s) v += p[s];
+    sums[row] = v;
+}
+
+template <bool RES_BN, bool RELU, bool SUMS>
+int launch_backward(const float *grad_out, const float *out, const float *x, const float *res, const float *scale,
+                    const float *res_scale, float *grad_x, float *grad_res, double *sums, double *partial, unsigned n_img,
+                    unsigned hw, unsigned n_ch, hipStream_t s) {
+    const BwdSplit sp = bwd_split(n_img, hw);
+    hipLaunchKernelGGL((bn_act_backward_kernel<RES_BN, RELU, SUMS>), dim3(sp.shares * n_ch), dim3(kBwdThreads), 0, s, grad_out, out, x,
+                       res, scale, res_scale, grad_x, grad_res, partial, n_img, hw, n_ch, sp);
+    IRN_LAUNCH_CHECK("bn_act_backward_kernel");
+    if (SUMS) {
+        const unsigned rows = (RES_BN ? 3u : 2u) * n_ch;
+        hipLaunchKernelGGL(bn_act_sums_kernel, dim3((rows + 63u) / 64u), dim3(64), 0, s, partial, sums, rows, sp.shares);
+        IRN_LAUNCH_CHECK("bn_act_sums_kernel");
+    }
+    return IRN_OK;
+}
+
 }  // namespace
 }  // namespace irn
+
+extern "C" int irn_bn_fold(const float *weight_dev, const float *bias_dev, const float *mean_dev, const float *var_dev, double eps,
+                           int n_channels, float *scale_dev, float *shift_dev, void *stream) {
+    using namespace irn;
+    if (!weight_dev || !bias_dev || !mean_dev || !var_dev || !scale_dev || !shift_dev) return fail(IRN_ERR_ARG, "irn_bn_fold: null pointer");
+    if (n_channels <= 0) return fail(IRN_ERR_ARG, "irn_bn_fold: %d channels", n_channels);
+    hipLaunchKernelGGL(bn_fold_kernel, dim3((unsigned)cdiv(n_channels, 256)), dim3(256), 0, (hipStream_t)stream, weight_dev, bias_dev,
+                       mean_dev, var_dev, eps, n_channels, scale_dev, shift_dev);
+    IRN_LAUNCH_CHECK("bn_fold_kernel");
+    return IRN_OK;
+}
+
+extern "C" int irn_bn_act_forward(const float *x_dev, const float *res_dev, const float *scale_dev, const float *shift_dev,
+                                  const float *res_scale_dev, const float *res_shift_dev, float *out_dev, int64_t n_images,
+                                  int n_channels, int64_t plane_elems, int relu, void *stream) {
+    using namespace irn;
+    if (!x_dev || !out_dev || !scale_dev || !shift_dev) return fail(IRN_ERR_ARG, "irn_bn_act_forward: null pointer");
+    if ((res_scale_dev != nullptr) != (res_shift_dev != nullptr) || (res_scale_dev && !res_dev))
+        return fail(IRN_ERR_ARG, "irn_bn_act_forward: res_scale and res_shift come together, and only with a residual");
+    if (n_images < 0 || n_channels <= 0 || plane_elems < 0) return fail(IRN_ERR_ARG, "irn_bn_act_forward: negative size");
+    if (((uintptr_t)x_dev | (uintptr_t)res_dev | (uintptr_t)out_dev) & 15u)
+        return fail(IRN_ERR_ARG, "irn_bn_act_forward: tensors must be 16-byte aligned");
+    const int64_t numel = n_images * n_channels * plane_elems;
+    if (numel == 0) return IRN_OK;
+    if (numel >= (1ll << 31)) return fail(IRN_ERR_ARG, "irn_bn_act_forward: %lld elements; at most 2^31 - 1 per call", (long long)numel);
+    if (out_dev < x_dev + numel && x_dev < out_dev + numel) return fail(IRN_ERR_ARG, "irn_bn_act_forward: out overlaps x (in place: irn_bn_act)");
+    return launch_mode(x_dev, out_dev, res_dev, scale_dev, shift_dev, res_scale_dev, res_shift_dev, (unsigned)numel, (unsigned)plane_elems,
+                       (unsigned)n_channels, relu, (hipStream_t)stream);
+}
+
+extern "C" size_t irn_bn_act_backward_workspace_bytes(int64_t n_images, int n_channels, int64_t plane_elems) {
+    if (n_images <= 0 || n_channels <= 0 || plane_elems <= 0 || n_images * n_channels * plane_elems >= (1ll << 31)) return 0;
+    return (size_t)3 * (size_t)n_channels * irn::bwd_split((unsigned)n_images, (unsigned)plane_elems).shares * sizeof(double);
+}
+
+extern "C" int irn_bn_act_backward(const float *grad_out_dev, const float *out_dev, const float *x_dev, const float *res_dev,
+                                   const float *scale_dev, const float *res_scale_dev, float *grad_x_dev, float *grad_res_dev,
+                                   double *sums_dev, int64_t n_images, int n_channels, int64_t plane_elems, int relu,
+                                   void *workspace_dev, size_t workspace_bytes, void *stream) {
+    using namespace irn;
+    if (!grad_out_dev) return fail(IRN_ERR_ARG, "irn_bn_act_backward: null pointer");
+    if (relu && !out_dev) return fail(IRN_ERR_ARG, "irn_bn_act_backward: the ReLU mask needs the forward's output");
+    if (grad_x_dev && !scale_dev) return fail(IRN_ERR_ARG, "irn_bn_act_backward: grad_x needs scale");
+    if (sums_dev && (!x_dev || (res_scale_dev && !res_dev)))
+        return fail(IRN_ERR_ARG, "irn_bn_act_backward: the sums need x, and res when the residual has a batch norm of its own");
+    if (n_images < 0 || n_channels <= 0 || plane_elems < 0) return fail(IRN_ERR_ARG, "irn_bn_act_backward: negative size");
+    if (((uintptr_t)grad_out_dev | (uintptr_t)out_dev | (uintptr_t)x_dev | (uintptr_t)res_dev | (uintptr_t)grad_x_dev |
+         (uintptr_t)grad_res_dev) & 15u)
+        return fail(IRN_ERR_ARG, "irn_bn_act_backward: tensors must be 16-byte aligned");
+    const int64_t numel = n_images * n_channels * plane_elems;
+    if (numel >= (1ll << 31)) return fail(IRN_ERR_ARG, "irn_bn_act_backward: %lld elements; at most 2^31 - 1 per call", (long long)numel);
+    hipStream_t s = (hipStream_t)stream;
+    const int n_sums = res_scale_dev ? 3 : 2;
+    if (numel == 0) {
+        if (sums_dev) IRN_HIP_TRY(hipMemsetAsync(sums_dev, 0, sizeof(double) * n_sums * n_channels, s));
+        return IRN_OK;
+    }
+    if (!sums_dev && !grad_x_dev && !grad_res_dev) return IRN_OK;
+    if (sums_dev) {
+        const size_t need = (size_t)n_sums * n_channels * bwd_split((unsigned)n_images, (unsigned)plane_elems).shares * sizeof(double);
+        if (!workspace_dev || workspace_bytes < need || ((uintptr_t)workspace_dev & 7u))
+            return fail(IRN_ERR_ARG, "irn_bn_act_backward: workspace of %zu bytes, %zu needed (irn_bn_act_backward_workspace_bytes)",
+                        workspace_bytes, need);
+    }
+    const unsigned ni = (unsigned)n_images, hw = (unsigned)plane_elems, nc = (unsigned)n_channels;
+    double *ws = (double *)workspace_dev;
+#define IRN_BN_BWD_CASE(RES_BN, SUMS)                                                                                                \
+    return relu ? launch_backward<RES_BN, true, SUMS>(grad_out_dev, out_dev, x_dev, res_dev, scale_dev, res_scale_dev, grad_x_dev,   \
+                                                      grad_res_dev, sums_dev, ws, ni, hw, nc, s)                                     \
+                : launch_backward<RES_BN, false, SUMS>(grad_out_dev, out_dev, x_dev, res_dev, scale_dev, res_scale_dev, grad_x_dev,  \
+                                                       grad_res_dev, sums_dev, ws, ni, hw, nc, s)
+    if (res_scale_dev) {
+        if (sums_dev) IRN_BN_BWD_CASE(true, true);
+        IRN_BN_BWD_CASE(true, false);
+    }
+    if (sums_dev) IRN_BN_BWD_CASE(false, true);
+    IRN_BN_BWD_CASE(false, false);
+#undef IRN_BN_BWD_CASE
+}
 
 extern "C" int irn_bn_act(float *x_dev, const float *res_dev, const float *scale_dev, const float *shift_dev,
                           const float *res_scale_dev, const float *res_shift_dev, int64_t n_images, int n_channels,
@@ -214,14 +505,7 @@ extern "C" int irn_bn_act(float *x_dev, const float *res_dev, const float *scale
     if (numel >= (1ll << 31)) return fail(IRN_ERR_ARG, "irn_bn_act: %lld elements; at most 2^31 - 1 per call", (long long)numel);
     const unsigned hw = (unsigned)plane_elems, n_ch = (unsigned)n_channels, n = (unsigned)numel;
     hipStream_t s = (hipStream_t)stream;
-    const int mode = !res_dev ? 0 : (res_scale_dev ? 2 : 1);
-#define IRN_BN_ACT_CASE(RES_MODE)                                                                                                   \
-    return relu ? launch<RES_MODE, true>(x_dev, res_dev, scale_dev, shift_dev, res_scale_dev, res_shift_dev, n, hw, n_ch, s)       \
-                : launch<RES_MODE, false>(x_dev, res_dev, scale_dev, shift_dev, res_scale_dev, res_shift_dev, n, hw, n_ch, s)
-    if (mode == 0) IRN_BN_ACT_CASE(0);
-    if (mode == 1) IRN_BN_ACT_CASE(1);
-    IRN_BN_ACT_CASE(2);
-#undef IRN_BN_ACT_CASE
+    return irn::launch_mode(x_dev, x_dev, res_dev, scale_dev, shift_dev, res_scale_dev, res_shift_dev, n, hw, n_ch, relu, s);
 }
 
 extern "C" int irn_bn_act_nhwc(float *x_dev, const float *res_dev, const float *scale_dev, const float *shift_dev,

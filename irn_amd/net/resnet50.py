@@ -11,7 +11,8 @@ Differences by design:
   * on the inference path (GPU tensor, autograd off) the elementwise tail of every unit — batch norm, the residual add
     and the ReLU (net/resnet50.py:34-54, :94-97) — is ONE in-place pass of a hand-written kernel over the convolution's
     output (`ops.bn_act_`, irn_amd/csrc/bn_act.hip) instead of three kernels and seven tensor transfers; the
-    convolutions stay on MIOpen.  With autograd on (the training seam) or on the CPU the composed PyTorch ops run.
+    convolutions stay on MIOpen.  With autograd on (the training seam) or on the CPU the composed PyTorch ops run —
+    unless TRAIN_FUSED_TAIL is set, which gives the training seam the same tail as one differentiable pass (`ops.bn_act`).
 """
 import os
 
@@ -153,6 +154,19 @@ def end_trunk_pass():
         torch.backends.cudnn.deterministic = True
 
 
+# The training seam's tail (off by default; step/train_cam sets it for `--cam_fused_tail 1`): under autograd, a dense NCHW
+# fp32 GPU activation goes through `ops.bn_act` — fold, one forward pass, one backward pass with the parameter gradients'
+# channel sums, no float atomics — instead of F.batch_norm -> add -> ReLU and ATen's backward of each.
+TRAIN_FUSED_TAIL = False
+
+
+def _train_fused(x, residual):
+    ok = lambda t: (t.is_cuda and t.dtype == torch.float32 and t.dim() == 4 and t.is_contiguous() and t.data_ptr() % 16 == 0
+                    and t.numel() < 2 ** 31)
+    return (TRAIN_FUSED_TAIL and torch.is_grad_enabled() and ok(x)
+            and (residual is None or (ok(residual) and residual.shape == x.shape and residual.device == x.device)))
+
+
 def _dense(x):
     """contiguous in NCHW or (4-D) in channels-last order"""
     return x.is_contiguous() or (x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last))
@@ -246,6 +260,9 @@ class FrozenBatchNorm(nn.BatchNorm2d):
             from .. import ops          # the HIP library; raises if it has not been built — there is no other GPU path
             scale, shift = self.folded()
             return ops.bn_act_(x, scale, shift, residual, relu, None if residual_bn is None else residual_bn.folded())
+        if _train_fused(x, residual):
+            from .. import ops
+            return ops.bn_act(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps, residual, relu, residual_bn)
         y = self.forward(x)
         if residual is not None:
             y = y + (residual if residual_bn is None else residual_bn.forward(residual))

@@ -42,7 +42,8 @@ class Net(nn.Module):
         """[B,3,H,W] -> logits [B,20] with gradients for stages 3-4 and the classifier only (net/resnet50_cam.py:25-37).
         The reference detaches stage 2's output and no parameter of stages 1-2 ever receives a gradient; here that half
         runs under `no_grad` instead — the same function and the same gradients, but no activation of it is saved and it
-        takes the inference path (fused batch norm passes).  Stages 3-4 are composed PyTorch ops under autograd."""
+        takes the inference path (fused batch norm passes).  Stages 3-4 are composed PyTorch ops under autograd, or with
+        `resnet50.TRAIN_FUSED_TAIL` the differentiable fused tail (`ops.bn_act`)."""
         with torch.no_grad():
             x = _r50.to_nchw(self.stage2(self.stage1(x)))
         f = self.stage4(self.stage3(x))

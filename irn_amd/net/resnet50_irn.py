@@ -111,7 +111,8 @@ class Net(nn.Module):
         self.dp_layers = nn.ModuleList([self.fc_dp1, self.fc_dp2, self.fc_dp3, self.fc_dp4,
                                         self.fc_dp5, self.fc_dp6, self.fc_dp7])
 
-    def forward(self, x):
+    def trunk(self, x):
+        """The five frozen stages: (f1 .. f5, channels-last?) — f1 NCHW, f2 .. f5 in the layout the pass ran in."""
         cl = _r50.channels_last_for(x)      # the trunk's stages on MIOpen's NHWC solvers where they are tuned (resnet50.py)
         f1 = self.stage1(x).detach()        # the trunk is frozen (net/resnet50_irn.py:111-115)
         f2 = self.stage2(_r50.to_stage_format(f1, cl)).detach()
@@ -119,9 +120,30 @@ class Net(nn.Module):
         f4 = self.stage4(f3).detach()
         f5 = self.stage5(f4).detach()
         _r50.end_trunk_pass()               # the heads run NCHW (reproducible mode: under MIOpen's deterministic attribute)
+        return f1, f2, f3, f4, f5, cl
+
+    def forward(self, x):
+        f1, f2, f3, f4, f5, cl = self.trunk(x)
         if cl and not (_r50.FUSED_GEMM and _r50.FUSED_EPILOGUE):
             f2, f3, f4, f5 = (_r50.to_nchw(f) for f in (f2, f3, f4, f5))      # (else each head's first GEMM reads them channels-last)
+        return self.heads(f1, f2, f3, f4, f5)
 
+    def _trunk_nchw(self, x):
+        f = self.trunk(x)
+        return (f[0],) + tuple(_r50.to_nchw(t) for t in f[1:5])
+
+    def forward_train(self, x):
+        """`forward` for a training step: the same function of x and the same gradients — the trunk receives none (the
+        reference detaches every stage, net/resnet50_irn.py:111-115) — but the trunk runs under `no_grad`, so on the
+        inference path (fused tails, and the tuned channels-last split-GEMM pass where the shipped database covers the
+        input size; in the reproducible mode in passes of a fixed number of rows, `resnet50.run_rows`) and without saving an
+        activation; the heads, which read NCHW under autograd, get f2 .. f5 converted."""
+        with torch.no_grad():
+            feats = _r50.run_rows(self._trunk_nchw, x)
+        return self.heads(*feats)
+
+    def heads(self, f1, f2, f3, f4, f5):
+        """(edge, dp) from the trunk's five features."""
         e2 = self.fc_edge2(f2)
         eh, ew = e2.shape[2:]
         taps = [self.fc_edge1(f1), e2] + [m(f)[..., :eh, :ew] for m, f in
@@ -212,12 +234,16 @@ class AffinityDisplacementLoss(Net):
         pair_disp = self.to_pair_displacement(dp_out)
         return pos_aff_loss, neg_aff_loss, self.to_displacement_loss(pair_disp), torch.abs(pair_disp)
 
-    def fused_losses(self, x, label):
+    def fused_losses(self, x, label, trunk="autograd"):
         """The four scalar losses of a training step (reference step/train_irn.py:58-64: positive affinity, negative
         affinity, foreground displacement, background displacement) from the images ``x`` and the reduced IR label maps
-        ``label`` (uint8 [B, Hp, Wp]) — `forward(x, True)` followed by the masked sums, without any [B, |S|, N] tensor."""
+        ``label`` (uint8 [B, Hp, Wp]) — `forward(x, True)` followed by the masked sums, without any [B, |S|, N] tensor.
+        ``trunk``: "autograd" runs the frozen trunk inside the autograd graph as the reference does (`Net.forward`),
+        "inference" under `no_grad` on the inference path (`Net.forward_train`)."""
         from ..misc import indexing
-        edge_out, dp_out = Net.forward(self, x)
+        if trunk not in ("autograd", "inference"):
+            raise ValueError("fused_losses: trunk is 'autograd' or 'inference', got %r" % (trunk,))
+        edge_out, dp_out = Net.forward_train(self, x) if trunk == "inference" else Net.forward(self, x)
         # reproducible mode: the gather backward, the same bits every time; otherwise the faster scatter with float atomics
         s, n = indexing.affinity_displacement_sums(torch.sigmoid(edge_out), dp_out, label, self.path_index.radius,
                                                    ordered=_r50.DETERMINISTIC is True)

@@ -1,5 +1,5 @@
 """Host-side wrappers of the kernels in libirn_hip.so outside the walk: label epilogue, CAM merge, the trunk's elementwise
-passes (bn_act_, stem_pool, upsample_bilinear), image resizing and the instance front end.  The hipBLASLt convolutions of the
+passes (bn_act_, its differentiable form bn_act, stem_pool, upsample_bilinear), image resizing and the instance front end.  The hipBLASLt convolutions of the
 trunk live in `irn_amd.gemm`; their functions are reachable from here too.
 
 Reference functions mirrored (names kept where the reference has one):
@@ -154,6 +154,136 @@ def bn_act_(x, scale, shift, residual=None, relu=True, residual_affine=None):
             check(lib.irn_bn_act(xi.data_ptr(), None if ri is None else ri.data_ptr(), scale.data_ptr(), shift.data_ptr(), rs, rb,
                                  int(xi.shape[0]), n_ch, plane, 1 if relu else 0, _stream()))
     return x
+
+
+def bn_fold(weight, bias, running_mean, running_var, eps):
+    """(scale, shift) fp32 [C] of an inference batch norm in ONE launch (irn_bn_fold): bit for bit
+    `FrozenBatchNorm._fold64()` rounded to fp32.  For the training seam, where the optimiser writes the parameters every step
+    and the cached `folded()` would refold every layer with a dozen small kernels."""
+    _need_cuda(weight, "bn_fold: weight")
+    n_ch = int(weight.numel())
+    ts = [t.detach() for t in (weight, bias, running_mean, running_var)]
+    for name, t in zip(("weight", "bias", "running_mean", "running_var"), ts):
+        _need_vec(t, "bn_fold: " + name, n_ch, weight.device)
+    out = torch.empty((2, n_ch), dtype=torch.float32, device=weight.device)
+    if n_ch:
+        with torch.cuda.device(weight.device):
+            check(lib.irn_bn_fold(ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr(), ts[3].data_ptr(), float(eps), n_ch,
+                                  out[0].data_ptr(), out[1].data_ptr(), _stream()))
+    return out[0], out[1]
+
+
+def bn_param_grads(s0, s1, running_mean, running_var, eps):
+    """(grad_weight, grad_bias) fp32 [C] of an inference batch norm y = (x - mean) / sqrt(var + eps) * weight + bias from the
+    channel sums S0 = sum dz and S1 = sum dz * x of the gradient dz that arrives at y (fp64 [C], `irn_bn_act_backward`):
+    grad_weight = (S1 - mean * S0) / sqrt(var + eps), grad_bias = S0, in double, rounded once.  Plain tensor arithmetic:
+    works on any device."""
+    mean, var = running_mean.detach().double(), running_var.detach().double()
+    return ((s1 - mean * s0) / torch.sqrt(var + eps)).float(), s0.float()
+
+
+def _bn_act_backward(grad_out, out, x, res, scale, res_scale, relu, want_x, want_res, want_sums):
+    """irn_bn_act_backward: (grad_x, grad_res, sums) with None for what was not asked for; sums fp64 [2 or 3, C]."""
+    n_img, n_ch = int(grad_out.shape[0]), int(grad_out.shape[1])
+    plane = grad_out[0, 0].numel() if n_img else 0
+    dev = grad_out.device
+    grad_x = torch.empty_like(grad_out) if want_x else None
+    grad_res = torch.empty_like(grad_out) if want_res else None
+    sums = ws = None
+    ws_bytes = 0
+    if want_sums:
+        sums = torch.empty((3 if res_scale is not None else 2, n_ch), dtype=torch.float64, device=dev)
+        ws_bytes = int(lib.irn_bn_act_backward_workspace_bytes(n_img, n_ch, plane))
+        ws = torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        check(lib.irn_bn_act_backward(grad_out.data_ptr(), ptr(out) if relu else None, ptr(x) if want_sums else None,
+                                      ptr(res) if (want_sums and res_scale is not None) else None, ptr(scale) if want_x else None,
+                                      ptr(res_scale), ptr(grad_x), ptr(grad_res), ptr(sums), n_img, n_ch, plane, 1 if relu else 0,
+                                      ptr(ws), ws_bytes, _stream()))
+    return grad_x, grad_res, sums
+
+
+class _BnAct(torch.autograd.Function):
+    """irn_bn_fold + irn_bn_act_forward with irn_bn_act_backward as the vector-Jacobian product; x is saved for the weight
+    gradient, the output for the ReLU mask, the residual when it has a batch norm of its own."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, mean, var, residual, r_weight, r_bias, r_mean, r_var, eps, r_eps, relu):
+        scale, shift = bn_fold(weight, bias, mean, var, eps)
+        res_bn = r_weight is not None
+        rs, rb = bn_fold(r_weight, r_bias, r_mean, r_var, r_eps) if res_bn else (None, None)
+        out = torch.empty_like(x)
+        n_img = int(x.shape[0])
+        if x.numel():
+            with torch.cuda.device(x.device):
+                check(lib.irn_bn_act_forward(x.data_ptr(), None if residual is None else residual.data_ptr(), scale.data_ptr(),
+                                             shift.data_ptr(), None if rs is None else rs.data_ptr(), None if rb is None else rb.data_ptr(),
+                                             out.data_ptr(), n_img, int(x.shape[1]), x[0, 0].numel(), 1 if relu else 0, _stream()))
+        ctx.relu, ctx.res_bn, ctx.has_res, ctx.eps, ctx.r_eps = relu, res_bn, residual is not None, eps, r_eps
+        ctx.save_for_backward(x, out if relu else None, residual if res_bn else None, scale, rs, mean, var, r_mean, r_var)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, out, residual, scale, rs, mean, var, r_mean, r_var = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want_x, want_res = need[0], ctx.has_res and need[5]
+        want_sums = need[1] or need[2] or (ctx.res_bn and (need[6] or need[7]))
+        grads = [None] * 13
+        if not (want_x or want_res or want_sums):
+            return tuple(grads)
+        grad_out = grad_out.contiguous().float()
+        if grad_out.data_ptr() % 16:
+            grad_out = grad_out.clone()
+        if grad_out.numel() == 0:
+            gx, gr, sums = (torch.zeros_like(x) if want_x else None, torch.zeros_like(x) if want_res else None,
+                            torch.zeros((3 if ctx.res_bn else 2, x.shape[1]), dtype=torch.float64, device=x.device))
+        else:
+            gx, gr, sums = _bn_act_backward(grad_out, out, x, residual, scale, rs, ctx.relu, want_x, want_res, want_sums)
+        grads[0], grads[5] = gx, gr
+        if need[1] or need[2]:
+            gw, gb = bn_param_grads(sums[0], sums[1], mean, var, ctx.eps)
+            grads[1], grads[2] = (gw if need[1] else None), (gb if need[2] else None)
+        if ctx.res_bn and (need[6] or need[7]):
+            gw, gb = bn_param_grads(sums[0], sums[2], r_mean, r_var, ctx.r_eps)
+            grads[6], grads[7] = (gw if need[6] else None), (gb if need[7] else None)
+        return tuple(grads)
+
+
+def bn_act(x, weight, bias, running_mean, running_var, eps, residual=None, relu=True, residual_bn=None):
+    """Inference-statistics batch norm (+ residual) (+ ReLU) as ONE differentiable pass out of place — the training form of
+    `bn_act_`, the elementwise tail of reference net/resnet50.py:34-54 under autograd:
+    ``out = act((x - mean) / sqrt(var + eps) * weight + bias (+ r))``, r = residual or, with ``residual_bn`` (a batch-norm
+    module, or a tuple (weight, bias, running_mean, running_var, eps): the projection shortcut's), that layer applied to the
+    residual.  Differentiable once in x, residual and the two layers' weight and bias (irn_bn_act_backward; no atomics, the
+    same bits every time); the forward equals `bn_act_` on the folded constants bit for bit.  x, residual: GPU fp32
+    [N, C, ...] contiguous and 16-byte aligned, fewer than 2^31 elements; the parameters GPU fp32 [C]."""
+    _need_cuda(x, "bn_act: x")
+    if x.dtype != torch.float32 or x.dim() < 2 or not x.is_contiguous() or x.data_ptr() % 16 or x.numel() >= 2 ** 31:
+        raise ValueError("bn_act: x must be a contiguous, 16-byte aligned fp32 [N, C, ...] tensor of fewer than 2^31 elements, got %s %s"
+                         % (x.dtype, tuple(x.shape)))
+    n_ch = int(x.shape[1])
+    if residual is not None and (not isinstance(residual, torch.Tensor) or residual.shape != x.shape or residual.dtype != torch.float32
+                                 or residual.device != x.device or not residual.is_contiguous() or residual.data_ptr() % 16):
+        raise ValueError("bn_act: residual must match x (shape %s, fp32, contiguous, 16-byte aligned, same device)" % (tuple(x.shape),))
+    r = (None,) * 5
+    if residual_bn is not None:
+        if residual is None:
+            raise ValueError("bn_act: residual_bn without a residual")
+        r = tuple(residual_bn) if isinstance(residual_bn, (tuple, list)) else (
+            residual_bn.weight, residual_bn.bias, residual_bn.running_mean, residual_bn.running_var, residual_bn.eps)
+        if len(r) != 5:
+            raise ValueError("bn_act: residual_bn is a module or (weight, bias, running_mean, running_var, eps)")
+    names = ("weight", "bias", "running_mean", "running_var")
+    for name, t in list(zip(names, (weight, bias, running_mean, running_var))) + (
+            [("residual " + n, t) for n, t in zip(names, r[:4])] if residual_bn is not None else []):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("bn_act: %s must be a tensor" % name)
+        _need_vec(t, "bn_act: " + name, n_ch, x.device)
+    return _BnAct.apply(x, weight, bias, running_mean, running_var, residual, r[0], r[1], r[2], r[3], float(eps),
+                        None if r[4] is None else float(r[4]), bool(relu))
 
 
 def _need_f32_contig(t, what, min_dim):

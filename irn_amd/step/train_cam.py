@@ -2,7 +2,7 @@
 
 Reads  args.train_list, args.val_list, args.voc12_root (cls_labels.npy beside the lists), args.cam_crop_size,
        args.cam_batch_size, args.cam_num_epoches, args.cam_learning_rate, args.cam_weight_decay, args.num_workers,
-       args.seed, args.cam_init_weights, args.cam_resize_long, args.cam_augment
+       args.seed, args.cam_init_weights, args.cam_resize_long, args.cam_augment, args.cam_fused_tail
 Writes args.cam_weights_name + '.pth' (the reference appends the suffix, step/train_cam.py:100, and make_cam reads the file
        under that name): the state dict of net.resnet50_cam.Net, which loads into CAM with strict=True
 
@@ -14,6 +14,9 @@ of the trunk, which the reference detaches, run under `no_grad` (`Net.forward_tr
 one device.  The draws of an item come from (seed, epoch, index) and the shuffle from seed + epoch, so a run is fixed by
 its seed whatever the number of loader workers; in the reproducible mode (IRN_DETERMINISTIC, default 1) the step sets the
 process's mode before its first convolution like train_irn, and two runs write the same file.  Initial weights:
+With `--cam_fused_tail 1` (default 0) the elementwise tail of every unit of the trained half — batch norm, residual add, ReLU
+and their backward — is one differentiable HIP pass each way (`ops.bn_act`, irn_amd/csrc/bn_act.hip) instead of ATen's
+composed kernels; reproducible like the default, other bits (one rounding per layer differs).
 `--cam_init_weights` (a state dict loaded non-strictly: a bare ResNet-50 trunk such as the ImageNet one, or a full `Net`
 state), else the seeded random state of net.weights; nothing is downloaded.
 """
@@ -104,13 +107,14 @@ def run(args):
     from ..net import resnet50 as _r50
     from . import _common
     # this IS the caller's process: its own torch.backends.cudnn.deterministic and the trunk's mode are put back on return
-    saved = (torch.backends.cudnn.deterministic, _r50.DETERMINISTIC)
+    saved = (torch.backends.cudnn.deterministic, _r50.DETERMINISTIC, _r50.TRAIN_FUSED_TAIL)
     try:
         # before the model is built or a convolution runs: MIOpen keeps the solver it resolved for a problem
         _common.apply_deterministic_setting()
+        _r50.TRAIN_FUSED_TAIL = bool(int(getattr(args, "cam_fused_tail", 0) or 0))
         return _run(args)
     finally:
-        torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
+        torch.backends.cudnn.deterministic, _r50.DETERMINISTIC, _r50.TRAIN_FUSED_TAIL = saved
 
 
 def _run(args):

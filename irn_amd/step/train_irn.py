@@ -2,7 +2,7 @@
 
 Reads  args.train_list, args.infer_list, args.voc12_root, args.ir_label_out_dir (the PNGs of cam_to_ir_label),
        args.irn_crop_size, args.irn_batch_size, args.irn_num_epoches, args.irn_learning_rate, args.irn_weight_decay,
-       args.num_workers, args.seed, args.irn_init_weights, args.irn_augment
+       args.num_workers, args.seed, args.irn_init_weights, args.irn_augment, args.irn_trunk
 Writes args.irn_weights_name: the state dict the label steps load (EdgeDisplacement through net.weights.load_checkpoint)
 
 The reference's loop with three differences.  The input batch is built on the GPU (`--irn_augment device`, the default):
@@ -16,7 +16,11 @@ tensors and no [B, |S|, N] tensor exists on the device.  And there is no nn.Data
 mode (IRN_DETERMINISTIC, default 1; run_train.py --deterministic) the step sets the process's mode before its first
 convolution like the label steps, the loss back-propagates through its ordered gather and the heads' `Upsample -> ReLU`
 through `ops.upsample_bilinear`: no float atomic takes part in a gradient.  `--deterministic 0` keeps the faster scatter
-kernels, whose gradients are reproducible to rounding only.  Initial weights: `--irn_init_weights` (a state dict, loaded
+kernels, whose gradients are reproducible to rounding only.  `--irn_trunk inference` (default `autograd`) runs the frozen
+trunk of a step under `no_grad` on the label steps' inference path (`Net.forward_train`): the process then completes its
+MIOpen database from the shipped one (`_common.miopen_setup`), a crop the database is tuned for goes through the
+channels-last split-GEMM pass in rows of 16, any other crop — in the reproducible mode — through NCHW passes of 2 rows, which
+can be slower than `autograd`.  Initial weights: `--irn_init_weights` (a state dict, loaded
 non-strictly: an ImageNet trunk, or an earlier checkpoint), else the seeded random state of net.weights; nothing is
 downloaded.
 """
@@ -83,9 +87,27 @@ def device_images(pack, crop, device):
     return pack["img"].to(device, non_blocking=True)
 
 
-def train_step(model, optimizer, img, label):
+def irn_trunk(args):
+    mode = getattr(args, "irn_trunk", "autograd") or "autograd"
+    if mode not in ("autograd", "inference"):
+        raise ValueError("train_irn: irn_trunk is 'autograd' or 'inference', got %r" % (mode,))
+    return mode
+
+
+def check_split_overflow(trunk):
+    """`--irn_trunk inference`: the trunk ran through the split-precision GEMMs; an activation beyond fp16's range there
+    invalidates the step (read-back: synchronises)."""
+    if trunk == "inference":
+        from .. import ops
+        if ops.split_overflowed():
+            raise RuntimeError("train_irn: an activation of the trunk was beyond fp16's range (|x| > 65504) or NaN inside the "
+                               "split-precision convolutions; the steps since the last check are INVALID.  Run with "
+                               "`run_train.py --split_gemm 0` (IRN_SPLIT_GEMM=0): the fp32 GEMMs have no such limit.")
+
+
+def train_step(model, optimizer, img, label, trunk="autograd"):
     """One optimisation step on a batch already on the device; returns the four losses as a device tensor [4]."""
-    parts = model.fused_losses(img, label)
+    parts = model.fused_losses(img, label) if trunk == "autograd" else model.fused_losses(img, label, trunk=trunk)
     pos_aff_loss, neg_aff_loss, dp_fg_loss, dp_bg_loss = parts
     total_loss = (pos_aff_loss + neg_aff_loss) / 2 + (dp_fg_loss + dp_bg_loss) / 2
     optimizer.zero_grad()
@@ -115,6 +137,10 @@ def run(args):
     try:
         # before the model is built or a convolution runs: MIOpen keeps the solver it resolved for a problem
         _common.apply_deterministic_setting()
+        if irn_trunk(args) == "inference":
+            # the tuned channels-last pass is taken only in a process whose MIOpen database has been completed from the shipped
+            # one; the default mode leaves MIOpen as it finds it, so that its solver choices do not move
+            _common.miopen_setup(torch.cuda.current_device())
         return _run(args)
     finally:
         torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
@@ -128,6 +154,7 @@ def _run(args):
     path_index = indexing.PathIndex(radius=10, default_size=(grid, grid))
     model = build_model(args, path_index)
 
+    trunk = irn_trunk(args)
     train_dataset, infer_dataset = make_datasets(args, seed)
     max_step = (len(train_dataset) // args.irn_batch_size) * args.irn_num_epoches
     if max_step == 0:
@@ -148,12 +175,13 @@ def _run(args):
         train_dataset.set_epoch(ep)
         for it, pack in enumerate(_loader(train_dataset, args, True, seed + ep)):
             img, label = device_batch(pack, args.irn_crop_size, device)
-            pending.append(train_step(model, optimizer, img, label))
+            pending.append(train_step(model, optimizer, img, label, trunk))
             if first is None:
                 first = [float(v) for v in pending[0].cpu()]
             if (optimizer.global_step - 1) % 50 == 0:
                 timer.update_progress(optimizer.global_step / max_step)
                 mean = torch.stack(pending).mean(0).cpu()          # the one read-back per 50 steps
+                check_split_overflow(trunk)
                 pending = []
                 print("step:%5d/%5d" % (optimizer.global_step - 1, max_step),
                       "loss:%.4f %.4f %.4f %.4f" % tuple(float(v) for v in mean),
@@ -162,6 +190,7 @@ def _run(args):
                       "etc:%s" % (timer.str_estimated_complete()), flush=True)
         timer.reset_stage()
 
+    check_split_overflow(trunk)                                    # before anything is saved
     model.eval()
     # the mean is that of the raw field: in eval mode `mean_shift` subtracts whatever the initial weights carried (zeros in
     # the reference, which always starts from a fresh module; an earlier checkpoint or the seeded random state do not)

@@ -5,7 +5,7 @@ asked for, so that labels and weights come out of one command:
     python run_train.py --voc12_root VOC2012 --cam_to_ir_label_pass True --train_irn_pass True
 
 The flags are run_sample.py's (the `irn_*` hyper-parameters that run_sample.py accepts and ignores are read here) plus
---seed, --irn_init_weights and --irn_augment.  run_sample.py itself keeps refusing the training passes; `--train_cam_pass` is refused
+--seed, --irn_init_weights, --irn_augment and --irn_trunk.  run_sample.py itself keeps refusing the training passes; `--train_cam_pass` is refused
 here as well: CAM training has a command of its own, `python run_train_cam.py` (irn_amd/step/train_cam.py).
 """
 import os
@@ -24,6 +24,12 @@ def build_parser():
                    help="device: the loader hands over bytes, the IR label map and the draws, the (image, label) batch is "
                         "rescaled / mirrored / cropped on the GPU (bit-identical); host: the PIL / numpy pipeline in the "
                         "loader workers")
+    p.add_argument("--irn_trunk", default="autograd", choices=("autograd", "inference"),
+                   help="autograd: the frozen trunk of a training step runs inside the autograd graph (NCHW, composed ops, fp32 "
+                        "MIOpen convolutions); inference: under no_grad on the label steps' path — fused tails, and for a crop the "
+                        "shipped MIOpen database is tuned for (512) the channels-last split-GEMM pass in rows of 16.  In the "
+                        "reproducible mode any OTHER crop runs the trunk in NCHW passes of 2 rows, which can be slower than "
+                        "autograd.  Same gradients up to rounding, other bits")
     return p
 
 
@@ -32,6 +38,10 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.train_cam_pass:
         raise SystemExit("--train_cam_pass: CAM training is run by `python run_train_cam.py`, not from here")
+    if args.split_gemm is not None:
+        os.environ["IRN_SPLIT_GEMM"] = str(int(args.split_gemm))           # workers read it when they import the trunk
+        from irn_amd.net import resnet50 as _r50
+        _r50.SPLIT_GEMM = bool(args.split_gemm)
     if args.deterministic is not None:
         os.environ["IRN_DETERMINISTIC"] = str(int(args.deterministic))
     pyutils.Logger(args.log_name + ".log")

@@ -6,7 +6,7 @@ every other step starts from:
     python run_sample.py --voc12_root VOC2012            # make_cam reads the file written above
 
 The flags are run_train.py's (the `cam_*` hyper-parameters, --train_list, --val_list, --cam_weights_name, --seed,
---deterministic) plus --cam_init_weights, --cam_resize_long and --cam_augment.  The step has a command of its own because
+--deterministic) plus --cam_init_weights, --cam_resize_long, --cam_augment and --cam_fused_tail.  The step has a command of its own because
 run_sample.py and run_train.py keep refusing `--train_cam_pass True`; the pass flags are parsed and ignored here.
 """
 import os
@@ -26,6 +26,9 @@ def build_parser():
     p.add_argument("--cam_augment", default="device", choices=("device", "host"),
                    help="device: the loader hands over bytes and draws, the batch is resized / mirrored / cropped on the GPU "
                         "(bit-identical); host: the reference's PIL / numpy pipeline in the loader workers")
+    p.add_argument("--cam_fused_tail", default=0, type=int, choices=(0, 1),
+                   help="1: batch norm + residual + ReLU of the trained stages as one differentiable HIP pass forward and one "
+                        "backward (ops.bn_act) instead of the composed autograd ops; reproducible either way, the bits differ")
     return p
 
 

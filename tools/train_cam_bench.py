@@ -9,7 +9,10 @@ upload, two launches) — the device time between two events around the call and
 device-side packing alone).  `host_pipeline`: the reference's PIL / numpy augmentation of one decoded image on one CPU
 thread, median per image.  `step`: images/s of `train_cam`'s own loop (loader with `--workers` processes, batch on the
 device, forward, backward, update) over `--steps` steps after `--warmup`, once with `--cam_augment device` and once with
-`host`; the clock stops behind a device synchronise.  Needs a GPU: there is no fallback.
+`host`; the clock stops behind a device synchronise.  `--fused_tail_rounds N` adds N pairs of the same `step` section with the
+trained stages' fused training tail off and on (`resnet50.TRAIN_FUSED_TAIL`, run_train_cam.py --cam_fused_tail), alternating,
+`--cam_augment device`; each line carries the peak of allocated device memory.  `--skip_pipeline` / `--skip_augment_steps`
+leave the input-pipeline sections / the device-host pairs out.  Needs a GPU: there is no fallback.
 """
 import argparse
 import json
@@ -101,10 +104,20 @@ def bench_host_pipeline(raw, host, n):
     return {"images": n, "decode_only_ms_median": statistics.median(t_raw), "decode_and_augment_ms_median": statistics.median(t_host)}
 
 
-def bench_step(args, a, dev):
+def bench_step(args, a, dev, fused_tail=False):
     from irn_amd.misc import torchutils
+    from irn_amd.net import resnet50 as _r50
     from irn_amd.step import train_cam
+    _r50.TRAIN_FUSED_TAIL = bool(fused_tail)
+    try:
+        return _bench_step(args, a, dev, torchutils, train_cam, bool(fused_tail))
+    finally:
+        _r50.TRAIN_FUSED_TAIL = False
+
+
+def _bench_step(args, a, dev, torchutils, train_cam, fused_tail):
     torch.manual_seed(0)
+    torch.cuda.reset_peak_memory_stats()
     model = train_cam.build_model(args).to(dev).train()
     train, _ = train_cam.make_datasets(args, 0)
     backbone, new = model.trainable_parameters()
@@ -126,7 +139,9 @@ def bench_step(args, a, dev):
         ep += 1
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    return {"augment": args.cam_augment, "steps": a.steps, "seconds": dt, "images_per_s": a.steps * a.batch / dt}
+    return {"augment": args.cam_augment, "fused_tail": int(fused_tail), "steps": a.steps, "seconds": dt,
+            "images_per_s": a.steps * a.batch / dt, "ms_per_step": dt / a.steps * 1e3,
+            "max_memory_allocated_mb": torch.cuda.max_memory_allocated() / 2 ** 20}
 
 
 def main(argv=None):
@@ -138,6 +153,9 @@ def main(argv=None):
     p.add_argument("--steps", default=20, type=int)
     p.add_argument("--workers", default=8, type=int)
     p.add_argument("--skip_step", action="store_true", help="the input pipeline only")
+    p.add_argument("--skip_pipeline", action="store_true", help="no `augment` / `host_pipeline` sections")
+    p.add_argument("--skip_augment_steps", action="store_true", help="no device / host pairs of the `step` section")
+    p.add_argument("--fused_tail_rounds", default=0, type=int, help="pairs of the `step` section with the fused training tail off / on")
     a = p.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("train_cam_bench needs a GPU")
@@ -149,14 +167,17 @@ def main(argv=None):
         lst = write_tree(root, a.images)
         args = step_args(root, lst, a, "device")
         raw, _ = train_cam.make_datasets(args, 0)
-        print(json.dumps({"augment": bench_augment(raw, a, dev)}), flush=True)
-        host, _ = train_cam.make_datasets(step_args(root, lst, a, "host"), 0)
-        print(json.dumps({"host_pipeline": bench_host_pipeline(raw, host, min(a.images, 64))}), flush=True)
+        if not a.skip_pipeline:
+            print(json.dumps({"augment": bench_augment(raw, a, dev)}), flush=True)
+            host, _ = train_cam.make_datasets(step_args(root, lst, a, "host"), 0)
+            print(json.dumps({"host_pipeline": bench_host_pipeline(raw, host, min(a.images, 64))}), flush=True)
         if not a.skip_step:
             try:
                 _common.apply_deterministic_setting()
-                for augment in ("device", "host", "device", "host"):          # alternating: the spread shows next to the difference
+                for augment in () if a.skip_augment_steps else ("device", "host", "device", "host"):   # alternating: the spread shows next to the difference
                     print(json.dumps({"step": bench_step(step_args(root, lst, a, augment), a, dev)}), flush=True)
+                for fused in (0, 1) * a.fused_tail_rounds:
+                    print(json.dumps({"step": bench_step(step_args(root, lst, a, "device"), a, dev, fused)}), flush=True)
             finally:
                 torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
 

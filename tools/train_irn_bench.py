@@ -11,7 +11,12 @@ thread, median per image.  `step`: images/s of `train_irn`'s own loop (loader wi
 forward, fused loss, backward, update) over `--steps` steps after `--warmup` of ONE pass over the list (each image is named
 several times) — the model is built, MIOpen's first-use searches have run and the loader's workers have started before the
 clock starts — with `--irn_augment device` and `host` alternating `--rounds` times; the clock stops behind a device
-synchronise.  Needs a GPU: there is no fallback.
+synchronise.  `--irn_trunk autograd` (default) / `inference` / `both` chooses the trunk of the step (run_train.py --irn_trunk):
+with `both` every round runs the augment modes given by `--augments` once per trunk mode, alternating.  `inference` and `both`
+set MIOpen up as `train_irn.run` does for `--irn_trunk inference` (`_common.miopen_setup`, before the model is built) — for the
+whole process, so the default path's own figure is that of a run with `--irn_trunk autograd`.  Every `step` line carries the
+trunk passes it counted by layout (`resnet50.PASS_STATS`) and the peak of allocated device memory.  `--skip_pipeline` leaves
+the input-pipeline sections out.  Needs a GPU: there is no fallback.
 """
 import argparse
 import json
@@ -108,9 +113,12 @@ def bench_host_pipeline(raw, host, n):
     return {"images": n, "decode_only_ms_median": statistics.median(t_raw), "decode_and_augment_ms_median": statistics.median(t_host)}
 
 
-def bench_step(args, a, dev, model, optimizer):
+def bench_step(args, a, dev, model, optimizer, trunk="autograd"):
+    from irn_amd.net import resnet50 as _r50
     from irn_amd.step import train_irn
     train, _ = train_irn.make_datasets(args, 0)
+    torch.cuda.reset_peak_memory_stats()
+    before = {k: _r50.PASS_STATS[k] for k in ("channels_last", "nchw", "pad_rows")}
     assert len(train) >= (a.warmup + a.steps) * a.batch          # one pass: the loader's start lies in the warm-up
     done, t0 = 0, None
     for pack in train_irn._loader(train, args, True, 0):
@@ -118,13 +126,17 @@ def bench_step(args, a, dev, model, optimizer):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
         img, label = train_irn.device_batch(pack, args.irn_crop_size, dev)
-        train_irn.train_step(model, optimizer, img, label)
+        train_irn.train_step(model, optimizer, img, label, trunk)
         done += 1
         if done == a.warmup + a.steps:
             break
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    return {"augment": args.irn_augment, "workers": a.workers, "steps": a.steps, "seconds": dt, "images_per_s": a.steps * a.batch / dt}
+    train_irn.check_split_overflow(trunk)
+    return {"augment": args.irn_augment, "irn_trunk": trunk, "workers": a.workers, "steps": a.steps, "seconds": dt,
+            "images_per_s": a.steps * a.batch / dt, "ms_per_step": dt / a.steps * 1e3,
+            "trunk_passes": {k: _r50.PASS_STATS[k] - before[k] for k in before},
+            "max_memory_allocated_mb": torch.cuda.max_memory_allocated() / 2 ** 20}
 
 
 def main(argv=None):
@@ -138,6 +150,9 @@ def main(argv=None):
     p.add_argument("--workers", default=8, type=int)
     p.add_argument("--rounds", default=2, type=int, help="device / host pairs of the step section: the spread shows next to the difference")
     p.add_argument("--skip_step", action="store_true", help="the input pipeline only")
+    p.add_argument("--skip_pipeline", action="store_true", help="no `augment_pair` / `host_pipeline` sections")
+    p.add_argument("--irn_trunk", default="autograd", choices=("autograd", "inference", "both"))
+    p.add_argument("--augments", default=["device", "host"], nargs="+", choices=("device", "host"))
     a = p.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("train_irn_bench needs a GPU")
@@ -150,20 +165,25 @@ def main(argv=None):
         lst, label_dir = write_tree(root, a.images, repeat=-(-(a.warmup + a.steps) * a.batch // a.images))
         args = step_args(root, lst, label_dir, a, "device")
         raw, _ = train_irn.make_datasets(args, 0)
-        print(json.dumps({"augment_pair": bench_augment(raw, a, dev)}), flush=True)
-        host, _ = train_irn.make_datasets(step_args(root, lst, label_dir, a, "host"), 0)
-        print(json.dumps({"host_pipeline": bench_host_pipeline(raw, host, min(a.images, 64))}), flush=True)
+        if not a.skip_pipeline:
+            print(json.dumps({"augment_pair": bench_augment(raw, a, dev)}), flush=True)
+            host, _ = train_irn.make_datasets(step_args(root, lst, label_dir, a, "host"), 0)
+            print(json.dumps({"host_pipeline": bench_host_pipeline(raw, host, min(a.images, 64))}), flush=True)
         if not a.skip_step:
+            trunks = ("autograd", "inference") if a.irn_trunk == "both" else (a.irn_trunk,)
             try:
                 _common.apply_deterministic_setting()
+                if "inference" in trunks:
+                    _common.miopen_setup(torch.cuda.current_device())          # before the first convolution, as train_irn.run does
                 torch.manual_seed(0)
                 grid = a.crop // 4
                 model = train_irn.build_model(args, indexing.PathIndex(radius=10, default_size=(grid, grid))).to(dev).train()
                 edge, dp = model.trainable_parameters()
                 opt = torchutils.PolyOptimizer([{"params": edge, "lr": 0.01, "weight_decay": 1e-4}, {"params": dp, "lr": 0.1, "weight_decay": 1e-4}],
                                                lr=0.01, weight_decay=1e-4, max_step=10 ** 9)
-                for augment in ("device", "host") * a.rounds:
-                    print(json.dumps({"step": bench_step(step_args(root, lst, label_dir, a, augment), a, dev, model, opt)}), flush=True)
+                for augment in tuple(a.augments) * a.rounds:
+                    for trunk in trunks:
+                        print(json.dumps({"step": bench_step(step_args(root, lst, label_dir, a, augment), a, dev, model, opt, trunk)}), flush=True)
             finally:
                 torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
 

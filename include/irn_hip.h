@@ -655,6 +655,29 @@ int irn_mask_overlap(const uint8_t *masks_dev, int n, const uint8_t *inst_dev, i
                      void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Label threshold sweep  (step/make_sem_seg_labels.py:43-49 + step/eval_sem_seg.py:10-17 at T values
+ * of sem_seg_bg_thres in one pass; no label map and no [c,out_h,out_w] tensor is written).
+ * Images, sizes, keys and scratch (n_images * 4 bytes) as for irn_label_epilogue; keys are required
+ * and c <= 20.  gt_dev[i]: dev uint8 [out_h][out_w], 255 = void, ANY alignment (a batch's maps may be
+ * packed back to back).  thres dev fp32 [t], ascending, 1 <= t <= IRN_EVAL_MAX_THRES.
+ * Per output pixel, with v_c the score irn_label_epilogue compares (x4 bilinear upsample of channel
+ * c divided by the image's global maximum): if some v_c is NaN, c* is the first such channel and
+ * j = t (the epilogue, like torch.argmax, takes a NaN for the maximum: the pixel is keys[c*]+1 at
+ * every threshold); otherwise c* is the first channel that reaches the maximum m and j the number
+ * of thresholds < m (thres[i] == m is background: the epilogue compares with a strict >).  The
+ * pixel is one count in hist dev int64 [22][21][t+1] at [row][keys[c*]+1][j] — the layout of
+ * irn_cam_confusion, so irn_cam_confusion_reduce turns hist into the T confusion matrices, each
+ * equal to irn_label_confusion of the labels irn_label_epilogue writes at that threshold.
+ * hist and bad (int64 [1]) are added into; GT 21..254 and a key outside 0..19 are skipped and
+ * counted per pixel, a NaN or descending threshold once per call.  Nothing synchronises.
+ * ------------------------------------------------------------------------------------------- */
+int irn_label_sweep_confusion(int n_images, const float *const *rw_dev, const int32_t *c, const int32_t *h,
+                              const int32_t *w, const int32_t *out_h, const int32_t *out_w,
+                              const int64_t *const *keys_dev, const uint8_t *const *gt_dev,
+                              const float *thres_dev, int t, int64_t *hist_dev, int64_t *bad_dev,
+                              void *scratch_dev, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * COCO mask encoding  (replaces the pycococreatortools / pycocotools arithmetic behind
  *                      step/make_cocoann.py:38-46: per mask a run-length code, an area and a box)
  * masks dev uint8 [n][h][w], row-major, nonzero = in the mask (what make_ins_seg_labels writes and

@@ -107,6 +107,7 @@ _SIGS = {
     "irn_cam_confusion_reduce": (i32, [vp, i32, vp, vp, vp]),
     "irn_label_confusion": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "irn_mask_overlap": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+    "irn_label_sweep_confusion": (i32, [i32, ppv, pi32, pi32, pi32, pi32, pi32, ppv, ppv, vp, i32, vp, vp, vp, vp]),
     "irn_mask_rle_scratch_bytes": (sz, [i32, i32, i32]),
     "irn_mask_rle_count": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "irn_mask_rle_emit": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),

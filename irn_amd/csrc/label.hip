@@ -36,6 +36,7 @@ struct LabelJob {
     float *rw_up;           // [c,oh,ow] or null
     unsigned *max_slot;     // order-preserving encoding of the running max
     int c, h, w, oh, ow;
+    const uint8_t *gt;      // [oh,ow] ground truth (255 = void), any alignment: the threshold sweep only, else null
 };
 
 namespace {
@@ -196,6 +197,143 @@ __global__ __launch_bounds__(256) void label_argmax_kernel(const LabelJob *__res
 }
 
 // ---------------------------------------------------------------------------------------------
+// Threshold sweep against the ground truth (irn_label_sweep_confusion): what `label_argmax_kernel` + irn_label_confusion
+// count at T background thresholds, in one pass and without a label map.  The background plane only decides whether the
+// best channel wins, so a pixel's label at EVERY threshold follows from (c*, m): the first channel that reaches the
+// maximum m of the normalised scores predicts keys[c*] + 1 where thres < m (the epilogue's strict >) and 0 elsewhere;
+// with j = number of thresholds < m the pixel is one count in hist[gt row][keys[c*] + 1][j], the layout of
+// irn_cam_confusion (eval.hip), reduced by irn_cam_confusion_reduce.  A NaN score wins at every threshold as it does in
+// the epilogue (torch.argmax): c* = the first NaN channel, j = t.  Scores: `bilerp_vals` / `taps_x4` / the division by
+// the maximum of `upsample_max_kernel`, in the four-pixels-per-thread shape of `label_argmax_kernel`.
+//
+// Counting as in eval.hip: uint32 bins private to the block in LDS (4096 pixels per chunk: no overflow), non-zero bins
+// flushed with 64-bit integer atomics — exact, whatever the grid and the arrival order.  Bin = (j * 22 + row) * c + c*;
+// an image has (t + 1) * 22 * c of them (113 080 at c = 20, t = 256), so a chunk's bins stay in registers and are
+// counted in passes over bin ranges of `cap` (the dynamic LDS the host sized for the call: one pass for a typical grid).
+// ---------------------------------------------------------------------------------------------
+constexpr int kSweepGroups = 4;                          // 4-pixel groups per thread and chunk
+constexpr int kSweepChunk = 256 * kSweepGroups;          // groups per chunk (4096 pixels)
+constexpr int kSweepCap = 15360;                         // most LDS bins per pass (60 KiB; thresholds and columns follow)
+constexpr int kSweepRows = IRN_EVAL_CLASSES + 1;         // GT rows + the void row
+constexpr int kSweepMaxC = IRN_EVAL_CLASSES - 1;
+constexpr uint32_t kSweepSkip = 0xffffffffu;
+
+__global__ __launch_bounds__(256) void label_sweep_kernel(const LabelJob *__restrict__ jobs, const float *__restrict__ thres,
+                                                          int t, int cap, int64_t *__restrict__ hist, int64_t *__restrict__ bad) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t sweep_lds[];
+    uint32_t *bins = sweep_lds;                                       // [cap], cap a multiple of 4
+    float *th = reinterpret_cast<float *>(sweep_lds + cap);           // [IRN_EVAL_MAX_THRES]
+    int *col = reinterpret_cast<int *>(th + IRN_EVAL_MAX_THRES);      // [kSweepMaxC]
+    uint32_t *nbad = reinterpret_cast<uint32_t *>(col + kSweepMaxC);
+    const LabelJob J = jobs[blockIdx.y];
+    const int tid = threadIdx.x;
+    if (tid == 0) *nbad = 0;
+    for (int i = tid; i < t; i += 256) th[i] = thres[i];
+    if (tid < J.c) {
+        const int64_t key = J.keys[tid];
+        col[tid] = (key >= 0 && key < kSweepMaxC) ? (int)key + 1 : -1;
+    }
+    __syncthreads();
+    uint32_t local_bad = 0;
+    if (blockIdx.x == 0 && blockIdx.y == 0)                           // once per call
+        for (int i = tid; i < t; i += 256)
+            if (th[i] != th[i] || (i > 0 && !(th[i - 1] <= th[i]))) ++local_bad;
+
+    const unsigned gw = (unsigned)(J.ow + 3) >> 2, groups = gw * (unsigned)J.oh;
+    const unsigned chunks = (groups + kSweepChunk - 1) / kSweepChunk;
+    const uint32_t nbins = (uint32_t)(t + 1) * kSweepRows * (uint32_t)J.c;
+    const float gmax = dec_ordered(*J.max_slot);
+    for (unsigned chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
+        uint32_t bin[4 * kSweepGroups];
+#pragma unroll
+        for (int i = 0; i < kSweepGroups; ++i) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) bin[4 * i + q] = kSweepSkip;
+            const unsigned g = chunk * kSweepChunk + (unsigned)i * 256 + (unsigned)tid;
+            if (g >= groups) continue;
+            const int oy = (int)(g / gw), ox = (int)(g - (unsigned)oy * gw) * 4;
+            const int nq = min(4, J.ow - ox);
+            const Taps ty = taps_x4(oy, J.h);
+            Taps tx[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) tx[q] = taps_x4(min(ox + q, J.ow - 1), J.w);
+            float m[4] = {0.f, 0.f, 0.f, 0.f};
+            int cs[4] = {0, 0, 0, 0}, nanc[4] = {-1, -1, -1, -1};
+            for (int c = 0; c < J.c; ++c) {
+                const float *r0 = J.rw + (long)c * J.h * J.w + ty.i0 * J.w, *r1 = J.rw + (long)c * J.h * J.w + ty.i1 * J.w;
+                const float a00 = r0[tx[0].i0], a01 = r0[tx[0].i1], a10 = r1[tx[0].i0], a11 = r1[tx[0].i1];
+                const float b00 = r0[tx[2].i0], b01 = r0[tx[2].i1], b10 = r1[tx[2].i0], b11 = r1[tx[2].i1];
+                float v[4];
+                v[0] = bilerp_vals(a00, a01, a10, a11, ty, tx[0]) / gmax;
+                v[1] = bilerp_vals(a00, a01, a10, a11, ty, tx[1]) / gmax;
+                v[2] = bilerp_vals(b00, b01, b10, b11, ty, tx[2]) / gmax;
+                v[3] = bilerp_vals(b00, b01, b10, b11, ty, tx[3]) / gmax;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    if (c == 0 || v[q] > m[q]) {                      // strict: the first channel that reaches the maximum keeps it
+                        m[q] = v[q];
+                        cs[q] = c;
+                    }
+                    if (v[q] != v[q] && nanc[q] < 0) nanc[q] = c;
+                }
+            }
+            const uint8_t *gp = J.gt + ((unsigned)oy * (unsigned)J.ow + (unsigned)ox);
+            uint8_t gv[4] = {0, 0, 0, 0};
+            if (nq == 4 && ((uintptr_t)gp & 3) == 0) {
+                const uint32_t u = *reinterpret_cast<const uint32_t *>(gp);
+                gv[0] = (uint8_t)u; gv[1] = (uint8_t)(u >> 8); gv[2] = (uint8_t)(u >> 16); gv[3] = (uint8_t)(u >> 24);
+            } else {
+                for (int q = 0; q < nq; ++q) gv[q] = gp[q];
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                if (q >= nq) continue;
+                const int row = gv[q] <= 20 ? (int)gv[q] : (gv[q] == 255 ? IRN_EVAL_CLASSES : -1);
+                if (row < 0) {
+                    ++local_bad;                                       // GT 21..254
+                    continue;
+                }
+                int lo = 0, hi = t;                                    // j = number of thresholds < m (ascending list)
+                while (lo < hi) {
+                    const int mid = (lo + hi) >> 1;
+                    if (th[mid] < m[q]) lo = mid + 1;
+                    else hi = mid;
+                }
+                const int j = nanc[q] >= 0 ? t : lo, cq = nanc[q] >= 0 ? nanc[q] : cs[q];
+                bin[4 * i + q] = ((uint32_t)j * kSweepRows + (uint32_t)row) * (uint32_t)J.c + (uint32_t)cq;
+            }
+        }
+        for (uint32_t b0 = 0; b0 < nbins; b0 += (uint32_t)cap) {
+            const uint32_t nb = min((uint32_t)cap, nbins - b0);
+            for (uint32_t b = tid; b < nb; b += 256) bins[b] = 0;
+            __syncthreads();
+#pragma unroll
+            for (int i = 0; i < 4 * kSweepGroups; ++i)
+                if (bin[i] - b0 < nb) atomicAdd(&bins[bin[i] - b0], 1u);
+            __syncthreads();
+            for (uint32_t b = tid; b < nb; b += 256) {
+                const uint32_t v = bins[b];
+                if (!v) continue;
+                const uint32_t id = b0 + b;
+                const int c = (int)(id % (uint32_t)J.c);
+                const uint32_t r = id / (uint32_t)J.c;
+                const int row = (int)(r % kSweepRows), j = (int)(r / kSweepRows);
+                if (col[c] < 0) {
+                    local_bad += v;                                    // a key outside 0..19: its pixels are out of range
+                    continue;
+                }
+                atomicAdd(reinterpret_cast<unsigned long long *>(hist + ((size_t)row * IRN_EVAL_CLASSES + col[c]) * (t + 1) + j),
+                          (unsigned long long)v);
+            }
+            __syncthreads();
+        }
+    }
+    if (local_bad) atomicAdd(nbad, local_bad);
+    __syncthreads();
+    if (tid == 0 && *nbad) atomicAdd(reinterpret_cast<unsigned long long *>(bad), (unsigned long long)*nbad);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Multi-scale CAM merge (reference step/make_cam.py:38-52): for both target grids — the stride-4
 // grid (ceil(H/4), ceil(W/4)) and the stride-16-rounded full size cropped to (H, W) — sum over the
 // scales of F.interpolate(size=..., bilinear, align_corners=False), keep the present classes, divide
@@ -318,6 +456,63 @@ extern "C" int irn_label_epilogue(int n_images, const float *const *rw_dev, cons
     IRN_LAUNCH_CHECK("upsample_max_kernel<2>");
     hipLaunchKernelGGL(label_argmax_kernel, dim3(bx, n_images), dim3(256), 0, stream, jobs_dev, bg_thres);
     IRN_LAUNCH_CHECK("label_argmax_kernel");
+    return scratch_release(stream);
+}
+
+extern "C" int irn_label_sweep_confusion(int n_images, const float *const *rw_dev, const int32_t *c, const int32_t *h,
+                                         const int32_t *w, const int32_t *out_h, const int32_t *out_w,
+                                         const int64_t *const *keys_dev, const uint8_t *const *gt_dev,
+                                         const float *thres_dev, int t, int64_t *hist_dev, int64_t *bad_dev,
+                                         void *scratch_dev, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n_images < 1 || n_images > 65535 || !rw_dev || !c || !h || !w || !out_h || !out_w || !keys_dev || !gt_dev || !thres_dev ||
+        !hist_dev || !bad_dev || !scratch_dev || t < 1 || t > IRN_EVAL_MAX_THRES)
+        return fail(IRN_ERR_ARG, "irn_label_sweep_confusion: bad argument (n_images=%d, t=%d; 1 <= t <= %d)", n_images, t,
+                    IRN_EVAL_MAX_THRES);
+    std::vector<LabelJob> jobs(n_images);
+    long max_px = 0, max_cells = 0;
+    int max_c = 0;
+    for (int i = 0; i < n_images; ++i) {
+        LabelJob &J = jobs[i];
+        if (!rw_dev[i] || c[i] < 1 || c[i] > kSweepMaxC || h[i] < 1 || w[i] < 1 || out_h[i] < 1 || out_w[i] < 1 ||
+            out_h[i] > 4 * h[i] || out_w[i] > 4 * w[i])
+            return fail(IRN_ERR_ARG, "irn_label_sweep_confusion: image %d: bad sizes (c=%d %dx%d -> %dx%d; 1 <= c <= %d)", i,
+                        c[i], h[i], w[i], out_h[i], out_w[i], kSweepMaxC);
+        if (!keys_dev[i] || !gt_dev[i])
+            return fail(IRN_ERR_ARG, "irn_label_sweep_confusion: image %d: keys and ground truth are required", i);
+        J.rw = rw_dev[i];
+        J.keys = keys_dev[i];
+        J.labels = nullptr;
+        J.argmax = nullptr;
+        J.rw_up = nullptr;
+        J.gt = gt_dev[i];
+        J.max_slot = (unsigned *)scratch_dev + i;
+        J.c = c[i]; J.h = h[i]; J.w = w[i]; J.oh = out_h[i]; J.ow = out_w[i];
+        max_px = std::max(max_px, (long)out_h[i] * out_w[i]);
+        max_cells = std::max(max_cells, (long)c[i] * h[i] * w[i]);
+        max_c = std::max(max_c, c[i]);
+    }
+    if (max_px >= (1L << 31) || max_cells >= (1L << 31))
+        return fail(IRN_ERR_ARG, "irn_label_sweep_confusion: image too large (32-bit pixel indices)");
+    LabelJob *jobs_dev = nullptr;
+    int rc = scratch_upload(jobs.data(), sizeof(LabelJob) * n_images, (void **)&jobs_dev, stream);
+    if (rc) return rc;
+    IRN_HIP_TRY(hipMemsetAsync(scratch_dev, 0, sizeof(unsigned) * n_images, stream));
+    const long per_image = std::max<long>(1, 4096 / n_images);
+    const int bc = (int)std::min<long>((max_cells + 255) / 256, per_image);
+    hipLaunchKernelGGL(upsample_max_kernel<1>, dim3(bc, n_images), dim3(256), 0, stream, jobs_dev);
+    IRN_LAUNCH_CHECK("upsample_max_kernel<1>");
+    hipLaunchKernelGGL(upsample_max_kernel<2>, dim3(bc, n_images), dim3(256), 0, stream, jobs_dev);
+    IRN_LAUNCH_CHECK("upsample_max_kernel<2>");
+    // LDS bins for the call's largest image, at most kSweepCap per pass; at most 128 chunks of 4096 pixels per image and
+    // launch row (a 1040 x 528 image strides once)
+    const long nbins = (long)(t + 1) * kSweepRows * max_c;
+    const int cap = (int)std::min<long>((nbins + 3) / 4 * 4, kSweepCap);
+    const size_t lds = sizeof(uint32_t) * cap + sizeof(float) * IRN_EVAL_MAX_THRES + sizeof(int) * kSweepMaxC + sizeof(uint32_t);
+    const int bx = (int)std::min<long>(((max_px + 3) / 4 + kSweepChunk - 1) / kSweepChunk + 1, 128);
+    hipLaunchKernelGGL(label_sweep_kernel, dim3(bx, n_images), dim3(256), lds, stream, jobs_dev, thres_dev, t, cap, hist_dev,
+                       bad_dev);
+    IRN_LAUNCH_CHECK("label_sweep_kernel");
     return scratch_release(stream);
 }
 

@@ -1179,9 +1179,9 @@ def crf_ir_label(img, high_res, keys, fg_thres, bg_thres, t=CRF_T, gt_prob=CRF_G
 
 
 # --------------------------------------------------------------------------------------------------------------------
-# evaluation counts (step/eval_cam.py, step/eval_sem_seg.py, step/eval_ins_seg.py): include/irn_hip.h irn_cam_confusion,
-# irn_label_confusion, irn_mask_overlap.  Accumulators are int64 GPU tensors that every call adds into; `bad` (int64 [1])
-# counts values outside the documented ranges and the caller raises when it is non-zero.
+# evaluation counts (step/eval_cam.py, step/eval_sem_seg.py, step/eval_ins_seg.py, step/tune_sem_seg.py): include/irn_hip.h
+# irn_cam_confusion, irn_label_confusion, irn_mask_overlap, irn_label_sweep_confusion.  Accumulators are int64 GPU tensors that every
+# call adds into; `bad` (int64 [1]) counts values outside the documented ranges and the caller raises when it is non-zero.
 # --------------------------------------------------------------------------------------------------------------------
 EVAL_CLASSES = 21                     # background + 20 VOC classes
 EVAL_MAX_THRES = 256                  # IRN_EVAL_MAX_THRES
@@ -1256,6 +1256,74 @@ def cam_confusion_matrices(hist):
     with torch.cuda.device(hist.device):
         check(lib.irn_cam_confusion_reduce(hist.data_ptr(), t, conf.data_ptr(), void.data_ptr(), _stream()))
     return conf, void
+
+
+def label_sweep_confusion(rws, out_sizes, keys, gts, thres, hist=None, bad=None):
+    """`label_epilogue` + `label_confusion` at every background threshold of `thres` in one pass, for a batch (no label
+    map and no upsampled tensor is written).
+
+    rws, out_sizes, keys: as for `label_epilogue` (at most 20 channels per image); gts: a list of uint8 [H,W] GPU tensors
+    (255 = void), or ONE flat uint8 GPU buffer that holds the maps of `out_sizes` back to back; thres: GPU fp32 [T] from
+    `eval_thresholds` (or anything it takes).  Adds into hist int64 [22,21,T+1] — the layout of `cam_confusion`, so
+    `cam_confusion_matrices(hist)` gives the T matrices `label_confusion` counts on the labels of each threshold — and
+    bad int64 [1]; returns (hist, bad).  Everything is checked before the launch: a refusal leaves hist / bad untouched."""
+    n = len(rws)
+    if n < 1 or len(out_sizes) != n or len(keys) != n:
+        raise ValueError("label_sweep_confusion: %d score maps, %d sizes, %d key lists" % (n, len(out_sizes), len(keys)))
+    for r in rws:
+        _need_cuda(r, "rw")
+    dev = rws[0].device
+    sizes = [(int(s[0]), int(s[1])) for s in out_sizes]
+    if isinstance(gts, torch.Tensor):
+        _need_cuda(gts, "gts")
+        total = sum(hh * ww for hh, ww in sizes)
+        if gts.dtype != torch.uint8 or gts.dim() != 1 or not gts.is_contiguous() or gts.numel() != total or gts.device != dev:
+            raise ValueError("label_sweep_confusion: the packed ground truth must be a flat uint8 buffer of %d bytes on %s"
+                             % (total, dev))
+        offs = np.concatenate([[0], np.cumsum([hh * ww for hh, ww in sizes])])
+        gt_ptrs = [gts.data_ptr() + int(o) for o in offs[:-1]]
+        gs = gts
+    else:
+        if len(gts) != n:
+            raise ValueError("label_sweep_confusion: %d ground-truth maps for %d images" % (len(gts), n))
+        gs = []
+        for i, g in enumerate(gts):
+            _need_cuda(g, "gt")
+            if g.dtype != torch.uint8 or g.dim() != 2 or g.device != dev:
+                raise ValueError("label_sweep_confusion: gt %d must be a uint8 [H,W] tensor on %s" % (i, dev))
+            if tuple(g.shape) != sizes[i]:
+                raise ValueError("label_sweep_confusion: gt %d is %s for an output of %s" % (i, tuple(g.shape), sizes[i]))
+            gs.append(g.contiguous())
+        gt_ptrs = [g.data_ptr() for g in gs]
+    rs, ks = [], []
+    for i in range(n):
+        if rws[i].dim() < 2 or rws[i].device != dev:
+            raise ValueError("label_sweep_confusion: rw %d must be a [C,1,h,w] or [C,h,w] tensor on %s" % (i, dev))
+        r = rws[i].reshape((-1,) + tuple(rws[i].shape[-2:])).contiguous().float()
+        if not 1 <= r.shape[0] <= EVAL_CLASSES - 1:
+            raise ValueError("label_sweep_confusion: image %d has %d channels (1..%d)" % (i, r.shape[0], EVAL_CLASSES - 1))
+        if not (1 <= sizes[i][0] <= 4 * r.shape[1] and 1 <= sizes[i][1] <= 4 * r.shape[2]):
+            raise ValueError("label_sweep_confusion: image %d: output %s from a %dx%d map" % (i, sizes[i], r.shape[1], r.shape[2]))
+        k = torch.as_tensor(keys[i], device=dev).to(torch.int64).reshape(-1).contiguous()
+        if k.numel() != r.shape[0]:
+            raise ValueError("label_sweep_confusion: image %d: %d keys for %d channels" % (i, k.numel(), r.shape[0]))
+        rs.append(r)
+        ks.append(k)
+    th = thres if isinstance(thres, torch.Tensor) and thres.is_cuda and thres.dtype == torch.float32 else eval_thresholds(thres, dev)
+    th = th.to(dev).reshape(-1).contiguous()
+    t = int(th.numel())
+    if not 1 <= t <= EVAL_MAX_THRES:
+        raise ValueError("label_sweep_confusion: %d thresholds (1..%d)" % (t, EVAL_MAX_THRES))
+    hist = _accumulator(hist, (EVAL_CLASSES + 1, EVAL_CLASSES, t + 1), dev, "hist")
+    bad = _accumulator(bad, (1,), dev, "bad")
+    scratch = torch.empty(max(n, 64), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.irn_label_sweep_confusion(
+            n, ptr_array([r.data_ptr() for r in rs]), i32_array([r.shape[0] for r in rs]), i32_array([r.shape[1] for r in rs]),
+            i32_array([r.shape[2] for r in rs]), i32_array([s[0] for s in sizes]), i32_array([s[1] for s in sizes]),
+            ptr_array([k.data_ptr() for k in ks]), ptr_array(gt_ptrs), th.data_ptr(), t, hist.data_ptr(), bad.data_ptr(),
+            scratch.data_ptr(), _stream()))
+    return hist, bad
 
 
 def label_confusion(pred, gt, conf=None, bad=None, pred_255_as=0, void=None):

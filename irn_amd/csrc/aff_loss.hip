@@ -86,7 +86,7 @@ __device__ __forceinline__ void pair_terms(PairAcc &acc, const Tiles &T, int src
     acc.n_neg += neg;
 }
 
-// R > 0: the directions and their paths are compile-time constants (radius 5 and 10, as affinity_unrolled_kernel);
+// R > 0: the directions and their paths are compile-time constants (radius 5 and 10, as affinity_wide_kernel);
 // R == 0: the table-driven loop of affinity_kernel for any radius.
 template <int R>
 __global__ __launch_bounds__(256) void aff_loss_forward_kernel(const float *__restrict__ edge, const float *__restrict__ dp,

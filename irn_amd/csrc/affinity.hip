@@ -7,9 +7,13 @@
 //   POW=true  : w   = fp32(aff ** beta)                (walk weight table, raster plane order;
 //               fuses the Hadamard power of misc/indexing.py:133)
 //
-// Roofline: per source pixel the kernel reads n_cells LDS words (242 at r=5, 2134 at r=10) and writes
-// n_dirs floats (34 / 152) — one pass, LDS-issue bound; it runs once per image against 2^exp_times
-// sweeps of the walk, so it is <2 % of the path.
+// Roofline: per source pixel the kernel reads n_cells LDS words (242 at r=5, 2134 at r=10) and writes n_dirs floats
+// (34 / 152) in one pass; it runs once per image against 2^exp_times sweeps of the walk, so it is <5 % of the path
+// (DESIGN.md §kernels).  Measured on the default workload (192 images of 128x128, radius 10, 1.87 GB of planes;
+// profiles/affinity_wide_ab.txt): the one-pixel-per-lane form with 4-byte reads took 0.50 ms + 0.03 ms for the pads;
+// two pixels per lane with 8-byte reads, the power loop cut to the products that reach the result, 8-byte stores and the
+// pads in the same launch take 0.12 ms less.  Of that, 0.08 ms came with the 8-byte reads and stores and 0.04 ms with
+// the shorter power loop: the LDS array and the vector pipe both bound the old form; what is left writes at ~4.5 TB/s.
 #include "path_unroll.hpp"
 
 namespace irn {
@@ -97,45 +101,101 @@ __global__ __launch_bounds__(256) void affinity_kernel(const AffJob *__restrict_
 // weight table).  In the table-driven loop above every LDS read costs a vector add for its address (the cell's offset
 // arrives in a scalar register) and the loop is bound by the vector pipe (profiles/r02_s27_affinity_counters.txt: 11.5 k
 // vector instructions per wave for 2.6 k LDS reads).  Unrolled, the cell offsets are the immediate offsets of the
-// ds_read instructions: 2134 reads + 1067 v_max3 + 152 powers and stores of straight-line code at radius 10 (~40 KB,
-// inside the instruction cache, every wave running the same stream).
+// ds_read instructions, and a lane computes AFF_P horizontally adjacent pixels: every path cell is one aligned
+// 4*AFF_P-byte read (path_unroll.hpp: WideTile, path_max_wide) that serves AFF_P v_max3 chains.
+// The blocks behind the tiles of an image zero what no tile writes: every plane's front pad and tail (AffJob).
 // ------------------------------------------------------------------------------------------------
-template <int R>
-__global__ __launch_bounds__(256) void affinity_unrolled_kernel(const AffJob *__restrict__ jobs, int beta_int) {
-    constexpr int HALO = R - 1, LW = AFF_TW + 2 * HALO, LH = AFF_TH + HALO, ND = kPaths<R>.n_dirs;
-    __shared__ float tile[LH * LW];
+constexpr int AFF_P = 2;           // pixels per lane
+constexpr int AFF_PAD_BLOCKS = 8;  // blocks per image that zero the pads
+
+typedef __attribute__((address_space(1))) float global_float;   // the planes are global memory: no flat stores, whose
+template <int P>                                                // LDS-side counter the tile reads would wait on
+using global_floatP = __attribute__((address_space(1))) floatP<P>;
+
+template <int R, int P>
+__global__ __launch_bounds__(256) void affinity_wide_kernel(const AffJob *__restrict__ jobs, int beta_int, int max_tiles) {
+    using T = WideTile<R, P>;
+    constexpr int ND = kPaths<R>.n_dirs;
+    __shared__ __attribute__((aligned(16))) float tile[P * T::COPY];
     const AffJob J = jobs[blockIdx.y];
-    const int tiles_x = (J.sw + AFF_TW - 1) / AFF_TW;
-    const int tiles_y = (J.sh + AFF_TH - 1) / AFF_TH;
+    if ((int)blockIdx.x >= max_tiles) {
+        // [out - pad_front, out) and [out + sh*sw, out + sh*sw + pad_tail) of every plane
+        const long n = (long)J.sh * J.sw;
+        for (int d = (int)blockIdx.x - max_tiles; d < ND; d += AFF_PAD_BLOCKS) {
+            float *plane = J.out + (long)d * J.plane_stride;
+            for (int i = threadIdx.x; i < J.pad_front; i += 256) plane[i - J.pad_front] = 0.f;
+            for (int i = threadIdx.x; i < J.pad_tail; i += 256) plane[n + i] = 0.f;
+        }
+        return;
+    }
+    const int tiles_x = (J.sw + T::TW - 1) / T::TW;
+    const int tiles_y = (J.sh + T::TH - 1) / T::TH;
     if ((int)blockIdx.x >= tiles_x * tiles_y) return;
-    const int ty0 = ((int)blockIdx.x / tiles_x) * AFF_TH;
-    const int tx0 = ((int)blockIdx.x % tiles_x) * AFF_TW;
-    for (int i = threadIdx.x; i < LH * LW; i += 256) {          // staging as in affinity_kernel
-        const int ly = i / LW, lx = i - ly * LW;
+    const int ty0 = ((int)blockIdx.x / tiles_x) * T::TH;
+    const int tx0 = ((int)blockIdx.x % tiles_x) * T::TW;
+    for (int i = threadIdx.x; i < T::LH * T::LW; i += 256) {          // staging as in affinity_kernel, once per copy
+        const int ly = i / T::LW, lx = i - ly * T::LW;
         const int gy = J.oy + ty0 + ly;
-        const int gx = J.ox + tx0 + lx - HALO;
+        const int gx = J.ox + tx0 + lx - T::HALO;
         float v = 1.0f;
         if (gy < J.gh && gx >= 0 && gx < J.gw) v = J.edge[(long)gy * J.gw + gx];
-        tile[i] = v;
+#pragma unroll
+        for (int s = 0; s < P; ++s)
+            if (lx >= s) tile[s * T::COPY + ly * T::STRIDE + lx - s] = v;   // copy s, shifted left by s floats
     }
     __syncthreads();
-    const int ly = threadIdx.x / AFF_TW, lx = threadIdx.x % AFF_TW;
+    const int ly = threadIdx.x / T::LANES_X, lx = (threadIdx.x % T::LANES_X) * P;
     const int sy = ty0 + ly, sx = tx0 + lx;
-    const bool valid = sy < J.sh && sx < J.sw;
-    const float *tb = tile + ly * LW + lx;              // cell (cy, cx) of this pixel sits at tb[cy * LW + cx + HALO]
-    float *out = J.out + (long)sy * J.sw + sx;
-    static_for<ND>([&](auto id) __attribute__((always_inline)) {
-        constexpr int d = decltype(id)::value;
-        // integer beta only (the launch sends any other beta to the table-driven kernel): the general fp64 pow() inlined
-        // once per direction would be 300 KB of code
-        double b = (double)(1.0f - path_max<R, d>(tb)), r = 1.0;
-        for (int e = beta_int; e; e >>= 1) {
-            if (e & 1) r *= b;
-            b *= b;
-        }
-        if (valid) *out = (float)r;
-        out += J.plane_stride;
-    });
+    // cell (cy, cx) of pixel sx + p sits at float cy * STRIDE + cx + HALO + p of copy 0 from here
+    const unsigned tb = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float *)tile + 4 * (ly * T::STRIDE + lx);
+    global_float *out = (global_float *)J.out + (long)sy * J.sw + sx;
+    const int n_valid = sy < J.sh ? min(P, J.sw - sx) : 0;        // pixels of this lane inside the source rectangle
+    // one 4P-byte store where the lane's pixels are all inside and the address is aligned in every plane
+    const bool vec = n_valid == P && ((uintptr_t)out & (4 * P - 1)) == 0 && J.plane_stride % P == 0;
+    auto planes = [&](auto wide) __attribute__((always_inline)) {
+        static_for<ND>([&](auto id) __attribute__((always_inline)) {
+            constexpr int d = decltype(id)::value;
+            const floatP<P> m = path_max_wide<R, P, d>(tb);
+            // integer beta only (the launch sends any other beta to the table-driven kernel): the general fp64 pow()
+            // inlined once per direction would be 300 KB of code
+            // The square-and-multiply loop of affinity_kernel's pow_beta without what does not reach the result: the
+            // multiplications of 1.0 by the first factor (exact) and the squarings behind the top bit.  Same products,
+            // same roundings.  beta_int is uniform: the empty asm keeps `if (e & 1)` a scalar branch, not a select.
+            double b[P], r[P];
+            static_for<P>([&](auto ip) __attribute__((always_inline)) { b[decltype(ip)::value] = (double)(1.0f - m[decltype(ip)::value]); });
+            int e = beta_int;
+            for (; e > 1 && !(e & 1); e >>= 1)   // (e >= 1 by the launch; bounded whatever arrives)
+                static_for<P>([&](auto ip) __attribute__((always_inline)) { b[decltype(ip)::value] *= b[decltype(ip)::value]; });
+            static_for<P>([&](auto ip) __attribute__((always_inline)) { r[decltype(ip)::value] = b[decltype(ip)::value]; });
+            for (e >>= 1; e; e >>= 1) {
+                static_for<P>([&](auto ip) __attribute__((always_inline)) { b[decltype(ip)::value] *= b[decltype(ip)::value]; });
+                if (e & 1) {
+                    asm volatile("");
+                    static_for<P>([&](auto ip) __attribute__((always_inline)) { r[decltype(ip)::value] *= b[decltype(ip)::value]; });
+                }
+            }
+            floatP<P> w;
+            static_for<P>([&](auto ip) __attribute__((always_inline)) { w[decltype(ip)::value] = (float)r[decltype(ip)::value]; });
+            if constexpr (decltype(wide)::value) {
+                *reinterpret_cast<global_floatP<P> *>(out) = w;
+            } else {
+                static_for<P>([&](auto ip) __attribute__((always_inline)) {
+                    constexpr int p = decltype(ip)::value;
+                    if (p < n_valid) out[p] = w[p];
+                });
+            }
+            out += J.plane_stride;
+        });
+    };
+    // Two copies of the stream, chosen per wave: the one with the wide stores carries no per-plane predicates (its lanes
+    // are switched off once, here) and is the one every wave of an even-width, aligned grid runs; a wave with a ragged
+    // or unaligned lane stores pixel by pixel, all of its lanes.  67 KB and 74 KB of straight-line code at radius 10
+    // (the one-pixel stream was ~40 KB); a wave runs one of them, and the times in the header are with that fetch.
+    if (__builtin_amdgcn_ballot_w64(n_valid > 0 && !vec) == 0) {
+        if (vec) planes(std::true_type{});
+    } else {
+        planes(std::false_type{});
+    }
 }
 
 // Backward of edge_to_affinity for the training seam (reference net/resnet50_irn.py:162-175: index_select
@@ -206,19 +266,31 @@ __global__ __launch_bounds__(256) void affinity_backward_kernel(const AffJob *__
 
 }  // namespace
 
+bool affinity_writes_pads(const DeviceTable &tab, bool with_pow, float beta) {
+    return with_pow && tab.order == 1 && (tab.radius == 10 || tab.radius == 5) && beta == (float)(int)beta &&
+           beta >= 1.0f && beta <= 64.0f;
+}
+
 int launch_affinity(const AffJob *jobs_dev, int n_jobs, int max_sh, int max_sw, const DeviceTable &tab,
                     bool with_pow, float beta, hipStream_t stream) {
-    const int tiles = cdiv(max_sh, AFF_TH) * cdiv(max_sw, AFF_TW);
     const int halo = tab.radius - 1;
     const size_t lds = sizeof(float) * (AFF_TH + halo) * (AFF_TW + 2 * halo);
-    dim3 grid(tiles, n_jobs);
     int beta_int = 0;
     if (with_pow && beta == (float)(int)beta && beta >= 1.0f && beta <= 64.0f) beta_int = (int)beta;
-    if (with_pow && beta_int > 0 && tab.order == 1 && tab.radius == 10)
-        hipLaunchKernelGGL(affinity_unrolled_kernel<10>, grid, dim3(256), 0, stream, jobs_dev, beta_int);
-    else if (with_pow && beta_int > 0 && tab.order == 1 && tab.radius == 5)
-        hipLaunchKernelGGL(affinity_unrolled_kernel<5>, grid, dim3(256), 0, stream, jobs_dev, beta_int);
-    else if (with_pow)
+    if (affinity_writes_pads(tab, with_pow, beta)) {
+        using T = WideTile<10, AFF_P>;
+        static_assert(T::TW == WideTile<5, AFF_P>::TW && T::TH == WideTile<5, AFF_P>::TH, "one tile for both radii");
+        const int tiles = cdiv(max_sh, T::TH) * cdiv(max_sw, T::TW);
+        dim3 grid(tiles + AFF_PAD_BLOCKS, n_jobs);
+        if (tab.radius == 10)
+            hipLaunchKernelGGL((affinity_wide_kernel<10, AFF_P>), grid, dim3(256), 0, stream, jobs_dev, beta_int, tiles);
+        else
+            hipLaunchKernelGGL((affinity_wide_kernel<5, AFF_P>), grid, dim3(256), 0, stream, jobs_dev, beta_int, tiles);
+        IRN_LAUNCH_CHECK("affinity_wide_kernel");
+        return IRN_OK;
+    }
+    dim3 grid(cdiv(max_sh, AFF_TH) * cdiv(max_sw, AFF_TW), n_jobs);
+    if (with_pow)
         hipLaunchKernelGGL(affinity_kernel<true>, grid, dim3(256), lds, stream, jobs_dev, tab.dir_start8,
                            tab.cell_off8, tab.n_dirs, tab.radius, beta, beta_int);
     else

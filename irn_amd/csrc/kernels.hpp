@@ -39,9 +39,14 @@ struct AffJob {
     int oy, ox;          // origin of the source rectangle inside the grid
     int sh, sw;          // source rectangle (output plane is [sh, sw] row-major)
     long plane_stride;   // floats between consecutive direction planes
+    int pad_front;       // floats before `out` and after the sh*sw floats of every plane that the kernel zeroes when
+    int pad_tail;        // affinity_writes_pads() holds (every other launch leaves them alone)
 };
 
 int launch_affinity(const AffJob *jobs_dev, int n_jobs, int max_sh, int max_sw, const DeviceTable &tab,
                     bool with_pow, float beta, hipStream_t stream);
+// true where that launch also zeroes every plane's pad_front / pad_tail (the unrolled kernel of radius 5 and 10 with an
+// integer beta); elsewhere the caller zeroes them itself
+bool affinity_writes_pads(const DeviceTable &tab, bool with_pow, float beta);
 
 }  // namespace irn

@@ -56,7 +56,8 @@ namespace {
 // small per-pixel kernels (grid.y = image)
 // ---------------------------------------------------------------------------------------------
 
-// Zeroes what the affinity kernel does not write: every plane's front pad and tail.
+// Zeroes what the table-driven affinity kernel does not write: every plane's front pad and tail (the unrolled kernel
+// does it in its own launch: affinity_writes_pads).
 __global__ __launch_bounds__(256) void zero_pad_kernel(const WalkImg *__restrict__ imgs, int n_dirs) {
     const WalkImg I = imgs[blockIdx.y];
     const int d = blockIdx.x;
@@ -892,14 +893,19 @@ extern "C" int irn_walk_run(irn_walk_ctx *ctx, const float *const *edge_dev, con
         J.out = I.wts;
         J.gh = I.h; J.gw = I.w; J.oy = 0; J.ox = 0; J.sh = I.h; J.sw = I.w;
         J.plane_stride = I.plane_stride;
+        J.pad_front = I.front_pad;
+        J.pad_tail = (int)(I.plane_stride - I.front_pad - (long)I.h * I.w);
     }
     IRN_HIP_TRY(hipMemcpyAsync(ctx->imgs_dev, imgs, sizeof(WalkImg) * n, hipMemcpyHostToDevice, stream));
     IRN_HIP_TRY(hipMemcpyAsync(ctx->jobs_dev, jobs, sizeof(AffJob) * n, hipMemcpyHostToDevice, stream));
     IRN_HIP_TRY(hipEventRecord(ctx->stage_ev[slot], stream));
 
     const DeviceTable &tab = *ctx->tab;
-    hipLaunchKernelGGL(zero_pad_kernel, dim3(tab.n_dirs, n), dim3(256), 0, stream, ctx->imgs_dev, tab.n_dirs);
-    IRN_LAUNCH_CHECK("zero_pad_kernel");
+    // on every call: the workspace is the caller's and may hold anything
+    if (!affinity_writes_pads(tab, true, beta)) {
+        hipLaunchKernelGGL(zero_pad_kernel, dim3(tab.n_dirs, n), dim3(256), 0, stream, ctx->imgs_dev, tab.n_dirs);
+        IRN_LAUNCH_CHECK("zero_pad_kernel");
+    }
     int rc = launch_affinity(ctx->jobs_dev, n, ctx->max_h, ctx->max_w, tab, true, beta, stream);
     if (rc) return rc;
     const bool resident = ctx->variant == 2 && ctx->res_ok && n_sweeps > 0;

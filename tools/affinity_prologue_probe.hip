@@ -1,6 +1,6 @@
 // What would it cost to build the affinities INSIDE resident_kernel<10>'s job prologue?
 //
-// Today: affinity_unrolled_kernel<10> writes the 152 half-plane weight planes (0.49 ms per 192 images = 10 us of CU time per
+// Today: the unrolled affinity kernel writes the 152 half-plane weight planes (0.49 ms per 192 images = 10 us of CU time per
 // 8 x 32 tile), and the resident kernel's prologue loads a tile's 304 DIRECTED weights per pixel from them (7.7 us per job).
 // Fused: the job would stage the edge tile + halo in LDS and compute, per lane, the weights of its wave's 38 directed
 // neighbours for its 4 pixels — forward ones from the path that starts at the pixel, backward ones from the path that starts
@@ -176,7 +176,7 @@ int main(int argc, char **argv) {
         float ms = 0.f;
         hipEventElapsedTime(&ms, a, b);
         printf("fused-affinity prologue, radius 10, %d workgroups x %d jobs: %.3f ms per launch = %.2f us per job "
-               "(today: 7.7 us weight load in the job + 10 us of CU time per tile in affinity_unrolled_kernel<10>)\n",
+               "(today: 7.7 us weight load in the job + 10 us of CU time per tile in the unrolled affinity kernel)\n",
                n_wg, jobs, ms, 1e3 * ms / jobs);
     }
     std::vector<float> o((size_t)n_wg * 512);

@@ -185,7 +185,7 @@ def test_bottleneck_split_path_vs_composed_modules_and_fp32_gemm_path(monkeypatc
 def test_production_passes_vs_the_reference_goldens(golden, monkeypatch):
     """The trunk exactly as the steps run it — 16-row channels-last passes, split-precision 1x1 GEMMs, row-fused split 3x3 in
     stages 2-4 — against the REFERENCE's own CPU forwards (tests/golden/nets512.npz, nets_scales.npz: net/resnet50_cam.py:55-70,
-    net/resnet50_irn.py:216-234 run by tests/golden/make_golden.py) at the north star's 1e-4: CAM at 256^2 / 512^2 / 1024^2 with
+    net/resnet50_irn.py:216-234 run by tests/golden/make_golden.py) at the north star's 1e-4: CAM at 256^2 / 512^2 / 768^2 / 1024^2 with
     the golden pair among seven others, EdgeDisplacement with ragged images padded to the 512^2 crop."""
     from irn_amd import ops, synth
     from irn_amd.net import resnet50 as r50, resnet50_cam, resnet50_irn, weights
@@ -201,7 +201,7 @@ def test_production_passes_vs_the_reference_goldens(golden, monkeypatch):
     cam = cam.to(dev).eval()
     norm = lambda t: t / (t.max(axis=(1, 2), keepdims=True) + 1e-5)
     rel = lambda a, ref: float(np.abs(a - ref).max() / max(1.0, np.abs(ref).max()))
-    for gname, key in (("nets512", "cam512"), ("nets_scales", "cam256"), ("nets_scales", "cam1024")):
+    for gname, key in (("nets512", "cam512"), ("nets512", "cam768"), ("nets_scales", "cam256"), ("nets_scales", "cam1024")):
         g = golden(gname)
         h, w, seed = (int(v) for v in g[key + "_seed"])
         pairs = [torch.from_numpy(synth.image_pair(h, w, seed + 100 * i)) for i in range(8)]       # pair 0 is the reference's input

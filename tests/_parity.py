@@ -10,9 +10,10 @@ import numpy as np
 TIE_TOL = 1e-4      # north star: scores within 1e-4 max-abs => only ties at that level can flip an argmax
 
 
-def label_mismatches(got, want, up, bg_thres, lut=None, what=""):
+def label_mismatches(got, want, up, bg_thres, lut=None, what="", tol=TIE_TOL):
     """got / want: [H,W] maps (labels through `lut`, or raw argmax indices when lut is None); up: the oracle's
-    normalised scores [C,H,W] (oracle.irn_oracle.sem_seg_epilogue()[0]).  Returns (count, largest top-2 gap among them)."""
+    normalised scores [C,H,W] (oracle.irn_oracle.sem_seg_epilogue()[0]); tol: the width of the tie band (TIE_TOL unless the
+    caller has a bar of its own for the scores).  Returns (count, largest top-2 gap among them)."""
     got, want = np.asarray(got), np.asarray(want)
     assert got.shape == want.shape, (what, got.shape, want.shape)
     diff = got != want
@@ -24,14 +25,14 @@ def label_mismatches(got, want, up, bg_thres, lut=None, what=""):
     best, second = order[-1], order[-2]
     cols = np.arange(stack.shape[1])
     gap = stack[best, cols] - stack[second, cols]
-    assert float(gap.max()) < TIE_TOL, "%s: %d pixels differ and one is NOT a tie: top-2 gap %.3g" % (what, n, float(gap.max()))
+    assert float(gap.max()) < tol, "%s: %d pixels differ and one is NOT a tie: top-2 gap %.3g" % (what, n, float(gap.max()))
     # ... and the product picked the other one of the tied pair (or another entry inside the tie band)
     pick = got[diff].astype(np.int64)
     if lut is not None:
         lut = np.asarray(lut)
-        in_band = stack >= (stack[best, cols] - TIE_TOL)[None]
+        in_band = stack >= (stack[best, cols] - tol)[None]
         ok = np.array([pick[j] in set(lut[np.nonzero(in_band[:, j])[0]].tolist()) for j in range(n)])
     else:
-        ok = stack[pick, cols] >= stack[best, cols] - TIE_TOL
+        ok = stack[pick, cols] >= stack[best, cols] - tol
     assert bool(ok.all()), "%s: %d of %d differing pixels chose an entry outside the tie band" % (what, int((~ok).sum()), n)
     return n, float(gap.max())

@@ -146,8 +146,9 @@ def test_run_sample_four_workers_write_the_files_of_one_on_a_mixed_tree(tmp_path
     print("four workers vs one worker, default batch sizes, tuned + untuned sizes: %d CAM files, %d label pixels, %d detections bit-identical"
           % (len(names), n_px, n_det))
     # the arithmetic switch: split-precision (default) against fp32 backbones on the same tree — CAMs inside the 1e-4 bar of the north
-    # star with an order of magnitude to spare (both are ~1e-5 from fp64); label pixels that differ are reported, not bounded: each
-    # run's labels are proven against the oracle on its own inputs in tests/test_gpu_steps.py
+    # star with an order of magnitude to spare (both are ~1e-5 from fp64); label pixels that differ between the two are reported here:
+    # tests/test_gpu_chain.py bounds BOTH trunk modes against the reference's own image-to-label chain (scores within 4 x the
+    # reference's float32-vs-float64 distance, labels differing only at its proven ties)
     dev, n_lab = 0.0, 0
     for n in names:
         a = np.load(tmp_path / "one_cam" / (n + ".npy"), allow_pickle=True).item()

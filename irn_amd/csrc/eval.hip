@@ -3,13 +3,16 @@
 //
 // Every kernel privatises its counters in LDS (one uint32 per bin, at most 4096 pixels per block, so a bin cannot
 // overflow) and flushes the non-zero bins once per block with 64-bit integer atomics into the caller's int64
-// accumulators.  Integer sums do not depend on arrival order: every result is exact and reproducible.
-#include "common.hpp"
+// accumulators.  Integer sums do not depend on arrival order: every result is exact and reproducible.  The threshold
+// histogram of irn_cam_confusion is counted by thres_hist.hpp, the code the label sweep (label.hip) counts with.
+#include "thres_hist.hpp"
 
 #include <cmath>
 
 using irn::cdiv;
 using irn::fail;
+namespace thist = irn::thist;
+using thist::add64, thist::gt_row, thist::kRows, thist::kMaxKeys;
 
 namespace {
 
@@ -17,49 +20,30 @@ constexpr int TPB = 256;                  // threads per block
 constexpr int PPT = 16;                   // pixels per thread (kept in registers by the CAM kernel)
 constexpr int PIX = TPB * PPT;            // pixels per block: bin counts stay below 2^32
 constexpr int NC = IRN_EVAL_CLASSES;      // 21 classes (background + 20)
-constexpr int ROWS = NC + 1;              // GT rows + the void row (GT 255)
-constexpr int MAXK = 20;                  // class keys per image
 constexpr int CAP = 16384;                // LDS bins of one pass of the CAM kernel (64 KiB)
-constexpr uint32_t SKIP = 0xffffffffu;
-
-__device__ inline void add64(int64_t *p, uint32_t v) {
-    atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v);
-}
-
-// GT byte -> confusion row (0..20, 21 = void) or -1 = out of range
-__device__ inline int gt_row(uint8_t g) { return g <= 20 ? (int)g : (g == 255 ? NC : -1); }
+static_assert(TPB == thist::kThreads, "thres_hist.hpp counts with blocks of this size");
 
 // ---------------------------------------------------------------------------------------------------------------------
-// CAM confusion, counting pass.  Bin of a pixel: (j * ROWS + row) * kc + c, with c the first arg-max plane, j the number
-// of thresholds below the maximum and kc = max(k, 1).  The pixels' bins are computed once into registers; when the bins
-// of one image exceed CAP, the block counts them in passes over bin ranges of CAP.
+// CAM confusion, counting pass: per pixel the GT row, the first arg-max plane c and the maximum m; the bins and their
+// counting are thres_hist.hpp's.  Without planes (k = 0) every pixel predicts class 0: one channel whose column is 0.
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(TPB) k_cam_hist(const float *__restrict__ cam, const int64_t *__restrict__ keys, int k,
                                                   const uint8_t *__restrict__ gt, int n, const float *__restrict__ thres,
                                                   int t, int64_t *__restrict__ hist, int64_t *__restrict__ bad) {
     __shared__ uint32_t bins[CAP];
     __shared__ float th[IRN_EVAL_MAX_THRES];
-    __shared__ int col[MAXK];
+    __shared__ int col[kMaxKeys];
     __shared__ uint32_t nbad;
     const int tid = threadIdx.x;
-    if (tid == 0) nbad = 0;
-    for (int i = tid; i < t; i += TPB) th[i] = thres[i];
-    if (tid < k) {
-        const int64_t key = keys[tid];
-        col[tid] = (key >= 0 && key < NC - 1) ? (int)key + 1 : -1;
-    }
-    __syncthreads();
-    uint32_t local_bad = 0;
-    if (blockIdx.x == 0)
-        for (int i = tid; i < t; i += TPB)
-            if (std::isnan(th[i]) || (i > 0 && !(th[i - 1] <= th[i]))) ++local_bad;
+    if (k == 0 && tid == 0) col[0] = 0;
+    uint32_t local_bad = thist::stage(thres, t, keys, k, blockIdx.x == 0, th, col, &nbad);
 
     const int kc = k > 0 ? k : 1;
     uint32_t bin[PPT];
     const int base = blockIdx.x * PIX + tid;
 #pragma unroll
     for (int i = 0; i < PPT; ++i) {
-        bin[i] = SKIP;
+        bin[i] = thist::kSkip;
         const int p = base + i * TPB;
         if (p >= n) continue;
         const int row = gt_row(gt[p]);
@@ -68,7 +52,7 @@ __global__ void __launch_bounds__(TPB) k_cam_hist(const float *__restrict__ cam,
             continue;
         }
         if (k == 0) {
-            bin[i] = (uint32_t)row;
+            bin[i] = thist::bin_of(0, row, 0, kc);
             continue;
         }
         float m = cam[p];
@@ -86,43 +70,10 @@ __global__ void __launch_bounds__(TPB) k_cam_hist(const float *__restrict__ cam,
             ++local_bad;
             continue;
         }
-        int lo = 0, hi = t;            // j = number of thresholds < m (lower bound in the ascending list)
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (th[mid] < m) lo = mid + 1;
-            else hi = mid;
-        }
-        bin[i] = ((uint32_t)lo * ROWS + (uint32_t)row) * (uint32_t)kc + (uint32_t)c;
+        bin[i] = thist::bin_of(thist::count_below(th, t, m), row, c, kc);
     }
-
-    const uint32_t nbins = (uint32_t)(t + 1) * ROWS * (uint32_t)kc;
-    for (uint32_t b0 = 0; b0 < nbins; b0 += CAP) {
-        const uint32_t nb = min((uint32_t)CAP, nbins - b0);
-        for (uint32_t b = tid; b < nb; b += TPB) bins[b] = 0;
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < PPT; ++i)
-            if (bin[i] - b0 < nb) atomicAdd(&bins[bin[i] - b0], 1u);
-        __syncthreads();
-        for (uint32_t b = tid; b < nb; b += TPB) {
-            const uint32_t v = bins[b];
-            if (!v) continue;
-            const uint32_t id = b0 + b;
-            const int c = (int)(id % (uint32_t)kc);
-            const uint32_t r = id / (uint32_t)kc;
-            const int row = (int)(r % ROWS), j = (int)(r / ROWS);
-            const int cl = k == 0 ? 0 : col[c];
-            if (cl < 0) {
-                local_bad += v;        // a key outside 0..19: its pixels are out of range
-                continue;
-            }
-            add64(hist + ((size_t)row * NC + cl) * (t + 1) + j, v);
-        }
-        __syncthreads();
-    }
-    if (local_bad) atomicAdd(&nbad, local_bad);
-    __syncthreads();
-    if (tid == 0 && nbad) add64(bad, nbad);
+    local_bad += thist::count(bin, bins, CAP, (uint32_t)(t + 1) * kRows * (uint32_t)kc, kc, col, t, hist);
+    thist::flush_bad(local_bad, &nbad, bad);
 }
 
 // hist [22][21][t+1] -> conf [t][21][21] (+ void [t][21]).  One thread per (row, column) of the histogram: a pixel of
@@ -130,7 +81,7 @@ __global__ void __launch_bounds__(TPB) k_cam_hist(const float *__restrict__ cam,
 __global__ void __launch_bounds__(TPB) k_cam_reduce(const int64_t *__restrict__ hist, int t, int64_t *__restrict__ conf,
                                                     int64_t *__restrict__ void_) {
     const int id = blockIdx.x * TPB + threadIdx.x;
-    if (id >= ROWS * NC) return;
+    if (id >= kRows * NC) return;
     const int row = id / NC, c = id % NC;
     if (row == NC && !void_) return;
     const int64_t *h = hist + (size_t)id * (t + 1);
@@ -155,10 +106,10 @@ __global__ void __launch_bounds__(TPB) k_cam_reduce(const int64_t *__restrict__ 
 __global__ void __launch_bounds__(TPB) k_label_hist(const uint8_t *__restrict__ pred, const uint8_t *__restrict__ gt, int n,
                                                     int map255, int64_t *__restrict__ conf, int64_t *__restrict__ void_,
                                                     int64_t *__restrict__ bad) {
-    __shared__ uint32_t bins[ROWS * NC];
+    __shared__ uint32_t bins[kRows * NC];
     __shared__ uint32_t nbad;
     const int tid = threadIdx.x;
-    for (int b = tid; b < ROWS * NC; b += TPB) bins[b] = 0;
+    for (int b = tid; b < kRows * NC; b += TPB) bins[b] = 0;
     if (tid == 0) nbad = 0;
     __syncthreads();
     uint32_t local_bad = 0;
@@ -178,7 +129,7 @@ __global__ void __launch_bounds__(TPB) k_label_hist(const uint8_t *__restrict__ 
     }
     if (local_bad) atomicAdd(&nbad, local_bad);
     __syncthreads();
-    for (int b = tid; b < ROWS * NC; b += TPB) {
+    for (int b = tid; b < kRows * NC; b += TPB) {
         const uint32_t v = bins[b];
         if (!v) continue;
         if (b < NC * NC) add64(conf + b, v);
@@ -235,10 +186,10 @@ bool pixels_ok(int h, int w) { return h >= 1 && w >= 1 && (int64_t)h * w <= (int
 
 extern "C" int irn_cam_confusion(const float *high_res_dev, const int64_t *keys_dev, int k, const uint8_t *gt_dev, int h,
                                  int w, const float *thres_dev, int t, int64_t *hist_dev, int64_t *bad_dev, void *stream) {
-    if (!gt_dev || !thres_dev || !hist_dev || !bad_dev || k < 0 || k > MAXK || (k > 0 && (!high_res_dev || !keys_dev)) ||
+    if (!gt_dev || !thres_dev || !hist_dev || !bad_dev || k < 0 || k > kMaxKeys || (k > 0 && (!high_res_dev || !keys_dev)) ||
         t < 1 || t > IRN_EVAL_MAX_THRES || !pixels_ok(h, w))
         return fail(IRN_ERR_ARG, "irn_cam_confusion: bad argument (k=%d, h=%d, w=%d, t=%d; 0 <= k <= %d, 1 <= t <= %d)",
-                    k, h, w, t, MAXK, IRN_EVAL_MAX_THRES);
+                    k, h, w, t, kMaxKeys, IRN_EVAL_MAX_THRES);
     const int n = h * w;
     hipLaunchKernelGGL(k_cam_hist, dim3(cdiv(n, PIX)), dim3(TPB), 0, (hipStream_t)stream, high_res_dev, keys_dev, k, gt_dev,
                        n, thres_dev, t, hist_dev, bad_dev);
@@ -250,7 +201,7 @@ extern "C" int irn_cam_confusion_reduce(const int64_t *hist_dev, int t, int64_t 
                                         void *stream) {
     if (!hist_dev || !conf_dev || t < 1 || t > IRN_EVAL_MAX_THRES)
         return fail(IRN_ERR_ARG, "irn_cam_confusion_reduce: bad argument (t=%d)", t);
-    hipLaunchKernelGGL(k_cam_reduce, dim3(cdiv(ROWS * NC, TPB)), dim3(TPB), 0, (hipStream_t)stream, hist_dev, t, conf_dev,
+    hipLaunchKernelGGL(k_cam_reduce, dim3(cdiv(kRows * NC, TPB)), dim3(TPB), 0, (hipStream_t)stream, hist_dev, t, conf_dev,
                        void_dev);
     IRN_LAUNCH_CHECK("k_cam_reduce");
     return IRN_OK;

@@ -1,7 +1,8 @@
 // Label epilogue (gfx950): bilinear x4 upsample + crop + /global-max + background plane + argmax +
 // keys look-up: the global maximum from two passes over the SOURCE cells (bounded search, below) and one pass
 // over the output pixels; the fp32 [C,H,W] upsampled tensor is never materialised unless the caller asks
-// for it (instance scoring).
+// for it (instance scoring).  The threshold sweep against the ground truth (irn_label_sweep_confusion) runs on the same
+// maximum passes and the same score core (`group_of` / `group_scores`) and counts with thres_hist.hpp, as eval.hip does.
 //
 // Replaces reference step/make_sem_seg_labels.py:43-49 and step/make_ins_seg_labels.py:137-145
 // (F.interpolate -> slice -> torch.max -> divide -> F.pad -> argmax -> .cpu() -> numpy LUT).
@@ -18,6 +19,7 @@
 // Roofline: reads C*h*w floats (L2-resident), writes H*W bytes; ~0.3 MB per 512^2 image against
 // 2.7 GB streamed by the walk — not a bottleneck.
 #include "kernels.hpp"
+#include "thres_hist.hpp"
 
 // Every rounding in this file is part of the contract (labels and CAMs must reproduce ATen's values).
 // HIP's __fmul_rn / __fsub_rn are inline `x * y` / `x - y` compiled under the HEADER's contraction
@@ -67,14 +69,29 @@ __device__ __forceinline__ Taps taps_x4(int dst, int n_in) {
     return t;
 }
 
-__device__ __forceinline__ float bilerp(const float *__restrict__ plane, int w, const Taps &ty, const Taps &tx) {
-    const float v00 = plane[ty.i0 * w + tx.i0], v01 = plane[ty.i0 * w + tx.i1];
-    const float v10 = plane[ty.i1 * w + tx.i0], v11 = plane[ty.i1 * w + tx.i1];
+// the interpolation's arithmetic, the only copy: ATen's three fused steps, every product rounded on its own
+__device__ __forceinline__ float bilerp_vals(float v00, float v01, float v10, float v11, const Taps &ty, const Taps &tx) {
     const float p01 = v01 * tx.l1, p11 = v11 * tx.l1;
     const float top = __builtin_fmaf(v00, tx.l0, p01);
     const float bot = __builtin_fmaf(v10, tx.l0, p11);
     const float pb = ty.l1 * bot;
     return __builtin_fmaf(ty.l0, top, pb);
+}
+
+__device__ __forceinline__ float bilerp(const float *__restrict__ plane, int w, const Taps &ty, const Taps &tx) {
+    return bilerp_vals(plane[ty.i0 * w + tx.i0], plane[ty.i0 * w + tx.i1], plane[ty.i1 * w + tx.i0], plane[ty.i1 * w + tx.i1], ty, tx);
+}
+
+// Maximum of `m` over a block of 256 threads, folded into *slot (order-preserving encoding) with one atomic per block.
+__device__ __forceinline__ void block_max_to_slot(float m, unsigned *slot) {
+    for (int s = 32; s > 0; s >>= 1) m = fmaxf(m, __shfl_xor(m, s));
+    __shared__ float wmax[4];
+    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+        if (m > -INFINITY) atomicMax(slot, enc_ordered(m));
+    }
 }
 
 // Global maximum of the upsampled scores WITHOUT evaluating every output pixel.  An output pixel with taps
@@ -114,60 +131,64 @@ __global__ __launch_bounds__(256) void upsample_max_kernel(const LabelJob *__res
             }
         }
     }
-    for (int s = 32; s > 0; s >>= 1) m = fmaxf(m, __shfl_xor(m, s));
-    __shared__ float wmax[4];
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-        if (m > -INFINITY) atomicMax(J.max_slot, enc_ordered(m));
-    }
+    block_max_to_slot(m, J.max_slot);
 }
 
-__device__ __forceinline__ float bilerp_vals(float v00, float v01, float v10, float v11, const Taps &ty, const Taps &tx) {
-    const float p01 = v01 * tx.l1, p11 = v11 * tx.l1;              // the arithmetic of `bilerp`, values already loaded
-    const float top = __builtin_fmaf(v00, tx.l0, p01);
-    const float bot = __builtin_fmaf(v10, tx.l0, p11);
-    const float pb = ty.l1 * bot;
-    return __builtin_fmaf(ty.l0, top, pb);
+// The score core of the argmax pass and of the threshold sweep.  One thread = FOUR horizontally adjacent output pixels
+// 4j .. 4j+3 of a row: at x4 the first two share one pair of source columns and the last two the next pair, so a channel
+// costs 8 loads instead of 16, the index arithmetic (a division by the row length) is paid once per four pixels, and the
+// labels leave as one 4-byte store per thread (256 contiguous bytes per wave) instead of four single bytes.  The
+// per-pixel arithmetic is `bilerp_vals` and an IEEE division by the global maximum.  (One pixel per thread with 64-bit
+// index arithmetic: 0.140 ms per 192 images of 512^2, 0.36 Tpixel/s.)
+struct Group {
+    int oy, ox, nq;         // first pixel; pixels inside the row (1..4)
+    unsigned o;             // its offset in an [oh, ow] map
+    Taps ty, tx[4];
+};
+
+__device__ __forceinline__ Group group_of(const LabelJob &J, unsigned g, unsigned gw) {
+    Group G;
+    G.oy = (int)(g / gw), G.ox = (int)(g - (unsigned)G.oy * gw) * 4;
+    G.nq = min(4, J.ow - G.ox);
+    G.o = (unsigned)G.oy * (unsigned)J.ow + (unsigned)G.ox;
+    G.ty = taps_x4(G.oy, J.h);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) G.tx[q] = taps_x4(min(G.ox + q, J.ow - 1), J.w);
+    return G;
 }
 
-// One thread = FOUR horizontally adjacent output pixels 4j .. 4j+3 of a row: at x4 the first two share one pair of
-// source columns and the last two the next pair, so a channel costs 8 loads instead of 16, the index arithmetic (a
-// division by the row length) is paid once per four pixels, and the labels leave as one 4-byte store per thread (256
-// contiguous bytes per wave) instead of four single bytes.  The per-pixel arithmetic is `bilerp` unchanged.  (One
-// pixel per thread with 64-bit index arithmetic: 0.140 ms per 192 images of 512^2, 0.36 Tpixel/s.)
+// v[q] = score of channel c at the group's pixel q, divided by the global maximum
+__device__ __forceinline__ void group_scores(const LabelJob &J, const Group &G, int c, float gmax, float (&v)[4]) {
+    const Taps &ty = G.ty, *tx = G.tx;
+    const float *r0 = J.rw + (long)c * J.h * J.w + ty.i0 * J.w, *r1 = J.rw + (long)c * J.h * J.w + ty.i1 * J.w;
+    // pixels 0, 1 read columns tx[0].{i0, i1}, pixels 2, 3 columns tx[2].{i0, i1} (tx[1] == tx[0]'s, tx[3] == tx[2]'s:
+    // src = j - 0.375, j - 0.125, j + 0.125, j + 0.375, clamped at 0)
+    const float a00 = r0[tx[0].i0], a01 = r0[tx[0].i1], a10 = r1[tx[0].i0], a11 = r1[tx[0].i1];
+    const float b00 = r0[tx[2].i0], b01 = r0[tx[2].i1], b10 = r1[tx[2].i0], b11 = r1[tx[2].i1];
+    v[0] = bilerp_vals(a00, a01, a10, a11, ty, tx[0]) / gmax;
+    v[1] = bilerp_vals(a00, a01, a10, a11, ty, tx[1]) / gmax;
+    v[2] = bilerp_vals(b00, b01, b10, b11, ty, tx[2]) / gmax;
+    v[3] = bilerp_vals(b00, b01, b10, b11, ty, tx[3]) / gmax;
+}
+
+// Labels, argmax and (on request) the upsampled scores: the selection starts from the background plane `bg`.
 __global__ __launch_bounds__(256) void label_argmax_kernel(const LabelJob *__restrict__ jobs, float bg) {
     const LabelJob J = jobs[blockIdx.y];
     const unsigned gw = (unsigned)(J.ow + 3) >> 2, groups = gw * (unsigned)J.oh;
     const unsigned npx = (unsigned)J.oh * (unsigned)J.ow;
     const float gmax = dec_ordered(*J.max_slot);
     for (unsigned g = blockIdx.x * 256 + threadIdx.x; g < groups; g += gridDim.x * 256) {
-        const int oy = (int)(g / gw), ox = (int)(g - (unsigned)oy * gw) * 4;
-        const int nq = min(4, J.ow - ox);
-        const Taps ty = taps_x4(oy, J.h);
-        Taps tx[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) tx[q] = taps_x4(min(ox + q, J.ow - 1), J.w);
+        const Group G = group_of(J, g, gw);
         float best[4] = {bg, bg, bg, bg};
         int idx[4] = {0, 0, 0, 0};
-        const unsigned o = (unsigned)oy * (unsigned)J.ow + (unsigned)ox;
         for (int c = 0; c < J.c; ++c) {
-            const float *r0 = J.rw + (long)c * J.h * J.w + ty.i0 * J.w, *r1 = J.rw + (long)c * J.h * J.w + ty.i1 * J.w;
-            // pixels 0, 1 read columns tx[0].{i0, i1}, pixels 2, 3 columns tx[2].{i0, i1} (tx[1] == tx[0]'s, tx[3] == tx[2]'s:
-            // src = j - 0.375, j - 0.125, j + 0.125, j + 0.375, clamped at 0)
-            const float a00 = r0[tx[0].i0], a01 = r0[tx[0].i1], a10 = r1[tx[0].i0], a11 = r1[tx[0].i1];
-            const float b00 = r0[tx[2].i0], b01 = r0[tx[2].i1], b10 = r1[tx[2].i0], b11 = r1[tx[2].i1];
             float v[4];
-            v[0] = bilerp_vals(a00, a01, a10, a11, ty, tx[0]) / gmax;
-            v[1] = bilerp_vals(a00, a01, a10, a11, ty, tx[1]) / gmax;
-            v[2] = bilerp_vals(b00, b01, b10, b11, ty, tx[2]) / gmax;
-            v[3] = bilerp_vals(b00, b01, b10, b11, ty, tx[3]) / gmax;
+            group_scores(J, G, c, gmax, v);
             if (J.rw_up) {
-                float *dst = J.rw_up + (long)c * npx + o;
-                if (nq == 4 && ((uintptr_t)dst & 15) == 0) *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+                float *dst = J.rw_up + (long)c * npx + G.o;
+                if (G.nq == 4 && ((uintptr_t)dst & 15) == 0) *reinterpret_cast<float4 *>(dst) = make_float4(v[0], v[1], v[2], v[3]);
                 else
-                    for (int q = 0; q < nq; ++q) dst[q] = v[q];
+                    for (int q = 0; q < G.nq; ++q) dst[q] = v[q];
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q)
@@ -178,20 +199,20 @@ __global__ __launch_bounds__(256) void label_argmax_kernel(const LabelJob *__res
                 }
         }
         if (J.argmax) {
-            int32_t *dst = J.argmax + o;
-            if (nq == 4 && ((uintptr_t)dst & 15) == 0) *reinterpret_cast<int4 *>(dst) = make_int4(idx[0], idx[1], idx[2], idx[3]);
+            int32_t *dst = J.argmax + G.o;
+            if (G.nq == 4 && ((uintptr_t)dst & 15) == 0) *reinterpret_cast<int4 *>(dst) = make_int4(idx[0], idx[1], idx[2], idx[3]);
             else
-                for (int q = 0; q < nq; ++q) dst[q] = idx[q];
+                for (int q = 0; q < G.nq; ++q) dst[q] = idx[q];
         }
         if (J.labels) {
             uint8_t lab[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) lab[q] = idx[q] == 0 ? (uint8_t)0 : (uint8_t)(J.keys[idx[q] - 1] + 1);
-            uint8_t *dst = J.labels + o;
-            if (nq == 4 && ((uintptr_t)dst & 3) == 0)
+            uint8_t *dst = J.labels + G.o;
+            if (G.nq == 4 && ((uintptr_t)dst & 3) == 0)
                 *reinterpret_cast<uint32_t *>(dst) = (uint32_t)lab[0] | ((uint32_t)lab[1] << 8) | ((uint32_t)lab[2] << 16) | ((uint32_t)lab[3] << 24);
             else
-                for (int q = 0; q < nq; ++q) dst[q] = lab[q];
+                for (int q = 0; q < G.nq; ++q) dst[q] = lab[q];
         }
     }
 }
@@ -203,71 +224,45 @@ __global__ __launch_bounds__(256) void label_argmax_kernel(const LabelJob *__res
 // maximum m of the normalised scores predicts keys[c*] + 1 where thres < m (the epilogue's strict >) and 0 elsewhere;
 // with j = number of thresholds < m the pixel is one count in hist[gt row][keys[c*] + 1][j], the layout of
 // irn_cam_confusion (eval.hip), reduced by irn_cam_confusion_reduce.  A NaN score wins at every threshold as it does in
-// the epilogue (torch.argmax): c* = the first NaN channel, j = t.  Scores: `bilerp_vals` / `taps_x4` / the division by
-// the maximum of `upsample_max_kernel`, in the four-pixels-per-thread shape of `label_argmax_kernel`.
-//
-// Counting as in eval.hip: uint32 bins private to the block in LDS (4096 pixels per chunk: no overflow), non-zero bins
-// flushed with 64-bit integer atomics — exact, whatever the grid and the arrival order.  Bin = (j * 22 + row) * c + c*;
-// an image has (t + 1) * 22 * c of them (113 080 at c = 20, t = 256), so a chunk's bins stay in registers and are
-// counted in passes over bin ranges of `cap` (the dynamic LDS the host sized for the call: one pass for a typical grid).
+// the epilogue (torch.argmax): c* = the first NaN channel, j = t.  Scores: `group_of` / `group_scores`, the functions
+// `label_argmax_kernel` calls, on the maximum of `upsample_max_kernel`.
+// Counting: thres_hist.hpp, shared with eval.hip.  An image has (t + 1) * 22 * c bins (113 080 at c = 20, t = 256), so a
+// chunk's bins (4096 pixels) stay in registers and are counted in passes over bin ranges of `cap` (the dynamic LDS the
+// host sized for the call: one pass for a typical grid).
 // ---------------------------------------------------------------------------------------------
 constexpr int kSweepGroups = 4;                          // 4-pixel groups per thread and chunk
 constexpr int kSweepChunk = 256 * kSweepGroups;          // groups per chunk (4096 pixels)
 constexpr int kSweepCap = 15360;                         // most LDS bins per pass (60 KiB; thresholds and columns follow)
-constexpr int kSweepRows = IRN_EVAL_CLASSES + 1;         // GT rows + the void row
-constexpr int kSweepMaxC = IRN_EVAL_CLASSES - 1;
-constexpr uint32_t kSweepSkip = 0xffffffffu;
+static_assert(thist::kThreads == 256, "thres_hist.hpp counts with blocks of this size");
 
 __global__ __launch_bounds__(256) void label_sweep_kernel(const LabelJob *__restrict__ jobs, const float *__restrict__ thres,
                                                           int t, int cap, int64_t *__restrict__ hist, int64_t *__restrict__ bad) {
     extern __shared__ __attribute__((aligned(16))) uint32_t sweep_lds[];
     uint32_t *bins = sweep_lds;                                       // [cap], cap a multiple of 4
     float *th = reinterpret_cast<float *>(sweep_lds + cap);           // [IRN_EVAL_MAX_THRES]
-    int *col = reinterpret_cast<int *>(th + IRN_EVAL_MAX_THRES);      // [kSweepMaxC]
-    uint32_t *nbad = reinterpret_cast<uint32_t *>(col + kSweepMaxC);
+    int *col = reinterpret_cast<int *>(th + IRN_EVAL_MAX_THRES);      // [thist::kMaxKeys]
+    uint32_t *nbad = reinterpret_cast<uint32_t *>(col + thist::kMaxKeys);
     const LabelJob J = jobs[blockIdx.y];
-    const int tid = threadIdx.x;
-    if (tid == 0) *nbad = 0;
-    for (int i = tid; i < t; i += 256) th[i] = thres[i];
-    if (tid < J.c) {
-        const int64_t key = J.keys[tid];
-        col[tid] = (key >= 0 && key < kSweepMaxC) ? (int)key + 1 : -1;
-    }
-    __syncthreads();
-    uint32_t local_bad = 0;
-    if (blockIdx.x == 0 && blockIdx.y == 0)                           // once per call
-        for (int i = tid; i < t; i += 256)
-            if (th[i] != th[i] || (i > 0 && !(th[i - 1] <= th[i]))) ++local_bad;
+    uint32_t local_bad = thist::stage(thres, t, J.keys, J.c, blockIdx.x == 0 && blockIdx.y == 0, th, col, nbad);
 
     const unsigned gw = (unsigned)(J.ow + 3) >> 2, groups = gw * (unsigned)J.oh;
     const unsigned chunks = (groups + kSweepChunk - 1) / kSweepChunk;
-    const uint32_t nbins = (uint32_t)(t + 1) * kSweepRows * (uint32_t)J.c;
+    const uint32_t nbins = (uint32_t)(t + 1) * thist::kRows * (uint32_t)J.c;
     const float gmax = dec_ordered(*J.max_slot);
     for (unsigned chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
         uint32_t bin[4 * kSweepGroups];
 #pragma unroll
         for (int i = 0; i < kSweepGroups; ++i) {
 #pragma unroll
-            for (int q = 0; q < 4; ++q) bin[4 * i + q] = kSweepSkip;
-            const unsigned g = chunk * kSweepChunk + (unsigned)i * 256 + (unsigned)tid;
+            for (int q = 0; q < 4; ++q) bin[4 * i + q] = thist::kSkip;
+            const unsigned g = chunk * kSweepChunk + (unsigned)i * 256 + threadIdx.x;
             if (g >= groups) continue;
-            const int oy = (int)(g / gw), ox = (int)(g - (unsigned)oy * gw) * 4;
-            const int nq = min(4, J.ow - ox);
-            const Taps ty = taps_x4(oy, J.h);
-            Taps tx[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) tx[q] = taps_x4(min(ox + q, J.ow - 1), J.w);
+            const Group G = group_of(J, g, gw);
             float m[4] = {0.f, 0.f, 0.f, 0.f};
             int cs[4] = {0, 0, 0, 0}, nanc[4] = {-1, -1, -1, -1};
             for (int c = 0; c < J.c; ++c) {
-                const float *r0 = J.rw + (long)c * J.h * J.w + ty.i0 * J.w, *r1 = J.rw + (long)c * J.h * J.w + ty.i1 * J.w;
-                const float a00 = r0[tx[0].i0], a01 = r0[tx[0].i1], a10 = r1[tx[0].i0], a11 = r1[tx[0].i1];
-                const float b00 = r0[tx[2].i0], b01 = r0[tx[2].i1], b10 = r1[tx[2].i0], b11 = r1[tx[2].i1];
                 float v[4];
-                v[0] = bilerp_vals(a00, a01, a10, a11, ty, tx[0]) / gmax;
-                v[1] = bilerp_vals(a00, a01, a10, a11, ty, tx[1]) / gmax;
-                v[2] = bilerp_vals(b00, b01, b10, b11, ty, tx[2]) / gmax;
-                v[3] = bilerp_vals(b00, b01, b10, b11, ty, tx[3]) / gmax;
+                group_scores(J, G, c, gmax, v);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     if (c == 0 || v[q] > m[q]) {                      // strict: the first channel that reaches the maximum keeps it
@@ -277,60 +272,30 @@ __global__ __launch_bounds__(256) void label_sweep_kernel(const LabelJob *__rest
                     if (v[q] != v[q] && nanc[q] < 0) nanc[q] = c;
                 }
             }
-            const uint8_t *gp = J.gt + ((unsigned)oy * (unsigned)J.ow + (unsigned)ox);
+            const uint8_t *gp = J.gt + G.o;
             uint8_t gv[4] = {0, 0, 0, 0};
-            if (nq == 4 && ((uintptr_t)gp & 3) == 0) {
+            if (G.nq == 4 && ((uintptr_t)gp & 3) == 0) {
                 const uint32_t u = *reinterpret_cast<const uint32_t *>(gp);
                 gv[0] = (uint8_t)u; gv[1] = (uint8_t)(u >> 8); gv[2] = (uint8_t)(u >> 16); gv[3] = (uint8_t)(u >> 24);
             } else {
-                for (int q = 0; q < nq; ++q) gv[q] = gp[q];
+                for (int q = 0; q < G.nq; ++q) gv[q] = gp[q];
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                if (q >= nq) continue;
-                const int row = gv[q] <= 20 ? (int)gv[q] : (gv[q] == 255 ? IRN_EVAL_CLASSES : -1);
+                if (q >= G.nq) continue;
+                const int row = thist::gt_row(gv[q]);
                 if (row < 0) {
                     ++local_bad;                                       // GT 21..254
                     continue;
                 }
-                int lo = 0, hi = t;                                    // j = number of thresholds < m (ascending list)
-                while (lo < hi) {
-                    const int mid = (lo + hi) >> 1;
-                    if (th[mid] < m[q]) lo = mid + 1;
-                    else hi = mid;
-                }
+                const int lo = thist::count_below(th, t, m[q]);
                 const int j = nanc[q] >= 0 ? t : lo, cq = nanc[q] >= 0 ? nanc[q] : cs[q];
-                bin[4 * i + q] = ((uint32_t)j * kSweepRows + (uint32_t)row) * (uint32_t)J.c + (uint32_t)cq;
+                bin[4 * i + q] = thist::bin_of(j, row, cq, J.c);
             }
         }
-        for (uint32_t b0 = 0; b0 < nbins; b0 += (uint32_t)cap) {
-            const uint32_t nb = min((uint32_t)cap, nbins - b0);
-            for (uint32_t b = tid; b < nb; b += 256) bins[b] = 0;
-            __syncthreads();
-#pragma unroll
-            for (int i = 0; i < 4 * kSweepGroups; ++i)
-                if (bin[i] - b0 < nb) atomicAdd(&bins[bin[i] - b0], 1u);
-            __syncthreads();
-            for (uint32_t b = tid; b < nb; b += 256) {
-                const uint32_t v = bins[b];
-                if (!v) continue;
-                const uint32_t id = b0 + b;
-                const int c = (int)(id % (uint32_t)J.c);
-                const uint32_t r = id / (uint32_t)J.c;
-                const int row = (int)(r % kSweepRows), j = (int)(r / kSweepRows);
-                if (col[c] < 0) {
-                    local_bad += v;                                    // a key outside 0..19: its pixels are out of range
-                    continue;
-                }
-                atomicAdd(reinterpret_cast<unsigned long long *>(hist + ((size_t)row * IRN_EVAL_CLASSES + col[c]) * (t + 1) + j),
-                          (unsigned long long)v);
-            }
-            __syncthreads();
-        }
+        local_bad += thist::count(bin, bins, (uint32_t)cap, nbins, J.c, col, t, hist);
     }
-    if (local_bad) atomicAdd(nbad, local_bad);
-    __syncthreads();
-    if (tid == 0 && *nbad) atomicAdd(reinterpret_cast<unsigned long long *>(bad), (unsigned long long)*nbad);
+    thist::flush_bad(local_bad, nbad, bad);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -385,14 +350,7 @@ __global__ __launch_bounds__(256) void cam_merge_sum_kernel(const MergeArgs A) {
         out[o] = acc;
         m = fmaxf(m, acc);
     }
-    for (int s = 32; s > 0; s >>= 1) m = fmaxf(m, __shfl_xor(m, s));
-    __shared__ float wmax[4];
-    if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        m = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-        if (m > -INFINITY) atomicMax(A.max_slots + (is_hi ? A.k : 0) + kk, enc_ordered(m));
-    }
+    block_max_to_slot(m, A.max_slots + (is_hi ? A.k : 0) + kk);
 }
 
 __global__ __launch_bounds__(256) void cam_merge_norm_kernel(const MergeArgs A) {
@@ -402,6 +360,53 @@ __global__ __launch_bounds__(256) void cam_merge_norm_kernel(const MergeArgs A) 
     float *out = (is_hi ? A.hi : A.lo) + (long)kk * n;
     const float den = dec_ordered(A.max_slots[(is_hi ? A.k : 0) + kk]) + 1e-5f;
     for (long o = (long)blockIdx.x * 256 + threadIdx.x; o < n; o += (long)gridDim.x * 256) out[o] = out[o] / den;
+}
+
+// Host side common to irn_label_epilogue and irn_label_sweep_confusion
+struct LabelBatch {
+    std::vector<LabelJob> jobs;
+    LabelJob *dev = nullptr;            // the jobs in library scratch, once launch_max_passes has uploaded them
+    long max_px = 0, max_cells = 0;     // largest output map / score tensor of the batch
+    int max_c = 0;
+};
+
+// Checks the sizes of every image and fills its job; `who` names the entry point in the messages; each of keys_dev ..
+// gt_dev may be null.  Nothing is enqueued.
+int label_jobs(const char *who, int n_images, const float *const *rw_dev, const int32_t *c, const int32_t *h, const int32_t *w,
+               const int32_t *out_h, const int32_t *out_w, const int64_t *const *keys_dev, uint8_t *const *labels_dev,
+               int32_t *const *argmax_dev, float *const *rw_up_dev, const uint8_t *const *gt_dev, void *scratch_dev, LabelBatch &B) {
+    B.jobs.resize(n_images);
+    for (int i = 0; i < n_images; ++i) {
+        if (!rw_dev[i] || c[i] < 1 || h[i] < 1 || w[i] < 1 || out_h[i] < 1 || out_w[i] < 1 || out_h[i] > 4 * h[i] || out_w[i] > 4 * w[i])
+            return fail(IRN_ERR_ARG, "%s: image %d: bad sizes (c=%d %dx%d -> %dx%d)", who, i, c[i], h[i], w[i], out_h[i], out_w[i]);
+        const LabelJob J = {rw_dev[i], keys_dev ? keys_dev[i] : nullptr, labels_dev ? labels_dev[i] : nullptr,
+                            argmax_dev ? argmax_dev[i] : nullptr, rw_up_dev ? rw_up_dev[i] : nullptr, (unsigned *)scratch_dev + i,
+                            c[i], h[i], w[i], out_h[i], out_w[i], gt_dev ? gt_dev[i] : nullptr};
+        if (J.labels && !J.keys) return fail(IRN_ERR_ARG, "%s: image %d: labels requested without keys", who, i);
+        B.jobs[i] = J;
+        B.max_px = std::max(B.max_px, (long)out_h[i] * out_w[i]);
+        B.max_cells = std::max(B.max_cells, (long)c[i] * h[i] * w[i]);
+        B.max_c = std::max(B.max_c, c[i]);
+    }
+    if (B.max_px >= (1L << 31) || B.max_cells >= (1L << 31)) return fail(IRN_ERR_ARG, "%s: image too large (32-bit pixel indices)", who);
+    return IRN_OK;
+}
+
+// Uploads the jobs, clears the maximum slots and enqueues the two maximum passes: ~4096 workgroups per launch whatever
+// the batch (16 per CU), each thread striding over several source cells — with one cell per thread (15 000 workgroups
+// per 192-image batch) they took 66 + 37 us, now 22 + 19.
+int launch_max_passes(LabelBatch &B, void *scratch_dev, hipStream_t stream) {
+    const int n_images = (int)B.jobs.size();
+    int rc = scratch_upload(B.jobs.data(), sizeof(LabelJob) * n_images, (void **)&B.dev, stream);
+    if (rc) return rc;
+    IRN_HIP_TRY(hipMemsetAsync(scratch_dev, 0, sizeof(unsigned) * n_images, stream));
+    const long per_image = std::max<long>(1, 4096 / n_images);
+    const int bc = (int)std::min<long>((B.max_cells + 255) / 256, per_image);
+    hipLaunchKernelGGL(upsample_max_kernel<1>, dim3(bc, n_images), dim3(256), 0, stream, B.dev);
+    IRN_LAUNCH_CHECK("upsample_max_kernel<1>");
+    hipLaunchKernelGGL(upsample_max_kernel<2>, dim3(bc, n_images), dim3(256), 0, stream, B.dev);
+    IRN_LAUNCH_CHECK("upsample_max_kernel<2>");
+    return IRN_OK;
 }
 
 }  // namespace
@@ -417,44 +422,17 @@ extern "C" int irn_label_epilogue(int n_images, const float *const *rw_dev, cons
     hipStream_t stream = (hipStream_t)stream_;
     if (n_images < 1 || !rw_dev || !c || !h || !w || !out_h || !out_w || !scratch_dev)
         return fail(IRN_ERR_ARG, "irn_label_epilogue: bad argument");
-    std::vector<LabelJob> jobs(n_images);
-    long max_px = 0, max_cells = 0;
-    for (int i = 0; i < n_images; ++i) {
-        LabelJob &J = jobs[i];
-        if (!rw_dev[i] || c[i] < 1 || h[i] < 1 || w[i] < 1 || out_h[i] < 1 || out_w[i] < 1 ||
-            out_h[i] > 4 * h[i] || out_w[i] > 4 * w[i])
-            return fail(IRN_ERR_ARG, "irn_label_epilogue: image %d: bad sizes (c=%d %dx%d -> %dx%d)", i, c[i], h[i],
-                        w[i], out_h[i], out_w[i]);
-        J.rw = rw_dev[i];
-        J.keys = keys_dev ? keys_dev[i] : nullptr;
-        J.labels = labels_dev ? labels_dev[i] : nullptr;
-        J.argmax = argmax_dev ? argmax_dev[i] : nullptr;
-        J.rw_up = rw_up_dev ? rw_up_dev[i] : nullptr;
-        if (J.labels && !J.keys)
-            return fail(IRN_ERR_ARG, "irn_label_epilogue: image %d: labels requested without keys", i);
-        J.max_slot = (unsigned *)scratch_dev + i;
-        J.c = c[i]; J.h = h[i]; J.w = w[i]; J.oh = out_h[i]; J.ow = out_w[i];
-        max_px = std::max(max_px, (long)out_h[i] * out_w[i]);
-        max_cells = std::max(max_cells, (long)c[i] * h[i] * w[i]);
-    }
-    LabelJob *jobs_dev = nullptr;
-    int rc = scratch_upload(jobs.data(), sizeof(LabelJob) * n_images, (void **)&jobs_dev, stream);
+    LabelBatch B;
+    int rc = label_jobs("irn_label_epilogue", n_images, rw_dev, c, h, w, out_h, out_w, keys_dev, labels_dev, argmax_dev, rw_up_dev,
+                        nullptr, scratch_dev, B);
     if (rc) return rc;
-    IRN_HIP_TRY(hipMemsetAsync(scratch_dev, 0, sizeof(unsigned) * n_images, stream));
-    if (max_px >= (1L << 31) || max_cells >= (1L << 31)) return fail(IRN_ERR_ARG, "irn_label_epilogue: image too large (32-bit pixel indices)");
-    // The two maximum passes: ~4096 workgroups per launch whatever the batch (16 per CU), each thread striding over several
-    // source cells — with one cell per thread (15 000 workgroups per 192-image batch) they took 66 + 37 us, now 22 + 19.
-    // The argmax pass is the opposite: its iterations are chains of dependent memory operations (score loads -> division ->
-    // keys look-up -> store), and one 4-pixel group per thread (49 000 workgroups) hides them better than twelve (92 vs
-    // 104 us per 192 images; profiles/r04_s20_label_kernels.txt).
-    const long per_image = std::max<long>(1, 4096 / n_images);
-    const int bx = (int)std::min<long>((max_px / 4 + 255) / 256 + 1, 512);
-    const int bc = (int)std::min<long>((max_cells + 255) / 256, per_image);
-    hipLaunchKernelGGL(upsample_max_kernel<1>, dim3(bc, n_images), dim3(256), 0, stream, jobs_dev);
-    IRN_LAUNCH_CHECK("upsample_max_kernel<1>");
-    hipLaunchKernelGGL(upsample_max_kernel<2>, dim3(bc, n_images), dim3(256), 0, stream, jobs_dev);
-    IRN_LAUNCH_CHECK("upsample_max_kernel<2>");
-    hipLaunchKernelGGL(label_argmax_kernel, dim3(bx, n_images), dim3(256), 0, stream, jobs_dev, bg_thres);
+    rc = launch_max_passes(B, scratch_dev, stream);
+    if (rc) return rc;
+    // The argmax pass is the opposite of the maximum passes: its iterations are chains of dependent memory operations
+    // (score loads -> division -> keys look-up -> store), and one 4-pixel group per thread (49 000 workgroups) hides them
+    // better than twelve (92 vs 104 us per 192 images; profiles/r04_s20_label_kernels.txt).
+    const int bx = (int)std::min<long>((B.max_px / 4 + 255) / 256 + 1, 512);
+    hipLaunchKernelGGL(label_argmax_kernel, dim3(bx, n_images), dim3(256), 0, stream, B.dev, bg_thres);
     IRN_LAUNCH_CHECK("label_argmax_kernel");
     return scratch_release(stream);
 }
@@ -469,48 +447,23 @@ extern "C" int irn_label_sweep_confusion(int n_images, const float *const *rw_de
         !hist_dev || !bad_dev || !scratch_dev || t < 1 || t > IRN_EVAL_MAX_THRES)
         return fail(IRN_ERR_ARG, "irn_label_sweep_confusion: bad argument (n_images=%d, t=%d; 1 <= t <= %d)", n_images, t,
                     IRN_EVAL_MAX_THRES);
-    std::vector<LabelJob> jobs(n_images);
-    long max_px = 0, max_cells = 0;
-    int max_c = 0;
-    for (int i = 0; i < n_images; ++i) {
-        LabelJob &J = jobs[i];
-        if (!rw_dev[i] || c[i] < 1 || c[i] > kSweepMaxC || h[i] < 1 || w[i] < 1 || out_h[i] < 1 || out_w[i] < 1 ||
-            out_h[i] > 4 * h[i] || out_w[i] > 4 * w[i])
-            return fail(IRN_ERR_ARG, "irn_label_sweep_confusion: image %d: bad sizes (c=%d %dx%d -> %dx%d; 1 <= c <= %d)", i,
-                        c[i], h[i], w[i], out_h[i], out_w[i], kSweepMaxC);
-        if (!keys_dev[i] || !gt_dev[i])
-            return fail(IRN_ERR_ARG, "irn_label_sweep_confusion: image %d: keys and ground truth are required", i);
-        J.rw = rw_dev[i];
-        J.keys = keys_dev[i];
-        J.labels = nullptr;
-        J.argmax = nullptr;
-        J.rw_up = nullptr;
-        J.gt = gt_dev[i];
-        J.max_slot = (unsigned *)scratch_dev + i;
-        J.c = c[i]; J.h = h[i]; J.w = w[i]; J.oh = out_h[i]; J.ow = out_w[i];
-        max_px = std::max(max_px, (long)out_h[i] * out_w[i]);
-        max_cells = std::max(max_cells, (long)c[i] * h[i] * w[i]);
-        max_c = std::max(max_c, c[i]);
-    }
-    if (max_px >= (1L << 31) || max_cells >= (1L << 31))
-        return fail(IRN_ERR_ARG, "irn_label_sweep_confusion: image too large (32-bit pixel indices)");
-    LabelJob *jobs_dev = nullptr;
-    int rc = scratch_upload(jobs.data(), sizeof(LabelJob) * n_images, (void **)&jobs_dev, stream);
+    LabelBatch B;
+    int rc = label_jobs("irn_label_sweep_confusion", n_images, rw_dev, c, h, w, out_h, out_w, keys_dev, nullptr, nullptr, nullptr,
+                        gt_dev, scratch_dev, B);
     if (rc) return rc;
-    IRN_HIP_TRY(hipMemsetAsync(scratch_dev, 0, sizeof(unsigned) * n_images, stream));
-    const long per_image = std::max<long>(1, 4096 / n_images);
-    const int bc = (int)std::min<long>((max_cells + 255) / 256, per_image);
-    hipLaunchKernelGGL(upsample_max_kernel<1>, dim3(bc, n_images), dim3(256), 0, stream, jobs_dev);
-    IRN_LAUNCH_CHECK("upsample_max_kernel<1>");
-    hipLaunchKernelGGL(upsample_max_kernel<2>, dim3(bc, n_images), dim3(256), 0, stream, jobs_dev);
-    IRN_LAUNCH_CHECK("upsample_max_kernel<2>");
+    for (int i = 0; i < n_images; ++i)                                // the sweep's own conditions, before anything is enqueued
+        if (c[i] > thist::kMaxKeys || !keys_dev[i] || !gt_dev[i])
+            return fail(IRN_ERR_ARG, "irn_label_sweep_confusion: image %d: c=%d (at most %d), keys and ground truth are required", i,
+                        c[i], thist::kMaxKeys);
+    rc = launch_max_passes(B, scratch_dev, stream);
+    if (rc) return rc;
     // LDS bins for the call's largest image, at most kSweepCap per pass; at most 128 chunks of 4096 pixels per image and
     // launch row (a 1040 x 528 image strides once)
-    const long nbins = (long)(t + 1) * kSweepRows * max_c;
+    const long nbins = (long)(t + 1) * thist::kRows * B.max_c;
     const int cap = (int)std::min<long>((nbins + 3) / 4 * 4, kSweepCap);
-    const size_t lds = sizeof(uint32_t) * cap + sizeof(float) * IRN_EVAL_MAX_THRES + sizeof(int) * kSweepMaxC + sizeof(uint32_t);
-    const int bx = (int)std::min<long>(((max_px + 3) / 4 + kSweepChunk - 1) / kSweepChunk + 1, 128);
-    hipLaunchKernelGGL(label_sweep_kernel, dim3(bx, n_images), dim3(256), lds, stream, jobs_dev, thres_dev, t, cap, hist_dev,
+    const size_t lds = sizeof(uint32_t) * cap + sizeof(float) * IRN_EVAL_MAX_THRES + sizeof(int) * thist::kMaxKeys + sizeof(uint32_t);
+    const int bx = (int)std::min<long>(((B.max_px + 3) / 4 + kSweepChunk - 1) / kSweepChunk + 1, 128);
+    hipLaunchKernelGGL(label_sweep_kernel, dim3(bx, n_images), dim3(256), lds, stream, B.dev, thres_dev, t, cap, hist_dev,
                        bad_dev);
     IRN_LAUNCH_CHECK("label_sweep_kernel");
     return scratch_release(stream);

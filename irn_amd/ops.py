@@ -26,6 +26,19 @@ from .gemm import (conv1x1_algo_count, conv1x1_nhwc, conv3x3_split, gemm16_algo_
                    gemm_ranks3x3, split16, split16_pad, split_overflowed, split_weight, split_weight_3x3)
 
 
+def _label_inputs(rws, out_sizes, keys):
+    """-> contiguous fp32 [C,h,w] score tensors, (H, W) int pairs and, where `keys` is given, flat int64 key tensors on the
+    scores' device: one of each per score tensor (a short list is an IndexError)."""
+    n, dev = len(rws), rws[0].device
+    for r in rws:
+        _need_cuda(r, "rw")
+    rs = [r.reshape((-1,) + tuple(r.shape[-2:])).contiguous().float() for r in rws]
+    sizes = [(int(out_sizes[i][0]), int(out_sizes[i][1])) for i in range(n)]
+    if keys is not None:
+        keys = [torch.as_tensor(keys[i], device=dev).to(torch.int64).reshape(-1).contiguous() for i in range(n)]
+    return rs, sizes, keys
+
+
 def label_epilogue(rws, out_sizes, bg_thres, keys=None, want_labels=True, want_argmax=False, want_rw_up=False, packed=False):
     """Batched x4-upsample / normalise / background / argmax.
 
@@ -36,13 +49,11 @@ def label_epilogue(rws, out_sizes, bg_thres, keys=None, want_labels=True, want_a
     views of ONE uint8 buffer, returned as 'labels_flat' (a step brings a whole batch to the host with one copy)."""
     n = len(rws)
     dev = rws[0].device
-    rs, cs, hs, ws, ohs, ows = [], [], [], [], [], []
-    for i in range(n):
-        _need_cuda(rws[i], "rw")
-        r = rws[i].reshape((-1,) + tuple(rws[i].shape[-2:])).contiguous().float()
-        rs.append(r)
-        cs.append(r.shape[0]); hs.append(r.shape[1]); ws.append(r.shape[2])
-        ohs.append(int(out_sizes[i][0])); ows.append(int(out_sizes[i][1]))
+    if want_labels and keys is None:
+        raise ValueError("labels need keys")
+    rs, sizes, ks = _label_inputs(rws, out_sizes, keys if want_labels else None)
+    cs, hs, ws = ([r.shape[d] for r in rs] for d in range(3))
+    ohs, ows = [s[0] for s in sizes], [s[1] for s in sizes]
     labels = flat = None
     if want_labels and packed:
         offs = np.concatenate([[0], np.cumsum([ohs[i] * ows[i] for i in range(n)])])
@@ -52,11 +63,6 @@ def label_epilogue(rws, out_sizes, bg_thres, keys=None, want_labels=True, want_a
         labels = [torch.empty((ohs[i], ows[i]), dtype=torch.uint8, device=dev) for i in range(n)]
     argmax = [torch.empty((ohs[i], ows[i]), dtype=torch.int32, device=dev) for i in range(n)] if want_argmax else None
     rw_up = [torch.empty((cs[i], ohs[i], ows[i]), dtype=torch.float32, device=dev) for i in range(n)] if want_rw_up else None
-    ks = None
-    if want_labels:
-        if keys is None:
-            raise ValueError("labels need keys")
-        ks = [torch.as_tensor(k, device=dev).to(torch.int64).contiguous() for k in keys]
     scratch = torch.empty(max(n, 64), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
         check(lib.irn_label_epilogue(
@@ -1215,6 +1221,13 @@ def eval_thresholds(thres, dev):
     return torch.from_numpy(th).to(dev)
 
 
+def _thres_tensor(thres, dev):
+    """-> (flat float32 tensor on dev, its length): a float32 GPU tensor as given, anything else through `eval_thresholds`."""
+    th = thres if isinstance(thres, torch.Tensor) and thres.is_cuda and thres.dtype == torch.float32 else eval_thresholds(thres, dev)
+    th = th.to(dev).reshape(-1).contiguous()
+    return th, int(th.numel())
+
+
 def cam_confusion(high_res, keys, gt, thres, hist=None, bad=None):
     """step/eval_cam.py:14-19 + the confusion count for one image at every threshold of `thres` in one pass.
 
@@ -1234,9 +1247,7 @@ def cam_confusion(high_res, keys, gt, thres, hist=None, bad=None):
     ks = torch.as_tensor(keys).to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
     if ks.numel() != k:
         raise ValueError("cam_confusion: %d keys for %d CAM planes" % (ks.numel(), k))
-    th = thres if isinstance(thres, torch.Tensor) and thres.is_cuda and thres.dtype == torch.float32 else eval_thresholds(thres, dev)
-    th = th.to(dev).contiguous()
-    t = int(th.numel())
+    th, t = _thres_tensor(thres, dev)
     hist = _accumulator(hist, (EVAL_CLASSES + 1, EVAL_CLASSES, t + 1), dev, "hist")
     bad = _accumulator(bad, (1,), dev, "bad")
     with torch.cuda.device(dev):
@@ -1260,7 +1271,7 @@ def cam_confusion_matrices(hist):
 
 def label_sweep_confusion(rws, out_sizes, keys, gts, thres, hist=None, bad=None):
     """`label_epilogue` + `label_confusion` at every background threshold of `thres` in one pass, for a batch (no label
-    map and no upsampled tensor is written).
+    map and no upsampled tensor is written), by the epilogue's own score functions and `cam_confusion`'s counting code.
 
     rws, out_sizes, keys: as for `label_epilogue` (at most 20 channels per image); gts: a list of uint8 [H,W] GPU tensors
     (255 = void), or ONE flat uint8 GPU buffer that holds the maps of `out_sizes` back to back; thres: GPU fp32 [T] from
@@ -1270,10 +1281,12 @@ def label_sweep_confusion(rws, out_sizes, keys, gts, thres, hist=None, bad=None)
     n = len(rws)
     if n < 1 or len(out_sizes) != n or len(keys) != n:
         raise ValueError("label_sweep_confusion: %d score maps, %d sizes, %d key lists" % (n, len(out_sizes), len(keys)))
-    for r in rws:
-        _need_cuda(r, "rw")
     dev = rws[0].device
-    sizes = [(int(s[0]), int(s[1])) for s in out_sizes]
+    for i, r in enumerate(rws):
+        _need_cuda(r, "rw")
+        if r.dim() < 2 or r.device != dev:
+            raise ValueError("label_sweep_confusion: rw %d must be a [C,1,h,w] or [C,h,w] tensor on %s" % (i, dev))
+    rs, sizes, ks = _label_inputs(rws, out_sizes, keys)
     if isinstance(gts, torch.Tensor):
         _need_cuda(gts, "gts")
         total = sum(hh * ww for hh, ww in sizes)
@@ -1295,23 +1308,14 @@ def label_sweep_confusion(rws, out_sizes, keys, gts, thres, hist=None, bad=None)
                 raise ValueError("label_sweep_confusion: gt %d is %s for an output of %s" % (i, tuple(g.shape), sizes[i]))
             gs.append(g.contiguous())
         gt_ptrs = [g.data_ptr() for g in gs]
-    rs, ks = [], []
-    for i in range(n):
-        if rws[i].dim() < 2 or rws[i].device != dev:
-            raise ValueError("label_sweep_confusion: rw %d must be a [C,1,h,w] or [C,h,w] tensor on %s" % (i, dev))
-        r = rws[i].reshape((-1,) + tuple(rws[i].shape[-2:])).contiguous().float()
+    for i, (r, k) in enumerate(zip(rs, ks)):
         if not 1 <= r.shape[0] <= EVAL_CLASSES - 1:
             raise ValueError("label_sweep_confusion: image %d has %d channels (1..%d)" % (i, r.shape[0], EVAL_CLASSES - 1))
         if not (1 <= sizes[i][0] <= 4 * r.shape[1] and 1 <= sizes[i][1] <= 4 * r.shape[2]):
             raise ValueError("label_sweep_confusion: image %d: output %s from a %dx%d map" % (i, sizes[i], r.shape[1], r.shape[2]))
-        k = torch.as_tensor(keys[i], device=dev).to(torch.int64).reshape(-1).contiguous()
         if k.numel() != r.shape[0]:
             raise ValueError("label_sweep_confusion: image %d: %d keys for %d channels" % (i, k.numel(), r.shape[0]))
-        rs.append(r)
-        ks.append(k)
-    th = thres if isinstance(thres, torch.Tensor) and thres.is_cuda and thres.dtype == torch.float32 else eval_thresholds(thres, dev)
-    th = th.to(dev).reshape(-1).contiguous()
-    t = int(th.numel())
+    th, t = _thres_tensor(thres, dev)
     if not 1 <= t <= EVAL_MAX_THRES:
         raise ValueError("label_sweep_confusion: %d thresholds (1..%d)" % (t, EVAL_MAX_THRES))
     hist = _accumulator(hist, (EVAL_CLASSES + 1, EVAL_CLASSES, t + 1), dev, "hist")

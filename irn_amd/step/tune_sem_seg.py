@@ -12,8 +12,8 @@ Prints the lines of eval_sem_seg at the configured point, one `beta .. exp_times
 The boundary map of an image does not depend on the three numbers: per batch the IRNet runs once (`edges_for`, as the label
 step runs it), every (beta, exp_times) pair costs one walk, and `ops.label_sweep_confusion` counts every threshold of that
 walk in one pass (one histogram of (GT, first arg-max class, number of thresholds below its score)).  The
-walker, its batches and the IRNet batches are those of make_sem_seg_labels, and the counting kernel shares its arithmetic
-with the label epilogue, so a grid point's counts are those of the files the two steps would have written.  Runs in the
+walker, its batches and the IRNet batches are those of make_sem_seg_labels, and the counting kernel computes its scores with
+the label epilogue's own device functions, so a grid point's counts are those of the files the two steps would have written.  Runs in the
 calling process on its current device like the evaluation steps (step/_eval.py)."""
 import os
 

@@ -106,6 +106,37 @@ def test_cam_confusion_accumulates_and_counts_bad_values():
     assert int(conf2[0].sum()) + int(((gt == 255)).sum()) == 20 * 30 - 7
 
 
+def test_cam_confusion_bad_keys_and_descending_thresholds():
+    from irn_amd import ops
+    rng = np.random.RandomState(11)
+    h, w = 130, 70                                            # 9100 pixels: three blocks of 4096
+    gt = _gt(h, w, rng)
+    cams = _cams(3, h, w, rng)
+    th = _thresholds(100, rng)
+    cstar, m = np.argmax(cams, axis=0), cams.max(axis=0)      # first arg-max plane; no NaN, every GT value in range
+    j = np.searchsorted(th, m, side="left")                   # number of thresholds < m
+    row = np.where(gt == 255, 21, gt).astype(np.int64)
+    on_plane = cstar == 1
+    assert 0 < on_plane.sum() < h * w and (on_plane & (gt == 255)).any()
+    # keys -1 and 20 on plane 1: its pixels are counted as bad, once each, and left out of the histogram
+    for k_bad in (-1, 20):
+        keys = np.int64([4, k_bad, 9])
+        hist, bad = ops.cam_confusion(torch.from_numpy(cams).to(_dev()), keys, torch.from_numpy(gt).to(_dev()), th)
+        want = np.zeros((22, 21, len(th) + 1), np.int64)
+        np.add.at(want, (row[~on_plane], keys[cstar[~on_plane]] + 1, j[~on_plane]), 1)
+        assert int(bad.item()) == int(on_plane.sum())
+        assert np.array_equal(hist.cpu().numpy(), want)
+    # a descending pair, as a float32 GPU tensor (which `eval_thresholds` never sees): once per call whatever the number
+    # of blocks; the counts still follow the list as given
+    th_bad = torch.from_numpy(np.float32([0.5, 0.3])).to(_dev())
+    for hh, ww in [(33, 47), (h, w)]:
+        g = _gt(hh, ww, rng)
+        c = _cams(3, hh, ww, rng)
+        hist, bad = ops.cam_confusion(torch.from_numpy(c).to(_dev()), [4, 7, 9], torch.from_numpy(g).to(_dev()), th_bad)
+        assert int(bad.item()) == 1
+        assert int(hist.sum().item()) == hh * ww
+
+
 @pytest.mark.parametrize("h,w", [(1, 1), (7, 5), (500, 375)])
 def test_label_confusion_exact(h, w):
     from irn_amd import ops

@@ -1,0 +1,167 @@
+"""Shared plumbing of the label steps (make_sem_seg_labels, make_ins_seg_labels); tune_sem_seg walks with the same pieces.
+
+A label step is `run_step`: the split sharded over the worker devices, one `_work` of the step's own module per shard.  Every
+`_work` is a loop over `items()` (one image at a time, with its CAM) inside `worker()` (network, loader, writer threads and
+walker of the shard, taken down again however the loop ends); what it does with a batch of images is the step's own.  The
+boundary / displacement maps come from `edges_for`, handed from step to step on the device as `edge_store_kw` says."""
+import contextlib
+import os
+import types
+
+import numpy as np
+import torch
+from PIL import Image
+
+from ..voc12 import dataloader as voc12_dataloader
+from . import _common
+
+RADIUS = 5   # hard-coded at both reference call sites (step/make_sem_seg_labels.py:41, step/make_ins_seg_labels.py:135)
+
+
+def irn_batch(args):
+    return int(getattr(args, "irn_batch", 0) or 8)              # images per IRNet trunk pass
+
+
+def walk_batch(args, default):
+    return int(getattr(args, "walk_batch", 0) or default)       # images per walk launch (results per image unchanged)
+
+
+def edges_for(model, pend, irn_batch, store=None, model_key=None, dump_dir=None):
+    """EdgeDisplacement forward for the pending images, `irn_batch` at a time: ragged images are padded to the
+    512^2 crop like the reference pads each one (net/resnet50_irn.py:225), so a chunk is ONE trunk pass.  With a `store`
+    (`_common.EDGE_STORE`) the maps the other label step already computed for an image (same network, same file) are taken
+    from device memory instead, and what is computed here is left there for it."""
+    todo = pend
+    if store is not None:
+        todo = []
+        for p in pend:
+            key = (model_key, getattr(model, "crop_size", None), getattr(model, "stride", None), p.get("stamp"))
+            dev = p["dev"] if "dev" in p else p["img"].device
+            hit = store.get(key, dev) if p.get("stamp") is not None else None
+            if hit is not None:
+                p["edge"], p["dp"] = hit
+                p.pop("img", None)
+            else:
+                p["_edge_key"] = key if p.get("stamp") is not None else None
+                todo.append(p)
+    for p in todo:
+        if p.get("img") is None:
+            # the loader skipped this image's pixels because the store held its maps then, and they are gone now (evicted
+            # between the loader's look and this one): decode it here
+            img = torch.from_numpy(np.array(Image.open(p["stamp"][0]).convert("RGB")))
+            p["img"] = _common.device_images({"img": img[None]}, (1.0,))[0]
+    for i in range(0, len(todo), irn_batch):
+        chunk = todo[i:i + irn_batch]
+        for p, (edge, dp) in zip(chunk, model.forward_batch([p.pop("img") for p in chunk])):
+            p["edge"], p["dp"] = edge, dp
+            key = p.pop("_edge_key", None)
+            if store is not None and key is not None:
+                store.put(key, edge, dp.clone())         # dp is a view into the batch's output: keep 1 image, not 8
+    if dump_dir:
+        # verification aid (args.edge_out_dir, off by default): the maps this step walks on, per image, so that a run can be
+        # checked against the oracle on ITS OWN inputs (the reference keeps them in memory only, step/make_sem_seg_labels.py:28-34).
+        # Synchronous on purpose: not a production path
+        os.makedirs(dump_dir, exist_ok=True)
+        for p in pend:
+            np.save(os.path.join(dump_dir, p["name"] + ".npy"), {"edge": p["edge"].cpu().numpy(), "dp": p["dp"].cpu().numpy()})
+
+
+def skip_image_predicate(model, args, device):
+    """`skip_image` for the step's dataset: True for images whose boundary / displacement maps the other label step left on
+    this device (the EdgeStore entry `edges_for` will hit) — their JPEG need not be decoded or uploaded."""
+    kw = edge_store_kw(model, args)
+    store = kw.get("store")
+    if store is None:
+        return None
+    mk, crop, stride = kw["model_key"], getattr(model, "crop_size", None), getattr(model, "stride", None)
+    return lambda name: store.peek((mk, crop, stride, _common.image_stamp(args.voc12_root, name)), device)
+
+
+_MODEL_KEYS = {}          # id(network) -> (weak reference to it, key of the ModelSpec it was built from); set in build_model
+
+
+def remember_model(model, spec_key):
+    """Note which checkpoint (class + path + mtime + size) a worker built `model` from: the identity the EdgeStore keys
+    its entries by.  The weak reference guards against a later object reusing the id of a freed network."""
+    import weakref
+    for k in [k for k, (ref, _) in _MODEL_KEYS.items() if ref() is None]:
+        del _MODEL_KEYS[k]
+    _MODEL_KEYS[id(model)] = (weakref.ref(model), spec_key)
+
+
+def model_key(model):
+    hit = _MODEL_KEYS.get(id(model))
+    return hit[1] if hit is not None and hit[0]() is model else None
+
+
+def edge_store_kw(model, args):
+    """Keyword arguments of `edges_for` that switch the device hand-off of the edge maps on (see _common.EdgeStore)."""
+    dump = {"dump_dir": args.edge_out_dir} if getattr(args, "edge_out_dir", None) else {}
+    if not _common.keep_edges(args):
+        return dump
+    key = model_key(model)
+    if key is None:
+        # a network handed over as a module (not built from a ModelSpec) has no identity that survives an in-place weight
+        # update or a recycled id(): no hand-off for it, every step computes its own maps
+        return dump
+    return {"store": _common.EDGE_STORE, "model_key": key, **dump}
+
+
+def build_model(model):
+    """A network, or the (class, checkpoint) a worker builds it from -> the network, remembered under its checkpoint's key."""
+    spec_key = model.key() if isinstance(model, _common.ModelSpec) else None
+    model = _common.materialise(model)
+    if spec_key is not None:
+        remember_model(model, spec_key)
+    return model
+
+
+def item(name, size, dev, args, cam_run):
+    """What a step keeps per image; `img` is the caller's to fill in.  The CAM: from the device if make_cam left it there, else its file."""
+    keys, keys_dev, cam = _common.CAM_STORE.get(name, args.cam_out_dir, dev, cam_run, _common.keep_cams(args))
+    return {"name": name, "size": size, "img": None, "dev": dev, "cam": cam, "keys": keys, "keys_dev": keys_dev,
+            "stamp": _common.image_stamp(args.voc12_root, name)}
+
+
+@contextlib.contextmanager
+def worker(process_id, model, dataset, args):
+    """One shard of a label step on its worker's device.  Walker (its context and device buffers) and writer are closed however
+    the block ends; the walk's fall-back count and the step's summary line come only after a block that ended well."""
+    model = build_model(model)
+    databin, n_gpus = dataset[process_id], len(dataset)
+    dev = torch.device("cuda", _common.worker_device(process_id, args))
+    _common.set_skip_image(databin, skip_image_predicate(model, args, dev))
+    loader = _common.make_loader(databin, int(args.num_workers) // n_gpus)
+    with contextlib.closing(_common.AsyncWriter(_common.writer_threads(args, n_gpus))) as writer, torch.no_grad(), torch.cuda.device(dev):
+        model.cuda()
+        with contextlib.closing(_common.make_walker(args, RADIUS)) as walker:
+            yield types.SimpleNamespace(model=model, walker=walker, writer=writer, loader=loader, dev=dev, databin=databin,
+                                        n_gpus=n_gpus, process_id=process_id)
+            _common.WALK_STATS["fallback_runs"] += walker.fallback_runs
+            _common.step_summary(process_id, walker)
+
+
+def items(w, args):
+    """The shard's images in order, each as `item` with its pixels on the device (`img` None where the skip predicate emptied them)."""
+    cam_run = _common.current_cam_run(args.cam_out_dir)
+    for it, pack in enumerate(w.loader):
+        name = pack["name"][0]
+        name = name if isinstance(name, str) else voc12_dataloader.decode_int_filename(name)
+        p = item(name, (int(pack["size"][0]), int(pack["size"][1])), w.dev, args, cam_run)
+        imgs = _common.device_images(pack, (1.0,))
+        p["img"] = None if imgs is None else imgs[0]
+        yield p
+        _common.progress(w.process_id, w.n_gpus, it, len(w.databin))
+
+
+def run_step(work, out_dir, args, opening="["):
+    """`run(args)` of a label step: `work` on every shard of `args.infer_list`, inside the reference's bracket (`opening`)."""
+    model = _common.ModelSpec(args.irn_network, "EdgeDisplacement", args.irn_weights_name, strict=False)   # built by the worker(s)
+    n_gpus = _common.n_gpus_or_raise(args)
+    dataset = voc12_dataloader.VOC12ClassificationDatasetMSF(args.infer_list, voc12_root=args.voc12_root,
+                                                             scales=(1.0,), raw=_common.device_preprocess(args))
+    dataset = _common.label_step_shards(dataset, n_gpus, args)     # strided (misc/torchutils.py:66-68) or CAM-owner aware
+    os.makedirs(out_dir, exist_ok=True)
+    print(opening, end="")
+    _common.spawn_workers(work, model, dataset, args)
+    print("]")

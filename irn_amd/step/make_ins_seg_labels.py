@@ -21,10 +21,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..voc12 import dataloader as voc12_dataloader
-from . import _common, make_sem_seg_labels
-
-RADIUS = 5   # step/make_ins_seg_labels.py:135
+from . import _labels
 
 find_centroids_with_refinement = ops.find_centroids_with_refinement
 cluster_centroids = ops.cluster_centroids
@@ -45,11 +42,11 @@ def instance_back(walker, items, front, beta, exp_times, bg_thres, deferred=Fals
     ks = [int(k) for k in k_dev.cpu().tolist()]
     rws = walker([it["edge"] for it in items], [it["cam"] for it in items], beta=beta, exp_times=exp_times,
                  inst_maps=cmaps, k_inst=ks)
-    ep = ops.label_epilogue(rws, [it["size"] for it in items], bg_thres, want_labels=False, want_argmax=True,
-                            want_rw_up=True)
+    def epilogue():
+        return ops.label_epilogue(rws, [it["size"] for it in items], bg_thres, want_labels=False, want_argmax=True, want_rw_up=True)
+    ep = epilogue()
     if walker.sync():                       # the persistent walk gave up and the batch was re-run on the streaming sweeps
-        ep = ops.label_epilogue(rws, [it["size"] for it in items], bg_thres, want_labels=False, want_argmax=True,
-                                want_rw_up=True)
+        ep = epilogue()
     n_ch = [it["cam"].shape[0] * k for it, k in zip(items, ks)]
     class_ids = [np.repeat(np.asarray(torch.as_tensor(it["keys"]).cpu()), k) for it, k in zip(items, ks)]
     detect = {"npy": ops.detect_instance_batch, "rle": ops.detect_instance_rle_batch}[fmt]
@@ -123,8 +120,7 @@ def _flush(model, walker, pend, args, writer, state):
                               **extra))
         state["front"] = None
     if pend:
-        make_sem_seg_labels.edges_for(model, pend, int(getattr(args, "irn_batch", 0) or 8),
-                                      **make_sem_seg_labels._edge_store_kw(model, args))
+        _labels.edges_for(model, pend, _labels.irn_batch(args), **_labels.edge_store_kw(model, args))
         items = list(pend)
         pend.clear()
         state["front"] = (items, instance_front(items))
@@ -134,54 +130,19 @@ def _flush(model, walker, pend, args, writer, state):
 
 
 def _work(process_id, model, dataset, args):
-    spec_key = model.key() if isinstance(model, _common.ModelSpec) else None
-    model = _common.materialise(model)      # a network, or the (class, checkpoint) a worker builds it from
-    if spec_key is not None:
-        make_sem_seg_labels.remember_model(model, spec_key)
-    databin = dataset[process_id]
-    n_gpus = len(dataset)
-    _common.set_skip_image(databin, make_sem_seg_labels.skip_image_predicate(
-        model, args, torch.device("cuda", _common.worker_device(process_id, args))))
-    loader = _common.make_loader(databin, int(args.num_workers) // n_gpus)
-    batch = int(getattr(args, "walk_batch", 0) or 32)   # images per walk launch (results per image unchanged)
-    writer = _common.AsyncWriter(threads=_common.writer_threads(args, n_gpus))
-    try:
-        dev_id = _common.worker_device(process_id, args)
-        with torch.no_grad(), torch.cuda.device(dev_id):
-            model.cuda()
-            dev = torch.device("cuda", dev_id)
-            walker = _common.make_walker(args, RADIUS)
-            pend, state = [], {}
-            cam_run, use_store = _common.current_cam_run(args.cam_out_dir), _common.keep_cams(args)
-            for it, pack in enumerate(loader):
-                name = pack["name"][0]
-                if not isinstance(name, str):
-                    name = voc12_dataloader.decode_int_filename(name)
-                size = (int(pack["size"][0]), int(pack["size"][1]))
-                keys, _keys_dev, cam = _common.CAM_STORE.get(name, args.cam_out_dir, dev, cam_run, use_store)
-                imgs = _common.device_images(pack, (1.0,))
-                pend.append({"name": name, "size": size, "img": None if imgs is None else imgs[0], "dev": dev,
-                             "cam": cam, "keys": keys, "stamp": _common.image_stamp(args.voc12_root, name)})
-                if len(pend) == batch:
-                    _flush(model, walker, pend, args, writer, state)
-                _common.progress(process_id, n_gpus, it, len(databin))
-            _flush(model, walker, pend, args, writer, state)      # the last batch's front half ...
-            _flush(model, walker, pend, args, writer, state)      # ... its back half ...
-            _flush(model, walker, pend, args, writer, state)      # ... and its collection
-            _common.WALK_STATS["fallback_runs"] += walker.fallback_runs
-            _common.step_summary(process_id, walker)
-            walker.close()
-    finally:
-        writer.close()
+    batch = _labels.walk_batch(args, 32)
+    with _labels.worker(process_id, model, dataset, args) as w:
+        pend, state = [], {}
+        for item in _labels.items(w, args):
+            pend.append(item)
+            if len(pend) == batch:
+                _flush(w.model, w.walker, pend, args, w.writer, state)
+        _flush(w.model, w.walker, pend, args, w.writer, state)      # the last batch's front half ...
+        _flush(w.model, w.walker, pend, args, w.writer, state)      # ... its back half ...
+        _flush(w.model, w.walker, pend, args, w.writer, state)      # ... and its collection
 
 
 def run(args):
-    model = _common.ModelSpec(args.irn_network, "EdgeDisplacement", args.irn_weights_name, strict=False)   # built by the worker(s)
-    n_gpus = _common.n_gpus_or_raise(args)
-    dataset = voc12_dataloader.VOC12ClassificationDatasetMSF(args.infer_list, voc12_root=args.voc12_root,
-                                                             scales=(1.0,), raw=_common.device_preprocess(args))
-    dataset = _common.label_step_shards(dataset, n_gpus, args)     # strided (misc/torchutils.py:66-68) or CAM-owner aware
-    os.makedirs(args.ins_seg_out_dir, exist_ok=True)
-    print("[ ", end="")
-    _common.spawn_workers(_work, model, dataset, args)
-    print("]")
+    _labels.run_step(_work, args.ins_seg_out_dir, args, opening="[ ")
+
+

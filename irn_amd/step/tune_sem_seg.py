@@ -15,8 +15,6 @@ walk in one pass (one histogram of (GT, first arg-max class, number of threshold
 walker, its batches and the IRNet batches are those of make_sem_seg_labels, and the counting kernel computes its scores with
 the label epilogue's own device functions, so a grid point's counts are those of the files the two steps would have written.  Runs in the
 calling process on its current device like the evaluation steps (step/_eval.py)."""
-import os
-
 import numpy as np
 import torch
 from PIL import Image
@@ -25,8 +23,7 @@ from .. import ops
 from ..misc import evaluation
 from ..voc12 import dataloader as voc12_dataloader
 from ..voc12 import eval_data
-from . import _common, _eval
-from . import make_sem_seg_labels as _labels
+from . import _common, _eval, _labels
 
 MAX_PAIRS = 64                        # (beta, exp_times) pairs = walks per batch
 
@@ -87,7 +84,7 @@ def report(conf, void, axes, configured):
 
 def _count(model, walker, pend, pairs, th, hist, bad, args):
     """One batch: the boundary maps once, then per (beta, exp_times) a walk and the count of every threshold."""
-    _labels.edges_for(model, pend, int(getattr(args, "irn_batch", 0) or 8), **_labels._edge_store_kw(model, args))
+    _labels.edges_for(model, pend, _labels.irn_batch(args), **_labels.edge_store_kw(model, args))
     edges, cams = [p["edge"] for p in pend], [p["cam"] for p in pend]
     sizes, keys = [p["size"] for p in pend], [p["keys_dev"] for p in pend]
     gts = _common.upload(torch.cat([p["gt"].reshape(-1) for p in pend]))     # the batch's maps back to back: one copy
@@ -110,7 +107,6 @@ def run(args):
     if not ids:
         raise ValueError("tune_sem_seg: the split %s lists no images" % args.chainer_eval_set)
     dev = _eval.device()
-    spec = _common.ModelSpec(args.irn_network, "EdgeDisplacement", args.irn_weights_name, strict=False)
 
     def load(id):
         gt = eval_data.class_label(args.voc12_root, id)
@@ -123,25 +119,23 @@ def run(args):
     try:
         _common.miopen_setup(dev.index)             # the MIOpen settings and the reproducible mode of the label steps
         with torch.no_grad(), torch.cuda.device(dev):
-            model = _common.materialise(spec)
-            _labels.remember_model(model, spec.key())
+            model = _labels.build_model(_common.ModelSpec(args.irn_network, "EdgeDisplacement", args.irn_weights_name, strict=False))
             model.cuda()
             walker = _common.make_walker(args, _labels.RADIUS)
-            batch = int(getattr(args, "walk_batch", 0) or 64)
+            batch = _labels.walk_batch(args, 64)
             th = torch.from_numpy(th32).to(dev)
             hist = torch.zeros((len(pairs), ops.EVAL_CLASSES + 1, ops.EVAL_CLASSES, len(th32) + 1), dtype=torch.int64, device=dev)
             bad = torch.zeros(1, dtype=torch.int64, device=dev)
-            cam_run, use_store = _common.current_cam_run(args.cam_out_dir), _common.keep_cams(args)
+            cam_run = _common.current_cam_run(args.cam_out_dir)
             pend = []
             try:
                 for id, it in _eval.items(ids, load, args):
-                    keys, keys_dev, cam = _common.CAM_STORE.get(id, args.cam_out_dir, dev, cam_run, use_store)
-                    if keys.numel() == 0:
+                    p = _labels.item(id, tuple(int(v) for v in it["gt"].shape), dev, args, cam_run)
+                    if p["keys"].numel() == 0:
                         raise ValueError("tune_sem_seg: %s has no class key in %s: an image without a CAM has no label to score"
                                          % (id, args.cam_out_dir))
-                    img = ops.msf_pack(_common.upload(it["image"]), (1.0,))[0]
-                    pend.append({"name": id, "size": tuple(int(v) for v in it["gt"].shape), "img": img, "dev": dev, "cam": cam,
-                                 "keys_dev": keys_dev, "gt": it["gt"], "stamp": _common.image_stamp(args.voc12_root, id)})
+                    p.update(img=ops.msf_pack(_common.upload(it["image"]), (1.0,))[0], gt=it["gt"])
+                    pend.append(p)
                     if len(pend) == batch:
                         bad = _count(model, walker, pend, pairs, th, hist, bad, args)
                 if pend:

@@ -38,7 +38,7 @@ def _make_voc(tmp, n=4):
 
 
 class _CaptureEdges:
-    """Records the edge / displacement maps the label steps actually computed (by wrapping make_sem_seg_labels.edges_for,
+    """Records the edge / displacement maps the label steps actually computed (by wrapping step/_labels.edges_for,
     which both label steps call), so that the oracle can be run on exactly the inputs the HIP path saw — a second
     forward of the backbone in THIS process need not be bit-identical (it has run unmanaged convolutions before: LESSONS.md 37)."""
 
@@ -60,7 +60,7 @@ class _CaptureEdges:
 
 def test_steps_end_to_end(tmp_path):
     from irn_amd.net import weights
-    from irn_amd.step import make_cam, make_ins_seg_labels, make_sem_seg_labels
+    from irn_amd.step import _labels, make_cam, make_ins_seg_labels, make_sem_seg_labels
     root, names, labels = _make_voc(tmp_path)
     torch.save(weights.random_cam_state(1), tmp_path / "res50_cam.pth")
     torch.save(weights.random_irn_state(2), tmp_path / "res50_irn.pth")
@@ -114,7 +114,7 @@ def test_steps_end_to_end(tmp_path):
     hits0, misses0 = _common.CAM_STORE.hits, _common.CAM_STORE.misses
     _common.EDGE_STORE.clear()
     e_hits0, e_misses0 = _common.EDGE_STORE.hits, _common.EDGE_STORE.misses
-    with _CaptureEdges(make_sem_seg_labels) as cap:
+    with _CaptureEdges(_labels) as cap:
         make_sem_seg_labels.run(args)
     edges = cap.edges
     assert _common.CAM_STORE.hits - hits0 == len(names) and _common.CAM_STORE.misses == misses0   # CAMs came from device memory
@@ -146,7 +146,7 @@ def test_steps_end_to_end(tmp_path):
     off_args = argparse.Namespace(**{**vars(args), "sem_seg_out_dir": str(tmp_path / "sem_nostore"), "keep_edges_on_device": False})
     os.makedirs(off_args.sem_seg_out_dir)
     e_total = _common.EDGE_STORE.hits + _common.EDGE_STORE.misses
-    with _CaptureEdges(make_sem_seg_labels) as cap_off:
+    with _CaptureEdges(_labels) as cap_off:
         make_sem_seg_labels.run(off_args)
     assert _common.EDGE_STORE.hits + _common.EDGE_STORE.misses == e_total
     worst = max(float(np.abs(cap_off.edges[n] - edges[n]).max()) for n in names)
@@ -158,7 +158,7 @@ def test_steps_end_to_end(tmp_path):
         assert np.array_equal(a, b), n
     r10_args = argparse.Namespace(**{**vars(args), "sem_seg_out_dir": str(tmp_path / "sem_r10"), "radius": 10})
     os.makedirs(r10_args.sem_seg_out_dir)
-    with _CaptureEdges(make_sem_seg_labels) as cap10:
+    with _CaptureEdges(_labels) as cap10:
         make_sem_seg_labels.run(r10_args)
     n = names[0]
     W, H = Image.open(root / "JPEGImages" / (n + ".jpg")).size
@@ -170,7 +170,7 @@ def test_steps_end_to_end(tmp_path):
     print("%s radius 10: %d of %d label pixels differ from the oracle (largest top-2 gap %.2e)" % (n, n_diff, png.size, gap))
 
     e_hits1 = _common.EDGE_STORE.hits
-    with _CaptureEdges(make_sem_seg_labels) as capi:
+    with _CaptureEdges(_labels) as capi:
         make_ins_seg_labels.run(args)
     assert _common.EDGE_STORE.hits - e_hits1 == len(names)             # boundary AND displacement maps of the semantic step reused
     written = [n for n in names if os.path.exists(os.path.join(args.ins_seg_out_dir, n + ".npy"))]

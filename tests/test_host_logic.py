@@ -777,7 +777,7 @@ def test_edge_store_keys_and_cap(tmp_path):
     """step/_common.EdgeStore: the boundary / displacement maps one label step leaves for the other are keyed by network,
     forward geometry and image FILE; another checkpoint, another image under the same name (new mtime / size) or another
     device is a miss; the oldest entries leave when the cap is reached; edges_for fills and uses it."""
-    from irn_amd.step import _common, make_sem_seg_labels
+    from irn_amd.step import _common, _labels
     root = tmp_path / "voc"
     (root / "JPEGImages").mkdir(parents=True)
     (root / "JPEGImages" / "2008_000001.jpg").write_bytes(b"a" * 100)
@@ -797,22 +797,22 @@ def test_edge_store_keys_and_cap(tmp_path):
     net = _Net()
     mk = lambda names: [{"name": n, "img": torch.full((2, 3, 16, 20), float(i)), "stamp": ("/p/" + n, 1, 2)} for i, n in enumerate(names)]
     a = mk(["x", "y", "z"])
-    make_sem_seg_labels.edges_for(net, a, 2, store=store, model_key=("ckpt", 1))
+    _labels.edges_for(net, a, 2, store=store, model_key=("ckpt", 1))
     assert _Net.calls == 2 and store.misses == 3 and store.hits == 0 and len(store) == 3 and "img" not in a[0]
     b = mk(["x", "y", "z", "w"])
-    make_sem_seg_labels.edges_for(net, b, 2, store=store, model_key=("ckpt", 1))
+    _labels.edges_for(net, b, 2, store=store, model_key=("ckpt", 1))
     assert _Net.calls == 3 and store.hits == 3                                    # only "w" went through the network
     for p, q in zip(a, b):
         assert torch.equal(p["edge"], q["edge"]) and torch.equal(p["dp"], q["dp"])
     c = mk(["x"])
-    make_sem_seg_labels.edges_for(net, c, 2, store=store, model_key=("ckpt", 2))   # another checkpoint: computed again
+    _labels.edges_for(net, c, 2, store=store, model_key=("ckpt", 2))   # another checkpoint: computed again
     assert _Net.calls == 4
     d = mk(["x"])
     d[0]["stamp"] = ("/p/x", 9, 2)                                                # the file changed
-    make_sem_seg_labels.edges_for(net, d, 2, store=store, model_key=("ckpt", 1))
+    _labels.edges_for(net, d, 2, store=store, model_key=("ckpt", 1))
     assert _Net.calls == 5
     e = mk(["x"])
-    make_sem_seg_labels.edges_for(net, e, 2)                                       # no store: always computed, nothing stored
+    _labels.edges_for(net, e, 2)                                       # no store: always computed, nothing stored
     assert _Net.calls == 6 and "stamp" in e[0]
     small = _common.EdgeStore(max_bytes=3 * 4 * 60)
     for i in range(5):
@@ -912,10 +912,10 @@ def test_instance_step_pipeline_order(monkeypatch):
     and in order, the back half of batch k never queues behind the forward of batch k+1, three closing turns drain the pipe.
     (Reference loop: step/make_ins_seg_labels.py:119-152, one image at a time.)"""
     import argparse
-    from irn_amd.step import make_ins_seg_labels as mis, make_sem_seg_labels as mss
+    from irn_amd.step import _labels, make_ins_seg_labels as mis
     log = []
-    monkeypatch.setattr(mss, "edges_for", lambda model, pend, irn_batch, **kw: log.append(("irnet", tuple(p["name"] for p in pend))))
-    monkeypatch.setattr(mss, "_edge_store_kw", lambda model, args: {})
+    monkeypatch.setattr(_labels, "edges_for", lambda model, pend, irn_batch, **kw: log.append(("irnet", tuple(p["name"] for p in pend))))
+    monkeypatch.setattr(_labels, "edge_store_kw", lambda model, args: {})
     monkeypatch.setattr(mis, "instance_front", lambda items: log.append(("front", tuple(it["name"] for it in items))) or ("cmaps", "k_dev"))
     monkeypatch.setattr(mis, "instance_back", lambda walker, items, front, beta, exp_times, bg, deferred=False:
                         log.append(("back", tuple(it["name"] for it in items))) or "pending-%s" % items[0]["name"])
@@ -941,6 +941,171 @@ def test_instance_step_pipeline_order(monkeypatch):
     # a batch is collected one turn after its back half: its detections cross PCIe under the next batch's kernels
     assert stages.index(("write", "a")) > stages.index(("front", "b")) and stages.index(("write", "b")) > stages.index(("front", "c"))
     assert [w[2] for w in log if w[0] == "write"] == ["pending-a1", "pending-b1", "pending-c1"]
+
+
+def _stub_label_worker(monkeypatch, packs, fail_cam_at=None):
+    """step/_labels.worker() / items() without a GPU: network, loader, writer, walker, device context, CAM store and uploads are
+    stand-ins that record what happens to them.  -> (events, args, model); the CAM look-up number `fail_cam_at` raises OSError."""
+    import argparse
+    import contextlib
+    from irn_amd.step import _common
+    events = []
+
+    class _Model:
+        def cuda(self):
+            events.append("model.cuda")
+
+    class _Walker:
+        fallback_runs, radius = 3, 5
+
+        def __call__(self, edges, cams, **kw):
+            events.append(("walk", len(edges)))
+            return ["rw"] * len(edges)
+
+        def sync(self):
+            return False
+
+        def close(self):
+            events.append("walker.close")
+
+    class _Writer:
+        def __init__(self, threads):
+            pass
+
+        def submit(self, fn, *a, **kw):
+            events.append(("submit", os.path.basename(a[0])))
+
+        def close(self):
+            events.append("writer.close")
+
+    def cam_get(name, cam_out_dir, dev, run_id=None, use_store=True):
+        events.append(("cam", name))
+        if fail_cam_at is not None and sum(1 for e in events if e[0] == "cam") > fail_cam_at:
+            raise OSError("no CAM file for " + name)
+        return torch.tensor([3, 7]), "keys_dev-" + name, "cam-" + name
+
+    monkeypatch.setattr(_common, "materialise", lambda model: events.append("materialise") or model)
+    monkeypatch.setattr(_common, "worker_device", lambda process_id, args=None: 0)
+    monkeypatch.setattr(_common, "make_loader", lambda databin, num_workers, prefetch=4: iter(packs))
+    monkeypatch.setattr(_common, "AsyncWriter", _Writer)
+    monkeypatch.setattr(_common, "make_walker", lambda args, radius: _Walker())
+    monkeypatch.setattr(_common, "step_summary", lambda rank, walker=None: events.append("summary"))
+    monkeypatch.setattr(_common, "progress", lambda pid, n, it, n_items: events.append(("tick", pid, n, it, n_items)))
+    monkeypatch.setattr(_common, "device_images", lambda pack, scales: None if pack["img"].numel() == 0 else [pack["img"][0].float()])
+    monkeypatch.setattr(_common.CAM_STORE, "get", cam_get)
+    monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())
+    args = argparse.Namespace(num_workers=0, voc12_root="/no/such/voc", cam_out_dir="/no/such/cam", sem_seg_out_dir="/no/such/sem",
+                              beta=10, exp_times=8, sem_seg_bg_thres=0.25, walk_batch=1)
+    return events, args, _Model()
+
+
+def _label_packs():
+    """Two collated loader items: a `str` name with pixels, an integer-encoded name whose pixels the skip predicate emptied."""
+    return [{"name": ["2008_000001"], "size": torch.tensor([[6], [4]]), "img": torch.ones(1, 6, 4, 3, dtype=torch.uint8)},
+            {"name": torch.tensor([2008000002]), "size": torch.tensor([[5], [7]]), "img": torch.zeros(1, 0, dtype=torch.uint8)}]
+
+
+def test_label_worker_closes_walker_and_writer_on_both_paths(monkeypatch):
+    """step/_labels.worker: leaving the block normally adds the walker's fall-back runs to WALK_STATS once, prints the summary,
+    then closes walker and writer; an exception in the block closes both, adds nothing and comes out as it was raised."""
+    from irn_amd.step import _common, _labels
+    events, args, model = _stub_label_worker(monkeypatch, _label_packs())
+    monkeypatch.setitem(_common.WALK_STATS, "fallback_runs", 10)
+    with _labels.worker(1, model, [["x"], ["y", "z"]], args) as w:
+        assert (w.model, w.databin, w.n_gpus, w.dev) == (model, ["y", "z"], 2, torch.device("cuda", 0))
+        assert w.walker.fallback_runs == 3 and hasattr(w.writer, "submit") and len(list(w.loader)) == 2
+        assert not torch.is_grad_enabled() and "walker.close" not in events
+    assert _common.WALK_STATS["fallback_runs"] == 13 and torch.is_grad_enabled()
+    assert events == ["materialise", "model.cuda", "summary", "walker.close", "writer.close"]
+    del events[:]
+    boom = RuntimeError("a bad CAM file")
+    with pytest.raises(RuntimeError) as info:
+        with _labels.worker(0, model, [["x"]], args):
+            raise boom
+    assert info.value is boom and _common.WALK_STATS["fallback_runs"] == 13
+    assert events == ["materialise", "model.cuda", "walker.close", "writer.close"]
+
+
+def test_label_items_yield_what_both_steps_consume(monkeypatch):
+    """step/_labels.items: per image the dict both label steps built (name decoded, size as ints, pixels or None, device, CAM,
+    keys on the host AND on the device, the image file's stamp), one CAM look-up each, the progress tick after the consumer's turn."""
+    from irn_amd.step import _common, _labels
+    events, args, model = _stub_label_worker(monkeypatch, _label_packs())
+    with _labels.worker(0, model, [["a", "b"]], args) as w:
+        got = []
+        for p in _labels.items(w, args):
+            got.append(p)
+            events.append(("consumed", p["name"]))
+    a, b = got
+    assert set(a) == set(b) == {"name", "size", "img", "dev", "cam", "keys", "keys_dev", "stamp"}
+    assert (a["name"], b["name"]) == ("2008_000001", "2008_000002")
+    assert a["size"] == (6, 4) and b["size"] == (5, 7) and all(type(v) is int for v in a["size"] + b["size"])
+    assert a["img"].shape == (6, 4, 3) and a["img"].dtype == torch.float32 and b["img"] is None
+    assert a["dev"] == b["dev"] == torch.device("cuda", 0)
+    assert (a["cam"], a["keys_dev"], b["cam"], b["keys_dev"]) == ("cam-2008_000001", "keys_dev-2008_000001", "cam-2008_000002", "keys_dev-2008_000002")
+    assert a["keys"].tolist() == [3, 7]
+    assert a["stamp"] == _common.image_stamp(args.voc12_root, "2008_000001") and b["stamp"][0].endswith("2008_000002.jpg")
+    loop = [e for e in events if e[0] in ("cam", "consumed", "tick")]
+    assert loop == [("cam", "2008_000001"), ("consumed", "2008_000001"), ("tick", 0, 1, 0, 2),
+                    ("cam", "2008_000002"), ("consumed", "2008_000002"), ("tick", 0, 1, 1, 2)]
+
+
+def test_semantic_step_hands_its_staging_buffer_back_on_an_exception(monkeypatch):
+    """make_sem_seg_labels._work: when the loop dies with a batch in flight (here: the next image's CAM cannot be read), that
+    batch's page-locked buffer goes back to _common.PINNED, walker and writer are closed and the error comes out; a run that
+    ends well gives every buffer back exactly once."""
+    from irn_amd import ops
+    from irn_amd.step import _common, _labels, make_sem_seg_labels
+
+    class _Pool:
+        def __init__(self):
+            self.taken, self.given = [], []
+
+        def take(self, nbytes):
+            self.taken.append(torch.zeros(max(int(nbytes), 1), dtype=torch.uint8))
+            return self.taken[-1]
+
+        def give(self, buf):
+            self.given.append(buf)
+
+    class _Done:
+        def synchronize(self):
+            pass
+
+    def edges_for(model, pend, irn_batch, **kw):
+        for p in pend:
+            p["edge"] = "edge-" + p["name"]
+
+    for fail_cam_at, n_taken in ((1, 1), (None, 2)):
+        events, args, model = _stub_label_worker(monkeypatch, _label_packs(), fail_cam_at=fail_cam_at)
+        pool = _Pool()
+        monkeypatch.setattr(_common, "PINNED", pool)
+        monkeypatch.setattr(_labels, "edges_for", edges_for)
+        monkeypatch.setattr(ops, "label_epilogue", lambda rws, sizes, thres, keys=None, packed=False:
+                            {"labels_flat": torch.zeros(sum(h * w for h, w in sizes), dtype=torch.uint8)})
+        monkeypatch.setattr(ops, "read_back", lambda src, host, side: _Done())
+        if fail_cam_at is None:
+            make_sem_seg_labels._work(0, model, [["a", "b"]], args)
+            assert [e for e in events if e[0] == "submit"] == [("submit", "2008_000001.png"), ("submit", "2008_000002.png")]
+        else:
+            with pytest.raises(OSError, match="no CAM file for 2008_000002"):
+                make_sem_seg_labels._work(0, model, [["a", "b"]], args)
+            assert ("walk", 1) in events and not [e for e in events if e[0] == "submit"]     # the batch was in flight, not collected
+        assert len(pool.taken) == n_taken and len(pool.given) == n_taken
+        assert all(g is t for g, t in zip(pool.given, pool.taken))
+        assert events[-2:] == ["walker.close", "writer.close"]
+
+
+def test_label_step_batch_defaults():
+    """step/_labels.irn_batch / walk_batch: 8 images per IRNet pass and the step's own walk batch (64 semantic, 32 instance)
+    when the argument is absent or 0, the given value otherwise."""
+    import argparse
+    from irn_amd.step import _labels
+    for args in (argparse.Namespace(), argparse.Namespace(irn_batch=0, walk_batch=0), argparse.Namespace(irn_batch=None, walk_batch=None)):
+        assert _labels.irn_batch(args) == 8
+        assert _labels.walk_batch(args, 64) == 64 and _labels.walk_batch(args, 32) == 32
+    args = argparse.Namespace(irn_batch=3, walk_batch=5)
+    assert _labels.irn_batch(args) == 3 and _labels.walk_batch(args, 64) == 5 and _labels.walk_batch(args, 32) == 5
 
 
 def test_split_weight_operands_reconstruct_the_weight_to_22_bits_and_the_split_product_is_fp32_grade():

@@ -579,6 +579,42 @@ int irn_detect_instance_batch_rle_emit(int n_images, const int32_t *h, const int
                                        const int64_t *runs, uint32_t *counts_dev, void *rle_scratch_dev, void *ws,
                                        size_t ws_bytes, void *stream);
 
+/* Detections against the ground truth, straight from the labelled map: the counts irn_mask_overlap (below) gives for the
+ * dense masks irn_detect_instance_batch_emit would have written, with no mask in between — the detection of a pixel is
+ * read from the one int32 id map the scratch describes after irn_detect_instance_batch_count.
+ *
+ * irn_detect_instance_batch_overlap: after _batch_count with the same inputs and scratch; n_det: host int32 [n_images], as
+ *   read from n_det_dev; min_area: host [n_images].  inst_dev[i]: dev uint8 [h][w], 0 = no instance, 1..g[i] = a GT
+ *   instance (any alignment); g: host int32 [n_images], 0..255 each.  Outputs, batch-wide, image i's detections at the
+ *   exclusive prefix of n_det, its GT instances at the exclusive prefix of g, its inter block at the exclusive prefix of
+ *   n_det * g; all WRITTEN (not added into):
+ *     score dev fp32 [G], channel dev int32 [G]   as irn_detect_instance_batch_emit / _rle_count give them
+ *     area_pred dev int64 [G]                     pixels of the detection
+ *     inter     dev int64 [sum n_det[i] * g[i]]   image i's block is [n_det[i]][g[i]]: |detection & GT instance|
+ *     area_gt   dev int64 [sum g[i]]              pixels of each GT instance (also of an image without detections)
+ *   bad dev int64 [1] is ADDED into: pixels whose GT id lies above g[i] (they belong to no instance, as in
+ *   irn_mask_overlap).  An output whose size is 0 may be NULL.  Nothing synchronises and no workspace is needed beyond
+ *   `scratch`: an image whose (n_det + 1) x (g + 1) table of counts has at most 4096 cells is counted in LDS per workgroup
+ *   and flushed with integer atomics, a larger one with integer atomics on the outputs directly.
+ * n_images == 0 is valid (nothing is done), and so are n_det[i] == 0 and g[i] == 0; n_images < 0, a null pointer, h*w
+ * above 2^30, n_det outside [0, h*w] and g outside [0, 255] give IRN_ERR_ARG before any device is touched.  Integer
+ * arithmetic apart from the score maximum (a maximum of int bit patterns): bit-reproducible, and independent of the batch
+ * an image is part of.
+ *
+ * irn_argmax_rethreshold_batch: the argmax map irn_label_epilogue writes at background threshold `thres`, from the
+ *   outputs of ONE epilogue at a threshold not above it: rw_up_dev[i] fp32 [n_channels][h][w] and argmax_dev[i] int32
+ *   [h][w] of that call -> out_dev[i] int32 [h][w] (may be argmax_dev[i] itself).  A pixel keeps its channel where that
+ *   channel's score is NaN or > thres (the epilogue's strict >) and becomes 0 elsewhere: bit for bit the epilogue's map.
+ *   A NaN threshold gives IRN_ERR_ARG.  Nothing synchronises. */
+int irn_detect_instance_batch_overlap(int n_images, const float *const *rw_up_dev, const int32_t *const *argmax_dev,
+                                      const int32_t *n_channels, const int32_t *h, const int32_t *w, const int32_t *n_det,
+                                      const double *min_area, const uint8_t *const *inst_dev, const int32_t *g,
+                                      float *score_dev, int32_t *channel_dev, int64_t *area_pred_dev, int64_t *inter_dev,
+                                      int64_t *area_gt_dev, int64_t *bad_dev, void *scratch_dev, void *stream);
+int irn_argmax_rethreshold_batch(int n_images, const float *const *rw_up_dev, const int32_t *const *argmax_dev,
+                                 const int32_t *n_channels, const int32_t *h, const int32_t *w, float thres,
+                                 int32_t *const *out_dev, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Dense CRF  (replaces misc/imutils.py:156-170 crf_inference_label over pydensecrf, and
  *             step/cam_to_ir_label.py:22-39)

@@ -98,6 +98,8 @@ _SIGS = {
     "irn_detect_instance_batch_rle_count": (i32, [i32, ppv, ppv, pi32, pi32, pi32, pi32, C.POINTER(C.c_double), vp, vp, vp, vp, vp, vp, vp, vp]),
     "irn_detect_instance_batch_rle_sort_bytes": (sz, [i64, i32]),
     "irn_detect_instance_batch_rle_emit": (i32, [i32, pi32, pi32, pi32, C.POINTER(i64), vp, vp, vp, sz, vp]),
+    "irn_detect_instance_batch_overlap": (i32, [i32, ppv, ppv, pi32, pi32, pi32, pi32, C.POINTER(C.c_double), ppv, pi32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "irn_argmax_rethreshold_batch": (i32, [i32, ppv, ppv, pi32, pi32, pi32, f32, ppv, vp]),
     "irn_crf_filter_workspace_bytes": (sz, [i32, i32, i32]),
     "irn_crf_filter": (i32, [vp, i32, i32, vp, i32, vp, pi32, vp, vp, vp, sz, vp]),
     "irn_crf_workspace_bytes": (sz, [i32, i32, i32]),

@@ -1134,6 +1134,250 @@ extern "C" int irn_detect_instance_batch_rle_emit(int n_images, const int32_t *h
     return scratch_release(stream);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Overlap counts against the ground truth, straight from the labelled map (what irn_detect_instance_batch_emit followed by
+// irn_mask_overlap count, eval.hip) — no dense mask plane anywhere.
+//
+// Pixel p lies in detection d = newid[prov[parent[p]]] (none: background) and in GT instance id = inst[p] (0: none; an id
+// above g is counted in `bad` over the whole image and then reads as none, as k_mask_overlap's whole-image row does).  The
+// pixel counts by (d + 1, id) form a table of (n_det + 1) x (g + 1) cells whose interior is `inter`, whose column sums are
+// the GT areas (row 0, the background, included: an image without detections still has them) and whose row sums are the
+// detections' areas (column 0 included).  Only the interior and the two margins are kept in memory: a cell's count goes to
+// inter[d][id - 1], area_gt[id - 1] and the detection's int32 area of det_stats_kernel, by integer atomics.
+//
+// A workgroup counts 4096 consecutive pixels.  When the image's table has at most kOvlCells = 4096 cells the workgroup
+// counts into a copy of it in LDS (uint32: a cell cannot exceed 4096) and flushes its non-zero cells once; a larger table
+// (a noisy map with thousands of fragments) is counted with global atomics directly.  The budget: 16 KiB of LDS per
+// workgroup lets ten workgroups share a CU's 160 KiB, more than the eight that its 32 wave slots hold, so the table
+// never lowers the occupancy; and the flush scans at most 16 cells per thread, no more than the 16 pixels the thread has
+// just counted.  A real image has tens of detections and a few GT instances: a few hundred cells.
+// Either way a wave first looks whether its 64 consecutive pixels share ONE (detection, GT id) pair — nearly always —
+// and then adds once for all of them; the maximum score is aggregated per detection as det_stats_kernel does.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+constexpr int kOvlPPT = 16, kOvlPix = 256 * kOvlPPT, kOvlCells = 4096;
+
+struct OvlJob {
+    const uint8_t *inst;        // [h,w] GT instance of every pixel
+    long long *inter;           // [n_det][g]
+    long long *area_gt;         // [g]
+    long long *area_pred;       // [n_det]
+    int g;
+    int in_lds;                 // the image's table fits kOvlCells
+};
+
+__device__ __forceinline__ void ovl_add64(long long *p, unsigned v) {
+    atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v);
+}
+
+// v pixels of cell (r, c): r = detection + 1 (0 = background), c = GT id (0 = none)
+__device__ __forceinline__ void ovl_cell(const DetJob &J, const OvlJob &O, int r, int c, unsigned v) {
+    if (r > 0) atomicAdd(J.area + (r - 1), (int)v);
+    if (c > 0) ovl_add64(O.area_gt + (c - 1), v);
+    if (r > 0 && c > 0) ovl_add64(O.inter + (size_t)(r - 1) * O.g + (c - 1), v);
+}
+
+__global__ __launch_bounds__(256) void det_overlap_kernel(const DetJob *__restrict__ jobs, const OvlJob *__restrict__ ojobs,
+                                                          long long *__restrict__ bad) {
+    __shared__ unsigned tab[kOvlCells];
+    __shared__ unsigned nbad;
+    const DetJob J = jobs[blockIdx.y];
+    const int npx = J.h * J.w;
+    const int base = blockIdx.x * kOvlPix;
+    if (base >= npx) return;
+    const OvlJob O = ojobs[blockIdx.y];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int cols = O.g + 1, cells = O.in_lds ? (J.n_det + 1) * cols : 0;
+    for (int i = tid; i < cells; i += 256) tab[i] = 0;
+    if (tid == 0) nbad = 0;
+    __syncthreads();
+    unsigned my_bad = 0;
+    for (int i = 0; i < kOvlPPT; ++i) {
+        const int p = base + i * 256 + tid;           // a wave's 64 pixels are consecutive
+        const bool in = p < npx;
+        int d = -1, bits = 0, id = 0;
+        if (in) {
+            id = O.inst[p];
+            if (id > O.g) {
+                ++my_bad;
+                id = 0;
+            }
+            const int c = J.cls[p];
+            if (c > 0 && J.n_det > 0) {
+                d = J.newid[J.prov[J.parent[p]]];
+                if ((unsigned)d >= (unsigned)J.n_det) d = -1;          // a count that is not this map's: write nowhere
+                const float sc = J.rw_up[(long)(c - 1) * npx + p];
+                bits = sc > 0.f ? __float_as_int(sc) : 0;
+            }
+        }
+        const bool fg = d >= 0;
+        const unsigned long long act = __ballot(fg);
+        if (act != 0) {
+            const int d0 = __shfl(d, __ffsll((long long)act) - 1);
+            if (__all(!fg || d == d0)) {
+                int mx = bits;
+                for (int sft = 32; sft > 0; sft >>= 1) mx = max(mx, __shfl_xor(mx, sft));
+                if (lane == 0 && mx > 0) atomicMax(J.score_bits + d0, mx);
+            } else if (fg && bits > 0) {
+                atomicMax(J.score_bits + d, bits);
+            }
+        }
+        const bool on = fg || id > 0;                 // cell (0, 0) is nobody's
+        const unsigned long long m = __ballot(on);
+        if (m == 0) continue;                         // (the whole wave)
+        const int first = __ffsll((long long)m) - 1;
+        const int d1 = __shfl(d, first), id1 = __shfl(id, first);
+        const bool one = __all(!on || (d == d1 && id == id1));
+        if (one ? lane == first : on) {
+            const int r = d + 1;
+            const unsigned v = one ? (unsigned)__popcll(m) : 1u;
+            if (O.in_lds) atomicAdd(&tab[r * cols + id], v);
+            else ovl_cell(J, O, r, id, v);
+        }
+    }
+    if (my_bad) atomicAdd(&nbad, my_bad);
+    __syncthreads();
+    for (int i = tid; i < cells; i += 256) {
+        const unsigned v = tab[i];
+        if (v) ovl_cell(J, O, i / cols, i % cols, v);
+    }
+    if (tid == 0 && nbad) ovl_add64(bad, nbad);
+}
+
+__global__ __launch_bounds__(256) void det_overlap_final_kernel(const DetJob *__restrict__ jobs, const OvlJob *__restrict__ ojobs) {
+    const DetJob J = jobs[blockIdx.y];
+    const int d = blockIdx.x * 256 + threadIdx.x;
+    if (d >= J.n_det) return;
+    const int area = J.area[d];
+    J.score[d] = final_score(area, J.min_area, J.score_bits[d]);
+    ojobs[blockIdx.y].area_pred[d] = area;
+}
+
+struct RethresJob {
+    const float *rw_up;         // [n_channels,h,w]
+    const int32_t *argmax;      // [h,w]
+    int32_t *out;               // [h,w]
+    int n_channels, npx;
+};
+
+// The label epilogue's selection (label.hip, label_argmax_kernel) starts from the background plane and keeps the first NaN
+// channel, else the first channel that reaches the maximum m when m > bg: which channel that is does not depend on bg, and
+// the scores it compares are the ones it stores in rw_up.  So the map at a threshold T >= the map's own keeps a pixel's
+// channel where that channel's stored score is NaN or > T, and reads 0 elsewhere.
+__global__ __launch_bounds__(256) void argmax_rethreshold_kernel(const RethresJob *__restrict__ jobs, float thres) {
+    const RethresJob J = jobs[blockIdx.y];
+    const int p = blockIdx.x * 256 + threadIdx.x;
+    if (p >= J.npx) return;
+    int a = J.argmax[p];
+    if (a > 0 && a <= J.n_channels) {
+        const float s = J.rw_up[(long)(a - 1) * J.npx + p];
+        if (!(s != s || s > thres)) a = 0;
+    }
+    J.out[p] = a;
+}
+
+}  // namespace
+
+extern "C" int irn_detect_instance_batch_overlap(int n_images, const float *const *rw_up_dev, const int32_t *const *argmax_dev,
+                                                 const int32_t *n_channels, const int32_t *h, const int32_t *w,
+                                                 const int32_t *n_det, const double *min_area, const uint8_t *const *inst_dev,
+                                                 const int32_t *g, float *score_dev, int32_t *channel_dev,
+                                                 int64_t *area_pred_dev, int64_t *inter_dev, int64_t *area_gt_dev,
+                                                 int64_t *bad_dev, void *scratch_dev, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const char *who = "irn_detect_instance_batch_overlap";
+    long long G = 0;
+    if (!rle_shapes_ok(n_images, h, w, n_det, &G))
+        return fail(IRN_ERR_ARG, "%s: bad argument (n_images >= 0, 1 <= h*w <= 2^30, 0 <= n_det <= h*w, no null pointer)", who);
+    if (n_images == 0) return IRN_OK;
+    if (!min_area || !inst_dev || !g || !bad_dev) return fail(IRN_ERR_ARG, "%s: null argument", who);
+    std::vector<DetJob> jobs;
+    int max_n = 0;
+    int rc = det_fill_jobs(who, n_images, rw_up_dev, argmax_dev, n_channels, h, w, scratch_dev, jobs, &max_n);
+    if (rc) return rc;
+    size_t n_gt = 0, n_inter = 0;
+    for (int i = 0; i < n_images; ++i) {
+        if (!inst_dev[i]) return fail(IRN_ERR_ARG, "%s: image %d: null instance map", who, i);
+        if (g[i] < 0 || g[i] > 255) return fail(IRN_ERR_ARG, "%s: image %d: %d GT instances (0..255)", who, i, g[i]);
+        n_gt += (size_t)g[i];
+        n_inter += (size_t)n_det[i] * (size_t)g[i];
+    }
+    if ((G > 0 && (!score_dev || !channel_dev || !area_pred_dev)) || (n_gt > 0 && !area_gt_dev) || (n_inter > 0 && !inter_dev))
+        return fail(IRN_ERR_ARG, "%s: null output", who);
+    std::vector<OvlJob> ojobs(n_images);
+    size_t at_det = 0, at_gt = 0, at_inter = 0;
+    int max_det = 0;
+    for (int i = 0; i < n_images; ++i) {
+        DetJob &J = jobs[i];
+        OvlJob &O = ojobs[i];
+        J.n_det = n_det[i];
+        J.min_area = min_area[i];
+        J.score = score_dev + at_det;
+        J.channel = channel_dev + at_det;
+        O.inst = inst_dev[i];
+        O.area_pred = (long long *)area_pred_dev + at_det;
+        O.area_gt = (long long *)area_gt_dev + at_gt;
+        O.inter = (long long *)inter_dev + at_inter;
+        O.g = g[i];
+        O.in_lds = ((long long)n_det[i] + 1) * (g[i] + 1) <= kOvlCells;
+        at_det += (size_t)n_det[i];
+        at_gt += (size_t)g[i];
+        at_inter += (size_t)n_det[i] * (size_t)g[i];
+        max_det = std::max(max_det, J.n_det);
+    }
+    // both job tables in ONE upload (a scratch slot is released once)
+    const size_t det_bytes = round_up(sizeof(DetJob) * n_images, 16);
+    std::vector<char> blob(det_bytes + sizeof(OvlJob) * n_images);
+    memcpy(blob.data(), jobs.data(), sizeof(DetJob) * n_images);
+    memcpy(blob.data() + det_bytes, ojobs.data(), sizeof(OvlJob) * n_images);
+    char *bd = nullptr;
+    rc = scratch_upload(blob.data(), blob.size(), (void **)&bd, stream);
+    if (rc) return rc;
+    const DetJob *jd = (const DetJob *)bd;
+    const OvlJob *od = (const OvlJob *)(bd + det_bytes);
+    if (n_gt) IRN_HIP_TRY(hipMemsetAsync(area_gt_dev, 0, sizeof(int64_t) * n_gt, stream));
+    if (n_inter) IRN_HIP_TRY(hipMemsetAsync(inter_dev, 0, sizeof(int64_t) * n_inter, stream));
+    const dim3 per_det(cdiv(max_det, 256), n_images);
+    if (max_det > 0) {
+        hipLaunchKernelGGL(det_order_kernel, per_det, dim3(256), 0, stream, jd);
+        IRN_LAUNCH_CHECK("det_order_kernel");
+    }
+    hipLaunchKernelGGL(det_overlap_kernel, dim3(cdiv(max_n, kOvlPix), n_images), dim3(256), 0, stream, jd, od, (long long *)bad_dev);
+    IRN_LAUNCH_CHECK("det_overlap_kernel");
+    if (max_det > 0) {
+        hipLaunchKernelGGL(det_overlap_final_kernel, per_det, dim3(256), 0, stream, jd, od);
+        IRN_LAUNCH_CHECK("det_overlap_final_kernel");
+    }
+    return scratch_release(stream);
+}
+
+extern "C" int irn_argmax_rethreshold_batch(int n_images, const float *const *rw_up_dev, const int32_t *const *argmax_dev,
+                                            const int32_t *n_channels, const int32_t *h, const int32_t *w, float thres,
+                                            int32_t *const *out_dev, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    const char *who = "irn_argmax_rethreshold_batch";
+    if (n_images < 0 || (n_images > 0 && (!rw_up_dev || !argmax_dev || !n_channels || !h || !w || !out_dev)) || thres != thres)
+        return fail(IRN_ERR_ARG, "%s: bad argument (n_images >= 0, no null pointer, a threshold that is not NaN)", who);
+    if (n_images == 0) return IRN_OK;
+    if (n_images > 65535) return fail(IRN_ERR_ARG, "%s: at most 65535 images per call", who);   // grid.y = image
+    std::vector<RethresJob> jobs(n_images);
+    int max_n = 0;
+    for (int i = 0; i < n_images; ++i) {
+        if (!rw_up_dev[i] || !argmax_dev[i] || !out_dev[i] || n_channels[i] < 1 || h[i] < 1 || w[i] < 1)
+            return fail(IRN_ERR_ARG, "%s: image %d: bad argument", who, i);
+        if ((long)h[i] * w[i] > (1L << 30)) return fail(IRN_ERR_ARG, "%s: image too large", who);
+        jobs[i] = RethresJob{rw_up_dev[i], argmax_dev[i], out_dev[i], n_channels[i], h[i] * w[i]};
+        max_n = std::max(max_n, h[i] * w[i]);
+    }
+    RethresJob *jd = nullptr;
+    int rc = scratch_upload(jobs.data(), sizeof(RethresJob) * n_images, (void **)&jd, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(argmax_rethreshold_kernel, dim3(cdiv(max_n, 256), n_images), dim3(256), 0, stream, jd, thres);
+    IRN_LAUNCH_CHECK("argmax_rethreshold_kernel");
+    return scratch_release(stream);
+}
+
 extern "C" int irn_detect_instance_count(const float *rw_up_dev, const int32_t *argmax_dev, int n_channels, int h,
                                          int w, int *n_det_out, void *scratch_dev, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;

@@ -1060,6 +1060,118 @@ def detect_instance_rle_batch(rw_ups, argmaxes, class_ids, n_channels, max_fragm
     return pending if deferred else pending.result()
 
 
+class PendingOverlaps(_PendingBatch):
+    """`detection_overlap_batch(..., deferred=True)`: the packed counts of a batch may still be crossing to the host on the
+    copy stream; `result()` waits for them and returns the list `detection_overlap_batch` returns (an image without a
+    detection has a record with N = 0, not an error)."""
+
+    def __init__(self, nds, host, done, gs, class_ids):
+        super().__init__(nds, host, done, None, 0.0)
+        self._gs, self._class_ids = gs, class_ids
+
+    def result(self):
+        if self._out is not None:
+            return self._out
+        nds, gs = self._nds, self._gs
+        G, NG, NI = sum(nds), sum(gs), sum(nd * g for nd, g in zip(nds, gs))
+        raw = np.zeros(0, np.uint8)
+        if self._host is not None:
+            self._done.synchronize()                                               # the batch's last host round trip
+            raw = self._host.numpy().copy()          # a few bytes per detection: the page-locked buffer goes back at once
+        # inter int64 [NI] | area_gt int64 [NG] | area_pred int64 [G] | score fp32 [G] | channel int32 [G]
+        i64 = raw[:8 * (NI + NG + G)].view(np.int64)
+        score = raw[8 * (NI + NG + G):8 * (NI + NG + G) + 4 * G].view(np.float32)
+        chan = raw[8 * (NI + NG + G) + 4 * G:8 * (NI + NG + G) + 8 * G].view(np.int32)
+        out, d, a, x = [], 0, 0, 0
+        for i, (nd, g) in enumerate(zip(nds, gs)):
+            out.append({"pred_class": np.asarray(self._class_ids[i])[chan[d:d + nd]], "pred_score": score[d:d + nd],
+                        "inter": i64[x:x + nd * g].reshape(nd, g), "area_pred": i64[NI + NG + d:NI + NG + d + nd],
+                        "area_gt": i64[NI + a:NI + a + g]})
+            d, a, x = d + nd, a + g, x + nd * g
+        self._out = out
+        return out
+
+
+def detection_overlap_batch(rw_ups, argmaxes, class_ids, n_channels, max_fragment_sizes, inst_maps, n_insts, bad=None,
+                            deferred=False):
+    """`detect_instance_batch` + `mask_overlap` for a batch without any mask (irn_detect_instance_batch_count / _overlap):
+    the detections of `detect_instance_batch` (same arguments, same order) are counted against the GT instance maps
+    straight from the labelled map.  inst_maps[i]: uint8 [H,W] GPU tensor (0 = no instance, 1..n_insts[i]); values above
+    n_insts[i] are counted in bad int64 [1] (added into), as `mask_overlap` counts them.  Returns per image
+    {"pred_class" i64 [N], "pred_score" f32 [N], "inter" i64 [N,G], "area_pred" i64 [N], "area_gt" i64 [G]} — the counts
+    `mask_overlap` gives on the masks of `detect_instance_batch`, under the names `misc.evaluation.instance_ap_voc` reads;
+    an image without any detection has a record with N = 0 (and its GT areas).  Two host round trips per call: the
+    detection counts, and one packed transfer of everything else; `deferred=True` leaves that one in flight on the copy
+    stream and returns a `PendingOverlaps`."""
+    n = len(rw_ups)
+    if not (len(argmaxes) == len(class_ids) == len(n_channels) == len(max_fragment_sizes) == len(inst_maps) == len(n_insts) == n):
+        raise ValueError("detection_overlap_batch: every argument is a list with one entry per image (%d score maps)" % n)
+    if n == 0:
+        return PendingOverlaps([], None, None, [], []) if deferred else []
+    dev = rw_ups[0].device
+    gs = [int(g) for g in n_insts]
+    insts = []
+    for i in range(n):
+        _need_cuda(inst_maps[i], "inst_map")
+        m = _u8_map(inst_maps[i], dev, "inst_map")
+        if tuple(m.shape) != tuple(argmaxes[i].shape):
+            raise ValueError("detection_overlap_batch: instance map %d is %s for a map of %s" % (i, tuple(m.shape), tuple(argmaxes[i].shape)))
+        if not 0 <= gs[i] <= 255:
+            raise ValueError("detection_overlap_batch: image %d has %d GT instances (0..255)" % (i, gs[i]))
+        insts.append(m)
+    bad = _accumulator(bad, (1,), dev, "bad")
+    dc = _detect_batch_count(rw_ups, argmaxes, n_channels)                         # host round trip 1
+    nds = dc.nds
+    G, NG, NI = sum(nds), sum(gs), sum(nd * g for nd, g in zip(nds, gs))
+    total = 8 * (NI + NG + G) + 8 * G
+    host = done = None
+    with torch.cuda.device(dev):
+        # inter int64 [NI] | area_gt int64 [NG] | area_pred int64 [G] | score fp32 [G] | channel int32 [G]; the staging
+        # buffer is the cached one when the call waits for its transfer, one of the batch's own when it is left in flight
+        packed = (torch.empty(total + 8, dtype=torch.uint8, device=dev) if deferred
+                  else _cached("det_ovl_out", dev, total + 8, torch.uint8))
+        base = (packed.data_ptr() + 7) // 8 * 8
+        shift = base - packed.data_ptr()
+        at = [base, base + 8 * NI, base + 8 * (NI + NG), base + 8 * (NI + NG + G), base + 8 * (NI + NG + G) + 4 * G]
+        check(lib.irn_detect_instance_batch_overlap(
+            n, dc.sc_p, dc.am_p, dc.cs_a, dc.hs_a, dc.ws_a, i32_array(nds), (C.c_double * n)(*[float(v) for v in max_fragment_sizes]),
+            ptr_array([m.data_ptr() for m in insts]), i32_array(gs), at[3] if G else None, at[4] if G else None,
+            at[2] if G else None, at[0] if NI else None, at[1] if NG else None, bad.data_ptr(), dc.scratch.data_ptr(), _stream()))
+        if total:
+            host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+            done = read_back(packed[shift:shift + total], host, side=deferred)     # host round trip 2
+    pending = PendingOverlaps(nds, host, done, gs, class_ids)
+    return pending if deferred else pending.result()
+
+
+def argmax_rethreshold_batch(rw_ups, argmaxes, thres):
+    """The `argmax` maps `label_epilogue(..., bg_thres=thres, want_argmax=True)` returns, from the `rw_up` / `argmax` of ONE
+    epilogue at a threshold not above `thres` (irn_argmax_rethreshold_batch): a pixel keeps its channel where that
+    channel's score is NaN or > thres and becomes 0 elsewhere.  Lists of GPU tensors in, a list of new int32 [H,W] maps
+    out, bit for bit the epilogue's."""
+    n = len(rw_ups)
+    if len(argmaxes) != n:
+        raise ValueError("argmax_rethreshold_batch: %d score maps, %d argmax maps" % (n, len(argmaxes)))
+    if n == 0:
+        return []
+    scs, ams = [], []
+    for i in range(n):
+        _need_cuda(rw_ups[i], "rw_up")
+        _need_cuda(argmaxes[i], "argmax")
+        sc, am = rw_ups[i].contiguous().float(), argmaxes[i].to(torch.int32).contiguous()
+        if sc.dim() != 3 or am.dim() != 2 or sc.shape[0] < 1 or tuple(sc.shape[1:]) != tuple(am.shape):
+            raise ValueError("argmax_rethreshold_batch: rw_up[%d] is %s for an argmax of %s" % (i, tuple(sc.shape), tuple(am.shape)))
+        scs.append(sc); ams.append(am)
+    dev = scs[0].device
+    outs = [torch.empty_like(am) for am in ams]
+    with torch.cuda.device(dev):
+        check(lib.irn_argmax_rethreshold_batch(
+            n, ptr_array([t.data_ptr() for t in scs]), ptr_array([t.data_ptr() for t in ams]), i32_array([t.shape[0] for t in scs]),
+            i32_array([t.shape[0] for t in ams]), i32_array([t.shape[1] for t in ams]), float(thres),
+            ptr_array([t.data_ptr() for t in outs]), _stream()))
+    return outs
+
+
 _CACHE = {}
 
 

@@ -28,24 +28,25 @@ from . import _common, _eval, _labels
 MAX_PAIRS = 64                        # (beta, exp_times) pairs = walks per batch
 
 
-def grid_axes(args):
+def grid_axes(args, thres="sem_seg_bg_thres", tune_thres="tune_bg_thres", max_thres=ops.EVAL_MAX_THRES, step="tune_sem_seg"):
     """-> (betas, exp_times, thresholds as requested, the same as ascending float32): every axis holds the configured value,
-    sorted and without repeats; thresholds are told apart as float32 (the label epilogue compares in float32)."""
+    sorted and without repeats; thresholds are told apart as float32 (the label epilogue compares in float32).  The keywords
+    name the threshold's two attributes of `args`, its limit and the step the refusals speak for (tune_ins_seg has its own)."""
     betas = sorted({float(args.beta)} | {float(b) for b in (getattr(args, "tune_beta", None) or ())})
     exps = sorted({int(args.exp_times)} | {int(e) for e in (getattr(args, "tune_exp_times", None) or ())})
     req = {}
-    for t in [float(args.sem_seg_bg_thres)] + [float(t) for t in (getattr(args, "tune_bg_thres", None) or ())]:
+    for t in [float(getattr(args, thres))] + [float(t) for t in (getattr(args, tune_thres, None) or ())]:
         req.setdefault(float(np.float32(t)), t)              # the first spelling of a float32 value names it
     th32 = np.unique(np.asarray(list(req), np.float32))
     if np.isnan(th32).any():
-        raise ValueError("tune_sem_seg: a background threshold is NaN")
-    if th32.size > ops.EVAL_MAX_THRES:
-        raise ValueError("tune_sem_seg: %d background thresholds (at most %d)" % (th32.size, ops.EVAL_MAX_THRES))
+        raise ValueError("%s: a background threshold is NaN" % step)
+    if th32.size > max_thres:
+        raise ValueError("%s: %d background thresholds (at most %d)" % (step, th32.size, max_thres))
     if len(betas) * len(exps) > MAX_PAIRS:
-        raise ValueError("tune_sem_seg: %d beta x %d exp_times = %d walks per image (at most %d)"
-                         % (len(betas), len(exps), len(betas) * len(exps), MAX_PAIRS))
+        raise ValueError("%s: %d beta x %d exp_times = %d walks per image (at most %d)"
+                         % (step, len(betas), len(exps), len(betas) * len(exps), MAX_PAIRS))
     if any(e < 0 for e in exps):
-        raise ValueError("tune_sem_seg: exp_times must not be negative")
+        raise ValueError("%s: exp_times must not be negative" % step)
     return betas, exps, [req[float(t)] for t in th32], th32
 
 

@@ -2,7 +2,8 @@
 """CLI boundary — same flags and step order as reference run_sample.py:8-137, for the steps this repository
 implements: the label-generation steps (make_cam, cam_to_ir_label, make_ins_seg, make_sem_seg), the evaluation
 steps that score them (eval_cam, eval_ins_seg, eval_sem_seg), the grid search over the semantic labels' three numbers
-(tune_sem_seg, step/tune_sem_seg.py; not in the reference) and the COCO export of the instance labels (make_cocoann,
+(tune_sem_seg, step/tune_sem_seg.py; not in the reference), the same search over the instance labels' three numbers
+(tune_ins_seg, step/tune_ins_seg.py; not in the reference) and the COCO export of the instance labels (make_cocoann,
 step/make_cocoann.py; not in the reference's run_sample.py, which leaves it to be run by hand).
 
 The training steps of the reference have commands of their own (train_cam: run_train_cam.py, train_irn: run_train.py);
@@ -63,6 +64,9 @@ def build_parser():
                    help="tune_sem_seg: more values of --exp_times on the grid; beta x exp_times gives at most 64 walks per image")
     p.add_argument("--tune_bg_thres", default=[], type=float, nargs="*",
                    help="tune_sem_seg: more values of --sem_seg_bg_thres, all counted in one pass per walk (at most 256)")
+    p.add_argument("--tune_ins_bg_thres", default=[], type=float, nargs="*",
+                   help="tune_ins_seg: more values of --ins_seg_bg_thres on its grid (with --tune_beta / --tune_exp_times; at most "
+                        "64: each one is a labelling pass per walk)")
     p.add_argument("--worker_devices", default="", type=str,
                    help="device ordinal of every worker process, e.g. 0,1,2,3 (default: one per visible GPU like the reference; "
                         "0,0 = two workers sharing GPU 0)")
@@ -112,7 +116,7 @@ def build_parser():
     for name, default in (("train_cam_pass", False), ("make_cam_pass", True), ("eval_cam_pass", False),
                           ("cam_to_ir_label_pass", False), ("train_irn_pass", False), ("make_ins_seg_pass", True),
                           ("eval_ins_seg_pass", False), ("make_cocoann_pass", False), ("make_sem_seg_pass", True),
-                          ("eval_sem_seg_pass", False), ("tune_sem_seg_pass", False)):
+                          ("eval_sem_seg_pass", False), ("tune_sem_seg_pass", False), ("tune_ins_seg_pass", False)):
         p.add_argument("--" + name, default=default, type=_flag)
     return p
 
@@ -175,6 +179,10 @@ def main(argv=None):
         from irn_amd.step import tune_sem_seg
         timer = pyutils.Timer("step.tune_sem_seg:")  # noqa: F841
         results["tune_sem_seg"] = tune_sem_seg.run(args)
+    if args.tune_ins_seg_pass is True:
+        from irn_amd.step import tune_ins_seg
+        timer = pyutils.Timer("step.tune_ins_seg:")  # noqa: F841
+        results["tune_ins_seg"] = tune_ins_seg.run(args)
     from irn_amd.step import _common
     _common.shutdown_workers()           # the per-GPU workers served every pass above
     return results                       # what the evaluation passes printed, by step name

@@ -1,0 +1,157 @@
+"""Host logic of step/tune_ins_seg.py, no GPU: the grid (the configured point is always on it, thresholds told apart as
+float32, the refusals name the step), the printed lines, `best` and the returned dict on hand-made records against
+`instance_ap_voc` called directly, the numpy restatement the GPU tests compare with, and the command line
+(`--tune_ins_seg_pass` parses; without it nothing of the step is imported or run; without a GPU the step refuses loudly)."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _detmap_overlap_ref as R  # noqa: E402
+
+
+def _args(**kw):
+    base = dict(beta=10.0, exp_times=8, ins_seg_bg_thres=0.25, sem_seg_bg_thres=0.7, tune_beta=[], tune_exp_times=[],
+                tune_bg_thres=[0.9], tune_ins_bg_thres=[])
+    base.update(kw)
+    return argparse.Namespace(**base)
+
+
+def test_grid_always_holds_the_configured_point_and_dedupes_as_float32():
+    from irn_amd.step import tune_ins_seg as T
+    assert T.grid_axes(_args())[:3] == ([10.0], [8], [0.25])                  # the semantic step's thresholds are not read
+    betas, exps, req, th32 = T.grid_axes(_args(tune_beta=[6, 14, 10], tune_exp_times=[5, 8, 5],
+                                               tune_ins_bg_thres=[0.4, 0.1, 0.25, 0.1 + 1e-10, 0.4]))
+    assert betas == [6.0, 10.0, 14.0] and exps == [5, 8]
+    assert req == [0.1, 0.25, 0.4] and th32.dtype == np.float32 and np.array_equal(th32, np.float32([0.1, 0.25, 0.4]))
+    _, _, req, th32 = T.grid_axes(_args(ins_seg_bg_thres=0.3, tune_ins_bg_thres=[0.3 + 1e-12, 0.2]))
+    assert req == [0.2, 0.3] and len(th32) == 2
+    assert T.grid_axes(argparse.Namespace(beta=10, exp_times=8, ins_seg_bg_thres=0.25))[:3] == ([10.0], [8], [0.25])
+
+
+def test_grid_refusals_name_the_step():
+    from irn_amd.step import tune_ins_seg as T
+    assert T.MAX_THRES == 64
+    T.grid_axes(_args(tune_ins_bg_thres=list(np.linspace(0.3, 0.9, 63))))                # 64 with the configured one
+    with pytest.raises(ValueError, match="tune_ins_seg: 65 background thresholds"):
+        T.grid_axes(_args(tune_ins_bg_thres=list(np.linspace(0.3, 0.9, 64))))
+    with pytest.raises(ValueError, match="tune_ins_seg: .*72 walks"):                    # beta 10 is on the grid too: 9 x 8
+        T.grid_axes(_args(tune_beta=list(range(1, 9)), tune_exp_times=list(range(1, 9))))
+    assert len(T.grid_axes(_args(beta=8, tune_beta=list(range(1, 9)), tune_exp_times=list(range(1, 9))))[0]) == 8   # 64: allowed
+    with pytest.raises(ValueError, match="tune_ins_seg: .*NaN"):
+        T.grid_axes(_args(tune_ins_bg_thres=[float("nan")]))
+    with pytest.raises(ValueError, match="tune_ins_seg: .*negative"):
+        T.grid_axes(_args(tune_exp_times=[-1]))
+
+
+def _records(shift):
+    """Two images, classes 2 and 5; `shift` moves the overlap of the first detection across the 0.5 IoU line."""
+    a = {"pred_class": np.array([2, 2, 5]), "pred_score": np.float32([0.9, 0.4, 0.7]), "gt_class": np.array([2, 5]),
+         "inter": np.array([[30 + shift, 0], [5, 0], [0, 40]]), "area_pred": np.array([60, 20, 50]), "area_gt": np.array([50, 45])}
+    b = {"pred_class": np.zeros(0, np.int64), "pred_score": np.zeros(0, np.float32), "gt_class": np.array([2]),
+         "inter": np.zeros((0, 1), np.int64), "area_pred": np.zeros(0, np.int64), "area_gt": np.array([33])}   # no detection
+    return [a, b]
+
+
+def test_report_prints_the_eval_line_then_the_grid_then_the_best(capsys):
+    from irn_amd.misc import evaluation
+    from irn_amd.step import tune_ins_seg as T
+    from irn_amd.step import tune_sem_seg
+    assert T.pick_best is tune_sem_seg.pick_best
+    axes = T.grid_axes(_args(tune_beta=[6], tune_ins_bg_thres=[0.4]))          # pairs (6, 8), (10, 8); thresholds 0.25, 0.4
+    points = [(6.0, 8, 0.25), (6.0, 8, 0.4), (10.0, 8, 0.25), (10.0, 8, 0.4)]
+    records = {p: _records(s) for p, s in zip(points, (0, 20, 20, 0))}         # the two better points tie
+    out = T.report(records, axes, (10.0, 8, 0.25))
+    lines = capsys.readouterr().out.strip().split("\n")
+    want = {p: evaluation.instance_ap_voc(records[p], iou_thresh=0.5) for p in points}
+    assert want[points[1]]["map"] > want[points[0]]["map"] and want[points[1]]["map"] == want[points[2]]["map"]
+    assert lines[0].startswith("0.5iou: {'ap': array(") and "'map'" in " ".join(lines)
+    tail = [l for l in lines if l.startswith(("beta ", "best "))]
+    assert tail == ["beta %g exp_times %d thres %g map %.6f" % (p + (want[p]["map"],)) for p in points] + \
+        ["best beta 6 exp_times 8 thres 0.4 map %.6f" % want[points[1]]["map"]]      # the tie goes to the smaller beta
+    assert out["best"] == (6.0, 8, 0.4) and set(out) == {"ap", "map", "grid", "aps", "best"}
+    assert out["grid"] == {p: want[p]["map"] for p in points} and list(out["grid"]) == points
+    assert np.array_equal(out["ap"], want[points[2]]["ap"], equal_nan=True) and out["map"] == want[points[2]]["map"]
+    for p in points:
+        assert np.array_equal(out["aps"][p], want[p]["ap"], equal_nan=True)
+
+
+def test_a_nan_map_never_wins(capsys):
+    from irn_amd.step import tune_ins_seg as T
+    assert T.pick_best({(10.0, 8, 0.25): float("nan"), (6.0, 9, 0.9): 0.0}) == (6.0, 9, 0.9)
+
+
+def test_numpy_restatement_on_a_hand_made_map():
+    am = np.array([[1, 1, 0, 2],
+                   [0, 1, 0, 2],
+                   [1, 0, 2, 2],
+                   [1, 0, 0, 1]], np.int32)
+    rw = np.stack([np.arange(16, dtype=np.float32).reshape(4, 4) / 16, np.full((4, 4), 0.5, np.float32)])
+    inst = np.array([[1, 1, 1, 2],
+                     [1, 1, 0, 2],
+                     [0, 0, 2, 7],
+                     [3, 0, 0, 3]], np.uint8)
+    lab, n = R.label4(am == 1)
+    assert n == 3 and lab[0, 0] == 1 and lab[2, 0] == 2 and lab[3, 3] == 3       # raster order of the first pixel
+    rec, bad = R.overlap(rw, am, 2, 2.0, inst, 3)
+    assert bad == 1
+    assert rec["channel"].tolist() == [0, 0, 0, 1] and rec["area_pred"].tolist() == [3, 2, 1, 4]
+    assert rec["pred_score"].tolist() == [5 / 16, 12 / 16, 0.0, 0.5]              # area 1 < min_area 2: score 0, place kept
+    assert rec["inter"].tolist() == [[3, 0, 0], [0, 0, 1], [0, 0, 1], [0, 3, 0]]  # the pixel under id 7 meets nobody
+    assert rec["area_gt"].tolist() == [5, 3, 2]
+
+
+def _main(tmp_path, extra):
+    import run_sample
+    from irn_amd.misc import pyutils
+    stdout = sys.stdout
+    try:
+        return run_sample.main(["--voc12_root", str(tmp_path), "--log_name", str(tmp_path / "log"), "--cam_out_dir", str(tmp_path / "cam"),
+                                "--sem_seg_out_dir", str(tmp_path / "sem"), "--ins_seg_out_dir", str(tmp_path / "ins"),
+                                "--make_cam_pass", "False", "--make_ins_seg_pass", "False", "--make_sem_seg_pass", "False"] + extra)
+    finally:
+        if isinstance(sys.stdout, pyutils.Logger):
+            sys.stdout.close()
+        sys.stdout = stdout
+
+
+def test_command_line(tmp_path, monkeypatch):
+    import run_sample
+    p = run_sample.build_parser()
+    a = p.parse_args(["--voc12_root", "x"])
+    assert a.tune_ins_seg_pass is False and a.tune_ins_bg_thres == [] and a.tune_beta == [] and a.tune_exp_times == []
+    assert run_sample.OUT_OF_SCOPE == ("train_cam_pass", "train_irn_pass")
+    a = p.parse_args(["--voc12_root", "x", "--tune_ins_seg_pass", "True", "--tune_beta", "6", "14", "--tune_exp_times", "5",
+                      "--tune_ins_bg_thres", "0.1", "0.4"])
+    assert a.tune_ins_seg_pass is True and a.tune_beta == [6.0, 14.0] and a.tune_exp_times == [5] and a.tune_ins_bg_thres == [0.1, 0.4]
+    assert (a.beta, a.exp_times, a.ins_seg_bg_thres, a.tune_bg_thres, a.tune_sem_seg_pass) == (10, 8, 0.25, [], False)
+    p.format_help()
+    # without the flag: the step is neither imported nor run
+    import irn_amd.step
+    monkeypatch.delitem(sys.modules, "irn_amd.step.tune_ins_seg", raising=False)
+    monkeypatch.delattr(irn_amd.step, "tune_ins_seg", raising=False)
+    assert _main(tmp_path, []) == {}
+    assert "irn_amd.step.tune_ins_seg" not in sys.modules and not hasattr(irn_amd.step, "tune_ins_seg")
+    # with it: the step runs — and names what it misses (the split file, before any device work)
+    with pytest.raises(FileNotFoundError, match="train.txt"):
+        _main(tmp_path, ["--tune_ins_seg_pass", "True"])
+    assert "irn_amd.step.tune_ins_seg" in sys.modules
+
+
+def test_step_refuses_loudly_without_gpu(tmp_path, monkeypatch):
+    import torch
+    import run_sample
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+    from irn_amd.step import tune_ins_seg as T
+    (tmp_path / "ImageSets" / "Segmentation").mkdir(parents=True)
+    (tmp_path / "ImageSets" / "Segmentation" / "train.txt").write_text("2008_000001\n")
+    args = run_sample.build_parser().parse_args(["--voc12_root", str(tmp_path)])
+    with pytest.raises(RuntimeError, match="need a GPU"):
+        T.run(args)
+    # the grid is refused before that, by name
+    args = run_sample.build_parser().parse_args(["--voc12_root", str(tmp_path), "--tune_ins_bg_thres"] + [str(0.3 + 0.01 * i) for i in range(64)])
+    with pytest.raises(ValueError, match="tune_ins_seg: 65 background thresholds"):
+        T.run(args)

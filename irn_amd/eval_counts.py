@@ -1,0 +1,119 @@
+"""Host side of irn_amd/csrc/eval.hip: the integer counts behind the evaluation steps (step/eval_cam.py,
+step/eval_sem_seg.py, step/eval_ins_seg.py of the reference): irn_cam_confusion, irn_label_confusion, irn_mask_overlap.
+Accumulators are int64 GPU tensors that every call adds into; `bad` (int64 [1]) counts values outside the documented
+ranges and the caller raises when it is non-zero.  `irn_amd.ops` re-exports the functions."""
+import numpy as np
+import torch
+
+from ._host import accumulator, u8_map
+from ._lib import _need_cuda, _stream, check, lib
+
+EVAL_CLASSES = 21                     # background + 20 VOC classes
+EVAL_MAX_THRES = 256                  # IRN_EVAL_MAX_THRES
+
+
+def _i64_zeros(shape, dev):
+    return torch.zeros(shape, dtype=torch.int64, device=dev)
+
+
+def eval_thresholds(thres, dev):
+    """Thresholds as the float32 GPU tensor the confusion kernel reads; ascending, 1..EVAL_MAX_THRES of them (the step
+    pads the background plane with float32(t), as np.pad does on a float32 CAM)."""
+    th = np.asarray(thres, np.float32).reshape(-1)
+    if not 1 <= th.size <= EVAL_MAX_THRES or np.isnan(th).any() or (np.diff(th) < 0).any():
+        raise ValueError("eval thresholds: 1..%d ascending values, got %s" % (EVAL_MAX_THRES, th))
+    return torch.from_numpy(th).to(dev)
+
+
+def _thres_tensor(thres, dev):
+    """-> (flat float32 tensor on dev, its length): a float32 GPU tensor as given, anything else through `eval_thresholds`."""
+    th = thres if isinstance(thres, torch.Tensor) and thres.is_cuda and thres.dtype == torch.float32 else eval_thresholds(thres, dev)
+    th = th.to(dev).reshape(-1).contiguous()
+    return th, int(th.numel())
+
+
+def cam_confusion(high_res, keys, gt, thres, hist=None, bad=None):
+    """step/eval_cam.py:14-19 + the confusion count for one image at every threshold of `thres` in one pass.
+
+    high_res: GPU fp32 [K,H,W] (K >= 0), keys: 0-based classes [K], gt: uint8 [H,W] (255 = void), thres: GPU fp32 [T] from
+    `eval_thresholds` (or anything it takes).  Adds into hist int64 [22,21,T+1] (row 21 = void GT, include/irn_hip.h) and
+    bad int64 [1]; returns (hist, bad).  `cam_confusion_matrices(hist)` turns the histogram into the T matrices."""
+    _need_cuda(high_res, "high_res")
+    dev = high_res.device
+    g = u8_map(gt, dev, "gt")
+    h, w = g.shape
+    cams = high_res.to(torch.float32).contiguous()
+    k = int(cams.shape[0]) if cams.dim() == 3 else -1
+    if k < 0 or (k and tuple(cams.shape[1:]) != (h, w)):
+        raise ValueError("cam_confusion: high_res %s for a GT of %dx%d" % (tuple(cams.shape), h, w))
+    if k > EVAL_CLASSES - 1:
+        raise ValueError("cam_confusion: %d CAM planes (at most %d)" % (k, EVAL_CLASSES - 1))
+    ks = torch.as_tensor(keys).to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+    if ks.numel() != k:
+        raise ValueError("cam_confusion: %d keys for %d CAM planes" % (ks.numel(), k))
+    th, t = _thres_tensor(thres, dev)
+    hist = accumulator(hist, (EVAL_CLASSES + 1, EVAL_CLASSES, t + 1), dev, "hist")
+    bad = accumulator(bad, (1,), dev, "bad")
+    with torch.cuda.device(dev):
+        check(lib.irn_cam_confusion(cams.data_ptr() if k else None, ks.data_ptr() if k else None, k, g.data_ptr(), h, w,
+                                    th.data_ptr(), t, hist.data_ptr(), bad.data_ptr(), _stream()))
+    return hist, bad
+
+
+def cam_confusion_matrices(hist):
+    """hist int64 [22,21,T+1] of `cam_confusion` -> (conf int64 [T,21,21] (row = GT, column = prediction), void int64
+    [T,21] (predictions at GT-255 pixels)), on the GPU."""
+    _need_cuda(hist, "hist")
+    t = int(hist.shape[2]) - 1
+    hist = accumulator(hist, (EVAL_CLASSES + 1, EVAL_CLASSES, t + 1), hist.device, "hist")
+    conf = _i64_zeros((t, EVAL_CLASSES, EVAL_CLASSES), hist.device)
+    void = _i64_zeros((t, EVAL_CLASSES), hist.device)
+    with torch.cuda.device(hist.device):
+        check(lib.irn_cam_confusion_reduce(hist.data_ptr(), t, conf.data_ptr(), void.data_ptr(), _stream()))
+    return conf, void
+
+
+def label_confusion(pred, gt, conf=None, bad=None, pred_255_as=0, void=None):
+    """step/eval_sem_seg.py:14-17 for one image: pred, gt uint8 [H,W] GPU tensors (pred 255 reads as `pred_255_as`; None =
+    out of range).  Adds into conf int64 [21,21], void int64 [21] (predictions at GT-255 pixels) and bad int64 [1];
+    returns (conf, void, bad)."""
+    _need_cuda(pred, "pred")
+    dev = pred.device
+    p = u8_map(pred, dev, "pred")
+    g = u8_map(gt, dev, "gt")
+    if p.shape != g.shape:
+        raise ValueError("label_confusion: prediction %s for a GT of %s" % (tuple(p.shape), tuple(g.shape)))
+    conf = accumulator(conf, (EVAL_CLASSES, EVAL_CLASSES), dev, "conf")
+    void = accumulator(void, (EVAL_CLASSES,), dev, "void")
+    bad = accumulator(bad, (1,), dev, "bad")
+    h, w = g.shape
+    with torch.cuda.device(dev):
+        check(lib.irn_label_confusion(p.data_ptr(), g.data_ptr(), h, w, -1 if pred_255_as is None else int(pred_255_as),
+                                      conf.data_ptr(), void.data_ptr(), bad.data_ptr(), _stream()))
+    return conf, void, bad
+
+
+def mask_overlap(masks, inst_map, n_inst, bad=None):
+    """The counts behind chainercv's mask_iou for one image: masks bool/uint8 [N,H,W] and inst_map uint8 [H,W] (0 = no
+    instance, 1..n_inst) on the GPU.  Returns (inter int64 [N,G], area_pred int64 [N], area_gt int64 [G]) on the GPU, with
+    IoU = inter / (area_pred + area_gt - inter); values of inst_map above n_inst are counted in bad int64 [1]."""
+    _need_cuda(inst_map, "inst_map")
+    dev = inst_map.device
+    inst = u8_map(inst_map, dev, "inst_map")
+    h, w = inst.shape
+    if not (isinstance(masks, torch.Tensor) and masks.dim() == 3 and masks.dtype in (torch.uint8, torch.bool)):
+        raise ValueError("mask_overlap: masks must be a bool / uint8 [N,H,W] tensor")
+    m = masks.to(dev)
+    m = (m.view(torch.uint8) if m.dtype == torch.bool else m).contiguous()
+    n, g = int(m.shape[0]), int(n_inst)
+    if tuple(m.shape[1:]) != (h, w):
+        raise ValueError("mask_overlap: masks %s for an instance map of %dx%d" % (tuple(m.shape), h, w))
+    inter = _i64_zeros((n, g), dev)
+    area_pred = _i64_zeros((n,), dev)
+    area_gt = _i64_zeros((g,), dev)
+    bad = accumulator(bad, (1,), dev, "bad")
+    with torch.cuda.device(dev):
+        check(lib.irn_mask_overlap(m.data_ptr() if n else None, n, inst.data_ptr(), g, h, w,
+                                   inter.data_ptr() if n and g else None, area_pred.data_ptr() if n else None,
+                                   area_gt.data_ptr() if g else None, bad.data_ptr(), _stream()))
+    return inter, area_pred, area_gt

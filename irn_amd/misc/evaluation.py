@@ -1,4 +1,4 @@
-"""Host side of the evaluation steps: chainercv's scores from the integer counts the GPU returns (irn_amd/ops.py
+"""Host side of the evaluation steps: chainercv's scores from the integer counts the GPU returns (irn_amd/eval_counts.py
 cam_confusion / label_confusion / mask_overlap).
 
     observed_classes(conf, void)      the size chainercv's growing confusion matrix reaches

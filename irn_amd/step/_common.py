@@ -640,7 +640,7 @@ def upload(t, staging=None):
     enqueue the next batch under them and the GPU idled 10 % of make_cam (7.5 ms of host time per image inside `.cuda()`,
     `tools/make_cam_profile.py`, round 4).  Here the bytes go through a recycled page-locked buffer and cross on the copy
     stream; the current stream waits for the copy on the DEVICE (an event), the host moves on."""
-    from .. import ops
+    from .. import _host
     dev = torch.device("cuda", torch.cuda.current_device())
     src = t.contiguous()
     nbytes = src.numel() * src.element_size()
@@ -652,7 +652,7 @@ def upload(t, staging=None):
         staging = PINNED.take(nbytes)
         staging[:nbytes].copy_(src.view(-1).view(torch.uint8) if src.dtype != torch.uint8 else src.view(-1))
     # (else: `t` already lives in the page-locked buffer `staging` — a loader thread put it there, make_loader)
-    cs = ops._copy_stream(dev)
+    cs = _host.copy_stream(dev)
     with torch.cuda.stream(cs):
         out = staging[:nbytes].to(dev, non_blocking=True)
         done = torch.cuda.Event()

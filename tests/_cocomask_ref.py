@@ -2,7 +2,7 @@
 rleToString, rleFrString, rleDecode) and of the JSON that irn_amd/step/make_cocoann.py writes, from the published
 algorithm.  Test infrastructure: pycocotools itself is not a dependency, so the tests compare against this restatement
 (tests/test_cocoann_cpu.py compares the restatement with the library wherever the library is installed).  Plain loops,
-one count at a time, as maskApi.c has them; nothing here is shared with irn_amd/ops.py.
+one count at a time, as maskApi.c has them; nothing here is shared with irn_amd/cocomask.py.
 """
 import json
 import os

@@ -1,5 +1,5 @@
 """numpy restatement of "all run-length codes from one id map": what the rle_* kernels of irn_amd/csrc/instance.hip
-compute for the detections of one image.  Test infrastructure; nothing here is shared with irn_amd/ops.py.
+compute for the detections of one image.  Test infrastructure; nothing here is shared with irn_amd/instance.py.
 
 The masks of an image's detections are disjoint, so one int map (`idmap[y, x]` = detection 0..n-1 of the pixel, -1 =
 background) holds all of them.  In pycocotools' column-major order j = x*h + y, a pixel whose id differs from its

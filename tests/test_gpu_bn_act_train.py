@@ -114,7 +114,7 @@ def test_forward_equals_the_inplace_kernel_and_backward_equals_the_restatement(s
     n = shape[0] * int(np.prod(shape[2:]))
     combos = [c for c in itertools.product([False, True], repeat=3) if any(c) and (mode != "plain" or not c[1])]
     for want_x, want_res, want_sums in combos:
-        gx, gr, sums = ops._bn_act_backward(t["grad_out"], out, t["x"], t["res"] if res_bn else None, scale, rs if res_bn else None,
+        gx, gr, sums = ops.bn_act_backward(t["grad_out"], out, t["x"], t["res"] if res_bn else None, scale, rs if res_bn else None,
                                             relu, want_x, want_res, want_sums)
         assert (gx is not None) == want_x and (gr is not None) == want_res and (sums is not None) == want_sums
         if want_x:
@@ -138,7 +138,7 @@ def test_five_calls_give_identical_bits(shape):
     rs, _ = ops.bn_fold(t["r_weight"], t["r_bias"], t["r_mean"], t["r_var"], EPS)
     first = None
     for _ in range(5):
-        got = ops._bn_act_backward(t["grad_out"], out, t["x"], t["res"], scale, rs, True, True, True, True)
+        got = ops.bn_act_backward(t["grad_out"], out, t["x"], t["res"], scale, rs, True, True, True, True)
         got = [v.clone() for v in got]
         if first is None:
             first = got
@@ -168,7 +168,7 @@ def test_autograd_function_honours_needs_input_grad(mode, relu):
             full = grads
             scale, _ = ops.bn_fold(base["weight"], base["bias"], base["mean"], base["var"], EPS)
             rs = ops.bn_fold(base["r_weight"], base["r_bias"], base["r_mean"], base["r_var"], EPS)[0] if res_bn else None
-            gx, gr, sums = ops._bn_act_backward(base["grad_out"], out.detach(), base["x"], base["res"] if res_bn else None, scale, rs,
+            gx, gr, sums = ops.bn_act_backward(base["grad_out"], out.detach(), base["x"], base["res"] if res_bn else None, scale, rs,
                                                 relu, True, mode != "plain", True)
             gw, gb = ops.bn_param_grads(sums[0], sums[1], base["mean"], base["var"], EPS)
             assert torch.equal(grads["x"], gx) and torch.equal(grads["weight"], gw) and torch.equal(grads["bias"], gb)

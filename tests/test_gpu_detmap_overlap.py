@@ -162,7 +162,7 @@ def test_argument_refusals_leave_the_outputs_untouched():
     from irn_amd import _lib, ops
     im = _image(31, 17, 65, 2, 3)
     rws, ams, insts = _gpu([im])
-    dc = ops._detect_batch_count(rws, ams, [2])
+    dc = ops.detect_batch_count(rws, ams, [2])
     nd = dc.nds[0]
     assert nd > 0
     outs = [torch.full((n,), 0x55, dtype=torch.uint8, device=_dev()) for n in (4 * nd, 4 * nd, 8 * nd, 8 * nd * 3, 8 * 3, 8)]

@@ -91,7 +91,7 @@ def kernels_alone(walker, items, reps=20):
     ep = ops.label_epilogue(rws, [it["size"] for it in items], 0.25, want_labels=False, want_argmax=True, want_rw_up=True)
     walker.sync()
     n_ch = [it["cam"].shape[0] * k for it, k in zip(items, ks)]
-    dc = ops._detect_batch_count(ep["rw_up"], ep["argmax"], n_ch)
+    dc = ops.detect_batch_count(ep["rw_up"], ep["argmax"], n_ch)
     n, dev, hs, ws, nds, scratch = dc.n, dc.dev, dc.hs, dc.ws, dc.nds, dc.scratch
     cs_a, hs_a, ws_a, sc_p, am_p = dc.cs_a, dc.hs_a, dc.ws_a, dc.sc_p, dc.am_p
     G, nd_a = sum(nds), i32_array(nds)

@@ -13,6 +13,7 @@ import warnings
 
 import torch
 
+from . import _tuned
 from ._lib import _need_cl, _need_cuda, _need_vec, _stream, check, lib
 
 _TABLE = None          # the shipped rank table of this device, read once per process: {"ranks": {problem: rank}, "ranks16", "ranks3x3"}
@@ -25,11 +26,10 @@ def _rank_table():
     """`irn_amd/data/gemm/<device>-hip<version>.json` (written by tools/conv1x1_tune.py and tools/gemm16_tune.py on a GPU box): for
     the problems listed, which entry of hipBLASLt's heuristic list was fastest.  Problems not listed use entry 0.  The table is
     data, not a timing: every process picks the same kernel for the same problem.  No file, or IRN_GEMM_TABLE=0: empty tables
-    (step/_common.warn_missing_shipped_data reports the former); a file that does not hold such tables is an error."""
+    (_tuned.warn_missing_shipped_data reports the former); a file that does not hold such tables is an error."""
     global _TABLE
     if _TABLE is None:
-        from .step import _common
-        path = os.path.join(_common.gemm_table_root(), _common.miopen_cache_key() + ".json")
+        path = os.path.join(_tuned.gemm_table_root(), _tuned.miopen_cache_key() + ".json")
         table = {"ranks": {}, "ranks16": {}, "ranks3x3": {}}
         if os.environ.get("IRN_GEMM_TABLE", "1") != "0" and os.path.exists(path):
             try:

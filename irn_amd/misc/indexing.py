@@ -20,7 +20,7 @@ import os
 import numpy as np
 import torch
 
-from .. import _lib
+from .. import _lib, _tuned
 from .._lib import check, i32_array, lib, ptr_array
 
 
@@ -289,9 +289,8 @@ def to_transition_matrix(affinity_dense, beta, times):
 # ------------------------------------------------------------------------------------------------
 
 def _poll_delay_file(device):
-    from ..step import _common
     base = os.environ.get("IRN_TUNING_CACHE") or os.path.join(os.path.expanduser("~"), ".cache", "irn_amd", "walk")
-    return os.path.join(base, "%s-dev%d.json" % (_common.miopen_cache_key(), torch.device(device).index or 0))
+    return os.path.join(base, "%s-dev%d.json" % (_tuned.miopen_cache_key(), torch.device(device).index or 0))
 
 
 def _lib_stamp():
@@ -327,6 +326,17 @@ def _save_poll_delay(device, delay):
         os.replace(tmp, path)
     except Exception:
         pass
+
+
+def poll_delay_report(device):
+    """Where the walk on cuda:`device` gets its poll delay from, as the steps' start-up line words it."""
+    device = torch.device("cuda", int(device))
+    saved = _saved_poll_delay(device)
+    if os.environ.get("IRN_POLL_DELAY"):
+        return "IRN_POLL_DELAY=%s" % os.environ["IRN_POLL_DELAY"]
+    if saved:
+        return "poll delay %d from %s" % (saved, _poll_delay_file(device))
+    return "poll delay: start-up probe at the first radius-10 batch"
 
 
 class RandomWalk:

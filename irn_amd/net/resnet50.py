@@ -20,6 +20,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import _tuned
+
 STAGE_BLOCKS = (3, 4, 6, 3)
 STAGE_PLANES = (64, 128, 256, 512)
 
@@ -34,7 +36,7 @@ FUSED_EPILOGUE = os.environ.get("IRN_FUSED_EPILOGUE", "1") != "0"
 # layout is chosen per input shape:
 #   IRN_CHANNELS_LAST = "auto" (default)  channels-last for the network-input shapes [n, H, W] listed in the find database
 #                                         shipped for this device (irn_amd/data/miopen/<key>/nhwc_shapes.json, written by
-#                                         tools/miopen_warmup.py --channels-last 1; step/_common.miopen_setup merges that
+#                                         tools/miopen_warmup.py --channels-last 1; _tuned.miopen_setup merges that
 #                                         database into the process's user database), NCHW for every other shape;
 #                       "1" / "0"          always / never.
 # The stem stays NCHW (a 3-channel input); its pooled output is converted once, and whoever consumes a stage's output in
@@ -42,7 +44,7 @@ FUSED_EPILOGUE = os.environ.get("IRN_FUSED_EPILOGUE", "1") != "0"
 # re-laid-out copy per call (94 MB per forward, < 1 % of it).
 CHANNELS_LAST_MODE = os.environ.get("IRN_CHANNELS_LAST", "auto")
 _TUNED_SHAPES = {}
-# The reproducible mode (step/_common.deterministic_backbones; set by `apply_deterministic_setting` in every process that sets
+# The reproducible mode (_tuned.deterministic_backbones; set by `apply_deterministic_setting` in every process that sets
 # MIOpen up): None = not managed here (a caller's own torch.backends.cudnn.deterministic is respected), True / False = managed.
 DETERMINISTIC = None
 
@@ -51,26 +53,25 @@ def tuned_nhwc_shapes():
     """Network-input shapes (n, H, W) the shipped find database OF THIS PROCESS'S MODE holds tuned NHWC solvers for (empty
     without a GPU or a database for this device / HIP version)."""
     try:
-        from ..step import _common
-        key = _common.miopen_mode_key()
+        key = _tuned.miopen_mode_key()
     except Exception:
         return set()
     if key not in _TUNED_SHAPES:
         shapes = set()
         try:
             import json
-            path = os.path.join(_common.miopen_seed_root(), key, "nhwc_shapes.json")
+            path = os.path.join(_tuned.miopen_seed_root(), key, "nhwc_shapes.json")
             if os.path.exists(path) and os.environ.get("IRN_MIOPEN_SEED", "1") != "0":
                 shapes = {tuple(int(v) for v in s) for s in json.load(open(path))}
             elif torch.cuda.is_available() and CHANNELS_LAST_MODE == "auto":
-                _common.warn_missing_shipped_data()
+                _tuned.warn_missing_shipped_data()
         except Exception:
             shapes = set()
         _TUNED_SHAPES[key] = shapes
     return _TUNED_SHAPES[key]
 
 
-def _tuned(x):
+def _tuned_shape(x):
     return (int(x.shape[0]), int(x.shape[2]), int(x.shape[3])) in tuned_nhwc_shapes()
 
 
@@ -87,9 +88,9 @@ def channels_last_for(x):
     if DETERMINISTIC is None and torch.backends.cudnn.deterministic:
         # a caller's own deterministic flag: MIOpen's attribute leaves no fast NHWC fp32 solver, the NCHW trunk it is
         return False
-    # auto: only in a process whose MIOpen user database has been completed from the shipped one (step/_common.miopen_setup:
+    # auto: only in a process whose MIOpen user database has been completed from the shipped one (_tuned.miopen_setup:
     # the steps' workers, the in-process step path, bench.py) — anywhere else the NHWC problems would be untuned
-    covered = bool(os.environ.get("IRN_MIOPEN_DB_SET")) and _tuned(x)
+    covered = bool(os.environ.get("IRN_MIOPEN_DB_SET")) and _tuned_shape(x)
     cl = CHANNELS_LAST_MODE == "1" or covered
     if DETERMINISTIC:
         torch.backends.cudnn.deterministic = not (cl and covered)

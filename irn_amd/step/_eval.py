@@ -1,13 +1,13 @@
 """Shared plumbing of the evaluation steps (eval_cam, eval_sem_seg, eval_ins_seg).
 
-They run in the calling process on its current device: loader threads (`_common.make_loader`) read and decode the
+They run in the calling process on its current device: loader threads (`_io.make_loader`) read and decode the
 prediction files and the ground truth, the counting kernels add every image into int64 accumulators that stay on the
 device, and the accumulators come back once at the end.  The worker pool is not used: it has no channel to send results
 back, and one process makes the counts independent of `--worker_devices` by construction."""
 import numpy as np
 import torch
 
-from . import _common
+from . import _io
 
 
 class EvalDataset(torch.utils.data.Dataset):
@@ -37,7 +37,7 @@ def device():
 
 def items(ids, load, args):
     """(id, item) in split order, decoded by loader threads; tensors without the collated batch dimension."""
-    loader = _common.make_loader(EvalDataset(ids, load), int(getattr(args, "num_workers", 0) or 0))
+    loader = _io.make_loader(EvalDataset(ids, load), int(getattr(args, "num_workers", 0) or 0))
     for pack in loader:
         pack.pop("_staging", None)
         yield pack["name"][0], {k: v[0] for k, v in pack.items() if k != "name"}

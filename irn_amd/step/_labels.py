@@ -7,15 +7,40 @@ boundary / displacement maps come from `edges_for`, handed from step to step on 
 import contextlib
 import os
 import types
+import weakref
 
 import numpy as np
 import torch
 from PIL import Image
 
 from ..voc12 import dataloader as voc12_dataloader
-from . import _common
+from .. import _tuned
+from . import _io, _pool, _report, _stores
 
 RADIUS = 5   # hard-coded at both reference call sites (step/make_sem_seg_labels.py:41, step/make_ins_seg_labels.py:135)
+
+
+def walk_radius(args, default):
+    """The reference hard-codes radius 5 at its call sites (step/make_sem_seg_labels.py:41,
+    step/make_ins_seg_labels.py:135); `args.radius` (run_sample.py --radius) overrides it, e.g. 10 for BASELINE
+    configs[2]."""
+    return int(getattr(args, "radius", 0) or default)
+
+
+def make_walker(args, default_radius):
+    """The steps' random walk: radius as `walk_radius`, and the schedule switch — `args.walk_accel` (run_sample.py
+    --walk_accel {0,1}; None = the environment variable IRN_WALK_ACCEL, else the library default 1) chooses between the
+    truncated Chebyshev series of the operator and the reference's own count of 2^exp_times applications
+    (misc/indexing.py:136-137); `args.walk_accel_tol_exp` = e moves the series' truncation bound to 10^-e."""
+    from ..misc import indexing
+    walker = indexing.RandomWalk(walk_radius(args, default_radius))
+    accel = getattr(args, "walk_accel", None)
+    if accel not in (None, ""):
+        walker.set_option("accel", 1 if int(accel) else 0)
+    tol = getattr(args, "walk_accel_tol_exp", None)
+    if tol not in (None, "", 0):
+        walker.set_option("accel_tol_exp", int(tol))
+    return walker
 
 
 def irn_batch(args):
@@ -29,7 +54,7 @@ def walk_batch(args, default):
 def edges_for(model, pend, irn_batch, store=None, model_key=None, dump_dir=None):
     """EdgeDisplacement forward for the pending images, `irn_batch` at a time: ragged images are padded to the
     512^2 crop like the reference pads each one (net/resnet50_irn.py:225), so a chunk is ONE trunk pass.  With a `store`
-    (`_common.EDGE_STORE`) the maps the other label step already computed for an image (same network, same file) are taken
+    (`_stores.EDGE_STORE`) the maps the other label step already computed for an image (same network, same file) are taken
     from device memory instead, and what is computed here is left there for it."""
     todo = pend
     if store is not None:
@@ -49,7 +74,7 @@ def edges_for(model, pend, irn_batch, store=None, model_key=None, dump_dir=None)
             # the loader skipped this image's pixels because the store held its maps then, and they are gone now (evicted
             # between the loader's look and this one): decode it here
             img = torch.from_numpy(np.array(Image.open(p["stamp"][0]).convert("RGB")))
-            p["img"] = _common.device_images({"img": img[None]}, (1.0,))[0]
+            p["img"] = _io.device_images({"img": img[None]}, (1.0,))[0]
     for i in range(0, len(todo), irn_batch):
         chunk = todo[i:i + irn_batch]
         for p, (edge, dp) in zip(chunk, model.forward_batch([p.pop("img") for p in chunk])):
@@ -74,7 +99,7 @@ def skip_image_predicate(model, args, device):
     if store is None:
         return None
     mk, crop, stride = kw["model_key"], getattr(model, "crop_size", None), getattr(model, "stride", None)
-    return lambda name: store.peek((mk, crop, stride, _common.image_stamp(args.voc12_root, name)), device)
+    return lambda name: store.peek((mk, crop, stride, _stores.image_stamp(args.voc12_root, name)), device)
 
 
 _MODEL_KEYS = {}          # id(network) -> (weak reference to it, key of the ModelSpec it was built from); set in build_model
@@ -83,7 +108,6 @@ _MODEL_KEYS = {}          # id(network) -> (weak reference to it, key of the Mod
 def remember_model(model, spec_key):
     """Note which checkpoint (class + path + mtime + size) a worker built `model` from: the identity the EdgeStore keys
     its entries by.  The weak reference guards against a later object reusing the id of a freed network."""
-    import weakref
     for k in [k for k, (ref, _) in _MODEL_KEYS.items() if ref() is None]:
         del _MODEL_KEYS[k]
     _MODEL_KEYS[id(model)] = (weakref.ref(model), spec_key)
@@ -95,22 +119,22 @@ def model_key(model):
 
 
 def edge_store_kw(model, args):
-    """Keyword arguments of `edges_for` that switch the device hand-off of the edge maps on (see _common.EdgeStore)."""
+    """Keyword arguments of `edges_for` that switch the device hand-off of the edge maps on (see _stores.EdgeStore)."""
     dump = {"dump_dir": args.edge_out_dir} if getattr(args, "edge_out_dir", None) else {}
-    if not _common.keep_edges(args):
+    if not _stores.keep_edges(args):
         return dump
     key = model_key(model)
     if key is None:
         # a network handed over as a module (not built from a ModelSpec) has no identity that survives an in-place weight
         # update or a recycled id(): no hand-off for it, every step computes its own maps (ADVICE round 4)
         return dump
-    return {"store": _common.EDGE_STORE, "model_key": key, **dump}
+    return {"store": _stores.EDGE_STORE, "model_key": key, **dump}
 
 
 def build_model(model):
     """A network, or the (class, checkpoint) a worker builds it from -> the network, remembered under its checkpoint's key."""
-    spec_key = model.key() if isinstance(model, _common.ModelSpec) else None
-    model = _common.materialise(model)
+    spec_key = model.key() if isinstance(model, _pool.ModelSpec) else None
+    model = _pool.materialise(model)
     if spec_key is not None:
         remember_model(model, spec_key)
     return model
@@ -118,9 +142,9 @@ def build_model(model):
 
 def item(name, size, dev, args, cam_run):
     """What a step keeps per image; `img` is the caller's to fill in.  The CAM: from the device if make_cam left it there, else its file."""
-    keys, keys_dev, cam = _common.CAM_STORE.get(name, args.cam_out_dir, dev, cam_run, _common.keep_cams(args))
+    keys, keys_dev, cam = _stores.CAM_STORE.get(name, args.cam_out_dir, dev, cam_run, _stores.keep_cams(args))
     return {"name": name, "size": size, "img": None, "dev": dev, "cam": cam, "keys": keys, "keys_dev": keys_dev,
-            "stamp": _common.image_stamp(args.voc12_root, name)}
+            "stamp": _stores.image_stamp(args.voc12_root, name)}
 
 
 @contextlib.contextmanager
@@ -128,40 +152,57 @@ def worker(process_id, model, dataset, args):
     """One shard of a label step on its worker's device.  Walker (its context and device buffers) and writer are closed however
     the block ends; the walk's fall-back count and the step's summary line come only after a block that ended well."""
     model = build_model(model)
-    databin, n_gpus = dataset[process_id], len(dataset)
-    dev = torch.device("cuda", _common.worker_device(process_id, args))
-    _common.set_skip_image(databin, skip_image_predicate(model, args, dev))
-    loader = _common.make_loader(databin, int(args.num_workers) // n_gpus)
-    with contextlib.closing(_common.AsyncWriter(_common.writer_threads(args, n_gpus))) as writer, torch.no_grad(), torch.cuda.device(dev):
+    dev = torch.device("cuda", _pool.worker_device(process_id, args))
+    with _io.shard_io(process_id, dataset, args) as (databin, n_gpus, loader, writer), torch.no_grad(), torch.cuda.device(dev):
+        _io.set_skip_image(databin, skip_image_predicate(model, args, dev))
         model.cuda()
-        with contextlib.closing(_common.make_walker(args, RADIUS)) as walker:
+        with contextlib.closing(make_walker(args, RADIUS)) as walker:
             yield types.SimpleNamespace(model=model, walker=walker, writer=writer, loader=loader, dev=dev, databin=databin,
                                         n_gpus=n_gpus, process_id=process_id)
-            _common.WALK_STATS["fallback_runs"] += walker.fallback_runs
-            _common.step_summary(process_id, walker)
+            _report.WALK_STATS["fallback_runs"] += walker.fallback_runs
+            _report.step_summary(process_id, walker)
+
+
+@contextlib.contextmanager
+def tuning(args, dev):
+    """The frame of a tuner (tune_sem_seg, tune_ins_seg) in the caller's process on `dev`: the label steps' MIOpen settings and
+    reproducible mode (`process_mode`), their network and their walker -> (model, walker).  The walker is closed however the
+    block ends.  A tuner whose loop ended well calls `end_walk(walker)` itself, before its read-backs and checks: those come
+    after the walker is closed and still belong inside the mode."""
+    with _tuned.process_mode(dev.index), torch.no_grad(), torch.cuda.device(dev):
+        model = build_model(_pool.ModelSpec(args.irn_network, "EdgeDisplacement", args.irn_weights_name, strict=False))
+        model.cuda()
+        with contextlib.closing(make_walker(args, RADIUS)) as walker:
+            yield model, walker
+
+
+def end_walk(walker):
+    """After a tuner's loop that ended well: the walk's fall-back count goes to WALK_STATS, the walker is closed."""
+    _report.WALK_STATS["fallback_runs"] += walker.fallback_runs
+    walker.close()
 
 
 def items(w, args):
     """The shard's images in order, each as `item` with its pixels on the device (`img` None where the skip predicate emptied them)."""
-    cam_run = _common.current_cam_run(args.cam_out_dir)
+    cam_run = _stores.current_cam_run(args.cam_out_dir)
     for it, pack in enumerate(w.loader):
         name = pack["name"][0]
         name = name if isinstance(name, str) else voc12_dataloader.decode_int_filename(name)
         p = item(name, (int(pack["size"][0]), int(pack["size"][1])), w.dev, args, cam_run)
-        imgs = _common.device_images(pack, (1.0,))
+        imgs = _io.device_images(pack, (1.0,))
         p["img"] = None if imgs is None else imgs[0]
         yield p
-        _common.progress(w.process_id, w.n_gpus, it, len(w.databin))
+        _io.progress(w.process_id, w.n_gpus, it, len(w.databin))
 
 
 def run_step(work, out_dir, args, opening="["):
     """`run(args)` of a label step: `work` on every shard of `args.infer_list`, inside the reference's bracket (`opening`)."""
-    model = _common.ModelSpec(args.irn_network, "EdgeDisplacement", args.irn_weights_name, strict=False)   # built by the worker(s)
-    n_gpus = _common.n_gpus_or_raise(args)
+    model = _pool.ModelSpec(args.irn_network, "EdgeDisplacement", args.irn_weights_name, strict=False)   # built by the worker(s)
+    n_gpus = _pool.n_gpus_or_raise(args)
     dataset = voc12_dataloader.VOC12ClassificationDatasetMSF(args.infer_list, voc12_root=args.voc12_root,
-                                                             scales=(1.0,), raw=_common.device_preprocess(args))
-    dataset = _common.label_step_shards(dataset, n_gpus, args)     # strided (misc/torchutils.py:66-68) or CAM-owner aware
+                                                             scales=(1.0,), raw=_io.device_preprocess(args))
+    dataset = _stores.label_step_shards(dataset, n_gpus, args)     # strided (misc/torchutils.py:66-68) or CAM-owner aware
     os.makedirs(out_dir, exist_ok=True)
     print(opening, end="")
-    _common.spawn_workers(work, model, dataset, args)
+    _pool.spawn_workers(work, model, dataset, args)
     print("]")

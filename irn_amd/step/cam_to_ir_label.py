@@ -18,7 +18,7 @@ from PIL import Image
 
 from .. import ops
 from ..voc12 import dataloader as voc12_dataloader
-from . import _common
+from . import _io, _pool
 
 
 def _save_png(path, label):
@@ -50,50 +50,44 @@ class IrLabelDataset(torch.utils.data.Dataset):
 
 def _work(process_id, model, dataset, args):
     del model                                   # no network: the CRF is the whole step
-    databin = dataset[process_id]
-    n_workers = len(dataset)
-    loader = _common.make_loader(databin, int(args.num_workers) // n_workers)
-    writer = _common.AsyncWriter(threads=_common.writer_threads(args, n_workers))
     fg_thres, bg_thres = float(args.conf_fg_thres), float(args.conf_bg_thres)
-    try:
-        dev_id = _common.worker_device(process_id, args)
+    with _io.shard_io(process_id, dataset, args) as (databin, n_workers, loader, writer):
+        dev_id = _pool.worker_device(process_id, args)
         with torch.cuda.device(dev_id):
             pending = None
             for it, pack in enumerate(loader):
                 name = pack["name"][0]
                 # uploads through page-locked buffers: the host never waits for the previous image's CRF here
-                img = _common.upload(pack["img"][0], pack.pop("_staging", None))
-                high_res = _common.upload(pack["high_res"][0])
-                keys = _common.upload(pack["keys"][0])
+                img = _io.upload(pack["img"][0], pack.pop("_staging", None))
+                high_res = _io.upload(pack["high_res"][0])
+                keys = _io.upload(pack["keys"][0])
                 conf = ops.crf_ir_label(img, high_res, keys, fg_thres, bg_thres)
-                host = _common.PINNED.take(conf.numel())
+                host = _io.PINNED.take(conf.numel())
                 host[:conf.numel()].copy_(conf.view(-1), non_blocking=True)
                 done = torch.cuda.Event()
                 done.record()
                 if pending is not None:          # the previous image's map is home while this one runs
                     _finish(pending, args, writer)
                 pending = (name, tuple(conf.shape), host, done)
-                _common.progress(process_id, n_workers, it, len(databin))
+                _io.progress(process_id, n_workers, it, len(databin))
             if pending is not None:
                 _finish(pending, args, writer)
-    finally:
-        writer.close()
 
 
 def _finish(pending, args, writer):
     name, (h, w), host, done = pending
     done.synchronize()
     conf = host[:h * w].numpy().reshape(h, w).copy()
-    _common.PINNED.give(host)
+    _io.PINNED.give(host)
     writer.submit(_save_png, os.path.join(args.ir_label_out_dir, name + ".png"), conf)
 
 
 def run(args):
-    n_gpus = _common.n_gpus_or_raise(args)
+    n_gpus = _pool.n_gpus_or_raise(args)
     dataset = IrLabelDataset(args.train_list, args.voc12_root, args.cam_out_dir)
     from ..misc import torchutils
     dataset = torchutils.split_dataset(dataset, n_gpus)
     os.makedirs(args.ir_label_out_dir, exist_ok=True)
     print("[", end="")
-    _common.spawn_workers(_work, None, dataset, args)
+    _pool.spawn_workers(_work, None, dataset, args)
     print("]")

@@ -9,7 +9,7 @@ The per-scale inputs are built on the GPU from the decoded uint8 image (irn_msf_
 normalise, flip pair; args.device_preprocess=False keeps the reference's PIL loop in the loader workers).
 The ResNet-50 forward passes run on PyTorch-ROCm (MIOpen), `cam_batch` images of one size per pass (default 8;
 the reference: one image + its flip); the merge (step/make_cam.py:38-52) is one HIP kernel pair (irn_cam_merge).
-Every image's {keys, cam} also stays on the device (`_common.CAM_STORE`) for label steps that run later in the same
+Every image's {keys, cam} also stays on the device (`_stores.CAM_STORE`) for label steps that run later in the same
 process.  One process per GPU over strided shards, no communication.
 """
 import os
@@ -20,7 +20,7 @@ import torch
 
 from ..misc import torchutils
 from ..voc12 import dataloader as voc12_dataloader
-from . import _common
+from . import _io, _pool, _report, _stores
 
 
 def merge_scales(outputs, size, label):
@@ -38,7 +38,7 @@ def _save_cam(path, keys_cpu, event, staging, cam_view, hi_view):
     try:
         np.save(path, {"keys": keys_cpu, "cam": cam_view.clone(), "high_res": hi_view.numpy()})
     finally:
-        _common.PINNED.give(staging)
+        _io.PINNED.give(staging)
 
 
 def _flush_group(model, group, scales, args, writer, store):
@@ -54,16 +54,16 @@ def _flush_group(model, group, scales, args, writer, store):
         x = torch.cat([g["imgs"][si] for g in group])
         before = (_r50.PASS_STATS["channels_last"], _r50.PASS_STATS["nchw"])
         outs.append(model.forward_batch(x))
-        _common.CAM_STATS["channels_last"] += _r50.PASS_STATS["channels_last"] - before[0]
-        _common.CAM_STATS["nchw"] += _r50.PASS_STATS["nchw"] - before[1]
-    _common.CAM_STATS["full_group_flushes" if len(group) >= int(getattr(args, "cam_batch", 0) or 8) else "partial_group_flushes"] += 1
+        _report.CAM_STATS["channels_last"] += _r50.PASS_STATS["channels_last"] - before[0]
+        _report.CAM_STATS["nchw"] += _r50.PASS_STATS["nchw"] - before[1]
+    _report.CAM_STATS["full_group_flushes" if len(group) >= int(getattr(args, "cam_batch", 0) or 8) else "partial_group_flushes"] += 1
     for i, g in enumerate(group):
         keys_cpu = torch.nonzero(g["label"])[:, 0]
         keys, cam, high_res = merge_scales([o[i] for o in outs], g["size"], g["label"])
         if store is not None:
             store.put(g["name"], keys_cpu, keys, cam, cam_out_dir=args.cam_out_dir, run_id=getattr(args, "cam_run_id", None))
         n_cam, n_hi = cam.numel() * 4, high_res.numel() * 4
-        staging = _common.PINNED.take(n_cam + n_hi)
+        staging = _io.PINNED.take(n_cam + n_hi)
         cam_view = staging[:n_cam].view(torch.float32).view(cam.shape)
         hi_view = staging[n_cam:n_cam + n_hi].view(torch.float32).view(high_res.shape)
         cam_view.copy_(cam, non_blocking=True)
@@ -75,21 +75,17 @@ def _flush_group(model, group, scales, args, writer, store):
 
 
 def _work(process_id, model, dataset, args):
-    model = _common.materialise(model)      # a network, or the (class, checkpoint) a worker builds it from
-    databin = dataset[process_id]
-    n_gpus = len(dataset)
-    loader = _common.make_loader(databin, int(args.num_workers) // n_gpus)
-    writer = _common.AsyncWriter(threads=_common.writer_threads(args, n_gpus))
+    model = _pool.materialise(model)      # a network, or the (class, checkpoint) a worker builds it from
     scales = tuple(float(s) for s in args.cam_scales)
     # images per trunk pass (the reference runs batch 2 = one image + flip, step/make_cam.py:32-33); images of one size
     # are stacked per scale — VOC is mostly 500x375 / 375x500 — and every size group is flushed at the end
     batch = int(getattr(args, "cam_batch", 0) or 8)
-    store = _common.CAM_STORE if _common.keep_cams(args) else None
-    _common.CAM_STORE.drop_dir(args.cam_out_dir)        # this directory's files are about to be rewritten
+    store = _stores.CAM_STORE if _stores.keep_cams(args) else None
+    _stores.CAM_STORE.drop_dir(args.cam_out_dir)        # this directory's files are about to be rewritten
     groups = {}
     pending_bytes, max_pending = 0, int(getattr(args, "cam_pending_bytes", 0) or (4 << 30))
-    try:
-        with torch.no_grad(), torch.cuda.device(_common.worker_device(process_id, args)):
+    with _io.shard_io(process_id, dataset, args) as (databin, n_gpus, loader, writer):
+        with torch.no_grad(), torch.cuda.device(_pool.worker_device(process_id, args)):
             model.cuda()
             for it, pack in enumerate(loader):
                 img_name = pack["name"][0]
@@ -102,10 +98,10 @@ def _work(process_id, model, dataset, args):
                     warnings.warn("%s: no positive class in the image-level label, skipped" % img_name)
                     staging = pack.pop("_staging", None) if isinstance(pack, dict) else None
                     if staging is not None:                  # the loader thread's page-locked copy of an image nobody uploads
-                        _common.PINNED.give(staging)
+                        _io.PINNED.give(staging)
                     continue
                 group = groups.setdefault(size, [])
-                imgs = _common.device_images(pack, scales)
+                imgs = _io.device_images(pack, scales)
                 group.append({"name": img_name, "size": size, "label": label, "imgs": imgs})
                 pending_bytes += sum(t.numel() * t.element_size() for t in imgs)
                 if len(group) == batch:
@@ -117,29 +113,27 @@ def _work(process_id, model, dataset, args):
                     big = max(groups.values(), key=len)
                     pending_bytes -= sum(t.numel() * t.element_size() for g in big for t in g["imgs"])
                     _flush_group(model, big, scales, args, writer, store)
-                _common.progress(process_id, n_gpus, it, len(databin))
+                _io.progress(process_id, n_gpus, it, len(databin))
             for group in groups.values():
                 _flush_group(model, group, scales, args, writer, store)
-    finally:
-        writer.close()
 
 
 def run(args):
-    model = _common.ModelSpec(args.cam_network, "CAM", args.cam_weights_name + ".pth", strict=True)   # built by the worker(s)
-    n_gpus = _common.n_gpus_or_raise(args)
+    model = _pool.ModelSpec(args.cam_network, "CAM", args.cam_weights_name + ".pth", strict=True)   # built by the worker(s)
+    n_gpus = _pool.n_gpus_or_raise(args)
     scales = tuple(float(s) for s in args.cam_scales)
     dataset = voc12_dataloader.VOC12ClassificationDatasetMSF(args.train_list, voc12_root=args.voc12_root,
-                                                             scales=scales, raw=_common.device_preprocess(args))
+                                                             scales=scales, raw=_io.device_preprocess(args))
     names = [voc12_dataloader.decode_int_filename(v) for v in dataset.img_name_list]
     dataset = torchutils.split_dataset(dataset, n_gpus)
     os.makedirs(args.cam_out_dir, exist_ok=True)
-    args.cam_run_id = _common.new_cam_run(args.cam_out_dir)      # device-held CAMs of earlier runs of this directory go stale
+    args.cam_run_id = _stores.new_cam_run(args.cam_out_dir)      # device-held CAMs of earlier runs of this directory go stale
     print("[ ", end="")
-    _common.spawn_workers(_work, model, dataset, args)
+    _pool.spawn_workers(_work, model, dataset, args)
     print("]")
     # which worker made (and, with keep_cams_on_device, still holds) every image's CAM: strided like the shards
     # (misc/torchutils.py:66-68) — the label steps of this run send an image to the worker that has its CAM
     owners = {name: i % n_gpus for i, name in enumerate(names)}
     owners["__n_workers__"] = n_gpus
-    _common.CAM_OWNERS[os.path.abspath(args.cam_out_dir)] = owners
+    _stores.CAM_OWNERS[os.path.abspath(args.cam_out_dir)] = owners
     torch.cuda.empty_cache()

@@ -17,7 +17,7 @@ import torch
 from PIL import Image
 
 from .. import ops
-from . import _common, _labels
+from . import _io, _labels
 
 
 def _save_png(path, label):
@@ -29,7 +29,7 @@ def _start_copy(batch, args):
     memory on the copy stream, behind everything enqueued so far; `_collect` waits for it when the next batch is already queued."""
     flat = batch["flat"] = ops.label_epilogue(batch["rws"], batch["sizes"], float(args.sem_seg_bg_thres), keys=batch["keys"],
                                               packed=True)["labels_flat"]
-    batch["staging"] = _common.PINNED.take(flat.numel())
+    batch["staging"] = _io.PINNED.take(flat.numel())
     batch["done"] = ops.read_back(flat, batch["staging"], side=True)
 
 
@@ -49,7 +49,7 @@ def _collect(walker, batch, args, writer):
     if batch is None:
         return
     if walker.sync():                       # the persistent walk gave up and the batch was re-run on the streaming sweeps
-        _common.PINNED.give(batch.pop("staging"))
+        _io.PINNED.give(batch.pop("staging"))
         _start_copy(batch, args)
     batch["done"].synchronize()
     host = batch["staging"].numpy()
@@ -58,7 +58,7 @@ def _collect(walker, batch, args, writer):
         lab = host[off:off + hh * ww].reshape(hh, ww).copy()      # 256 KB: the staging buffer goes back at once
         off += hh * ww
         writer.submit(_save_png, os.path.join(args.sem_seg_out_dir, name + ".png"), lab)
-    _common.PINNED.give(batch.pop("staging"))
+    _io.PINNED.give(batch.pop("staging"))
 
 
 def _work(process_id, model, dataset, args):
@@ -80,7 +80,7 @@ def _work(process_id, model, dataset, args):
         except BaseException:           # the batch in flight stays uncollected: its buffer goes back once the copy into it has landed
             if running is not None and "staging" in running:
                 running["done"].synchronize()
-                _common.PINNED.give(running.pop("staging"))
+                _io.PINNED.give(running.pop("staging"))
             raise
 
 

@@ -26,6 +26,7 @@ import torch
 import torch.nn.functional as F
 from torch.utils.data import DataLoader
 
+from .. import _tuned
 from ..misc import pyutils, torchutils
 from ..net import weights
 from ..net.resnet50_cam import Net
@@ -104,17 +105,9 @@ def validate(model, loader, crop, device):
 
 def run(args):
     """Returns {'first_loss': float, 'steps': int, 'val_losses': [one per epoch]}."""
-    from ..net import resnet50 as _r50
-    from . import _common
-    # this IS the caller's process: its own torch.backends.cudnn.deterministic and the trunk's mode are put back on return
-    saved = (torch.backends.cudnn.deterministic, _r50.DETERMINISTIC, _r50.TRAIN_FUSED_TAIL)
-    try:
-        # before the model is built or a convolution runs: MIOpen keeps the solver it resolved for a problem
-        _common.apply_deterministic_setting()
-        _r50.TRAIN_FUSED_TAIL = bool(int(getattr(args, "cam_fused_tail", 0) or 0))
+    # the mode only (MIOpen stays as the caller has it), before the model is built or a convolution runs
+    with _tuned.process_mode(fused_tail=int(getattr(args, "cam_fused_tail", 0) or 0)):
         return _run(args)
-    finally:
-        torch.backends.cudnn.deterministic, _r50.DETERMINISTIC, _r50.TRAIN_FUSED_TAIL = saved
 
 
 def _run(args):

@@ -18,7 +18,7 @@ convolution like the label steps, the loss back-propagates through its ordered g
 through `ops.upsample_bilinear`: no float atomic takes part in a gradient.  `--deterministic 0` keeps the faster scatter
 kernels, whose gradients are reproducible to rounding only.  `--irn_trunk inference` (default `autograd`) runs the frozen
 trunk of a step under `no_grad` on the label steps' inference path (`Net.forward_train`): the process then completes its
-MIOpen database from the shipped one (`_common.miopen_setup`), a crop the database is tuned for goes through the
+MIOpen database from the shipped one (`_tuned.miopen_setup`), a crop the database is tuned for goes through the
 channels-last split-GEMM pass in rows of 16, any other crop — in the reproducible mode — through NCHW passes of 2 rows, which
 can be slower than `autograd`.  Initial weights: `--irn_init_weights` (a state dict, loaded
 non-strictly: an ImageNet trunk, or an earlier checkpoint), else the seeded random state of net.weights; nothing is
@@ -29,6 +29,7 @@ import os
 import torch
 from torch.utils.data import DataLoader
 
+from .. import _tuned
 from ..misc import indexing, pyutils, torchutils
 from ..net import weights
 from ..net.resnet50_irn import AffinityDisplacementLoss
@@ -130,20 +131,13 @@ def displacement_mean(model, loader, device):
 
 def run(args):
     """Returns {'first_losses': [4 floats], 'steps': int}: the losses of the first step and the steps taken."""
-    from ..net import resnet50 as _r50
-    from . import _common
-    # this IS the caller's process: its own torch.backends.cudnn.deterministic and the trunk's mode are put back on return
-    saved = (torch.backends.cudnn.deterministic, _r50.DETERMINISTIC)
-    try:
-        # before the model is built or a convolution runs: MIOpen keeps the solver it resolved for a problem
-        _common.apply_deterministic_setting()
+    # the mode only, before the model is built or a convolution runs
+    with _tuned.process_mode():
         if irn_trunk(args) == "inference":
             # the tuned channels-last pass is taken only in a process whose MIOpen database has been completed from the shipped
             # one; the default mode leaves MIOpen as it finds it, so that its solver choices do not move
-            _common.miopen_setup(torch.cuda.current_device())
+            _tuned.miopen_setup(torch.cuda.current_device())
         return _run(args)
-    finally:
-        torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
 
 
 def _run(args):

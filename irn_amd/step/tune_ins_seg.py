@@ -29,7 +29,7 @@ from .. import ops
 from ..misc import evaluation
 from ..voc12 import dataloader as voc12_dataloader
 from ..voc12 import eval_data
-from . import _common, _eval, _labels, make_ins_seg_labels
+from . import _eval, _io, _labels, _report, _stores, make_ins_seg_labels
 from .tune_sem_seg import grid_axes as _grid_axes
 from .tune_sem_seg import pick_best
 
@@ -67,7 +67,7 @@ def _count(model, walker, pend, axes, records, bad, args):
     cmaps, k_dev = make_ins_seg_labels.instance_front(pend)
     ks = [int(k) for k in k_dev.cpu().tolist()]
     edges, cams, sizes = [p["edge"] for p in pend], [p["cam"] for p in pend], [p["size"] for p in pend]
-    insts = [_common.upload(p["inst_map"]) for p in pend]
+    insts = [_io.upload(p["inst_map"]) for p in pend]
     gs = [len(p["gt_class"]) for p in pend]
     n_ch = [p["cam"].shape[0] * k for p, k in zip(pend, ks)]
     class_ids = [np.repeat(np.asarray(torch.as_tensor(p["keys"]).cpu()), k) for p, k in zip(pend, ks)]
@@ -105,37 +105,25 @@ def run(args):
         _eval.check_shape(id, "image", img.shape[:2], inst_map.shape)
         return {"inst_map": inst_map, "inst_class": inst_class, "image": img}
 
-    from ..net import resnet50 as _r50
-    saved = (torch.backends.cudnn.deterministic, _r50.DETERMINISTIC)
     records = {(b, e, t): [] for b in betas for e in exps for t in req}
-    try:
-        _common.miopen_setup(dev.index)             # the MIOpen settings and the reproducible mode of the label steps
-        with torch.no_grad(), torch.cuda.device(dev):
-            model = _labels.build_model(_common.ModelSpec(args.irn_network, "EdgeDisplacement", args.irn_weights_name, strict=False))
-            model.cuda()
-            walker = _common.make_walker(args, _labels.RADIUS)
-            batch = _labels.walk_batch(args, 32)
-            bad = torch.zeros(1, dtype=torch.int64, device=dev)
-            cam_run = _common.current_cam_run(args.cam_out_dir)
-            pend = []
-            try:
-                for id, it in _eval.items(ids, load, args):
-                    p = _labels.item(id, tuple(int(v) for v in it["inst_map"].shape), dev, args, cam_run)
-                    if p["keys"].numel() == 0:
-                        raise ValueError("tune_ins_seg: %s has no class key in %s: an image without a CAM has no instance to score"
-                                         % (id, args.cam_out_dir))
-                    p.update(img=ops.msf_pack(_common.upload(it["image"]), (1.0,))[0], inst_map=it["inst_map"],
-                             gt_class=it["inst_class"].numpy())
-                    pend.append(p)
-                    if len(pend) == batch:
-                        _count(model, walker, pend, axes, records, bad, args)
-                if pend:
-                    _count(model, walker, pend, axes, records, bad, args)
-                _common.WALK_STATS["fallback_runs"] += walker.fallback_runs
-            finally:
-                walker.close()
-            _eval.raise_if_bad(bad, "tune_ins_seg")
-            _common.check_split_overflow("tune_ins_seg")
-    finally:
-        torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
+    with _labels.tuning(args, dev) as (model, walker):
+        batch = _labels.walk_batch(args, 32)
+        bad = torch.zeros(1, dtype=torch.int64, device=dev)
+        cam_run = _stores.current_cam_run(args.cam_out_dir)
+        pend = []
+        for id, it in _eval.items(ids, load, args):
+            p = _labels.item(id, tuple(int(v) for v in it["inst_map"].shape), dev, args, cam_run)
+            if p["keys"].numel() == 0:
+                raise ValueError("tune_ins_seg: %s has no class key in %s: an image without a CAM has no instance to score"
+                                 % (id, args.cam_out_dir))
+            p.update(img=ops.msf_pack(_io.upload(it["image"]), (1.0,))[0], inst_map=it["inst_map"],
+                     gt_class=it["inst_class"].numpy())
+            pend.append(p)
+            if len(pend) == batch:
+                _count(model, walker, pend, axes, records, bad, args)
+        if pend:
+            _count(model, walker, pend, axes, records, bad, args)
+        _labels.end_walk(walker)             # before the read-backs and checks, which still belong inside the mode
+        _eval.raise_if_bad(bad, "tune_ins_seg")
+        _report.check_split_overflow("tune_ins_seg")
     return report(records, axes, configured)

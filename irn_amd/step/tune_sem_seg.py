@@ -23,7 +23,7 @@ from .. import ops
 from ..misc import evaluation
 from ..voc12 import dataloader as voc12_dataloader
 from ..voc12 import eval_data
-from . import _common, _eval, _labels
+from . import _eval, _io, _labels, _report, _stores
 
 MAX_PAIRS = 64                        # (beta, exp_times) pairs = walks per batch
 
@@ -88,7 +88,7 @@ def _count(model, walker, pend, pairs, th, hist, bad, args):
     _labels.edges_for(model, pend, _labels.irn_batch(args), **_labels.edge_store_kw(model, args))
     edges, cams = [p["edge"] for p in pend], [p["cam"] for p in pend]
     sizes, keys = [p["size"] for p in pend], [p["keys_dev"] for p in pend]
-    gts = _common.upload(torch.cat([p["gt"].reshape(-1) for p in pend]))     # the batch's maps back to back: one copy
+    gts = _io.upload(torch.cat([p["gt"].reshape(-1) for p in pend]))     # the batch's maps back to back: one copy
     for p, (beta, exp_times) in enumerate(pairs):
         rws = walker(edges, cams, beta=beta, exp_times=exp_times)
         # before the count, not after: the count adds into an accumulator and cannot be redone once a fallback re-run has
@@ -115,39 +115,27 @@ def run(args):
         _eval.check_shape(id, "image", img.shape[:2], gt.shape)
         return {"gt": gt, "image": img}
 
-    from ..net import resnet50 as _r50
-    saved = (torch.backends.cudnn.deterministic, _r50.DETERMINISTIC)
-    try:
-        _common.miopen_setup(dev.index)             # the MIOpen settings and the reproducible mode of the label steps
-        with torch.no_grad(), torch.cuda.device(dev):
-            model = _labels.build_model(_common.ModelSpec(args.irn_network, "EdgeDisplacement", args.irn_weights_name, strict=False))
-            model.cuda()
-            walker = _common.make_walker(args, _labels.RADIUS)
-            batch = _labels.walk_batch(args, 64)
-            th = torch.from_numpy(th32).to(dev)
-            hist = torch.zeros((len(pairs), ops.EVAL_CLASSES + 1, ops.EVAL_CLASSES, len(th32) + 1), dtype=torch.int64, device=dev)
-            bad = torch.zeros(1, dtype=torch.int64, device=dev)
-            cam_run = _common.current_cam_run(args.cam_out_dir)
-            pend = []
-            try:
-                for id, it in _eval.items(ids, load, args):
-                    p = _labels.item(id, tuple(int(v) for v in it["gt"].shape), dev, args, cam_run)
-                    if p["keys"].numel() == 0:
-                        raise ValueError("tune_sem_seg: %s has no class key in %s: an image without a CAM has no label to score"
-                                         % (id, args.cam_out_dir))
-                    p.update(img=ops.msf_pack(_common.upload(it["image"]), (1.0,))[0], gt=it["gt"])
-                    pend.append(p)
-                    if len(pend) == batch:
-                        bad = _count(model, walker, pend, pairs, th, hist, bad, args)
-                if pend:
-                    bad = _count(model, walker, pend, pairs, th, hist, bad, args)
-                _common.WALK_STATS["fallback_runs"] += walker.fallback_runs
-            finally:
-                walker.close()
-            _eval.raise_if_bad(bad, "tune_sem_seg")
-            conf, void = zip(*(ops.cam_confusion_matrices(hist[p]) for p in range(len(pairs))))
-            conf, void = torch.stack(conf).cpu().numpy(), torch.stack(void).cpu().numpy()
-            _common.check_split_overflow("tune_sem_seg")
-    finally:
-        torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
+    with _labels.tuning(args, dev) as (model, walker):
+        batch = _labels.walk_batch(args, 64)
+        th = torch.from_numpy(th32).to(dev)
+        hist = torch.zeros((len(pairs), ops.EVAL_CLASSES + 1, ops.EVAL_CLASSES, len(th32) + 1), dtype=torch.int64, device=dev)
+        bad = torch.zeros(1, dtype=torch.int64, device=dev)
+        cam_run = _stores.current_cam_run(args.cam_out_dir)
+        pend = []
+        for id, it in _eval.items(ids, load, args):
+            p = _labels.item(id, tuple(int(v) for v in it["gt"].shape), dev, args, cam_run)
+            if p["keys"].numel() == 0:
+                raise ValueError("tune_sem_seg: %s has no class key in %s: an image without a CAM has no label to score"
+                                 % (id, args.cam_out_dir))
+            p.update(img=ops.msf_pack(_io.upload(it["image"]), (1.0,))[0], gt=it["gt"])
+            pend.append(p)
+            if len(pend) == batch:
+                bad = _count(model, walker, pend, pairs, th, hist, bad, args)
+        if pend:
+            bad = _count(model, walker, pend, pairs, th, hist, bad, args)
+        _labels.end_walk(walker)             # before the read-backs and checks, which still belong inside the mode
+        _eval.raise_if_bad(bad, "tune_sem_seg")
+        conf, void = zip(*(ops.cam_confusion_matrices(hist[p]) for p in range(len(pairs))))
+        conf, void = torch.stack(conf).cpu().numpy(), torch.stack(void).cpu().numpy()
+        _report.check_split_overflow("tune_sem_seg")
     return report(conf, void, axes, configured)

@@ -226,7 +226,7 @@ def test_steps_two_worker_processes_on_one_device(tmp_path, monkeypatch, mode):
                      (`edge_out_dir`), every differing pixel proven a < 1e-4 tie of the oracle's score stack.
     No allowance on any pixel count."""
     from irn_amd.net import weights
-    from irn_amd.step import _common, make_cam, make_ins_seg_labels, make_sem_seg_labels
+    from irn_amd.step import _common, _pool, make_cam, make_ins_seg_labels, make_sem_seg_labels
     from oracle import build_oracle, irn_oracle as O
     monkeypatch.setenv("IRN_DETERMINISTIC", "1" if mode == "deterministic" else "0")      # spawned workers inherit it
     root, names, labels = _make_voc(tmp_path, n=6)
@@ -254,7 +254,7 @@ def test_steps_two_worker_processes_on_one_device(tmp_path, monkeypatch, mode):
             stats_sem = _common.pool_stats()
             make_ins_seg_labels.run(args)
             stats = _common.pool_stats()
-            pool = _common._POOL[0]
+            pool = _pool._POOL[0]
             assert pool is not None and pool.alive() and len(pool.devices) == len(stats)
         finally:
             _common.shutdown_workers()
@@ -513,7 +513,7 @@ def test_upload_never_blocks_and_equals_cuda():
     """step/_common.upload: host -> device through a recycled page-locked buffer on the copy stream, ordered into the
     current stream by an event — the same bytes as `.cuda()`, without the host waiting for the stream to drain."""
     import time
-    from irn_amd.step import _common
+    from irn_amd.step import _common, _io
     dev = torch.device("cuda", 0)
     g = torch.Generator().manual_seed(0)
     items = [torch.randint(0, 256, (375, 500, 3), dtype=torch.uint8, generator=g), torch.randn(2, 3, 33, 47, generator=g),
@@ -526,7 +526,7 @@ def test_upload_never_blocks_and_equals_cuda():
                 assert torch.equal(d.cpu(), t)
         torch.cuda.synchronize()
         _common.upload(items[0])
-        assert len(_common._UPLOADS) <= 2                      # landed copies gave their staging buffers back
+        assert len(_io._UPLOADS) <= 2                      # landed copies gave their staging buffers back
         # behind a long-running kernel chain the call returns at once (a pageable .cuda() would wait for the chain)
         a = torch.randn(4096, 4096, device=dev)
         torch.cuda.synchronize()

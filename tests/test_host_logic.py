@@ -99,20 +99,6 @@ def test_cam_merge_matches_reference_golden(golden):
         assert np.abs(hi.numpy() - cm[name + "_high_res"]).max() <= 1e-6
 
 
-def test_async_writer_writes_everything_and_surfaces_errors(tmp_path):
-    from irn_amd.step import _common
-    w = _common.AsyncWriter(threads=2, max_pending=3)
-    for i in range(10):
-        w.submit(np.save, str(tmp_path / ("f%d.npy" % i)), {"i": i})
-    w.close()
-    assert sorted(p.name for p in tmp_path.iterdir()) == sorted("f%d.npy" % i for i in range(10))
-    assert np.load(str(tmp_path / "f7.npy"), allow_pickle=True).item() == {"i": 7}
-    w = _common.AsyncWriter(threads=1, max_pending=1)
-    w.submit(np.save, str(tmp_path / "no_such_dir" / "x.npy"), 1)
-    with pytest.raises(Exception):
-        w.close()
-
-
 def test_bicubic_plan_host_table_equals_oracle():
     """irn_bicubic_plan is host-only (no GPU): the fixed-point tap tables the kernels consume are Pillow's."""
     from irn_amd import ops
@@ -241,109 +227,6 @@ def test_backbones_at_512_match_reference(golden):
         assert np.abs(dp.numpy() - g["irn_dp"]).max() <= 1e-4 * max(1.0, np.abs(g["irn_dp"]).max())
 
 
-def test_thread_loader_collates_like_dataloader(tmp_path):
-    """irn_amd.step._common.make_loader (thread prefetcher) yields exactly what DataLoader(batch_size=1, shuffle=False)
-    yields for the multi-scale dataset, raw and pre-scaled items, with and without worker threads."""
-    from PIL import Image
-    from torch.utils.data import DataLoader
-    from irn_amd.step import _common
-    from irn_amd.voc12 import dataloader as vd
-    (tmp_path / "JPEGImages").mkdir()
-    names, labels = [], {}
-    rng = np.random.RandomState(0)
-    for i in range(5):
-        n = "2008_%06d" % (i + 1)
-        names.append(n)
-        Image.fromarray((rng.rand(40 + i, 50, 3) * 255).astype(np.uint8)).save(tmp_path / "JPEGImages" / (n + ".jpg"))
-        labels[int(n.replace("_", ""))] = np.eye(20, dtype=np.float32)[i]
-    (tmp_path / "train.txt").write_text("\n".join(names) + "\n")
-    np.save(tmp_path / "cls_labels.npy", labels)
-    for raw in (True, False):
-        ds = vd.VOC12ClassificationDatasetMSF(str(tmp_path / "train.txt"), voc12_root=str(tmp_path), scales=(1.0, 0.5), raw=raw)
-        want = list(DataLoader(ds, shuffle=False, num_workers=0))
-        for nw in (0, 3):
-            got = list(_common.make_loader(ds, nw))
-            assert len(got) == len(want)
-            for x, y in zip(want, got):
-                assert x["name"] == y["name"] and torch.equal(x["label"], y["label"])
-                assert [int(v) for v in x["size"]] == [int(v) for v in y["size"]]
-                if raw:
-                    assert torch.equal(x["img"], y["img"])
-                else:
-                    assert all(torch.equal(p, q) for p, q in zip(x["img"], y["img"]))
-
-
-def test_cam_store_hit_and_file_fallback(tmp_path):
-    """step/_common.CamStore: a CAM put by make_cam is handed to the label steps from memory; anything else comes from the
-    `.npy` the reference's make_cam writes (step/make_cam.py:55-56) — same values either way.  Entries belong to ONE
-    output directory AND to one make_cam run: a later put replaces an earlier one, and an entry of a run the directory
-    no longer carries the stamp of (make_cam ran again somewhere else) is never served."""
-    from irn_amd.step import _common
-    store = _common.CamStore(max_bytes=1 << 20)
-    dev = torch.device("cpu")
-    keys = torch.tensor([3, 7])
-    cam = torch.rand(2, 8, 9)
-    np.save(tmp_path / "2008_000001.npy", {"keys": keys, "cam": cam, "high_res": np.zeros((2, 32, 36), np.float32)})
-    run1 = _common.new_cam_run(str(tmp_path))
-    assert _common.current_cam_run(str(tmp_path)) == run1 and _common.current_cam_run(str(tmp_path / "nowhere")) is None
-    store.put("2008_000001", keys, keys.clone(), cam.clone(), cam_out_dir=str(tmp_path), run_id=run1)
-    k_cpu, k_dev, c = store.get("2008_000001", str(tmp_path), dev, run1)
-    assert store.hits == 1 and store.misses == 0 and torch.equal(k_cpu, keys) and torch.equal(c, cam)
-    # keep_cams_on_device off: the store is not consulted
-    store.get("2008_000001", str(tmp_path), dev, run1, use_store=False)
-    assert store.hits == 1 and store.misses == 1
-    # a second run with other weights: same name, new values -> the new ones are served
-    cam2 = torch.rand(2, 8, 9)
-    store.put("2008_000001", keys, keys.clone(), cam2.clone(), cam_out_dir=str(tmp_path), run_id=run1)
-    assert torch.equal(store.get("2008_000001", str(tmp_path), dev, run1)[2], cam2) and len(store) == 1
-    assert store._bytes == cam2.numel() * 4
-    # make_cam ran again for this directory in ANOTHER process (new stamp, new file): this store's entry is stale
-    run2 = _common.new_cam_run(str(tmp_path))
-    assert run2 != run1
-    cam_new = torch.rand(2, 8, 9)
-    np.save(tmp_path / "2008_000001.npy", {"keys": keys, "cam": cam_new, "high_res": np.zeros((2, 32, 36), np.float32)})
-    got = store.get("2008_000001", str(tmp_path), dev, _common.current_cam_run(str(tmp_path)))
-    assert torch.equal(got[2], cam_new) and store.misses == 2
-    # an entry without a stamp (or a directory without one) is never a hit
-    assert torch.equal(store.get("2008_000001", str(tmp_path), dev, None)[2], cam_new) and store.misses == 3
-    # the same name under another output directory is another entry: served from ITS file
-    other = tmp_path / "other"
-    other.mkdir()
-    cam3 = torch.rand(2, 8, 9)
-    np.save(other / "2008_000001.npy", {"keys": keys, "cam": cam3, "high_res": np.zeros((2, 32, 36), np.float32)})
-    assert torch.equal(store.get("2008_000001", str(other), dev, run2)[2], cam3) and store.misses == 4
-    store.drop_dir(str(tmp_path))
-    assert len(store) == 0 and store._bytes == 0
-    k_cpu, k_dev, c = store.get("2008_000001", str(tmp_path), dev, run2)
-    assert store.misses == 5 and torch.equal(k_cpu, keys) and torch.equal(k_dev, keys) and torch.equal(c, cam_new)
-    big = torch.zeros(1, 1024, 1024)                       # 4 MB > the 1 MB cap: not kept, never an error
-    store.put("big", keys[:1], keys[:1], big, cam_out_dir=str(tmp_path), run_id=run2)
-    assert len(store) == 0
-    for i in range(40):                                    # 40 x 36 KB > 1 MB: the oldest entries leave
-        store.put("n%d" % i, keys, keys, torch.zeros(1, 96, 96), cam_out_dir=str(tmp_path), run_id=run2)
-    assert store._bytes <= 1 << 20 and ("%s" % tmp_path, "n39") in store._items and ("%s" % tmp_path, "n0") not in store._items
-
-
-def test_split_by_owner_hits_and_balance():
-    """Label-step shards that follow make_cam's CAM placement: every image whose CAM a worker holds goes to that worker
-    while the shards stay within 25 % of the even share; unknown images fill the lightest shards; every image exactly
-    once (the reference's strided split, misc/torchutils.py:66-68, is the fallback)."""
-    from irn_amd.step import _common
-    rng = np.random.default_rng(0)
-    names = ["img%04d" % i for i in range(1000)]
-    made = {"img%04d" % i: int(i % 8) for i in rng.permutation(1200)[:900]}      # CAMs of 900 images, strided over 8 workers
-    shards = _common.split_by_owner(list(range(1000)), 8, names, made)
-    seen = sorted(int(i) for s in shards for i in s.indices)
-    assert seen == list(range(1000))
-    assert max(len(s) for s in shards) <= int(np.ceil(1000 / 8 * 1.25))
-    hits = sum(1 for k, s in enumerate(shards) for i in s.indices if made.get(names[int(i)]) == k)
-    known = sum(1 for n in names if n in made)
-    assert hits >= 0.97 * known, (hits, known)
-    # a pathological placement (everything on worker 0) is capped, not followed
-    shards = _common.split_by_owner(list(range(100)), 4, names[:100], {n: 0 for n in names[:100]})
-    assert [len(s) for s in shards][0] == 32 and sorted(int(i) for s in shards for i in s.indices) == list(range(100))
-
-
 def test_frozen_batch_norm_folding_and_composed_path():
     """FrozenBatchNorm.folded() is the batch norm as one multiply-add (the constants irn_bn_act consumes), and apply_ on
     the CPU (or with autograd on) is the reference's composed tail: FixedBatchNorm -> += residual -> ReLU
@@ -433,108 +316,6 @@ def test_load_checkpoint_skips_only_what_the_checkpoint_overwrites(tmp_path):
     w = part.state_dict()[dropped]
     assert bool(torch.isfinite(w).all()) and float(w.abs().max()) < 1.0 and float(w.std()) > 1e-4     # a real initialisation
     assert init.kaiming_uniform_ is before
-
-
-def test_model_spec_is_built_once_per_checkpoint_version(tmp_path):
-    """step/_common.ModelSpec: what a step's run(args) hands its (persistent) workers instead of a pickled network — built by
-    the worker on first use, reused by later steps naming the same checkpoint, rebuilt when the file changes."""
-    import os
-    from irn_amd.net import weights
-    from irn_amd.step import _common
-    path = str(tmp_path / "cam.pth")
-    torch.save(weights.random_cam_state(1), path)
-    spec = _common.ModelSpec("net.resnet50_cam", "CAM", path, strict=True)
-    a = _common.materialise(spec)
-    assert _common.materialise(_common.ModelSpec("net.resnet50_cam", "CAM", path, strict=True)) is a     # same key, same object
-    assert _common.materialise(a) is a                                                                   # networks pass through
-    sd = weights.random_cam_state(7)
-    torch.save(sd, path)
-    os.utime(path, ns=(os.stat(path).st_atime_ns, os.stat(path).st_mtime_ns + 10 ** 9))
-    b = _common.materialise(spec)
-    assert b is not a and torch.equal(b.state_dict()["classifier.weight"], sd["classifier.weight"])
-    assert sum(1 for k in _common._MODELS if k[2] == os.path.abspath(path)) == 1                         # the old version was dropped
-
-
-def test_miopen_setup_is_stable_seeded_and_exclusive(tmp_path, monkeypatch):
-    """One MIOpen user database per (device, HIP version, device ordinal), stable across runs, seeded from the package's
-    shipped database when empty, and never shared by two live processes (a second claimant gets a private copy)."""
-    import subprocess
-    import sys
-    from irn_amd.step import _common
-    for k in ("IRN_MIOPEN_DB_SET", "IRN_MIOPEN_BASE", "MIOPEN_USER_DB_PATH", "MIOPEN_FIND_MODE"):
-        monkeypatch.delenv(k, raising=False)
-    monkeypatch.setenv("IRN_MIOPEN_CACHE", str(tmp_path))
-    monkeypatch.setattr(_common, "_MIOPEN_LOCKS", [])
-    monkeypatch.delenv("IRN_DETERMINISTIC", raising=False)
-    d0 = _common.miopen_setup(0)
-    key = _common.miopen_mode_key()
-    assert key == _common.miopen_cache_key() + "-det"             # the reproducible mode is the default and has its own databases
-    import torch
-    from irn_amd.net import resnet50 as r50
-    assert r50.DETERMINISTIC is True and torch.backends.cudnn.deterministic is True
-    assert d0 == os.path.join(str(tmp_path), key, "dev0") and os.environ["MIOPEN_USER_DB_PATH"] == d0
-    assert os.environ["MIOPEN_FIND_MODE"] == "2" and _common.miopen_setup(0) == d0
-    open(os.path.join(d0, "gfx950_256.ufdb.txt"), "w").write("found")
-    # a second live process on the same device: private copy of what the first one has, removed when it exits
-    code = ("import os, sys; sys.path.insert(0, %r); from irn_amd.step import _common; d = _common.miopen_setup(0); "
-            "print(d); print(sorted(os.listdir(d)))" % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    env = {k: v for k, v in os.environ.items() if k not in ("IRN_MIOPEN_DB_SET",)}
-    out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-1500:]
-    d1, files = out.stdout.strip().splitlines()[-2:]
-    assert d1 == os.path.join(str(tmp_path), key, "dev0-pid%s" % d1.rsplit("pid", 1)[1]) and "gfx950_256.ufdb.txt" in files
-    assert not os.path.exists(d1)
-    # another ordinal is another directory; a user-chosen find mode survives
-    monkeypatch.delenv("IRN_MIOPEN_DB_SET")
-    monkeypatch.setenv("MIOPEN_FIND_MODE", "1")
-    assert _common.miopen_setup(3).endswith(os.path.join(key, "dev3")) and os.environ["MIOPEN_FIND_MODE"] == "1"
-    # the fast mode: its own key, PyTorch's flag off
-    monkeypatch.delenv("IRN_MIOPEN_DB_SET")
-    monkeypatch.setenv("IRN_DETERMINISTIC", "0")
-    assert _common.miopen_setup(3).endswith(os.path.join(_common.miopen_cache_key(), "dev3"))
-    assert r50.DETERMINISTIC is False and torch.backends.cudnn.deterministic is False
-    monkeypatch.setattr(r50, "DETERMINISTIC", None)
-
-
-def test_det_database_is_the_tuned_one_minus_the_split_k_implicit_gemms():
-    """irn_amd/data/miopen/<key>-det (tools/miopen_det_filter.py): same problems, same channels-last shape list; the NHWC
-    implicit-GEMM solver is gone from exactly the forward records whose tuned configuration splits K, another fast solver
-    remains in every one of them, nothing else changed."""
-    import glob
-    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "irn_amd", "data", "miopen")
-    fast = sorted(d for d in glob.glob(os.path.join(root, "*")) if os.path.isdir(d) and not d.endswith("-det"))
-    assert fast
-    for src in fast:
-        dst = src + "-det"
-        assert os.path.isdir(dst), "run tools/miopen_det_filter.py"
-        assert open(os.path.join(src, "nhwc_shapes.json")).read() == open(os.path.join(dst, "nhwc_shapes.json")).read()
-        rec = lambda d: dict(l.rstrip("\n").split("=", 1) for l in open(glob.glob(os.path.join(d, "*.ufdb.txt"))[0]) if "=" in l)
-        a, b = rec(src), rec(dst)
-        assert a.keys() == b.keys()
-        gtc = "ConvAsmImplicitGemmGTCDynamicFwdXdlopsNHWC:"
-        changed = [k for k in a if a[k] != b[k]]
-        assert changed and all("NHWC" in k and k.endswith("-F") for k in changed)
-        for k in changed:
-            ents_a, ents_b = a[k].split(";"), b[k].split(";")
-            assert [e for e in ents_a if not e.startswith(gtc)] == ents_b
-            assert any(not e.startswith("ConvDirectNaive") for e in ents_b), k
-
-
-def test_merge_miopen_db_adds_missing_entries_only(tmp_path):
-    """The shipped find database completes a user database: entries the user database lacks are appended, entries it has
-    (what this machine measured) are kept, other files are left alone."""
-    from irn_amd.step import _common
-    src, dst = tmp_path / "src", tmp_path / "dst"
-    src.mkdir()
-    dst.mkdir()
-    (src / "gfx.ufdb.txt").write_text("a-NCHW=solverA:1\nb-NHWC-NHWC-NHWC=solverB:2\n")
-    (src / "gfx.udb.txt").write_text("p=1,2,3")
-    (src / "nhwc_shapes.json").write_text("[[16, 512, 512]]")
-    (dst / "gfx.ufdb.txt").write_text("a-NCHW=mine:0.5\n")
-    assert _common.merge_miopen_db(str(src), str(dst)) == 2
-    assert (dst / "gfx.ufdb.txt").read_text() == "a-NCHW=mine:0.5\nb-NHWC-NHWC-NHWC=solverB:2\n"
-    assert (dst / "gfx.udb.txt").read_text() == "p=1,2,3\n" and not (dst / "nhwc_shapes.json").exists()
-    assert _common.merge_miopen_db(str(src), str(dst)) == 0
 
 
 def test_trunk_layout_is_chosen_per_input_shape(monkeypatch):
@@ -637,93 +418,6 @@ def test_reproducible_mode_runs_the_trunk_in_passes_of_a_fixed_size(monkeypatch)
     assert torch.equal(r50.run_rows(lambda c: c + 1.0, x), x + 1.0)
 
 
-def test_missing_shipped_data_warns_once_and_names_the_remedy(monkeypatch, tmp_path):
-    """the tuned find database and the GEMM rank table exist for one (architecture, CU count, HIP
-    version) key; on any other box the steps ran ~10 % slower without a word.  Now one RuntimeWarning per process and kind
-    names the key looked for, the keys shipped and the tool that writes the data; the per-step summary lists the sizes
-    whose trunk passes fell to NCHW."""
-    import warnings
-    from irn_amd.step import _common
-    from irn_amd.net import resnet50 as r50
-    monkeypatch.setattr(_common, "miopen_cache_key", lambda: "gfx999-cu1-hip0.0")
-    monkeypatch.setattr(_common, "_WARNED", set())
-    monkeypatch.delenv("IRN_DETERMINISTIC", raising=False)
-    with warnings.catch_warnings(record=True) as w:
-        warnings.simplefilter("always")
-        rep = _common.warn_missing_shipped_data()
-        _common.warn_missing_shipped_data()                                    # once per process
-    assert rep["miopen"] is False and rep["gemm"] is False and rep["mode_key"] == "gfx999-cu1-hip0.0-det"
-    msgs = [str(x.message) for x in w if issubclass(x.category, RuntimeWarning)]
-    assert len(msgs) == 2
-    mi = [m for m in msgs if "MIOpen" in m][0]
-    ge = [m for m in msgs if "GEMM rank table" in m][0]
-    assert "gfx999-cu1-hip0.0-det" in mi and "gfx950-cu256-hip7.0.51831-det" in mi and "tools/miopen_warmup.py" in mi and "miopen_det_filter" in mi
-    assert "gfx999-cu1-hip0.0" in ge and "gfx950-cu256-hip7.0.51831" in ge and "tools/conv1x1_tune.py" in ge
-    # the shipped key itself: nothing to say
-    monkeypatch.setattr(_common, "miopen_cache_key", lambda: "gfx950-cu256-hip7.0.51831")
-    monkeypatch.setattr(_common, "_WARNED", set())
-    with warnings.catch_warnings(record=True) as w:
-        warnings.simplefilter("always")
-        rep = _common.warn_missing_shipped_data()
-    assert rep["miopen"] and rep["gemm"] and not [x for x in w if issubclass(x.category, RuntimeWarning)]
-    # miopen_setup is where every worker / rank / in-process step passes: it warns too
-    monkeypatch.setattr(_common, "miopen_cache_key", lambda: "gfx999-cu1-hip0.0")
-    monkeypatch.setattr(_common, "_WARNED", set())
-    monkeypatch.setattr(_common, "_MIOPEN_LOCKS", [])
-    for k in ("IRN_MIOPEN_DB_SET", "IRN_MIOPEN_BASE", "MIOPEN_USER_DB_PATH"):
-        monkeypatch.delenv(k, raising=False)
-    monkeypatch.setenv("IRN_MIOPEN_CACHE", str(tmp_path))
-    saved = (torch.backends.cudnn.deterministic, r50.DETERMINISTIC)
-    try:
-        with pytest.warns(RuntimeWarning, match="no tuned MIOpen find database for 'gfx999-cu1-hip0.0-det'"):
-            _common.miopen_setup(0)
-    finally:
-        torch.backends.cudnn.deterministic, r50.DETERMINISTIC = saved
-    # step summary: NCHW passes by size, then reset
-    monkeypatch.setattr(r50, "PASS_STATS", {"channels_last": 5, "nchw": 3, "pad_rows": 4, "nchw_sizes": {"281x500": 2, "96x112": 1}})
-    line = _common.untuned_report()
-    assert "3 of 8 trunk passes ran NCHW" in line and "281x500 x2" in line and "96x112 x1" in line and "4 zero rows" in line
-    assert _common.untuned_report() == "" and r50.PASS_STATS["nchw"] == 0
-    line = _common.startup_line(3, 8, 0, "/db")
-    assert "worker 3/8" in line and "NOT SHIPPED" in line and "reproducible" in line
-
-
-def test_rank_table_is_read_once_and_a_malformed_one_raises_with_its_path(monkeypatch, tmp_path):
-    """irn_amd/gemm.py: the three rank dicts come from ONE read of `<gemm_table_root>/<key>.json`; no file or IRN_GEMM_TABLE=0 mean
-    empty tables; a file that is there but is not JSON, or holds a key or a rank that is no integer, raises and names the file (a
-    shipped table that silently does nothing costs ~10 % and nobody sees it)."""
-    import json
-    from irn_amd import gemm, ops
-    from irn_amd.step import _common
-    monkeypatch.setattr(_common, "gemm_table_root", lambda: str(tmp_path))
-    monkeypatch.setattr(_common, "miopen_cache_key", lambda: "gfx999-cu1-hip0.0")
-    monkeypatch.delenv("IRN_GEMM_TABLE", raising=False)
-    path = tmp_path / "gfx999-cu1-hip0.0.json"
-    monkeypatch.setattr(gemm, "_TABLE", None)
-    assert gemm.gemm_ranks() == {} and gemm.gemm_ranks16() == {} and gemm.gemm_ranks3x3() == {}          # no file
-    path.write_text(json.dumps({"ranks": {"4096,256,64,1,0,1": 3}, "ranks16": {"4096,768,64,1,0,1": 2}, "ranks3x3": {"1156,128,128": 5}}))
-    assert gemm.gemm_ranks() == {}                                                                       # ... and not looked for again
-    monkeypatch.setattr(gemm, "_TABLE", None)
-    opened = []
-    real_load = json.load
-    monkeypatch.setattr(json, "load", lambda fh: opened.append(fh.name) or real_load(fh))
-    assert ops.gemm_ranks() == {(4096, 256, 64, 1, 0, 1): 3} and ops.gemm_ranks16() == {(4096, 768, 64, 1, 0, 1): 2}
-    assert ops.gemm_ranks3x3() == {(1156, 128, 128): 5} and opened == [str(path)]
-    monkeypatch.setattr(gemm, "_TABLE", None)
-    monkeypatch.setenv("IRN_GEMM_TABLE", "0")
-    assert gemm.gemm_ranks() == {} and gemm.gemm_ranks3x3() == {} and opened == [str(path)]
-    monkeypatch.delenv("IRN_GEMM_TABLE")
-    for text in ("{\"ranks\": {", "[1, 2]", json.dumps({"ranks": {"4096,256,sixty-four,1,0,1": 3}}), json.dumps({"ranks": {"4096,256,64,1,0,1": 3}, "ranks16": {"8,8,8,0,0,0": 1.5}}),
-                 json.dumps({"ranks3x3": {"1156,128,128": "5"}}), json.dumps({"ranks": [3]})):
-        path.write_text(text)
-        for accessor in (gemm.gemm_ranks, gemm.gemm_ranks16, gemm.gemm_ranks3x3):
-            monkeypatch.setattr(gemm, "_TABLE", None)
-            with pytest.raises(ValueError) as e:
-                accessor()
-            assert str(path) in str(e.value) and "malformed" in str(e.value), text
-    monkeypatch.setattr(gemm, "_TABLE", None)           # (the next reader of this process loads the real one)
-
-
 def test_gemm_params_fold_is_the_composed_definition_and_follows_bn2_and_the_switches(monkeypatch):
     """Bottleneck.gemm_params (reference net/resnet50.py:34-54 with FixedBatchNorm folded in): w * (gamma / sqrt(var + eps)) in
     float64, rounded to fp32 once; b3 = shift3 + shift_d for a projection unit; bn2's constants are read where they are used, so
@@ -773,53 +467,6 @@ def test_gemm_params_fold_is_the_composed_definition_and_follows_bn2_and_the_swi
             assert unit.gemm_params() is not None and unit._gemm[0] != before, name
 
 
-def test_edge_store_keys_and_cap(tmp_path):
-    """step/_common.EdgeStore: the boundary / displacement maps one label step leaves for the other are keyed by network,
-    forward geometry and image FILE; another checkpoint, another image under the same name (new mtime / size) or another
-    device is a miss; the oldest entries leave when the cap is reached; edges_for fills and uses it."""
-    from irn_amd.step import _common, _labels
-    root = tmp_path / "voc"
-    (root / "JPEGImages").mkdir(parents=True)
-    (root / "JPEGImages" / "2008_000001.jpg").write_bytes(b"a" * 100)
-    stamp = _common.image_stamp(str(root), "2008_000001")
-    assert stamp[0].endswith("2008_000001.jpg") and stamp[2] == 100
-    (root / "JPEGImages" / "2008_000001.jpg").write_bytes(b"b" * 101)
-    assert _common.image_stamp(str(root), "2008_000001") != stamp and _common.image_stamp(str(root), "missing")[1:] == (-1, -1)
-
-    class _Net:                      # stands in for EdgeDisplacement: counts its forwards
-        crop_size, stride, calls = 512, 4, 0
-
-        def forward_batch(self, items):
-            _Net.calls += 1
-            return [(it[:1, 0, ::4, ::4] + 1.0, it[:, 0, ::4, ::4] * 2.0) for it in items]
-
-    store = _common.EdgeStore(max_bytes=1 << 20)
-    net = _Net()
-    mk = lambda names: [{"name": n, "img": torch.full((2, 3, 16, 20), float(i)), "stamp": ("/p/" + n, 1, 2)} for i, n in enumerate(names)]
-    a = mk(["x", "y", "z"])
-    _labels.edges_for(net, a, 2, store=store, model_key=("ckpt", 1))
-    assert _Net.calls == 2 and store.misses == 3 and store.hits == 0 and len(store) == 3 and "img" not in a[0]
-    b = mk(["x", "y", "z", "w"])
-    _labels.edges_for(net, b, 2, store=store, model_key=("ckpt", 1))
-    assert _Net.calls == 3 and store.hits == 3                                    # only "w" went through the network
-    for p, q in zip(a, b):
-        assert torch.equal(p["edge"], q["edge"]) and torch.equal(p["dp"], q["dp"])
-    c = mk(["x"])
-    _labels.edges_for(net, c, 2, store=store, model_key=("ckpt", 2))   # another checkpoint: computed again
-    assert _Net.calls == 4
-    d = mk(["x"])
-    d[0]["stamp"] = ("/p/x", 9, 2)                                                # the file changed
-    _labels.edges_for(net, d, 2, store=store, model_key=("ckpt", 1))
-    assert _Net.calls == 5
-    e = mk(["x"])
-    _labels.edges_for(net, e, 2)                                       # no store: always computed, nothing stored
-    assert _Net.calls == 6 and "stamp" in e[0]
-    small = _common.EdgeStore(max_bytes=3 * 4 * 60)
-    for i in range(5):
-        small.put(("k", i), torch.zeros(1, 4, 5), torch.zeros(2, 4, 5))
-    assert len(small) == 3 and small.get(("k", 0), torch.device("cpu")) is None and small.get(("k", 4), torch.device("cpu")) is not None
-
-
 def test_bottleneck_gemm_params_fold_batch_norm_into_weight_and_bias():
     """Bottleneck.gemm_params: conv -> FrozenBatchNorm == conv with (weight * scale) + shift, shortcut shift merged into conv3's
     bias; checked on the CPU against the module's own composed forward (reference net/resnet50.py:11-14, :34-54)."""
@@ -846,23 +493,6 @@ def test_bottleneck_gemm_params_fold_batch_norm_into_weight_and_bias():
         with torch.no_grad():
             unit.bn3.bias.add_(1.0)
         assert unit.gemm_params() is not p and not torch.equal(unit.gemm_params()["b3"], p["b3"])
-
-
-def test_device_key_comes_from_the_architecture_not_the_marketing_name(monkeypatch):
-    """`torch.cuda.get_device_name` is empty under rocprofv3 and generic without amdgpu.ids: the key of the shipped databases
-    (MIOpen find database, GEMM rank table) is built from gcnArchName + CU count + HIP version."""
-    import types
-    import torch
-    from irn_amd.step import _common
-    monkeypatch.setattr(torch.cuda, "get_device_properties", lambda i: types.SimpleNamespace(gcnArchName="gfx950:sramecc+:xnack-", multi_processor_count=256))
-    monkeypatch.setattr(torch.cuda, "get_device_name", lambda i=0: "")
-    key = _common.miopen_cache_key()
-    assert key.startswith("gfx950-cu256-hip") and " " not in key
-    import os
-    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "irn_amd", "data")
-    shipped = os.listdir(os.path.join(root, "miopen"))
-    assert any(d.startswith("gfx950-cu256-hip") for d in shipped), shipped
-    assert any(f.startswith("gfx950-cu256-hip") and f.endswith(".json") for f in os.listdir(os.path.join(root, "gemm")))
 
 
 def test_dataset_skips_the_pixels_when_the_step_says_so(tmp_path):
@@ -941,159 +571,6 @@ def test_instance_step_pipeline_order(monkeypatch):
     # a batch is collected one turn after its back half: its detections cross PCIe under the next batch's kernels
     assert stages.index(("write", "a")) > stages.index(("front", "b")) and stages.index(("write", "b")) > stages.index(("front", "c"))
     assert [w[2] for w in log if w[0] == "write"] == ["pending-a1", "pending-b1", "pending-c1"]
-
-
-def _stub_label_worker(monkeypatch, packs, fail_cam_at=None):
-    """step/_labels.worker() / items() without a GPU: network, loader, writer, walker, device context, CAM store and uploads are
-    stand-ins that record what happens to them.  -> (events, args, model); the CAM look-up number `fail_cam_at` raises OSError."""
-    import argparse
-    import contextlib
-    from irn_amd.step import _common
-    events = []
-
-    class _Model:
-        def cuda(self):
-            events.append("model.cuda")
-
-    class _Walker:
-        fallback_runs, radius = 3, 5
-
-        def __call__(self, edges, cams, **kw):
-            events.append(("walk", len(edges)))
-            return ["rw"] * len(edges)
-
-        def sync(self):
-            return False
-
-        def close(self):
-            events.append("walker.close")
-
-    class _Writer:
-        def __init__(self, threads):
-            pass
-
-        def submit(self, fn, *a, **kw):
-            events.append(("submit", os.path.basename(a[0])))
-
-        def close(self):
-            events.append("writer.close")
-
-    def cam_get(name, cam_out_dir, dev, run_id=None, use_store=True):
-        events.append(("cam", name))
-        if fail_cam_at is not None and sum(1 for e in events if e[0] == "cam") > fail_cam_at:
-            raise OSError("no CAM file for " + name)
-        return torch.tensor([3, 7]), "keys_dev-" + name, "cam-" + name
-
-    monkeypatch.setattr(_common, "materialise", lambda model: events.append("materialise") or model)
-    monkeypatch.setattr(_common, "worker_device", lambda process_id, args=None: 0)
-    monkeypatch.setattr(_common, "make_loader", lambda databin, num_workers, prefetch=4: iter(packs))
-    monkeypatch.setattr(_common, "AsyncWriter", _Writer)
-    monkeypatch.setattr(_common, "make_walker", lambda args, radius: _Walker())
-    monkeypatch.setattr(_common, "step_summary", lambda rank, walker=None: events.append("summary"))
-    monkeypatch.setattr(_common, "progress", lambda pid, n, it, n_items: events.append(("tick", pid, n, it, n_items)))
-    monkeypatch.setattr(_common, "device_images", lambda pack, scales: None if pack["img"].numel() == 0 else [pack["img"][0].float()])
-    monkeypatch.setattr(_common.CAM_STORE, "get", cam_get)
-    monkeypatch.setattr(torch.cuda, "device", lambda dev: contextlib.nullcontext())
-    args = argparse.Namespace(num_workers=0, voc12_root="/no/such/voc", cam_out_dir="/no/such/cam", sem_seg_out_dir="/no/such/sem",
-                              beta=10, exp_times=8, sem_seg_bg_thres=0.25, walk_batch=1)
-    return events, args, _Model()
-
-
-def _label_packs():
-    """Two collated loader items: a `str` name with pixels, an integer-encoded name whose pixels the skip predicate emptied."""
-    return [{"name": ["2008_000001"], "size": torch.tensor([[6], [4]]), "img": torch.ones(1, 6, 4, 3, dtype=torch.uint8)},
-            {"name": torch.tensor([2008000002]), "size": torch.tensor([[5], [7]]), "img": torch.zeros(1, 0, dtype=torch.uint8)}]
-
-
-def test_label_worker_closes_walker_and_writer_on_both_paths(monkeypatch):
-    """step/_labels.worker: leaving the block normally adds the walker's fall-back runs to WALK_STATS once, prints the summary,
-    then closes walker and writer; an exception in the block closes both, adds nothing and comes out as it was raised."""
-    from irn_amd.step import _common, _labels
-    events, args, model = _stub_label_worker(monkeypatch, _label_packs())
-    monkeypatch.setitem(_common.WALK_STATS, "fallback_runs", 10)
-    with _labels.worker(1, model, [["x"], ["y", "z"]], args) as w:
-        assert (w.model, w.databin, w.n_gpus, w.dev) == (model, ["y", "z"], 2, torch.device("cuda", 0))
-        assert w.walker.fallback_runs == 3 and hasattr(w.writer, "submit") and len(list(w.loader)) == 2
-        assert not torch.is_grad_enabled() and "walker.close" not in events
-    assert _common.WALK_STATS["fallback_runs"] == 13 and torch.is_grad_enabled()
-    assert events == ["materialise", "model.cuda", "summary", "walker.close", "writer.close"]
-    del events[:]
-    boom = RuntimeError("a bad CAM file")
-    with pytest.raises(RuntimeError) as info:
-        with _labels.worker(0, model, [["x"]], args):
-            raise boom
-    assert info.value is boom and _common.WALK_STATS["fallback_runs"] == 13
-    assert events == ["materialise", "model.cuda", "walker.close", "writer.close"]
-
-
-def test_label_items_yield_what_both_steps_consume(monkeypatch):
-    """step/_labels.items: per image the dict both label steps built (name decoded, size as ints, pixels or None, device, CAM,
-    keys on the host AND on the device, the image file's stamp), one CAM look-up each, the progress tick after the consumer's turn."""
-    from irn_amd.step import _common, _labels
-    events, args, model = _stub_label_worker(monkeypatch, _label_packs())
-    with _labels.worker(0, model, [["a", "b"]], args) as w:
-        got = []
-        for p in _labels.items(w, args):
-            got.append(p)
-            events.append(("consumed", p["name"]))
-    a, b = got
-    assert set(a) == set(b) == {"name", "size", "img", "dev", "cam", "keys", "keys_dev", "stamp"}
-    assert (a["name"], b["name"]) == ("2008_000001", "2008_000002")
-    assert a["size"] == (6, 4) and b["size"] == (5, 7) and all(type(v) is int for v in a["size"] + b["size"])
-    assert a["img"].shape == (6, 4, 3) and a["img"].dtype == torch.float32 and b["img"] is None
-    assert a["dev"] == b["dev"] == torch.device("cuda", 0)
-    assert (a["cam"], a["keys_dev"], b["cam"], b["keys_dev"]) == ("cam-2008_000001", "keys_dev-2008_000001", "cam-2008_000002", "keys_dev-2008_000002")
-    assert a["keys"].tolist() == [3, 7]
-    assert a["stamp"] == _common.image_stamp(args.voc12_root, "2008_000001") and b["stamp"][0].endswith("2008_000002.jpg")
-    loop = [e for e in events if e[0] in ("cam", "consumed", "tick")]
-    assert loop == [("cam", "2008_000001"), ("consumed", "2008_000001"), ("tick", 0, 1, 0, 2),
-                    ("cam", "2008_000002"), ("consumed", "2008_000002"), ("tick", 0, 1, 1, 2)]
-
-
-def test_semantic_step_hands_its_staging_buffer_back_on_an_exception(monkeypatch):
-    """make_sem_seg_labels._work: when the loop dies with a batch in flight (here: the next image's CAM cannot be read), that
-    batch's page-locked buffer goes back to _common.PINNED, walker and writer are closed and the error comes out; a run that
-    ends well gives every buffer back exactly once."""
-    from irn_amd import ops
-    from irn_amd.step import _common, _labels, make_sem_seg_labels
-
-    class _Pool:
-        def __init__(self):
-            self.taken, self.given = [], []
-
-        def take(self, nbytes):
-            self.taken.append(torch.zeros(max(int(nbytes), 1), dtype=torch.uint8))
-            return self.taken[-1]
-
-        def give(self, buf):
-            self.given.append(buf)
-
-    class _Done:
-        def synchronize(self):
-            pass
-
-    def edges_for(model, pend, irn_batch, **kw):
-        for p in pend:
-            p["edge"] = "edge-" + p["name"]
-
-    for fail_cam_at, n_taken in ((1, 1), (None, 2)):
-        events, args, model = _stub_label_worker(monkeypatch, _label_packs(), fail_cam_at=fail_cam_at)
-        pool = _Pool()
-        monkeypatch.setattr(_common, "PINNED", pool)
-        monkeypatch.setattr(_labels, "edges_for", edges_for)
-        monkeypatch.setattr(ops, "label_epilogue", lambda rws, sizes, thres, keys=None, packed=False:
-                            {"labels_flat": torch.zeros(sum(h * w for h, w in sizes), dtype=torch.uint8)})
-        monkeypatch.setattr(ops, "read_back", lambda src, host, side: _Done())
-        if fail_cam_at is None:
-            make_sem_seg_labels._work(0, model, [["a", "b"]], args)
-            assert [e for e in events if e[0] == "submit"] == [("submit", "2008_000001.png"), ("submit", "2008_000002.png")]
-        else:
-            with pytest.raises(OSError, match="no CAM file for 2008_000002"):
-                make_sem_seg_labels._work(0, model, [["a", "b"]], args)
-            assert ("walk", 1) in events and not [e for e in events if e[0] == "submit"]     # the batch was in flight, not collected
-        assert len(pool.taken) == n_taken and len(pool.given) == n_taken
-        assert all(g is t for g, t in zip(pool.given, pool.taken))
-        assert events[-2:] == ["walker.close", "writer.close"]
 
 
 def test_label_step_batch_defaults():

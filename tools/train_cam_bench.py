@@ -159,10 +159,9 @@ def main(argv=None):
     a = p.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("train_cam_bench needs a GPU")
-    from irn_amd.net import resnet50 as _r50
-    from irn_amd.step import _common, train_cam
+    from irn_amd import _tuned
+    from irn_amd.step import train_cam
     dev = torch.device("cuda", torch.cuda.current_device())
-    saved = (torch.backends.cudnn.deterministic, _r50.DETERMINISTIC)
     with tempfile.TemporaryDirectory() as root:
         lst = write_tree(root, a.images)
         args = step_args(root, lst, a, "device")
@@ -172,14 +171,11 @@ def main(argv=None):
             host, _ = train_cam.make_datasets(step_args(root, lst, a, "host"), 0)
             print(json.dumps({"host_pipeline": bench_host_pipeline(raw, host, min(a.images, 64))}), flush=True)
         if not a.skip_step:
-            try:
-                _common.apply_deterministic_setting()
+            with _tuned.process_mode():
                 for augment in () if a.skip_augment_steps else ("device", "host", "device", "host"):   # alternating: the spread shows next to the difference
                     print(json.dumps({"step": bench_step(step_args(root, lst, a, augment), a, dev)}), flush=True)
                 for fused in (0, 1) * a.fused_tail_rounds:
                     print(json.dumps({"step": bench_step(step_args(root, lst, a, "device"), a, dev, fused)}), flush=True)
-            finally:
-                torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
 
 
 if __name__ == "__main__":

@@ -13,7 +13,7 @@ several times) — the model is built, MIOpen's first-use searches have run and 
 clock starts — with `--irn_augment device` and `host` alternating `--rounds` times; the clock stops behind a device
 synchronise.  `--irn_trunk autograd` (default) / `inference` / `both` chooses the trunk of the step (run_train.py --irn_trunk):
 with `both` every round runs the augment modes given by `--augments` once per trunk mode, alternating.  `inference` and `both`
-set MIOpen up as `train_irn.run` does for `--irn_trunk inference` (`_common.miopen_setup`, before the model is built) — for the
+set MIOpen up as `train_irn.run` does for `--irn_trunk inference` (`_tuned.miopen_setup`, before the model is built) — for the
 whole process, so the default path's own figure is that of a run with `--irn_trunk autograd`.  Every `step` line carries the
 trunk passes it counted by layout (`resnet50.PASS_STATS`) and the peak of allocated device memory.  `--skip_pipeline` leaves
 the input-pipeline sections out.  Needs a GPU: there is no fallback.
@@ -157,10 +157,9 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit("train_irn_bench needs a GPU")
     from irn_amd.misc import indexing, torchutils
-    from irn_amd.net import resnet50 as _r50
-    from irn_amd.step import _common, train_irn
+    from irn_amd import _tuned
+    from irn_amd.step import train_irn
     dev = torch.device("cuda", torch.cuda.current_device())
-    saved = (torch.backends.cudnn.deterministic, _r50.DETERMINISTIC)
     with tempfile.TemporaryDirectory() as root:
         lst, label_dir = write_tree(root, a.images, repeat=-(-(a.warmup + a.steps) * a.batch // a.images))
         args = step_args(root, lst, label_dir, a, "device")
@@ -171,10 +170,9 @@ def main(argv=None):
             print(json.dumps({"host_pipeline": bench_host_pipeline(raw, host, min(a.images, 64))}), flush=True)
         if not a.skip_step:
             trunks = ("autograd", "inference") if a.irn_trunk == "both" else (a.irn_trunk,)
-            try:
-                _common.apply_deterministic_setting()
+            with _tuned.process_mode():
                 if "inference" in trunks:
-                    _common.miopen_setup(torch.cuda.current_device())          # before the first convolution, as train_irn.run does
+                    _tuned.miopen_setup(torch.cuda.current_device())          # before the first convolution, as train_irn.run does
                 torch.manual_seed(0)
                 grid = a.crop // 4
                 model = train_irn.build_model(args, indexing.PathIndex(radius=10, default_size=(grid, grid))).to(dev).train()
@@ -184,8 +182,6 @@ def main(argv=None):
                 for augment in tuple(a.augments) * a.rounds:
                     for trunk in trunks:
                         print(json.dumps({"step": bench_step(step_args(root, lst, label_dir, a, augment), a, dev, model, opt, trunk)}), flush=True)
-            finally:
-                torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
 
 
 if __name__ == "__main__":

@@ -639,7 +639,23 @@ int irn_argmax_rethreshold_batch(int n_images, const float *const *rw_up_dev, co
  *   writes zeros and needs no workspace (ws may be NULL).
  * workspace of both: irn_crf_workspace_bytes(h, w, n_labels) (n_labels = k+1 for irn_crf_ir_label);
  *   0 = unsupported size.
+ * irn_crf_label_sweep: the CRF label maps of one image at t_count thresholds (step/tune_ir_label.py).
+ *   thres HOST fp32 [t_count], 1 <= t_count <= IRN_CRF_MAX_SWEEP, strictly ascending, no NaN.  Plane i
+ *   of planes dev uint8 [t_count][h][w] is the CRF seeded with argmax([thres[i], high_res]) (strict >,
+ *   the first class wins: the seeds of irn_crf_ir_label), its argmax taken through the keys: 0 =
+ *   background, else keys[c]+1.  It is what irn_crf_ir_label computes for thres[i] as fg or as bg
+ *   threshold, bit for bit: conf(fg, bg) = plane_fg, 255 where plane_fg == 0, 0 where plane_bg == 0
+ *   too.  Features, both lattices and the normalisations are built once per call; the mean field runs
+ *   over the thresholds in chunks of max(1, 64 / (k+1)) CRFs, so one filter pass carries at most 64
+ *   channels (what irn_crf_ir_label carries at k = 31), and a CRF's result does not depend on its
+ *   chunk.  k == 0 writes zeros and needs no workspace.  k + 1 <= 32.  Bad arguments (t_count, the
+ *   thresholds, k, the image size, null pointers) give IRN_ERR_ARG before any device work, a short
+ *   workspace IRN_ERR_STATE.  Nothing synchronises.
+ *   workspace: irn_crf_sweep_workspace_bytes(h, w, n_labels = k+1, t_count) (0 = unsupported): at most
+ *   irn_crf_workspace_bytes(h, w, 32) + 4 * t_count * h * w bytes (+ alignment); the lattice value
+ *   arrays do not grow with t_count.
  * ------------------------------------------------------------------------------------------- */
+#define IRN_CRF_MAX_SWEEP 16
 size_t irn_crf_filter_workspace_bytes(int n, int d, int channels);
 int irn_crf_filter(const float *feat_dev, int n, int d, const float *in_dev, int channels, float *out_dev,
                    int32_t *n_vertices, int32_t *keys_dev, int32_t *nbr_dev, void *ws, size_t ws_bytes, void *stream);
@@ -650,6 +666,10 @@ int irn_crf_inference_label(const uint8_t *rgb_dev, const int32_t *labels_dev, i
 int irn_crf_ir_label(const uint8_t *rgb_dev, const float *high_res_dev, const int64_t *keys_dev, int k, int h, int w,
                      float fg_thres, float bg_thres, int t, float gt_prob, uint8_t *conf_dev, void *ws,
                      size_t ws_bytes, void *stream);
+size_t irn_crf_sweep_workspace_bytes(int h, int w, int n_labels, int t_count);
+int irn_crf_label_sweep(const uint8_t *rgb_dev, const float *high_res_dev, const int64_t *keys_dev, int k, int h, int w,
+                        const float *thres, int t_count, int t, float gt_prob, uint8_t *planes_dev, void *ws,
+                        size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Evaluation counts  (replace the chainercv counting behind step/eval_cam.py:10-20,
@@ -678,6 +698,15 @@ int irn_crf_ir_label(const uint8_t *rgb_dev, const float *high_res_dev, const in
  *   in the mask; may be NULL when n == 0), inst dev uint8 [h][w] (0 = no instance, 1..g = instance).
  *   inter dev int64 [n][g] (pixels in mask i and instance j+1), area_pred dev int64 [n], area_gt dev
  *   int64 [g]; n == 0 and g == 0 are valid (the arrays of size 0 may be NULL).
+ * irn_ir_label_confusion: step/cam_to_ir_label.py:36-39 + the confusion count for every (fg, bg) pair of
+ *   a threshold grid, from the planes of irn_crf_label_sweep; no IR label map is written.  planes dev
+ *   uint8 [t_count][h][w] (1 <= t_count <= IRN_CRF_MAX_SWEEP; values 0..20), fg_idx HOST int32 [f] and
+ *   bg_idx HOST int32 [b] (1 <= f, b <= 16; plane numbers in [0, t_count), repeats allowed), gt dev uint8
+ *   [h][w].  Per pixel and pair, with fgv = planes[fg_idx[i]] and bgv = planes[bg_idx[j]], the label is
+ *   fgv if fgv != 0, else 0 if bgv == 0, else 255, and the pixel is one count in hist dev int64
+ *   [f][b][22][22] at [i][j][row][col]: row = GT 0..20 or 21 for GT 255, col = label 0..20 or 21 for
+ *   255.  A GT of 21..254, or a value above 20 in ANY of the t_count planes, skips the pixel for every
+ *   pair and counts once in bad.  Bad arguments give IRN_ERR_ARG before any device work.
  * ------------------------------------------------------------------------------------------- */
 #define IRN_EVAL_CLASSES 21
 #define IRN_EVAL_MAX_THRES 256
@@ -689,6 +718,8 @@ int irn_label_confusion(const uint8_t *pred_dev, const uint8_t *gt_dev, int h, i
 int irn_mask_overlap(const uint8_t *masks_dev, int n, const uint8_t *inst_dev, int g, int h, int w,
                      int64_t *inter_dev, int64_t *area_pred_dev, int64_t *area_gt_dev, int64_t *bad_dev,
                      void *stream);
+int irn_ir_label_confusion(const uint8_t *planes_dev, int t_count, const int32_t *fg_idx, int f, const int32_t *bg_idx,
+                           int b, const uint8_t *gt_dev, int h, int w, int64_t *hist_dev, int64_t *bad_dev, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Label threshold sweep  (step/make_sem_seg_labels.py:43-49 + step/eval_sem_seg.py:10-17 at T values

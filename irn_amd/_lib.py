@@ -105,6 +105,9 @@ _SIGS = {
     "irn_crf_workspace_bytes": (sz, [i32, i32, i32]),
     "irn_crf_inference_label": (i32, [vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, sz, vp]),
     "irn_crf_ir_label": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, i32, f32, vp, vp, sz, vp]),
+    "irn_crf_sweep_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "irn_crf_label_sweep": (i32, [vp, vp, vp, i32, i32, i32, C.POINTER(f32), i32, i32, f32, vp, vp, sz, vp]),
+    "irn_ir_label_confusion": (i32, [vp, i32, pi32, i32, pi32, i32, vp, i32, i32, vp, vp, vp]),
     "irn_cam_confusion": (i32, [vp, vp, i32, vp, i32, i32, vp, i32, vp, vp, vp]),
     "irn_cam_confusion_reduce": (i32, [vp, i32, vp, vp, vp]),
     "irn_label_confusion": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),

@@ -3,11 +3,13 @@ step/cam_to_ir_label.py:22-39 of the reference) over include/irn_hip.h's irn_crf
 functions.  GPU tensors in, GPU tensors out; no CPU fallback."""
 import ctypes as C
 
+import numpy as np
 import torch
 
 from ._lib import _need_cuda, _stream, check, lib
 
 CRF_T, CRF_GT_PROB = 10, 0.7          # the reference's defaults (misc/imutils.py:156)
+CRF_MAX_SWEEP = 16                    # IRN_CRF_MAX_SWEEP
 _CRF_WS = {}                          # (device index, stream) -> grow-only workspace of the CRF entries
 
 
@@ -111,4 +113,43 @@ def crf_ir_label(img, high_res, keys, fg_thres, bg_thres, t=CRF_T, gt_prob=CRF_G
         check(lib.irn_crf_ir_label(rgb.data_ptr(), cams.data_ptr() if k else None, ks.data_ptr() if k else None, k, h, w,
                                    float(fg_thres), float(bg_thres), int(t), float(gt_prob), out.data_ptr(),
                                    None if ws is None else ws.data_ptr(), nbytes, _stream()))
+    return out
+
+
+def crf_label_sweep(img, high_res, keys, thres, t=CRF_T, gt_prob=CRF_GT_PROB, out=None):
+    """The CRF label maps of one image at every threshold of `thres` (1..CRF_MAX_SWEEP values; cast to float32, strictly
+    ascending after the cast): plane i is the CRF seeded with argmax([thres[i], high_res]) taken through `keys`, 0 background
+    and class+1 foreground — the map `crf_ir_label` computes for that threshold as fg or as bg threshold, bit for bit.  The
+    image's lattices are built once and the CRFs run in chunks of one filter each (include/irn_hip.h).  Returns uint8 [T,H,W]
+    on the GPU; `ir_label_confusion` counts a threshold grid from it."""
+    _need_cuda(high_res, "high_res")
+    dev = high_res.device
+    rgb = _crf_rgb(img, dev)
+    h, w = rgb.shape[:2]
+    cams = high_res.float().contiguous()
+    k = int(cams.shape[0]) if cams.dim() == 3 else 0
+    if k and tuple(cams.shape[1:]) != (h, w):
+        raise ValueError("crf_label_sweep: high_res %s for an image of %dx%d" % (tuple(cams.shape), h, w))
+    ks = torch.as_tensor(keys, device=dev).to(torch.int64).reshape(-1).contiguous()
+    if ks.numel() != k:
+        raise ValueError("crf_label_sweep: %d keys for %d CAM planes" % (ks.numel(), k))
+    th = np.ascontiguousarray(np.asarray(thres, np.float32).reshape(-1))
+    n_t = int(th.size)
+    if not 1 <= n_t <= CRF_MAX_SWEEP or np.isnan(th).any() or (np.diff(th) <= 0).any():
+        raise ValueError("crf_label_sweep: 1..%d strictly ascending float32 thresholds, got %s" % (CRF_MAX_SWEEP, th))
+    if out is None:
+        out = torch.empty((n_t, h, w), dtype=torch.uint8, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == torch.uint8 and out.is_contiguous()
+              and tuple(out.shape) == (n_t, h, w)):
+        raise ValueError("crf_label_sweep: out must be a contiguous uint8 %s tensor on %s" % ((n_t, h, w), dev))
+    ws, nbytes = None, 0
+    with torch.cuda.device(dev):
+        if k:
+            nbytes = int(lib.irn_crf_sweep_workspace_bytes(h, w, k + 1, n_t))
+            if nbytes == 0:
+                raise ValueError("crf_label_sweep: unsupported size %dx%d with %d classes" % (h, w, k))
+            ws = _crf_workspace(dev, nbytes)
+        check(lib.irn_crf_label_sweep(rgb.data_ptr(), cams.data_ptr() if k else None, ks.data_ptr() if k else None, k, h, w,
+                                      th.ctypes.data_as(C.POINTER(C.c_float)), n_t, int(t), float(gt_prob), out.data_ptr(),
+                                      None if ws is None else ws.data_ptr(), nbytes, _stream()))
     return out

@@ -424,20 +424,33 @@ __global__ void __launch_bounds__(TPB) k_features(const uint8_t *__restrict__ rg
     fb[5 * p + 4] = __fdiv_rn((float)rgb[3 * p + 2], BILAT_SRGB);
 }
 
-// step/cam_to_ir_label.py:26-28 / 32-34: argmax over [thr, cam_0 .. cam_{k-1}], the first maximum winning
-__global__ void __launch_bounds__(TPB) k_prologue(const float *__restrict__ cams, int k, int n, float thr_fg,
-                                                  float thr_bg, int32_t *__restrict__ lab) {
+// thresholds of one launch, by value (the entries take them from the host)
+struct Thresholds {
+    float v[IRN_CRF_MAX_SWEEP];
+};
+
+// step/cam_to_ir_label.py:26-28 / 32-34: argmax over [thr, cam_0 .. cam_{k-1}], the first maximum winning, for each of
+// the ncrf thresholds; lab is [crf][pixel]
+__global__ void __launch_bounds__(TPB) k_prologue(const float *__restrict__ cams, int k, int n, Thresholds th, int ncrf,
+                                                  int32_t *__restrict__ lab) {
     const int p = blockIdx.x * TPB + threadIdx.x;
     if (p >= n) return;
-    float bf = thr_fg, bb = thr_bg;
-    int lf = 0, lb = 0;
+    float best[IRN_CRF_MAX_SWEEP];
+    int lb[IRN_CRF_MAX_SWEEP];
+#pragma unroll
+    for (int i = 0; i < IRN_CRF_MAX_SWEEP; i++) {
+        best[i] = th.v[i];
+        lb[i] = 0;
+    }
     for (int c = 0; c < k; c++) {
         const float v = cams[(size_t)c * n + p];
-        if (v > bf) { bf = v; lf = c + 1; }
-        if (v > bb) { bb = v; lb = c + 1; }
+#pragma unroll
+        for (int i = 0; i < IRN_CRF_MAX_SWEEP; i++)
+            if (i < ncrf && v > best[i]) { best[i] = v; lb[i] = c + 1; }
     }
-    lab[p] = lf;
-    lab[n + p] = lb;
+#pragma unroll
+    for (int i = 0; i < IRN_CRF_MAX_SWEEP; i++)
+        if (i < ncrf) lab[(size_t)i * n + p] = lb[i];
 }
 
 struct Unary {
@@ -521,26 +534,31 @@ __global__ void __launch_bounds__(TPB) k_update(const int32_t *__restrict__ lab,
     softmax_row(kg, l, q + (size_t)p * c + ch0);
 }
 
-// argmax of each crf's Q (first maximum), then either the labels (+ Q as [label][pixel]) of a single CRF or the
-// combination of step/cam_to_ir_label.py:36-39 over the fg / bg pair
+// argmax of each crf's Q (first maximum), then any of: the labels (+ Q as [label][pixel]) of the first CRF, the
+// combination of step/cam_to_ir_label.py:36-39 over the first two (fg, bg), or every CRF's label through the keys as
+// one uint8 plane each (planes is [crf][pixel])
 __global__ void __launch_bounds__(TPB) k_finish(const float *__restrict__ q, int n, int ncrf, int l,
                                                 const int64_t *__restrict__ keys, int32_t *__restrict__ labels,
-                                                float *__restrict__ q_out, uint8_t *__restrict__ conf) {
+                                                float *__restrict__ q_out, uint8_t *__restrict__ conf,
+                                                uint8_t *__restrict__ planes) {
     const int p = blockIdx.x * TPB + threadIdx.x;
     if (p >= n) return;
     const float *row = q + (size_t)p * ncrf * l;
-    int pred[2] = {0, 0};
+    long fg = 0, bgc = 0;
     for (int crf = 0; crf < ncrf; crf++) {
         float best = row[crf * l];
+        int pred = 0;
         for (int i = 1; i < l; i++)
-            if (row[crf * l + i] > best) { best = row[crf * l + i]; pred[crf] = i; }
+            if (row[crf * l + i] > best) { best = row[crf * l + i]; pred = i; }
+        const long v = (keys && pred) ? keys[pred - 1] + 1 : pred;
+        if (crf == 0) fg = v;
+        if (crf == 1) bgc = v;
+        if (planes) planes[(size_t)crf * n + p] = (uint8_t)v;
     }
-    if (labels) labels[p] = pred[0];
+    if (labels) labels[p] = (int32_t)fg;
     if (q_out)
         for (int i = 0; i < l; i++) q_out[(size_t)i * n + p] = row[i];
     if (conf) {
-        const long fg = pred[0] == 0 ? 0 : keys[pred[0] - 1] + 1;
-        const long bgc = pred[1] == 0 ? 0 : keys[pred[1] - 1] + 1;
         long v = fg;
         if (fg == 0) v = 255;
         if (fg + bgc == 0) v = 0;
@@ -548,24 +566,28 @@ __global__ void __launch_bounds__(TPB) k_finish(const float *__restrict__ q, int
     }
 }
 
-// Everything one image needs, carved from the caller's workspace
+// Everything one image needs, carved from the caller's workspace: seeds for `nseed` CRFs, Q and the lattice values for
+// the `ncrf` of them that share a filter pass (c = ncrf * l channels)
 struct CrfWs {
     float *feat_g, *feat_b, *q;
     int32_t *lab;
     Lattice g, b;
 };
 
-size_t carve_crf(void *base, CrfWs &W, int h, int w, int l) {
+size_t carve_crf(void *base, CrfWs &W, int h, int w, int l, int nseed = 2, int ncrf = 2) {
     Carver cv(base);
-    const int n = h * w, c = 2 * l;
+    const int n = h * w, c = ncrf * l;
     W.feat_g = cv.take<float>((size_t)n * 2);
     W.feat_b = cv.take<float>((size_t)n * 5);
-    W.lab = cv.take<int32_t>((size_t)n * 2);
+    W.lab = cv.take<int32_t>((size_t)n * nseed);
     W.q = cv.take<float>((size_t)n * c);
     carve(cv, W.g, n, 2, c);
     carve(cv, W.b, n, 5, c);
     return cv.off;
 }
+
+// CRFs of one filter pass of the sweep: never more than 2 * MAX_LABELS channels, what irn_crf_ir_label carries at most
+inline int sweep_chunk(int l, int t_count) { return std::min(t_count, std::max(1, 2 * MAX_LABELS / l)); }
 
 bool crf_args_ok(int h, int w, int l, const char *who) {
     if (h < 1 || w < 1 || (long)h * w > (1L << 26) / 6) return fail(IRN_ERR_ARG, "%s: bad image size %dx%d", who, h, w), false;
@@ -577,22 +599,36 @@ bool crf_args_ok(int h, int w, int l, const char *who) {
     return true;
 }
 
-// Run the mean field over ncrf CRFs sharing one image's lattices; labels of each crf already in W.lab
-int mean_field(CrfWs &W, int n, int ncrf, int l, int t, float gt_prob, hipStream_t s) {
+inline Unary unary_of(int l, float gt_prob) {
     const double n_energy = l > 1 ? -std::log((1.0 - gt_prob) / (l - 1)) : 0.0;
     const double p_energy = -std::log((double)gt_prob);
-    const Unary u{-(float)p_energy, -(float)n_energy};
-    const int c = ncrf * l;
-    k_q_init<<<cdiv(n * ncrf, TPB), TPB, 0, s>>>(W.lab, n, ncrf, l, u, W.q);
-    IRN_LAUNCH_CHECK("k_q_init");
-    if (t <= 0 || l == 1) return IRN_OK;            // one label: Q = 1 whatever the pairwise terms
+    return Unary{-(float)p_energy, -(float)n_energy};
+}
+
+// The mean field in two halves.  An image's pairwise kernels: features, both lattices and their normalisations, once per
+// image whatever runs over them (nothing to build without iterations, or with one label: Q = 1 whatever the pairwise terms)
+int build_kernels(CrfWs &W, const uint8_t *rgb, int h, int w, int l, int t, hipStream_t s) {
+    if (t <= 0 || l == 1) return IRN_OK;
+    k_features<<<cdiv(h * w, TPB), TPB, 0, s>>>(rgb, h, w, W.feat_g, W.feat_b);
+    IRN_LAUNCH_CHECK("k_features");
     int rc;
     if ((rc = build_lattice(W.g, W.feat_g, s)) || (rc = build_lattice(W.b, W.feat_b, s))) return rc;
     if ((rc = compute_norm(W.g, s)) || (rc = compute_norm(W.b, s))) return rc;
+    return IRN_OK;
+}
+
+// ... and the iterations of one chunk: ncrf CRFs seeded by lab [ncrf][n] as one filter over ncrf * l channels, into W.q.
+// A channel's values never meet another's, so a CRF's Q does not depend on which others share its chunk.
+int iterate_chunk(CrfWs &W, const int32_t *lab, int n, int ncrf, int l, int t, float gt_prob, hipStream_t s) {
+    const Unary u = unary_of(l, gt_prob);
+    const int c = ncrf * l;
+    k_q_init<<<cdiv(n * ncrf, TPB), TPB, 0, s>>>(lab, n, ncrf, l, u, W.q);
+    IRN_LAUNCH_CHECK("k_q_init");
+    if (t <= 0 || l == 1) return IRN_OK;
     for (int it = 0; it < t; it++) {
         const float *vg = splat_blur(W.g, W.q, W.g.norm, c, s);
         const float *vb = splat_blur(W.b, W.q, W.b.norm, c, s);
-        k_update<2, 5><<<cdiv(n * ncrf, TPB), TPB, 0, s>>>(W.lab, n, ncrf, l, u, vg, W.g.offset, W.g.bary, W.g.norm,
+        k_update<2, 5><<<cdiv(n * ncrf, TPB), TPB, 0, s>>>(lab, n, ncrf, l, u, vg, W.g.offset, W.g.bary, W.g.norm,
                                                             W.g.prm.alpha, vb, W.b.offset, W.b.bary, W.b.norm,
                                                             W.b.prm.alpha, W.q);
         IRN_LAUNCH_CHECK("k_update");
@@ -677,12 +713,11 @@ extern "C" int irn_crf_inference_label(const uint8_t *rgb_dev, const int32_t *la
     CrfWs W;
     carve_crf(ws, W, h, w, n_labels);
     const int n = h * w;
-    IRN_HIP_TRY(hipMemcpyAsync(W.lab, labels_dev, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
-    k_features<<<cdiv(n, TPB), TPB, 0, s>>>(rgb_dev, h, w, W.feat_g, W.feat_b);
-    IRN_LAUNCH_CHECK("k_features");
-    int rc = mean_field(W, n, 1, n_labels, t, gt_prob, s);
-    if (rc) return rc;
-    k_finish<<<cdiv(n, TPB), TPB, 0, s>>>(W.q, n, 1, n_labels, nullptr, labels_out_dev, q_dev, nullptr);
+    int rc;
+    if ((rc = build_kernels(W, rgb_dev, h, w, n_labels, t, s)) ||
+        (rc = iterate_chunk(W, labels_dev, n, 1, n_labels, t, gt_prob, s)))
+        return rc;
+    k_finish<<<cdiv(n, TPB), TPB, 0, s>>>(W.q, n, 1, n_labels, nullptr, labels_out_dev, q_dev, nullptr, nullptr);
     IRN_LAUNCH_CHECK("k_finish");
     return IRN_OK;
 }
@@ -704,12 +739,66 @@ extern "C" int irn_crf_ir_label(const uint8_t *rgb_dev, const float *high_res_de
     if (ws_bytes < need) return fail(IRN_ERR_STATE, "irn_crf_ir_label: workspace %zu < %zu bytes", ws_bytes, need);
     CrfWs W;
     carve_crf(ws, W, h, w, l);
-    k_prologue<<<cdiv(n, TPB), TPB, 0, s>>>(high_res_dev, k, n, fg_thres, bg_thres, W.lab);
-    k_features<<<cdiv(n, TPB), TPB, 0, s>>>(rgb_dev, h, w, W.feat_g, W.feat_b);
-    IRN_LAUNCH_CHECK("k_features");
-    int rc = mean_field(W, n, 2, l, t, gt_prob, s);
-    if (rc) return rc;
-    k_finish<<<cdiv(n, TPB), TPB, 0, s>>>(W.q, n, 2, l, keys_dev, nullptr, nullptr, conf_dev);
+    Thresholds th{};
+    th.v[0] = fg_thres;
+    th.v[1] = bg_thres;
+    k_prologue<<<cdiv(n, TPB), TPB, 0, s>>>(high_res_dev, k, n, th, 2, W.lab);
+    IRN_LAUNCH_CHECK("k_prologue");
+    int rc;
+    if ((rc = build_kernels(W, rgb_dev, h, w, l, t, s)) || (rc = iterate_chunk(W, W.lab, n, 2, l, t, gt_prob, s))) return rc;
+    k_finish<<<cdiv(n, TPB), TPB, 0, s>>>(W.q, n, 2, l, keys_dev, nullptr, nullptr, conf_dev, nullptr);
     IRN_LAUNCH_CHECK("k_finish");
+    return IRN_OK;
+}
+
+extern "C" size_t irn_crf_sweep_workspace_bytes(int h, int w, int n_labels, int t_count) {
+    if (t_count < 1 || t_count > IRN_CRF_MAX_SWEEP || irn_crf_workspace_bytes(h, w, n_labels) == 0) return 0;
+    CrfWs W;
+    return carve_crf(nullptr, W, h, w, n_labels, t_count, sweep_chunk(n_labels, t_count));
+}
+
+extern "C" int irn_crf_label_sweep(const uint8_t *rgb_dev, const float *high_res_dev, const int64_t *keys_dev, int k, int h,
+                                   int w, const float *thres, int t_count, int t, float gt_prob, uint8_t *planes_dev,
+                                   void *ws, size_t ws_bytes, void *stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    if (t_count < 1 || t_count > IRN_CRF_MAX_SWEEP)
+        return fail(IRN_ERR_ARG, "irn_crf_label_sweep: t_count %d outside 1..%d", t_count, IRN_CRF_MAX_SWEEP);
+    if (!thres) return fail(IRN_ERR_ARG, "irn_crf_label_sweep: thres is a null pointer");
+    Thresholds th{};
+    for (int i = 0; i < t_count; i++) {
+        if (thres[i] != thres[i]) return fail(IRN_ERR_ARG, "irn_crf_label_sweep: threshold %d is NaN", i);
+        if (i > 0 && !(thres[i - 1] < thres[i]))
+            return fail(IRN_ERR_ARG, "irn_crf_label_sweep: thresholds not strictly ascending (%g then %g at %d)",
+                        (double)thres[i - 1], (double)thres[i], i);
+        th.v[i] = thres[i];
+    }
+    if (k < 0 || t < 0 || !(gt_prob > 0.0f && gt_prob < 1.0f))
+        return fail(IRN_ERR_ARG, "irn_crf_label_sweep: bad argument (k=%d, t=%d, gt_prob=%g)", k, t, (double)gt_prob);
+    const int l = k + 1;
+    if (!crf_args_ok(h, w, l, "irn_crf_label_sweep")) return IRN_ERR_ARG;
+    if (!rgb_dev || !planes_dev || (k > 0 && (!high_res_dev || !keys_dev || !ws)))
+        return fail(IRN_ERR_ARG, "irn_crf_label_sweep: a null pointer (rgb, planes, or with k > 0 high_res, keys, ws)");
+    const int n = h * w;
+    if (k == 0) {                       // no class keys: every plane is the all-zero map irn_crf_ir_label writes
+        IRN_HIP_TRY(hipMemsetAsync(planes_dev, 0, (size_t)t_count * n, s));
+        return IRN_OK;
+    }
+    const size_t need = irn_crf_sweep_workspace_bytes(h, w, l, t_count);
+    if (ws_bytes < need) return fail(IRN_ERR_STATE, "irn_crf_label_sweep: workspace %zu < %zu bytes", ws_bytes, need);
+    const int chunk = sweep_chunk(l, t_count);
+    CrfWs W;
+    carve_crf(ws, W, h, w, l, t_count, chunk);
+    k_prologue<<<cdiv(n, TPB), TPB, 0, s>>>(high_res_dev, k, n, th, t_count, W.lab);
+    IRN_LAUNCH_CHECK("k_prologue");
+    int rc = build_kernels(W, rgb_dev, h, w, l, t, s);
+    if (rc) return rc;
+    for (int c0 = 0; c0 < t_count; c0 += chunk) {
+        const int ncrf = std::min(chunk, t_count - c0);
+        const int32_t *lab = W.lab + (size_t)c0 * n;
+        if ((rc = iterate_chunk(W, lab, n, ncrf, l, t, gt_prob, s))) return rc;
+        k_finish<<<cdiv(n, TPB), TPB, 0, s>>>(W.q, n, ncrf, l, keys_dev, nullptr, nullptr, nullptr,
+                                              planes_dev + (size_t)c0 * n);
+        IRN_LAUNCH_CHECK("k_finish");
+    }
     return IRN_OK;
 }

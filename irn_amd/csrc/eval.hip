@@ -1,5 +1,6 @@
 // Evaluation counts on the GPU (include/irn_hip.h "Evaluation counts"): the confusion matrices behind
-// step/eval_cam.py and step/eval_sem_seg.py and the mask_iou counts behind step/eval_ins_seg.py.
+// step/eval_cam.py and step/eval_sem_seg.py, the mask_iou counts behind step/eval_ins_seg.py, and the confusion matrices
+// of a whole fg x bg threshold grid of IR labels (step/tune_ir_label.py; not in the reference).
 //
 // Every kernel privatises its counters in LDS (one uint32 per bin, at most 4096 pixels per block, so a bin cannot
 // overflow) and flushes the non-zero bins once per block with 64-bit integer atomics into the caller's int64
@@ -180,6 +181,112 @@ __global__ void __launch_bounds__(TPB) k_mask_overlap(const uint8_t *__restrict_
     if (tid == 0 && mask && total) add64(area_pred + y, total);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// IR-label grid confusion: every (fg, bg) pair of a threshold grid from the CRF label planes, no label map written.
+// The label of pair (i, j) is fgv if fgv != 0, else 0 if bgv == 0, else 255.  A pixel with fgv != 0 is in the same cell
+// for every j, and one with fgv == 0 is in column 0 or 21 by j alone, so a block counts
+//     az[i][row][v]   pixels whose plane fg[i] reads v (v = 0..20)
+//     un[i][j][row]   those of them with v == 0 whose plane bg[j] is not 0 (the unsure ones)
+// as uint32 in LDS (f*22*21 + f*b*22 words, sized by the call's f and b: 51 KiB at 16 x 16, 1.8 KiB at 2 x 2), f + (number
+// of unsure pairs) atomics per pixel instead of f*b, and expands them when it flushes: column v >= 1 of every j gets
+// az[i][row][v], column 21 gets un, column 0 gets az[i][row][0] - un.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int IR_MAX = IRN_CRF_MAX_SWEEP;     // planes, and pairs per axis
+constexpr int IR_COLS = NC + 1;               // columns of hist: labels 0..20 and 255
+
+struct PairIdx {
+    uint8_t fg[IR_MAX], bg[IR_MAX];
+};
+
+// four bytes of a plane from pixel p on: one 32-bit load where the address allows it (`valid` = pixels left, 1..4)
+__device__ __forceinline__ uint32_t load4(const uint8_t *__restrict__ q, int valid) {
+    if (valid == 4 && (reinterpret_cast<uintptr_t>(q) & 3) == 0) return *reinterpret_cast<const uint32_t *>(q);
+    uint32_t v = 0;
+    for (int k = 0; k < valid; ++k) v |= (uint32_t)q[k] << (8 * k);
+    return v;
+}
+
+__global__ void __launch_bounds__(TPB) k_ir_label_hist(const uint8_t *__restrict__ planes, int t_count, PairIdx idx, int f,
+                                                       int b, const uint8_t *__restrict__ gt, int n,
+                                                       int64_t *__restrict__ hist, int64_t *__restrict__ bad) {
+    extern __shared__ uint32_t lds[];
+    __shared__ uint32_t nbad;
+    const int tid = threadIdx.x;
+    const int n_az = f * kRows * NC, n_un = f * b * kRows;
+    uint32_t *az = lds, *un = lds + n_az;
+    for (int c = tid; c < n_az + n_un; c += TPB) lds[c] = 0;
+    if (tid == 0) nbad = 0;
+    __syncthreads();
+    uint32_t local_bad = 0;
+    const int base = blockIdx.x * PIX + tid * 4;
+#pragma unroll 1
+    for (int g = 0; g < PPT / 4; ++g) {
+        const int p = base + g * TPB * 4;
+        if (p >= n) break;
+        const int valid = min(4, n - p);
+        const uint32_t gw = load4(gt + p, valid);
+        // which planes read 0 at each of the four pixels, and which pixels are out of range in any plane
+        uint32_t zero[4] = {0, 0, 0, 0}, skip = 0;
+        for (int t = 0; t < t_count; ++t) {
+            const uint32_t w = load4(planes + (size_t)t * n + p, valid);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t v = (w >> (8 * k)) & 255u;
+                zero[k] |= (v == 0 ? 1u : 0u) << t;
+                skip |= (v > (uint32_t)(NC - 1) ? 1u : 0u) << k;
+            }
+        }
+        int row[4];
+        uint32_t unsure[4];                   // bit j: plane bg[j] is not 0
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            row[k] = gt_row((uint8_t)(gw >> (8 * k)));
+            if (k < valid && (row[k] < 0 || ((skip >> k) & 1u))) {
+                ++local_bad;
+                row[k] = -1;
+            }
+            if (k >= valid) row[k] = -1;
+            unsure[k] = 0;
+        }
+        for (int j = 0; j < b; ++j) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) unsure[k] |= ((~zero[k] >> idx.bg[j]) & 1u) << j;
+        }
+        for (int i = 0; i < f; ++i) {
+            const int ti = idx.fg[i];
+            const uint32_t w = load4(planes + (size_t)ti * n + p, valid);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (row[k] < 0) continue;
+                const uint32_t v = (w >> (8 * k)) & 255u;
+                atomicAdd(&az[(i * kRows + row[k]) * NC + (int)v], 1u);
+                if (v) continue;
+                for (uint32_t m = unsure[k]; m; m &= m - 1)
+                    atomicAdd(&un[(i * b + (__ffs(m) - 1)) * kRows + row[k]], 1u);
+            }
+        }
+    }
+    if (local_bad) atomicAdd(&nbad, local_bad);
+    __syncthreads();
+    // flush: one pass over az, a non-zero cell going to its column of every j
+    for (int c = tid; c < n_az; c += TPB) {
+        const uint32_t cnt = az[c];
+        if (!cnt) continue;
+        const int v = c % NC, ir = c / NC, r = ir % kRows, i = ir / kRows;
+        for (int j = 0; j < b; ++j) {
+            int64_t *cell = hist + (((size_t)i * b + j) * kRows + r) * IR_COLS;
+            if (v) {
+                add64(cell + v, cnt);
+                continue;
+            }
+            const uint32_t u = un[(i * b + j) * kRows + r];
+            if (cnt - u) add64(cell, cnt - u);
+            if (u) add64(cell + NC, u);
+        }
+    }
+    if (tid == 0 && nbad) add64(bad, nbad);
+}
+
 bool pixels_ok(int h, int w) { return h >= 1 && w >= 1 && (int64_t)h * w <= (int64_t)0x7fffffff - PIX; }
 
 }  // namespace
@@ -215,6 +322,37 @@ extern "C" int irn_label_confusion(const uint8_t *pred_dev, const uint8_t *gt_de
     hipLaunchKernelGGL(k_label_hist, dim3(cdiv(n, PIX)), dim3(TPB), 0, (hipStream_t)stream, pred_dev, gt_dev, n,
                        pred_255_as, conf_dev, void_dev, bad_dev);
     IRN_LAUNCH_CHECK("k_label_hist");
+    return IRN_OK;
+}
+
+extern "C" int irn_ir_label_confusion(const uint8_t *planes_dev, int t_count, const int32_t *fg_idx, int f,
+                                      const int32_t *bg_idx, int b, const uint8_t *gt_dev, int h, int w, int64_t *hist_dev,
+                                      int64_t *bad_dev, void *stream) {
+    if (t_count < 1 || t_count > IR_MAX)
+        return fail(IRN_ERR_ARG, "irn_ir_label_confusion: t_count %d outside 1..%d", t_count, IR_MAX);
+    if (f < 1 || f > IR_MAX || b < 1 || b > IR_MAX)
+        return fail(IRN_ERR_ARG, "irn_ir_label_confusion: grid f=%d x b=%d, each axis must be 1..%d", f, b, IR_MAX);
+    if (!fg_idx || !bg_idx) return fail(IRN_ERR_ARG, "irn_ir_label_confusion: fg_idx or bg_idx is a null pointer");
+    PairIdx idx{};
+    for (int i = 0; i < f; ++i) {
+        if (fg_idx[i] < 0 || fg_idx[i] >= t_count)
+            return fail(IRN_ERR_ARG, "irn_ir_label_confusion: fg_idx[%d] = %d outside [0, t_count = %d)", i, fg_idx[i], t_count);
+        idx.fg[i] = (uint8_t)fg_idx[i];
+    }
+    for (int j = 0; j < b; ++j) {
+        if (bg_idx[j] < 0 || bg_idx[j] >= t_count)
+            return fail(IRN_ERR_ARG, "irn_ir_label_confusion: bg_idx[%d] = %d outside [0, t_count = %d)", j, bg_idx[j], t_count);
+        idx.bg[j] = (uint8_t)bg_idx[j];
+    }
+    if (!pixels_ok(h, w) || (int64_t)h * w * t_count > (int64_t)0x7fffffff)
+        return fail(IRN_ERR_ARG, "irn_ir_label_confusion: bad image size %dx%d for %d planes", h, w, t_count);
+    if (!planes_dev || !gt_dev || !hist_dev || !bad_dev)
+        return fail(IRN_ERR_ARG, "irn_ir_label_confusion: a null pointer (planes, gt, hist or bad)");
+    const int n = h * w;
+    const size_t lds = (size_t)(f * kRows * NC + f * b * kRows) * sizeof(uint32_t);
+    hipLaunchKernelGGL(k_ir_label_hist, dim3(cdiv(n, PIX)), dim3(TPB), lds, (hipStream_t)stream, planes_dev, t_count, idx, f,
+                       b, gt_dev, n, hist_dev, bad_dev);
+    IRN_LAUNCH_CHECK("k_ir_label_hist");
     return IRN_OK;
 }
 

@@ -1,7 +1,10 @@
 """Host side of irn_amd/csrc/eval.hip: the integer counts behind the evaluation steps (step/eval_cam.py,
-step/eval_sem_seg.py, step/eval_ins_seg.py of the reference): irn_cam_confusion, irn_label_confusion, irn_mask_overlap.
+step/eval_sem_seg.py, step/eval_ins_seg.py of the reference): irn_cam_confusion, irn_label_confusion, irn_mask_overlap,
+and the grid count of step/tune_ir_label.py, irn_ir_label_confusion.
 Accumulators are int64 GPU tensors that every call adds into; `bad` (int64 [1]) counts values outside the documented
 ranges and the caller raises when it is non-zero.  `irn_amd.ops` re-exports the functions."""
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -117,3 +120,29 @@ def mask_overlap(masks, inst_map, n_inst, bad=None):
                                    inter.data_ptr() if n and g else None, area_pred.data_ptr() if n else None,
                                    area_gt.data_ptr() if g else None, bad.data_ptr(), _stream()))
     return inter, area_pred, area_gt
+
+
+def ir_label_confusion(planes, fg_idx, bg_idx, gt, hist=None, bad=None):
+    """step/cam_to_ir_label.py:36-39 + the confusion count for every (fg, bg) pair of a threshold grid, from the planes of
+    `crf_label_sweep`: planes uint8 [T,H,W] (GPU), fg_idx [F] / bg_idx [B] plane numbers (1..16 each, repeats allowed), gt
+    uint8 [H,W] (255 = void).  Pair (i, j) labels a pixel planes[fg_idx[i]] where that is not 0, else 0 where
+    planes[bg_idx[j]] is 0 too, else 255.  Adds into hist int64 [F,B,22,22] (row = GT, 21 = void; column = label, 21 = 255)
+    and bad int64 [1]; returns (hist, bad).  No label map is written."""
+    _need_cuda(planes, "planes")
+    dev = planes.device
+    if planes.dtype != torch.uint8 or planes.dim() != 3:
+        raise ValueError("ir_label_confusion: planes must be a uint8 [T,H,W] tensor, got %s %s" % (planes.dtype, tuple(planes.shape)))
+    pl = planes.contiguous()
+    g = u8_map(gt, dev, "gt")
+    t, h, w = (int(v) for v in pl.shape)
+    if tuple(g.shape) != (h, w):
+        raise ValueError("ir_label_confusion: planes %s for a GT of %s" % (tuple(pl.shape), tuple(g.shape)))
+    fg = np.ascontiguousarray(np.asarray(fg_idx, np.int32).reshape(-1))
+    bg = np.ascontiguousarray(np.asarray(bg_idx, np.int32).reshape(-1))
+    hist = accumulator(hist, (fg.size, bg.size, EVAL_CLASSES + 1, EVAL_CLASSES + 1), dev, "hist")
+    bad = accumulator(bad, (1,), dev, "bad")
+    pi32 = C.POINTER(C.c_int32)
+    with torch.cuda.device(dev):
+        check(lib.irn_ir_label_confusion(pl.data_ptr(), t, fg.ctypes.data_as(pi32), int(fg.size), bg.ctypes.data_as(pi32),
+                                         int(bg.size), g.data_ptr(), h, w, hist.data_ptr(), bad.data_ptr(), _stream()))
+    return hist, bad

@@ -4,6 +4,7 @@ cam_confusion / label_confusion / mask_overlap).
     observed_classes(conf, void)      the size chainercv's growing confusion matrix reaches
     iou_from_confusion(conf, void)    calc_semantic_segmentation_confusion + the iou of step/eval_cam.py:22-28
     sem_seg_scores(conf, void)        step/eval_sem_seg.py:19-31 (fp / fn / iou of the [:21, :21] matrix)
+    ir_label_scores(hist)             step/tune_ir_label.py: accuracy, coverage and all-pixel iou of one IR-label grid point
     instance_ap_voc(records)          eval_instance_segmentation_voc(iou_thresh=0.5): calc_instance_segmentation_voc_prec_rec
                                       + calc_detection_voc_ap(use_07_metric=False), from per-image overlap counts
 
@@ -49,6 +50,24 @@ def sem_seg_scores(conf, void=None):
         fn = 1. - resj / denominator
         iou = gtjresj / denominator
     return {"fp": fp, "fn": fn, "iou": iou, "confusion": conf}
+
+
+def ir_label_scores(hist):
+    """Scores of one (fg, bg) point of step/tune_ir_label.py from hist int64 [22,22] of ops.ir_label_confusion (row = GT,
+    21 = void; column = IR label, 21 = 255 unsure) -> dict
+      iou, miou     sem_seg_scores of the [:21, :21] matrix: the accuracy on the confident pixels
+      coverage      the share of the non-void pixels that get a label
+      iou_all, miou_all   per class diag / (GT pixels, unsure ones included, + labelled pixels - diag): unsure pixels count
+                    as misses."""
+    hist = np.asarray(hist, np.int64)
+    conf, void = hist[:21, :21], hist[21, :21]
+    s = sem_seg_scores(conf, void)
+    diag = np.diag(conf)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        coverage = conf.sum() / hist[:21, :].sum()
+        iou_all = diag / (hist[:21, :].sum(axis=1) + conf.sum(axis=0) - diag)
+    return {"iou": s["iou"], "miou": nanmean(s["iou"]), "coverage": float(coverage), "iou_all": iou_all,
+            "miou_all": nanmean(iou_all)}
 
 
 def mask_iou_from_counts(inter, area_a, area_b):

@@ -1,0 +1,113 @@
+"""Tuning step (not in the reference): score a grid of --conf_fg_thres x --conf_bg_thres against the ground truth in ONE
+pass over the split — what cam_to_ir_label and a count of its PNGs give per grid point, without a label file.
+
+Reads  args.voc12_root (ImageSets/Segmentation/<args.chainer_eval_set>.txt, JPEGImages/<id>.jpg, SegmentationClass/<id>.png),
+       args.cam_out_dir/<id>.npy (`high_res` / `keys` of make_cam),
+       args.conf_fg_thres, args.conf_bg_thres (the configured point: always on the grid),
+       args.tune_conf_fg_thres, args.tune_conf_bg_thres (more values per axis)
+Prints the configured point's {'iou', 'miou', 'coverage', 'miou_all'}, one `fg .. bg .. miou .. coverage .. miou_all ..` line
+       per grid point and the best one (highest miou_all); returns the configured point's dict + 'grid' {(fg, bg): miou_all},
+       'scores' {(fg, bg): dict of evaluation.ir_label_scores}, 'hist' (numpy int64 [F,B,22,22]) and 'best'.  Writes nothing.
+
+IR labels are mined on args.train_list, but ground truth exists only for the segmentation split, so the ids of
+args.chainer_eval_set are scored (eval_cam makes the same choice).  The IR label of a pixel is fg if fg != 0, else 0 if bg == 0,
+else 255, where fg / bg are the CRF label maps seeded at the two thresholds (step/cam_to_ir_label.py:26-39), and a CRF label
+map depends on ONE threshold only: an F x B grid needs the CRF at the T distinct thresholds of both axes, not 2*F*B of them,
+and all T share the image's two lattices.  Per image `ops.crf_label_sweep` runs them (chunks of one filter each) and
+`ops.ir_label_confusion` counts every pair from the T planes; the histogram stays on the device and comes back once
+(DESIGN.md §23).  A plane is bit-equal to what `ops.crf_ir_label` computes for that threshold, so a grid point's counts are
+those of the PNGs cam_to_ir_label would write there.  An image without class keys contributes its all-zero map, as
+cam_to_ir_label writes it.  Runs in the calling process on its current device like the evaluation steps (step/_eval.py)."""
+import os
+
+import numpy as np
+import torch
+from PIL import Image
+
+from .. import ops
+from ..misc import evaluation
+from ..voc12 import dataloader as voc12_dataloader
+from ..voc12 import eval_data
+from . import _eval, _io
+
+MAX_AXIS = 16                         # values per axis (irn_ir_label_confusion)
+MAX_THRES = ops.CRF_MAX_SWEEP         # distinct thresholds over both axes together: CRFs per image
+
+
+def grid_axes(args):
+    """-> (fg values as requested, bg values as requested, all distinct thresholds ascending float32, fg plane numbers, bg
+    plane numbers): each axis holds its configured value, sorted and without repeats; values are told apart as float32 (the
+    seeds compare in float32) and the first spelling of a float32 value names it."""
+    axes = []
+    for what, conf, tune in (("foreground", "conf_fg_thres", "tune_conf_fg_thres"), ("background", "conf_bg_thres", "tune_conf_bg_thres")):
+        req = {}
+        for t in [float(getattr(args, conf))] + [float(t) for t in (getattr(args, tune, None) or ())]:
+            req.setdefault(float(np.float32(t)), t)
+        th32 = np.unique(np.asarray(list(req), np.float32))
+        if np.isnan(th32).any():
+            raise ValueError("tune_ir_label: a %s threshold is NaN" % what)
+        if th32.size > MAX_AXIS:
+            raise ValueError("tune_ir_label: %d %s thresholds (at most %d)" % (th32.size, what, MAX_AXIS))
+        axes.append(([req[float(t)] for t in th32], th32))
+    (fgs, fg32), (bgs, bg32) = axes
+    th32 = np.unique(np.concatenate([fg32, bg32]))
+    if th32.size > MAX_THRES:
+        raise ValueError("tune_ir_label: %d distinct thresholds over both axes (at most %d: each is one CRF per image)"
+                         % (th32.size, MAX_THRES))
+    return fgs, bgs, th32, np.searchsorted(th32, fg32).astype(np.int32), np.searchsorted(th32, bg32).astype(np.int32)
+
+
+def pick_best(grid):
+    """The grid point of the highest score; ties go to the smaller fg, then the smaller bg (a NaN never wins against a number)."""
+    def rank(point):
+        m = grid[point]
+        return (m == m, m if m == m else 0.0, -point[0], -point[1])
+    return max(grid, key=rank)
+
+
+def report(hist, fgs, bgs, configured):
+    """Scores of every grid point from hist int64 [F,B,22,22], printed in the step's format; returns the step's dict."""
+    scores = {(fg, bg): evaluation.ir_label_scores(hist[i, j]) for i, fg in enumerate(fgs) for j, bg in enumerate(bgs)}
+    grid = {point: s["miou_all"] for point, s in scores.items()}
+    here = scores[configured]
+    out = {k: here[k] for k in ("iou", "miou", "coverage", "miou_all")}
+    print(out)
+    for (fg, bg), s in scores.items():
+        print("fg %g bg %g miou %.6f coverage %.6f miou_all %.6f" % (fg, bg, s["miou"], s["coverage"], s["miou_all"]))
+    best = pick_best(grid)
+    s = scores[best]
+    print("best fg %g bg %g miou %.6f coverage %.6f miou_all %.6f" % (best + (s["miou"], s["coverage"], s["miou_all"])))
+    out.update(grid=grid, scores=scores, hist=hist, best=best)
+    return out
+
+
+def run(args):
+    fgs, bgs, th32, fg_idx, bg_idx = grid_axes(args)          # refusals before any image is read
+    configured = (fgs[int(np.searchsorted(th32[fg_idx], np.float32(args.conf_fg_thres)))],
+                  bgs[int(np.searchsorted(th32[bg_idx], np.float32(args.conf_bg_thres)))])
+    ids = eval_data.seg_ids(args.voc12_root, args.chainer_eval_set)
+    if not ids:
+        raise ValueError("tune_ir_label: the split %s lists no images" % args.chainer_eval_set)
+    dev = _eval.device()
+
+    def load(id):
+        gt = eval_data.class_label(args.voc12_root, id)
+        img = np.array(Image.open(voc12_dataloader.get_img_path(id, args.voc12_root)).convert("RGB"))
+        _eval.check_shape(id, "image", img.shape[:2], gt.shape)
+        cam = np.load(os.path.join(args.cam_out_dir, id + ".npy"), allow_pickle=True).item()
+        keys = np.asarray(cam["keys"], np.int64).reshape(-1)
+        if keys.size:
+            high_res = np.ascontiguousarray(cam["high_res"], np.float32)
+            _eval.check_shape(id, "high_res", high_res.shape, (keys.size,) + gt.shape)
+        else:
+            high_res = np.zeros((0,) + gt.shape, np.float32)
+        return {"gt": gt, "image": img, "high_res": high_res, "keys": keys}
+
+    with torch.cuda.device(dev):
+        hist = bad = None
+        for id, it in _eval.items(ids, load, args):
+            planes = ops.crf_label_sweep(_io.upload(it["image"]), _io.upload(it["high_res"]), _io.upload(it["keys"]), th32)
+            hist, bad = ops.ir_label_confusion(planes, fg_idx, bg_idx, _io.upload(it["gt"]), hist, bad)
+        _eval.raise_if_bad(bad, "tune_ir_label")
+        hist = hist.cpu().numpy()
+    return report(hist, fgs, bgs, configured)

@@ -3,7 +3,8 @@
 implements: the label-generation steps (make_cam, cam_to_ir_label, make_ins_seg, make_sem_seg), the evaluation
 steps that score them (eval_cam, eval_ins_seg, eval_sem_seg), the grid search over the semantic labels' three numbers
 (tune_sem_seg, step/tune_sem_seg.py; not in the reference), the same search over the instance labels' three numbers
-(tune_ins_seg, step/tune_ins_seg.py; not in the reference) and the COCO export of the instance labels (make_cocoann,
+(tune_ins_seg, step/tune_ins_seg.py; not in the reference), the search over the IR labels' two thresholds (tune_ir_label,
+step/tune_ir_label.py; not in the reference) and the COCO export of the instance labels (make_cocoann,
 step/make_cocoann.py; not in the reference's run_sample.py, which leaves it to be run by hand).
 
 The training steps of the reference have commands of their own (train_cam: run_train_cam.py, train_irn: run_train.py);
@@ -67,6 +68,11 @@ def build_parser():
     p.add_argument("--tune_ins_bg_thres", default=[], type=float, nargs="*",
                    help="tune_ins_seg: more values of --ins_seg_bg_thres on its grid (with --tune_beta / --tune_exp_times; at most "
                         "64: each one is a labelling pass per walk)")
+    p.add_argument("--tune_conf_fg_thres", default=[], type=float, nargs="*",
+                   help="tune_ir_label: more values of --conf_fg_thres on its grid (not in the reference; at most 16 per axis and "
+                        "16 distinct thresholds over both axes: each is one CRF per image)")
+    p.add_argument("--tune_conf_bg_thres", default=[], type=float, nargs="*",
+                   help="tune_ir_label: more values of --conf_bg_thres on its grid")
     p.add_argument("--worker_devices", default="", type=str,
                    help="device ordinal of every worker process, e.g. 0,1,2,3 (default: one per visible GPU like the reference; "
                         "0,0 = two workers sharing GPU 0)")
@@ -116,7 +122,8 @@ def build_parser():
     for name, default in (("train_cam_pass", False), ("make_cam_pass", True), ("eval_cam_pass", False),
                           ("cam_to_ir_label_pass", False), ("train_irn_pass", False), ("make_ins_seg_pass", True),
                           ("eval_ins_seg_pass", False), ("make_cocoann_pass", False), ("make_sem_seg_pass", True),
-                          ("eval_sem_seg_pass", False), ("tune_sem_seg_pass", False), ("tune_ins_seg_pass", False)):
+                          ("eval_sem_seg_pass", False), ("tune_sem_seg_pass", False), ("tune_ins_seg_pass", False),
+                          ("tune_ir_label_pass", False)):
         p.add_argument("--" + name, default=default, type=_flag)
     return p
 
@@ -183,6 +190,10 @@ def main(argv=None):
         from irn_amd.step import tune_ins_seg
         timer = pyutils.Timer("step.tune_ins_seg:")  # noqa: F841
         results["tune_ins_seg"] = tune_ins_seg.run(args)
+    if args.tune_ir_label_pass is True:
+        from irn_amd.step import tune_ir_label
+        timer = pyutils.Timer("step.tune_ir_label:")  # noqa: F841
+        results["tune_ir_label"] = tune_ir_label.run(args)
     from irn_amd.step import _common
     _common.shutdown_workers()           # the per-GPU workers served every pass above
     return results                       # what the evaluation passes printed, by step name

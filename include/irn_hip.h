@@ -445,6 +445,18 @@ int irn_split16(const float *x_dev, const float *scale_dev, const float *shift_d
  *   operand is the same buffer read with leading dimension 3 cin and 9 cin columns.  algo_rank / workspace as irn_conv1x1_nhwc. */
 int irn_split16_pad(const float *x_dev, const float *scale_dev, const float *shift_dev, int relu, void *out_dev, int64_t n_images,
                     int h, int w, int n_channels, int in_padded, int out_padded, unsigned *overflow_dev, void *stream);
+/* The same two passes with the overflow attributed PER SAMPLE (a sample = one leading row of the network input: n_pixels /
+ * pixels_per_sample of them in the dense form, n_images in the padded form): flags_dev is dev uint32 [n_samples], never NULL, and
+ * bit 0 of flags_dev[s] is set (atomicOr; the other bits and the words of other samples are left alone) when an element of sample
+ * s failed the same test on the same value — |y| > 65504 or NaN, y = the value that is split, after scale / shift / relu.  Sample
+ * of a row: row / pixels_per_sample (dense; n_pixels must be a multiple of pixels_per_sample), the image index n (padded, either
+ * direction); border rows of the bordered output are written as zeros and flag nothing, border rows of a bordered input are never
+ * read.  The fp16 output is bit for bit that of irn_split16 / irn_split16_pad, which keep their single flag word; the caller
+ * zeroes flags_dev and reads it behind the stream — a set bit means "this sample needs the fp32 path", the others do not. */
+int irn_split16_samples(const float *x_dev, const float *scale_dev, const float *shift_dev, int relu, void *out_dev, int64_t n_pixels,
+                        int n_channels, int64_t pixels_per_sample, unsigned *flags_dev, void *stream);
+int irn_split16_pad_samples(const float *x_dev, const float *scale_dev, const float *shift_dev, int relu, void *out_dev, int64_t n_images,
+                            int h, int w, int n_channels, int in_padded, int out_padded, unsigned *flags_dev, void *stream);
 int irn_conv3x3_split_gemm(const void *a16_dev, const void *w16_dev, float *out_dev, int64_t n_images, int h, int w, int cin, int cout,
                            float alpha, int row_fused, int algo_rank, void *workspace_dev, size_t workspace_bytes, void *stream);
 int irn_gemm16_algo_count(int64_t m, int k, int cout, int has_bias, int has_residual, int relu, size_t workspace_bytes,

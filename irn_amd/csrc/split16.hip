@@ -37,7 +37,7 @@ template <bool BN, bool RELU>
 __global__ __launch_bounds__(kThreads) void split16_kernel(const float *__restrict__ x, const float *__restrict__ scale,
                                                            const float *__restrict__ shift, _Float16 *__restrict__ out,
                                                            unsigned n_pieces, unsigned n_ch, unsigned pieces_per_row,
-                                                           unsigned *__restrict__ overflow, PadMap pm) {
+                                                           unsigned *__restrict__ overflow, unsigned rows_per_sample, PadMap pm) {
     const unsigned p = blockIdx.x * (unsigned)kThreads + threadIdx.x;
     if (p >= n_pieces) return;
     unsigned row = p / pieces_per_row;
@@ -84,11 +84,14 @@ __global__ __launch_bounds__(kThreads) void split16_kernel(const float *__restri
         lo[k] = (_Float16)((v[k] - (float)h) * 2048.f);
         bad |= !(fabsf(v[k]) <= kFp16Max);               // beyond fp16's range, or NaN
     }
+    // rows_per_sample != 0: `overflow` is one word per sample (irn_split16_samples); `row` counts the rows the threads enumerate,
+    // so a sample is rows_per_sample of them in either form.  The division exists in this rare branch only — in front of the
+    // stores, where `row` is alive anyway (behind them it would cost the plain kernel two registers).
+    if (bad && overflow) atomicOr(rows_per_sample ? overflow + row / rows_per_sample : overflow, 1u);
     _Float16 *dst = out + (size_t)row * (3u * n_ch) + c0;
     *reinterpret_cast<h8v *>(dst) = hi;
     *reinterpret_cast<h8v *>(dst + n_ch) = hi;
     *reinterpret_cast<h8v *>(dst + 2u * n_ch) = lo;
-    if (bad && overflow) atomicOr(overflow, 1u);
 }
 
 }  // namespace
@@ -97,7 +100,7 @@ __global__ __launch_bounds__(kThreads) void split16_kernel(const float *__restri
 namespace irn {
 namespace {
 int split16_launch(const float *x_dev, const float *scale_dev, const float *shift_dev, int relu, void *out_dev, int64_t n_pixels,
-                   int n_channels, unsigned *overflow_dev, void *stream, PadMap pm) {
+                   int n_channels, unsigned *overflow_dev, int64_t pixels_per_sample, void *stream, PadMap pm) {
     if (!x_dev || !out_dev) return fail(IRN_ERR_ARG, "irn_split16: null pointer");
     if ((scale_dev != nullptr) != (shift_dev != nullptr)) return fail(IRN_ERR_ARG, "irn_split16: scale and shift come together");
     if (relu && !scale_dev) return fail(IRN_ERR_ARG, "irn_split16: relu only with the batch norm in front of it");
@@ -106,6 +109,12 @@ int split16_launch(const float *x_dev, const float *scale_dev, const float *shif
         return fail(IRN_ERR_ARG, "irn_split16: tensors and constants must be 16-byte aligned");
     int64_t rows = n_pixels;                       // rows the threads enumerate: the bordered form's when it is the output
     if (pm.out_pad) rows = n_pixels / ((int64_t)pm.h * pm.w) * (pm.h + 2) * (pm.w + 2);
+    // per-sample flags (pixels_per_sample > 0): whole samples only, so that every enumerated row has a flag word of its own sample
+    if (pixels_per_sample < 0 || pixels_per_sample >= (1ll << 31)) return fail(IRN_ERR_ARG, "irn_split16: pixels_per_sample must be in [1, 2^31)");
+    if (pixels_per_sample && !overflow_dev) return fail(IRN_ERR_ARG, "irn_split16: per-sample flags need flags_dev");
+    if (pixels_per_sample && n_pixels % pixels_per_sample) return fail(IRN_ERR_ARG, "irn_split16: n_pixels must be a multiple of pixels_per_sample");
+    unsigned rps = (unsigned)pixels_per_sample;
+    if (rps && pm.out_pad) rps = (pm.h + 2u) * (pm.w + 2u);
     const int64_t numel = rows * n_channels;
     if (numel == 0) return IRN_OK;
     if (numel >= (1ll << 31)) return fail(IRN_ERR_ARG, "irn_split16: %lld elements; at most 2^31 - 1 per call", (long long)numel);
@@ -113,9 +122,9 @@ int split16_launch(const float *x_dev, const float *scale_dev, const float *shif
     const dim3 grid((n_pieces + kThreads - 1) / kThreads), block(kThreads);
     hipStream_t s = (hipStream_t)stream;
     _Float16 *out = (_Float16 *)out_dev;
-    if (!scale_dev) hipLaunchKernelGGL((split16_kernel<false, false>), grid, block, 0, s, x_dev, scale_dev, shift_dev, out, n_pieces, (unsigned)n_channels, ppr, overflow_dev, pm);
-    else if (relu) hipLaunchKernelGGL((split16_kernel<true, true>), grid, block, 0, s, x_dev, scale_dev, shift_dev, out, n_pieces, (unsigned)n_channels, ppr, overflow_dev, pm);
-    else hipLaunchKernelGGL((split16_kernel<true, false>), grid, block, 0, s, x_dev, scale_dev, shift_dev, out, n_pieces, (unsigned)n_channels, ppr, overflow_dev, pm);
+    if (!scale_dev) hipLaunchKernelGGL((split16_kernel<false, false>), grid, block, 0, s, x_dev, scale_dev, shift_dev, out, n_pieces, (unsigned)n_channels, ppr, overflow_dev, rps, pm);
+    else if (relu) hipLaunchKernelGGL((split16_kernel<true, true>), grid, block, 0, s, x_dev, scale_dev, shift_dev, out, n_pieces, (unsigned)n_channels, ppr, overflow_dev, rps, pm);
+    else hipLaunchKernelGGL((split16_kernel<true, false>), grid, block, 0, s, x_dev, scale_dev, shift_dev, out, n_pieces, (unsigned)n_channels, ppr, overflow_dev, rps, pm);
     IRN_LAUNCH_CHECK("split16_kernel");
     return IRN_OK;
 }
@@ -124,7 +133,14 @@ int split16_launch(const float *x_dev, const float *scale_dev, const float *shif
 
 extern "C" int irn_split16(const float *x_dev, const float *scale_dev, const float *shift_dev, int relu, void *out_dev,
                            int64_t n_pixels, int n_channels, unsigned *overflow_dev, void *stream) {
-    return irn::split16_launch(x_dev, scale_dev, shift_dev, relu, out_dev, n_pixels, n_channels, overflow_dev, stream, irn::PadMap{0u, 0u, 0, 0});
+    return irn::split16_launch(x_dev, scale_dev, shift_dev, relu, out_dev, n_pixels, n_channels, overflow_dev, 0, stream, irn::PadMap{0u, 0u, 0, 0});
+}
+
+extern "C" int irn_split16_samples(const float *x_dev, const float *scale_dev, const float *shift_dev, int relu, void *out_dev,
+                                   int64_t n_pixels, int n_channels, int64_t pixels_per_sample, unsigned *flags_dev, void *stream) {
+    if (pixels_per_sample < 1 || !flags_dev) return irn::fail(IRN_ERR_ARG, "irn_split16_samples: pixels_per_sample >= 1 and flags_dev are needed");
+    return irn::split16_launch(x_dev, scale_dev, shift_dev, relu, out_dev, n_pixels, n_channels, flags_dev, pixels_per_sample, stream,
+                               irn::PadMap{0u, 0u, 0, 0});
 }
 
 extern "C" int irn_split16_pad(const float *x_dev, const float *scale_dev, const float *shift_dev, int relu, void *out_dev,
@@ -133,6 +149,16 @@ extern "C" int irn_split16_pad(const float *x_dev, const float *scale_dev, const
     using namespace irn;
     if (n_images < 0 || h < 1 || w < 1) return fail(IRN_ERR_ARG, "irn_split16_pad: n_images >= 0, h, w >= 1");
     if ((int64_t)n_images * (h + 2) * (w + 2) * n_channels >= (1ll << 31)) return fail(IRN_ERR_ARG, "irn_split16_pad: at most 2^31 - 1 padded elements per call");
-    return split16_launch(x_dev, scale_dev, shift_dev, relu, out_dev, n_images * h * w, n_channels, overflow_dev, stream,
+    return split16_launch(x_dev, scale_dev, shift_dev, relu, out_dev, n_images * h * w, n_channels, overflow_dev, 0, stream,
+                          PadMap{(unsigned)h, (unsigned)w, in_padded ? 1 : 0, out_padded ? 1 : 0});
+}
+
+extern "C" int irn_split16_pad_samples(const float *x_dev, const float *scale_dev, const float *shift_dev, int relu, void *out_dev,
+                                       int64_t n_images, int h, int w, int n_channels, int in_padded, int out_padded, unsigned *flags_dev,
+                                       void *stream) {
+    using namespace irn;
+    if (n_images < 0 || h < 1 || w < 1 || !flags_dev) return fail(IRN_ERR_ARG, "irn_split16_pad_samples: n_images >= 0, h, w >= 1 and flags_dev are needed");
+    if ((int64_t)n_images * (h + 2) * (w + 2) * n_channels >= (1ll << 31)) return fail(IRN_ERR_ARG, "irn_split16_pad_samples: at most 2^31 - 1 padded elements per call");
+    return split16_launch(x_dev, scale_dev, shift_dev, relu, out_dev, n_images * h * w, n_channels, flags_dev, (int64_t)h * w, stream,
                           PadMap{(unsigned)h, (unsigned)w, in_padded ? 1 : 0, out_padded ? 1 : 0});
 }

@@ -3,8 +3,9 @@ reference net/resnet50.py:34-54 with FixedBatchNorm folded into the operands):
     conv1x1_nhwc                          fp32 GEMM with bias / residual / ReLU in its epilogue
     split16, split_weight, gemm16_nhwc    the split-precision form of the same: fp16 hi/lo operands, fp32 accumulation
     split16_pad, split_weight_3x3, conv3x3_split     3x3 / stride 1 as accumulating split GEMMs on one zero-bordered operand
-and their state: the shipped rank table, the per-stream workspace, the fp16 overflow flags.  `irn_amd.ops` re-exports the
+and their state: the shipped rank table, the per-stream workspace, the fp16 overflow flags (process-wide, or per sample inside `sample_flags`).  `irn_amd.ops` re-exports the
 functions; the state lives here only.  GPU tensors in, GPU tensors out; no CPU fallback."""
+import contextlib
 import ctypes as C
 import json
 import math
@@ -170,10 +171,37 @@ def split_overflowed(reset=True):
     return bad
 
 
-def split16(x, scale=None, shift=None, relu=False):
+_SAMPLE_FLAGS = [None]     # the per-sample flag tensor every split pass records into while a `sample_flags` block is open
+
+
+def _need_flags(flags, n, device, what):
+    """`flags` is a contiguous int32 [n] tensor on `device`: one word per sample (leading row) of the activation."""
+    if (not isinstance(flags, torch.Tensor) or flags.dtype != torch.int32 or flags.device != device or not flags.is_contiguous()
+            or flags.dim() != 1 or flags.numel() != n):
+        raise ValueError("%s: flags must be a contiguous int32 [%d] tensor on %s (one word per sample), got %s" % (
+            what, n, device, "%s %s on %s" % (flags.dtype, tuple(flags.shape), flags.device) if isinstance(flags, torch.Tensor) else type(flags)))
+
+
+@contextlib.contextmanager
+def sample_flags(flags):
+    """Inside the block every `split16` / `split16_pad` / `conv3x3_split` that is not given `flags` of its own records into
+    `flags` (int32 [n_samples], bit 0 of word s = a value of sample s left fp16's range or was NaN; the caller zeroes it and
+    reads it behind the stream) INSTEAD of the process-wide flag `split_overflowed` reads: a trunk forward — `model(x)` with
+    n_samples = x.shape[0] — is instrumented without an argument through every unit.  Every activation split inside must have
+    n_samples leading rows.  `flags` None: the block changes nothing.  The former state comes back however the block ends."""
+    prev, _SAMPLE_FLAGS[0] = _SAMPLE_FLAGS[0], flags
+    try:
+        yield flags
+    finally:
+        _SAMPLE_FLAGS[0] = prev
+
+
+def split16(x, scale=None, shift=None, relu=False, flags=None):
     """fp32 channels-last activation [N, C, H, W] -> fp16 [N*H*W, 3C] = [hi | hi | lo'] per pixel (irn_split16), the A operand
     of `gemm16_nhwc`; with `scale` / `shift` (fp32 [C]) the inference batch norm (+ ReLU) of the convolution that produced
-    `x` is applied on the way (reference net/resnet50.py:40-42) and `x` is never written back."""
+    `x` is applied on the way (reference net/resnet50.py:40-42) and `x` is never written back.  `flags` (int32 [N], or the
+    tensor of an enclosing `sample_flags`): the overflow is recorded per sample there (irn_split16_samples) and the
+    process-wide flag is left alone; the fp16 result is the same bits."""
     _need_cuda(x, "x")
     _need_cl(x, "split16: x")
     n, c, h, w_ = (int(v) for v in x.shape)
@@ -186,12 +214,25 @@ def split16(x, scale=None, shift=None, relu=False):
     for name, t in (("scale", scale), ("shift", shift)):
         if t is not None:
             _need_vec(t, "split16: " + name, c, x.device)
+    if flags is None:
+        flags = _SAMPLE_FLAGS[0]
+    sp, tp = None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr()
     with torch.cuda.device(x.device):
         per = max(1, (2 ** 31 - 1) // c)
+        if flags is not None:
+            _need_flags(flags, n, x.device, "split16")
+            pps = h * w_
+            per = per // pps * pps                       # whole samples per call
+            if per == 0:
+                raise ValueError("split16: a sample of %d x %d elements; per-sample flags need fewer than 2^31 per sample" % (pps, c))
+            for i in range(0, m, per):
+                check(lib.irn_split16_samples(x.data_ptr() + 4 * i * c, sp, tp, 1 if relu else 0, out.data_ptr() + 2 * i * 3 * c, min(per, m - i), c,
+                                              pps, flags.data_ptr() + 4 * (i // pps), _stream()))
+            return out
         for i in range(0, m, per):                       # at most 2^31 - 1 elements per call
             rows = min(per, m - i)
-            check(lib.irn_split16(x.data_ptr() + 4 * i * c, None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr(),
-                                  1 if relu else 0, out.data_ptr() + 2 * i * 3 * c, rows, c, _split_flag(x.device).data_ptr(), _stream()))
+            check(lib.irn_split16(x.data_ptr() + 4 * i * c, sp, tp, 1 if relu else 0, out.data_ptr() + 2 * i * 3 * c, rows, c,
+                                  _split_flag(x.device).data_ptr(), _stream()))
     return out
 
 
@@ -256,11 +297,12 @@ def split_weight_3x3(w64):
     return torch.stack(taps).contiguous(), 2.0 ** -p
 
 
-def split16_pad(x, shape, scale=None, shift=None, relu=False, in_padded=False, out=None):
+def split16_pad(x, shape, scale=None, shift=None, relu=False, in_padded=False, out=None, flags=None):
     """`split16` between a dense map and its zero-bordered form (irn_split16_pad).  shape = (n, c, h, w) of the DENSE map.
     in_padded: `x` is the bordered fp32 form [n (h+2)(w+2), c] (a `conv3x3_split` result), the result is the dense fp16
     [n h w, 3c]; `out` given (a bordered fp16 buffer's interior view, borders already zero): `x` is a dense channels-last fp32
-    tensor and the split goes into the bordered form, zero border rows included."""
+    tensor and the split goes into the bordered form, zero border rows included.  `flags`: as in `split16`, one word per image
+    (irn_split16_pad_samples)."""
     n, c, h, w_ = (int(v) for v in shape)
     _need_cuda(x, "x")
     if c % 8:
@@ -277,10 +319,15 @@ def split16_pad(x, shape, scale=None, shift=None, relu=False, in_padded=False, o
         raise ValueError("split16_pad: out must be a contiguous fp16 buffer of the bordered form (its border rows are written too)")
     if n * h * w_ == 0:
         return out
+    if flags is None:
+        flags = _SAMPLE_FLAGS[0]
+    if flags is not None:
+        _need_flags(flags, n, x.device, "split16_pad")
     with torch.cuda.device(x.device):
-        check(lib.irn_split16_pad(x.data_ptr(), None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr(),
-                                  1 if relu else 0, out.data_ptr(), n, h, w_, c, 1 if in_padded else 0, 1 if out_padded else 0,
-                                  _split_flag(x.device).data_ptr(), _stream()))
+        fn = lib.irn_split16_pad if flags is None else lib.irn_split16_pad_samples
+        check(fn(x.data_ptr(), None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr(),
+                 1 if relu else 0, out.data_ptr(), n, h, w_, c, 1 if in_padded else 0, 1 if out_padded else 0,
+                 (_split_flag(x.device) if flags is None else flags).data_ptr(), _stream()))
     return out
 
 

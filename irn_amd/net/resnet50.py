@@ -14,6 +14,7 @@ Differences by design:
     convolutions stay on MIOpen.  With autograd on (the training seam) or on the CPU the composed PyTorch ops run —
     unless TRAIN_FUSED_TAIL is set, which gives the training seam the same tail as one differentiable pass (`ops.bn_act`).
 """
+import contextlib
 import os
 
 import torch
@@ -125,6 +126,8 @@ def run_rows(fn, x):
     n = int(x.shape[0])
     if rows is None or n == rows:
         return fn(x)
+    from .. import gemm
+    flags = gemm._SAMPLE_FLAGS[0]       # per-sample fp16-range flags of an enclosing `gemm.sample_flags`: one word per row of x
     outs = []
     for i in range(0, n, rows):
         chunk = x[i:i + rows]
@@ -132,7 +135,17 @@ def run_rows(fn, x):
         if valid < rows:
             PASS_STATS["pad_rows"] += rows - valid
             chunk = torch.cat([chunk, chunk.new_zeros((rows - valid,) + tuple(chunk.shape[1:]))])
-        y = fn(chunk)
+        if flags is None:
+            y = fn(chunk)
+        elif valid == rows:
+            with gemm.sample_flags(flags[i:i + rows]):         # the pass records into its own rows' words
+                y = fn(chunk)
+        else:
+            # the fill rows get scratch words that go with their outputs (a zero image overflows too once a shift is large)
+            scratch = flags.new_zeros(rows)
+            with gemm.sample_flags(scratch):
+                y = fn(chunk)
+            flags[i:i + valid] |= scratch[:valid]
         outs.append(tuple(t[:valid] for t in y) if isinstance(y, tuple) else y[:valid])
     if len(outs) == 1:
         return outs[0]
@@ -192,6 +205,10 @@ FUSED_GEMM = os.environ.get("IRN_FUSED_GEMM", "1") != "0"
 #       of its own (10 bytes per element), worth it only where the GEMMs it feeds are large — cin * (sum of their cout) >=
 #       SPLIT_MIN_INPUT (stage 4 of the trunk; profiles/r06_s2_split_gemm_fp16_note.txt).
 SPLIT_GEMM = os.environ.get("IRN_SPLIT_GEMM", "1") != "0"
+# IRN_SPLIT_GEMM=auto: split precision as above, and make_cam / make_sem_seg_labels / make_ins_seg_labels record the fp16-range
+# flag per sample (ops.split_sample_flags), write nothing of an image that left the range and compute that image again on the
+# fp32 GEMMs (`fp32_gemms`) — its files are those of an IRN_SPLIT_GEMM=0 run, everybody else's those of an IRN_SPLIT_GEMM=1 run.
+SPLIT_AUTO = os.environ.get("IRN_SPLIT_GEMM", "1").strip().lower() == "auto"
 SPLIT_MIN_PLANES = int(os.environ.get("IRN_SPLIT_MIN_PLANES", "64"))
 SPLIT_MIN_INPUT = int(os.environ.get("IRN_SPLIT_MIN_INPUT", str(1 << 20)))
 #   conv2 (3x3, stride 1) of units with at least SPLIT_MIN_PLANES_3X3 planes on maps of at least SPLIT_MIN_ROWS_3X3 pixels per
@@ -203,6 +220,30 @@ SPLIT_MIN_INPUT = int(os.environ.get("IRN_SPLIT_MIN_INPUT", str(1 << 20)))
 #       (profiles/r06_s9_conv3x3_row_fused_ab.txt): stages 2-4.
 SPLIT_MIN_PLANES_3X3 = int(os.environ.get("IRN_SPLIT_MIN_PLANES_3X3", "128"))
 SPLIT_MIN_ROWS_3X3 = int(os.environ.get("IRN_SPLIT_MIN_ROWS_3X3", "8192"))
+
+
+@contextlib.contextmanager
+def fp32_gemms():
+    """The split-precision GEMMs off inside the block (what IRN_SPLIT_GEMM=0 computes), the former setting back however it
+    ends.  `Bottleneck.gemm_params` keys its cache on the switch: nothing to clear."""
+    global SPLIT_GEMM
+    saved, SPLIT_GEMM = SPLIT_GEMM, False
+    try:
+        yield
+    finally:
+        SPLIT_GEMM = saved
+
+
+def set_split_mode(value):
+    """`--split_gemm` / IRN_SPLIT_GEMM as one value — 0, 1 or "auto" (any case; integers and their strings alike) — into the
+    environment (workers read it when they import this module) and the two module switches.  -> the normalised string."""
+    global SPLIT_GEMM, SPLIT_AUTO
+    v = str(value).strip().lower()
+    if v not in ("0", "1", "auto"):
+        raise ValueError("split_gemm must be 0, 1 or auto, got %r" % (value,))
+    os.environ["IRN_SPLIT_GEMM"] = v
+    SPLIT_GEMM, SPLIT_AUTO = v != "0", v == "auto"
+    return v
 
 
 def _gemm_path(x):
@@ -325,18 +366,23 @@ class Bottleneck(nn.Module):
                                             FrozenBatchNorm(c_out))
 
     _gemm = None
+    _gemm_other = None
 
     def gemm_params(self):
         """The unit's 1x1 convolutions as GEMM operands: weights [cout, cin] with their batch norm's scale folded in
         (double precision, rounded once), the shifts as biases; for a projection unit the shortcut's shift rides in
         conv3's bias (the shortcut GEMM has none).  Cached until a parameter or statistic is written or moved, or a switch
-        that decides which operands exist changes.  bn2 is not in here: `_forward_gemm` reads `bn2.folded()` where it uses it."""
+        that decides which operands exist changes (both settings of SPLIT_GEMM are kept once both were asked for).  bn2 is not in here: `_forward_gemm` reads `bn2.folded()` where it uses it."""
         from .. import gemm
         convs = [self.conv1, self.conv3] + ([] if self.downsample is None else [self.downsample[0]])
         bns = [self.bn1, self.bn3] + ([] if self.downsample is None else [self.downsample[1]])
         src = [c.weight for c in convs] + [self.conv2.weight] + [t for b in bns for t in (b.weight, b.bias, b.running_mean, b.running_var)]
         key = (tuple((t.data_ptr(), _version(t)) for t in src), SPLIT_GEMM, SPLIT_MIN_PLANES, SPLIT_MIN_PLANES_3X3, SPLIT_MIN_INPUT,
                gemm.CONV3X3_ROW_FUSED)
+        if (self._gemm is None or self._gemm[0] != key) and self._gemm_other is not None and self._gemm_other[0] == key:
+            # the other setting of SPLIT_GEMM, kept from before the switch was flipped (`fp32_gemms`, bench.py's fp32 legs): no
+            # second fold — preparing the split operands reads a maximum back from the device
+            self._gemm, self._gemm_other = self._gemm_other, self._gemm
         if self._gemm is None or self._gemm[0] != key:
             with torch.no_grad():
                 folded, folded64 = [], []
@@ -367,6 +413,8 @@ class Bottleneck(nn.Module):
                         p["w1_16"], p["a1"] = gemm.split_weight(folded64[0].flatten(1))
                         if self.downsample is not None and tuple(self.downsample[0].stride) == (1, 1):
                             p["wd_16"], p["ad"] = gemm.split_weight(folded64[2].flatten(1))
+            # what was current stays at hand when it differs in SPLIT_GEMM alone
+            self._gemm_other = self._gemm if self._gemm is not None and self._gemm[0][0] == key[0] and self._gemm[0][2:] == key[2:] else None
             self._gemm = (key, p)
         return self._gemm[1]
 

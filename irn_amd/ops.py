@@ -46,6 +46,7 @@ from .eval_counts import (EVAL_CLASSES, EVAL_MAX_THRES, cam_confusion, cam_confu
                           label_confusion, mask_overlap)
 from .gemm import (conv1x1_algo_count, conv1x1_nhwc, conv3x3_split, gemm16_algo_count, gemm16_nhwc, gemm_ranks, gemm_ranks16,
                    gemm_ranks3x3, split16, split16_pad, split_overflowed, split_weight, split_weight_3x3)
+from .gemm import sample_flags as split_sample_flags
 from .instance import (PendingDetections, PendingOverlaps, PendingRleDetections, argmax_rethreshold_batch, cluster_centroids,
                        cluster_centroids_batch, detect_batch_count, detect_instance, detect_instance_batch, detect_instance_rle_batch,
                        detection_overlap_batch, find_centroids_batch, find_centroids_with_refinement, label4)

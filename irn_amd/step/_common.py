@@ -5,6 +5,7 @@
     step/_io.py         loader threads, page-locked pool, uploads, writer threads, shard_io
     step/_report.py     start-up and summary lines, the fp16-range check, the counters bench.py reads
     step/_labels.py     walk_radius, make_walker
+    step/_split_auto.py `--split_gemm auto`: per-image fp16-range flags on their way to the host, the redo list
 Every object has one home, is only ever changed in place and is never rebound, so `_common.CAM_STORE` IS `_stores.CAM_STORE`.
 Code inside the package imports the home modules, and that is where it looks names up: a monkeypatch has to name the home
 module, a patch of `_common` reaches nobody."""
@@ -30,7 +31,7 @@ from ._io import (_UPLOADS, MAX_LOADER_THREADS, PINNED, AsyncWriter, PinnedPool,
 from ._labels import make_walker, walk_radius                                                                           # noqa: F401
 from ._pool import (_MODELS, _POOL, ModelSpec, WorkerPool, get_pool, import_network, materialise, n_gpus_or_raise,       # noqa: F401
                     pool_stats, shutdown_workers, spawn_workers, step_timeout, worker_device, worker_devices)
-from ._report import (CAM_STATS, WALK_STATS, check_split_overflow, say, startup_line, step_summary,                     # noqa: F401
+from ._report import (CAM_STATS, SPLIT_STATS, WALK_STATS, check_split_overflow, say, startup_line, step_summary,                     # noqa: F401
                       untuned_report)
 from ._stores import (CAM_OWNERS, CAM_STORE, EDGE_STORE, CamStore, EdgeStore, current_cam_run, image_stamp,              # noqa: F401
                       keep_cams, keep_edges, label_step_shards, new_cam_run, split_by_owner)

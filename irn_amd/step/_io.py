@@ -178,6 +178,10 @@ class AsyncWriter:
         self._reap(self._max - 1)
         self._pending.append(self._pool.submit(fn, *args, **kw))
 
+    def drain(self):
+        """Wait for every write submitted so far (re-raises a failed one); the writer stays open."""
+        self._reap(0)
+
     def close(self):
         try:
             self._reap(0)

@@ -15,7 +15,7 @@ from PIL import Image
 
 from ..voc12 import dataloader as voc12_dataloader
 from .. import _tuned
-from . import _io, _pool, _report, _stores
+from . import _io, _pool, _report, _split_auto, _stores
 
 RADIUS = 5   # hard-coded at both reference call sites (step/make_sem_seg_labels.py:41, step/make_ins_seg_labels.py:135)
 
@@ -51,11 +51,13 @@ def walk_batch(args, default):
     return int(getattr(args, "walk_batch", 0) or default)       # images per walk launch (results per image unchanged)
 
 
-def edges_for(model, pend, irn_batch, store=None, model_key=None, dump_dir=None):
+def edges_for(model, pend, irn_batch, store=None, model_key=None, dump_dir=None, auto=False):
     """EdgeDisplacement forward for the pending images, `irn_batch` at a time: ragged images are padded to the
     512^2 crop like the reference pads each one (net/resnet50_irn.py:225), so a chunk is ONE trunk pass.  With a `store`
     (`_stores.EDGE_STORE`) the maps the other label step already computed for an image (same network, same file) are taken
-    from device memory instead, and what is computed here is left there for it."""
+    from device memory instead, and what is computed here is left there for it.  `auto` (`--split_gemm auto`): the passes record
+    the fp16-range flag per row; every image computed here gets `_split_flags` (device int32 [2]: image, flip) and keeps its
+    `_edge_key` — `flag_read` sends the words to the host, `drop_flagged` acts on them.  A store hit is final and gets neither."""
     todo = pend
     if store is not None:
         todo = []
@@ -77,11 +79,22 @@ def edges_for(model, pend, irn_batch, store=None, model_key=None, dump_dir=None)
             p["img"] = _io.device_images({"img": img[None]}, (1.0,))[0]
     for i in range(0, len(todo), irn_batch):
         chunk = todo[i:i + irn_batch]
-        for p, (edge, dp) in zip(chunk, model.forward_batch([p.pop("img") for p in chunk])):
+        flags = torch.zeros(2 * len(chunk), dtype=torch.int32, device=chunk[0]["img"].device) if auto else None
+        with _split_auto.recording(flags):
+            maps = model.forward_batch([p.pop("img") for p in chunk])
+        if auto:
+            # an image that left the range is computed again later and nothing of this pass is written; until the host knows,
+            # the walk and the instance kernels get zero maps for it instead of NaN (decided on the device)
+            bad, zero = (flags.view(-1, 2) != 0).any(dim=1), flags.new_zeros((), dtype=torch.float32)
+        for j, (p, (edge, dp)) in enumerate(zip(chunk, maps)):
+            if auto:
+                edge, dp = torch.where(bad[j], zero, edge), torch.where(bad[j], zero, dp)
             p["edge"], p["dp"] = edge, dp
             key = p.pop("_edge_key", None)
             if store is not None and key is not None:
                 store.put(key, edge, dp.clone())         # dp is a view into the batch's output: keep 1 image, not 8
+            if auto:
+                p["_split_flags"], p["_edge_key"] = flags[2 * j:2 * j + 2], key
     if dump_dir:
         # verification aid (args.edge_out_dir, off by default): the maps this step walks on, per image, so that a run can be
         # checked against the oracle on ITS OWN inputs (the reference keeps them in memory only, step/make_sem_seg_labels.py:28-34).
@@ -89,6 +102,47 @@ def edges_for(model, pend, irn_batch, store=None, model_key=None, dump_dir=None)
         os.makedirs(dump_dir, exist_ok=True)
         for p in pend:
             np.save(os.path.join(dump_dir, p["name"] + ".npy"), {"edge": p["edge"].cpu().numpy(), "dp": p["dp"].cpu().numpy()})
+
+
+def flag_read(items):
+    """`--split_gemm auto`: the flag words `edges_for(auto=True)` left with `items`, gathered ([2 n] int32, zeros for store hits)
+    and sent to page-locked memory on the current stream -> the `_split_auto.FlagRead` to look at behind the batch's own
+    read-back, or None when no image of the batch was computed here."""
+    if not any("_split_flags" in p for p in items):
+        return None
+    zero = None
+    words = []
+    for p in items:
+        f = p.get("_split_flags")
+        if f is None:
+            zero = f = zero if zero is not None else torch.zeros(2, dtype=torch.int32, device=p["edge"].device)
+        words.append(f)
+    read = _split_auto.FlagRead(torch.cat(words), [p["name"] for p in items])
+    read.edge_keys = {p["name"]: p.get("_edge_key") for p in items}
+    read.sizes = {p["name"]: p["size"] for p in items}
+    return read
+
+
+def drop_flagged(read, redo, store=None, wait=False):
+    """Behind the batch's read-back: the names of the batch that left fp16's range (none without a `read`).  They go on the
+    worker's `redo` list with their size, and the maps the split pass put into `store` for them are dropped; the caller writes
+    no file for them."""
+    if read is None:
+        return set()
+    bad = read.names(wait=wait)
+    for name in bad:
+        redo.add(name, read.sizes[name])
+        if store is not None and read.edge_keys.get(name) is not None:
+            store.drop(read.edge_keys[name])
+    read.release()
+    return set(bad)
+
+
+def redo_items(redo, w, args):
+    """The redo list as `item`s (pixels decoded again by `edges_for`), in name order, with their CAMs as they are NOW — the
+    fp32 one where make_cam recomputed the image too."""
+    cam_run = _stores.current_cam_run(args.cam_out_dir)
+    return [item(name, size, w.dev, args, cam_run) for name, size in sorted(redo.items())]
 
 
 def skip_image_predicate(model, args, device):

@@ -239,8 +239,9 @@ atexit.register(shutdown_workers)
 
 
 def pool_stats():
-    """Per-worker counters after the last step ({} entries before any): CAM hand-offs served from device memory, and
-    batches the persistent walk handed to the streaming sweeps."""
+    """Per-worker counters after the last step ({} entries before any): CAM hand-offs served from device memory, batches the
+    persistent walk handed to the streaming sweeps, and `split_fallback_images` — images `--split_gemm auto` computed again on
+    the fp32 GEMMs (_report.worker_stats)."""
     return [] if _POOL[0] is None else [dict(s) for s in _POOL[0].stats]
 
 

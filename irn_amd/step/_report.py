@@ -12,6 +12,9 @@ from . import _stores
 # shipped find database is tuned for), and its size-group flushes (full groups of `cam_batch` images vs partial ones)
 CAM_STATS = {"channels_last": 0, "nchw": 0, "full_group_flushes": 0, "partial_group_flushes": 0}      # (passes, not flushes: a partial group is one padded pass, an untuned size one pass per image — net/resnet50.run_rows)
 WALK_STATS = {"fallback_runs": 0}
+# `--split_gemm auto`: images of this process that left fp16's range on the split-precision GEMMs and were computed again on the
+# fp32 ones (step/_split_auto.py), summed over the steps
+SPLIT_STATS = {"fallback_images": 0}
 
 
 def untuned_report(reset=True):
@@ -80,9 +83,21 @@ def step_summary(rank, walker=None):
         say("[worker %d] %s" % (int(rank), m))
 
 
+def split_fallback_line(names):
+    """The line a worker says at the end of a step that recomputed `names` on the fp32 GEMMs; "" for none."""
+    names = list(names)
+    if not names:
+        return ""
+    return ("irn_amd: split_gemm auto: %d image(s) left fp16's range on the split-precision GEMMs and were computed again on the fp32 "
+            "GEMMs (no file was written from the split pass): %s%s" % (len(names), ", ".join(names[:8]),
+                                                                      ", ... (%d more)" % (len(names) - 8) if len(names) > 8 else ""))
+
+
 def check_split_overflow(what):
     """End of a step: did an activation leave fp16's range inside the split-precision 1x1 convolutions (net/resnet50.py
-    SPLIT_GEMM)?  Then this step's outputs are invalid and the step raises — loudly, like a worker's exception."""
+    SPLIT_GEMM)?  Then this step's outputs are invalid and the step raises — loudly, like a worker's exception.  (The process-wide
+    flag: with `--split_gemm auto` the passes of make_cam and the label steps record per sample instead and recover, so only a
+    split pass outside them can raise here.)"""
     from .. import ops
     if ops.split_overflowed():
         raise RuntimeError("%s: an activation of the backbone was beyond fp16's range (|x| > 65504) or NaN inside the split-precision "
@@ -102,4 +117,5 @@ def worker_stats():
     """The counters of this process that a pool worker sends back with every finished step (`_pool.pool_stats`)."""
     return {"cam_store_hits": _stores.CAM_STORE.hits, "cam_store_misses": _stores.CAM_STORE.misses,
             "edge_store_hits": _stores.EDGE_STORE.hits, "edge_store_misses": _stores.EDGE_STORE.misses,
-            "walk_fallback_runs": WALK_STATS["fallback_runs"], "cam_trunk_passes": dict(CAM_STATS)}
+            "walk_fallback_runs": WALK_STATS["fallback_runs"], "cam_trunk_passes": dict(CAM_STATS),
+            "split_fallback_images": SPLIT_STATS["fallback_images"]}

@@ -79,6 +79,10 @@ class CamStore(_DeviceStore):
         keys = torch.as_tensor(d["keys"])
         return keys, keys.to(device), torch.as_tensor(d["cam"]).to(device)
 
+    def drop(self, name, cam_out_dir):
+        """Forget one image's entry (`--split_gemm auto`: a CAM computed from an activation beyond fp16's range)."""
+        self._forget(self._key(name, cam_out_dir))
+
     def drop_dir(self, cam_out_dir):
         """Forget the entries of one output directory (make_cam.run starts with this: its files are about to change)."""
         d = os.path.abspath(cam_out_dir)
@@ -145,6 +149,10 @@ class EdgeStore(_DeviceStore):
 
     def put(self, key, edge, dp):
         self._insert(key, (edge, dp), (edge.numel() + dp.numel()) * 4)
+
+    def drop(self, key):
+        """Forget one entry (`--split_gemm auto`: maps computed from an activation beyond fp16's range)."""
+        self._forget(key)
 
 
 EDGE_STORE = EdgeStore()

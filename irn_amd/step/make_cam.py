@@ -20,7 +20,7 @@ import torch
 
 from ..misc import torchutils
 from ..voc12 import dataloader as voc12_dataloader
-from . import _io, _pool, _report, _stores
+from . import _io, _pool, _report, _split_auto, _stores
 
 
 def merge_scales(outputs, size, label):
@@ -31,32 +31,43 @@ def merge_scales(outputs, size, label):
     return ops.cam_merge(outputs, size, label)
 
 
-def _save_cam(path, keys_cpu, event, staging, cam_view, hi_view):
+def _save_cam(path, keys_cpu, event, staging, cam_view, hi_view, auto=None):
     """Writer-thread half of a CAM hand-off: wait for the image's device-to-host copies, write the reference's
-    dictionary (step/make_cam.py:55-56), recycle the staging buffer."""
+    dictionary (step/make_cam.py:55-56), recycle the staging buffer.  `auto` = (the flush's flag words — copied on the same stream
+    in front of the image, so behind `event` they have landed —, the image's index in the flush, its name, the worker's redo
+    list): an image that left fp16's range is not written; its name goes on the list."""
     event.synchronize()
     try:
+        if auto is not None and auto[0].flagged(auto[1]):
+            auto[3].add(auto[2])
+            return
         np.save(path, {"keys": keys_cpu, "cam": cam_view.clone(), "high_res": hi_view.numpy()})
     finally:
         _io.PINNED.give(staging)
+        if auto is not None:
+            auto[0].release()
 
 
-def _flush_group(model, group, scales, args, writer, store):
+def _flush_group(model, group, scales, args, writer, store, redo=None):
     """One trunk pass per scale for all images of a size group ([image, flip, image, flip, ...]), then the per-image
     merge (irn_cam_merge) and the asynchronous write of the reference's dictionary.  Nothing here waits for the device:
     the present classes come from the host-side label, the results leave through page-locked staging on the stream, and
-    the writer threads wait for each image's copy event — so the next group's passes are queued while this one runs."""
+    the writer threads wait for each image's copy event — so the next group's passes are queued while this one runs.  With a
+    `redo` list (`--split_gemm auto`) the passes record the fp16-range flag per row and scale; the words leave with the images."""
     if not group:
         return
     from ..net import resnet50 as _r50
     outs = []
+    flags = torch.zeros((len(scales), 2 * len(group)), dtype=torch.int32, device=group[0]["imgs"][0].device) if redo is not None else None
     for si in range(len(scales)):
         x = torch.cat([g["imgs"][si] for g in group])
         before = (_r50.PASS_STATS["channels_last"], _r50.PASS_STATS["nchw"])
-        outs.append(model.forward_batch(x))
+        with _split_auto.recording(None if flags is None else flags[si]):
+            outs.append(model.forward_batch(x))
         _report.CAM_STATS["channels_last"] += _r50.PASS_STATS["channels_last"] - before[0]
         _report.CAM_STATS["nchw"] += _r50.PASS_STATS["nchw"] - before[1]
     _report.CAM_STATS["full_group_flushes" if len(group) >= int(getattr(args, "cam_batch", 0) or 8) else "partial_group_flushes"] += 1
+    read = None if flags is None else _split_auto.FlagRead(flags, [g["name"] for g in group], users=len(group))
     for i, g in enumerate(group):
         keys_cpu = torch.nonzero(g["label"])[:, 0]
         keys, cam, high_res = merge_scales([o[i] for o in outs], g["size"], g["label"])
@@ -70,8 +81,34 @@ def _flush_group(model, group, scales, args, writer, store):
         hi_view.copy_(high_res, non_blocking=True)
         event = torch.cuda.Event()
         event.record()
-        writer.submit(_save_cam, os.path.join(args.cam_out_dir, g["name"] + ".npy"), keys_cpu, event, staging, cam_view, hi_view)
+        job = (os.path.join(args.cam_out_dir, g["name"] + ".npy"), keys_cpu, event, staging, cam_view, hi_view)
+        if read is None:
+            writer.submit(_save_cam, *job)
+        else:
+            writer.submit(_save_cam, *job, auto=(read, i, g["name"], redo))
     group.clear()
+
+
+def _redo_fp32(model, databin, index_of, redo, scales, batch, args, writer, store):
+    """`--split_gemm auto`, after the shard's loop: the images on the redo list once more — decoded again, every scale again,
+    in the same `pass_rows` passes — with the split-precision GEMMs off; written and stored like any other image, so the files
+    are those of a `--split_gemm 0` run.  The entries the split pass left in the store are dropped first."""
+    from torch.utils.data import default_collate
+    from ..net import resnet50 as _r50
+    names = sorted(n for n, _ in redo.items())
+    for name in names:
+        _stores.CAM_STORE.drop(name, args.cam_out_dir)
+    groups = {}
+    with _r50.fp32_gemms():
+        for name in names:
+            pack = default_collate([databin[index_of[name]]])
+            size = (int(pack["size"][0]), int(pack["size"][1]))
+            group = groups.setdefault(size, [])
+            group.append({"name": name, "size": size, "label": pack["label"][0], "imgs": _io.device_images(pack, scales)})
+            if len(group) == batch:
+                _flush_group(model, group, scales, args, writer, store)
+        for group in groups.values():
+            _flush_group(model, group, scales, args, writer, store)
 
 
 def _work(process_id, model, dataset, args):
@@ -82,6 +119,8 @@ def _work(process_id, model, dataset, args):
     batch = int(getattr(args, "cam_batch", 0) or 8)
     store = _stores.CAM_STORE if _stores.keep_cams(args) else None
     _stores.CAM_STORE.drop_dir(args.cam_out_dir)        # this directory's files are about to be rewritten
+    redo = _split_auto.Redo() if _split_auto.enabled() else None      # --split_gemm auto: images to compute again on the fp32 GEMMs
+    index_of = {}
     groups = {}
     pending_bytes, max_pending = 0, int(getattr(args, "cam_pending_bytes", 0) or (4 << 30))
     with _io.shard_io(process_id, dataset, args) as (databin, n_gpus, loader, writer):
@@ -102,20 +141,26 @@ def _work(process_id, model, dataset, args):
                     continue
                 group = groups.setdefault(size, [])
                 imgs = _io.device_images(pack, scales)
+                index_of[img_name] = it
                 group.append({"name": img_name, "size": size, "label": label, "imgs": imgs})
                 pending_bytes += sum(t.numel() * t.element_size() for t in imgs)
                 if len(group) == batch:
                     pending_bytes -= sum(t.numel() * t.element_size() for g in group for t in g["imgs"])
-                    _flush_group(model, group, scales, args, writer, store)
+                    _flush_group(model, group, scales, args, writer, store, redo)
                 elif pending_bytes > max_pending:
                     # VOC has hundreds of distinct image sizes: incomplete size groups may not pile up on the device
                     # without bound (34 MB per waiting 500x375 image) — the fullest one goes early
                     big = max(groups.values(), key=len)
                     pending_bytes -= sum(t.numel() * t.element_size() for g in big for t in g["imgs"])
-                    _flush_group(model, big, scales, args, writer, store)
+                    _flush_group(model, big, scales, args, writer, store, redo)
                 _io.progress(process_id, n_gpus, it, len(databin))
             for group in groups.values():
-                _flush_group(model, group, scales, args, writer, store)
+                _flush_group(model, group, scales, args, writer, store, redo)
+            if redo is not None:
+                writer.drain()                 # every image's flags have been looked at
+                if len(redo):
+                    _redo_fp32(model, databin, index_of, redo, scales, batch, args, writer, store)
+                redo.report(process_id)
 
 
 def run(args):

@@ -21,7 +21,8 @@ import numpy as np
 import torch
 
 from .. import ops
-from . import _labels
+from ..net import resnet50 as _r50
+from . import _labels, _split_auto
 
 find_centroids_with_refinement = ops.find_centroids_with_refinement
 cluster_centroids = ops.cluster_centroids
@@ -88,9 +89,16 @@ def save_rle(path, det):
                  offsets=det["offsets"], area=det["area"], bbox=det["bbox"], **{"class": det["class"]})
 
 
-def _write(names, pending, args, writer):
+def _write(names, pending, args, writer, flags=None, redo=None, store=None):
+    """Hand the batch's detections to the writer threads.  `flags` (`--split_gemm auto`: the batch's fp16-range flag words, sent
+    to the host right behind its IRNet forward, long before the detections `pending.result()` waits for): an image that left
+    the range gets no file and goes on `redo`."""
     rle = ins_seg_format(args) == "rle"
-    for name, det in zip(names, pending.result()):
+    dets = pending.result()
+    bad = _labels.drop_flagged(flags, redo, store, wait=True)
+    for name, det in zip(names, dets):
+        if name in bad:
+            continue
         if isinstance(det, Exception):
             warnings.warn("%s: %s — no file written" % (name, det))
             continue
@@ -100,7 +108,7 @@ def _write(names, pending, args, writer):
             writer.submit(np.save, os.path.join(args.ins_seg_out_dir, name + ".npy"), det)
 
 
-def _flush(model, walker, pend, args, writer, state):
+def _flush(model, walker, pend, args, writer, state, redo=None):
     """One turn of the step's three-stage pipeline; `state` = {"front": batch whose IRNet forward + clustering are enqueued,
     "emit": batch whose detections are crossing PCIe}.  In this order:
       1. the batch in `front` gets its back half (the K read-back, by now long computed; walk, epilogue, detections) —
@@ -108,24 +116,28 @@ def _flush(model, walker, pend, args, writer, state):
       2. the batch in `pend` gets its IRNet forward, centroid refinement and clustering enqueued — the GPU works on them while
          the caller's loop decodes and uploads the next batch (round 5: the K read-back used to stall that loop for the whole
          forward, 40 % of the step);
-      3. the batch in `emit` is collected and handed to the writer threads."""
+      3. the batch in `emit` is collected and handed to the writer threads.
+    With a `redo` list (`--split_gemm auto`) stage 2 records the IRNet forward's per-image fp16-range flags and stage 3 acts on them."""
     done = None
     if state.get("front") is not None:
-        items, front = state["front"]
+        items, front, *auto = state["front"]                # auto: (the batch's flag words on their way to the host, the edge store)
         extra = {"fmt": "rle"} if ins_seg_format(args) == "rle" else {}        # the default call is the one it always was
         if getattr(args, "detect_timings", None) is not None:                   # a caller's dict for the detection calls' `timings`
             extra["timings"] = args.detect_timings
         done = ([it["name"] for it in items],
                 instance_back(walker, items, front, float(args.beta), int(args.exp_times), float(args.ins_seg_bg_thres), deferred=True,
-                              **extra))
+                              **extra), *auto)
         state["front"] = None
     if pend:
-        _labels.edges_for(model, pend, _labels.irn_batch(args), **_labels.edge_store_kw(model, args))
+        kw = _labels.edge_store_kw(model, args)
+        _labels.edges_for(model, pend, _labels.irn_batch(args), auto=redo is not None, **kw)
         items = list(pend)
         pend.clear()
-        state["front"] = (items, instance_front(items))
+        auto = (_labels.flag_read(items), kw.get("store")) if redo is not None else ()
+        state["front"] = (items, instance_front(items), *auto)
     if state.get("emit") is not None:
-        _write(*state["emit"], args, writer)
+        names, pending, *auto = state["emit"]
+        _write(names, pending, args, writer, *((auto[0], redo, auto[1]) if auto else ()))
     state["emit"] = done
 
 
@@ -133,13 +145,23 @@ def _work(process_id, model, dataset, args):
     batch = _labels.walk_batch(args, 32)
     with _labels.worker(process_id, model, dataset, args) as w:
         pend, state = [], {}
+        redo = _split_auto.Redo() if _split_auto.enabled() else None      # --split_gemm auto
         for item in _labels.items(w, args):
             pend.append(item)
             if len(pend) == batch:
-                _flush(w.model, w.walker, pend, args, w.writer, state)
-        _flush(w.model, w.walker, pend, args, w.writer, state)      # the last batch's front half ...
-        _flush(w.model, w.walker, pend, args, w.writer, state)      # ... its back half ...
-        _flush(w.model, w.walker, pend, args, w.writer, state)      # ... and its collection
+                _flush(w.model, w.walker, pend, args, w.writer, state, redo)
+        _flush(w.model, w.walker, pend, args, w.writer, state, redo)      # the last batch's front half ...
+        _flush(w.model, w.walker, pend, args, w.writer, state, redo)      # ... its back half ...
+        _flush(w.model, w.walker, pend, args, w.writer, state, redo)      # ... and its collection
+        if redo is not None:
+            # the images that left fp16's range once more, IRNet on the fp32 GEMMs: their maps go back into the store
+            todo = _labels.redo_items(redo, w, args)
+            with _r50.fp32_gemms():
+                for i in range(0, len(todo), batch):
+                    pend = todo[i:i + batch]
+                    for _ in range(3):
+                        _flush(w.model, w.walker, pend, args, w.writer, state)
+            redo.report(process_id)
 
 
 def run(args):

@@ -17,7 +17,8 @@ import torch
 from PIL import Image
 
 from .. import ops
-from . import _io, _labels
+from ..net import resnet50 as _r50
+from . import _io, _labels, _split_auto
 
 
 def _save_png(path, label):
@@ -30,22 +31,26 @@ def _start_copy(batch, args):
     flat = batch["flat"] = ops.label_epilogue(batch["rws"], batch["sizes"], float(args.sem_seg_bg_thres), keys=batch["keys"],
                                               packed=True)["labels_flat"]
     batch["staging"] = _io.PINNED.take(flat.numel())
-    batch["done"] = ops.read_back(flat, batch["staging"], side=True)
+    batch["done"] = ops.read_back(flat, batch["staging"], side=True)      # (behind the batch's flag words, if any: `_enqueue`)
 
 
-def _enqueue(model, walker, pend, args):
+def _enqueue(model, walker, pend, args, auto=False):
     """IRNet forward, walk, label epilogue and the transfer of the label maps of the images in `pend`, enqueued only;
-    returns what `_collect` needs."""
-    _labels.edges_for(model, pend, _labels.irn_batch(args), **_labels.edge_store_kw(model, args))
+    returns what `_collect` needs.  `auto` (`--split_gemm auto`): the forward's per-image fp16-range flags leave for the host in
+    front of the label maps, on the same stream."""
+    kw = _labels.edge_store_kw(model, args)
+    _labels.edges_for(model, pend, _labels.irn_batch(args), auto=auto, **kw)
     rws = walker([p["edge"] for p in pend], [p["cam"] for p in pend], beta=float(args.beta), exp_times=int(args.exp_times))
-    batch = {"names": [p["name"] for p in pend], "rws": rws, "sizes": [p["size"] for p in pend], "keys": [p["keys_dev"] for p in pend]}
+    batch = {"names": [p["name"] for p in pend], "rws": rws, "sizes": [p["size"] for p in pend], "keys": [p["keys_dev"] for p in pend],
+             "flags": _labels.flag_read(pend) if auto else None, "store": kw.get("store")}
     _start_copy(batch, args)
     pend.clear()
     return batch
 
 
-def _collect(walker, batch, args, writer):
-    """Wait for the batch enqueued last and hand its label maps (already on their way to the host) to the writer threads."""
+def _collect(walker, batch, args, writer, redo=None):
+    """Wait for the batch enqueued last and hand its label maps (already on their way to the host) to the writer threads —
+    except those of images that left fp16's range (`--split_gemm auto`): they go on `redo`, nothing is written."""
     if batch is None:
         return
     if walker.sync():                       # the persistent walk gave up and the batch was re-run on the streaming sweeps
@@ -53,10 +58,14 @@ def _collect(walker, batch, args, writer):
         _start_copy(batch, args)
     batch["done"].synchronize()
     host = batch["staging"].numpy()
+    # the flag words were copied on the current stream BEFORE the epilogue whose output `done` marks as landed
+    bad = _labels.drop_flagged(batch.pop("flags", None), redo, batch.get("store"))
     off = 0
     for name, (hh, ww) in zip(batch["names"], batch["sizes"]):
         lab = host[off:off + hh * ww].reshape(hh, ww).copy()      # 256 KB: the staging buffer goes back at once
         off += hh * ww
+        if name in bad:
+            continue
         writer.submit(_save_png, os.path.join(args.sem_seg_out_dir, name + ".png"), lab)
     _io.PINNED.give(batch.pop("staging"))
 
@@ -67,16 +76,29 @@ def _work(process_id, model, dataset, args):
         # a batch is enqueued and left running while the loop gathers the next one (decoded images from the loader
         # threads, their uploads, the CAMs); it is collected just before the next batch is enqueued
         pend, running = [], None
+        auto = _split_auto.enabled()
+        redo = _split_auto.Redo() if auto else None
         try:
             for item in _labels.items(w, args):
                 pend.append(item)
                 if len(pend) == batch:
-                    _collect(w.walker, running, args, w.writer)
-                    running = _enqueue(w.model, w.walker, pend, args)
-            _collect(w.walker, running, args, w.writer)
+                    _collect(w.walker, running, args, w.writer, redo)
+                    running = _enqueue(w.model, w.walker, pend, args, auto)
+            _collect(w.walker, running, args, w.writer, redo)
+            running = None
             if pend:
-                running = _enqueue(w.model, w.walker, pend, args)
-                _collect(w.walker, running, args, w.writer)
+                running = _enqueue(w.model, w.walker, pend, args, auto)
+                _collect(w.walker, running, args, w.writer, redo)
+                running = None
+            if auto:
+                # the images that left fp16's range once more, IRNet on the fp32 GEMMs: their maps go back into the store
+                todo = _labels.redo_items(redo, w, args)
+                with _r50.fp32_gemms():
+                    for i in range(0, len(todo), batch):
+                        running = _enqueue(w.model, w.walker, todo[i:i + batch], args)
+                        _collect(w.walker, running, args, w.writer)
+                        running = None
+                redo.report(process_id)
         except BaseException:           # the batch in flight stays uncollected: its buffer goes back once the copy into it has landed
             if running is not None and "staging" in running:
                 running["done"].synchronize()

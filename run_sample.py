@@ -27,6 +27,23 @@ def _flag(v):
     return str(v).strip().lower() in ("1", "true", "yes", "y")
 
 
+def _split_gemm(v):
+    """--split_gemm: 0 / 1 as the integers they always were, or "auto"."""
+    v = str(v).strip().lower()
+    if v not in ("0", "1", "auto"):
+        raise argparse.ArgumentTypeError("0, 1 or auto, got %r" % v)
+    return v if v == "auto" else int(v)
+
+
+def apply_split_gemm(args, auto=True):
+    """--split_gemm into IRN_SPLIT_GEMM (workers read it when they import the trunk) and the trunk's module switches of this
+    process; unset: both stay as the environment made them.  `auto` False: a command whose steps have no per-image fallback
+    runs "auto" as 1."""
+    if args.split_gemm is not None:
+        from irn_amd.net import resnet50 as _r50
+        _r50.set_split_mode(args.split_gemm if auto or args.split_gemm != "auto" else 1)
+
+
 def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--num_workers", default=(os.cpu_count() or 2) // 2, type=int)
@@ -97,9 +114,13 @@ def build_parser():
                         "find database without split-K solvers, MIOpen's deterministic attribute elsewhere); 0 = the last 2-4 %% of "
                         "speed, outputs then move by ~1e-5 from run to run (not in the reference).  Unset: the environment "
                         "variable IRN_DETERMINISTIC, else 1")
-    p.add_argument("--split_gemm", default=None, type=int, choices=(0, 1),
+    p.add_argument("--split_gemm", default=None, type=_split_gemm, choices=(0, 1, "auto"),
                    help="1 (default): the trunk's 1x1 convolutions as fp16 hi/lo split products with fp32 accumulation (fp32-level "
-                        "accuracy, ~15 %% faster end to end); 0: plain fp32 GEMMs (also IRN_SPLIT_GEMM)")
+                        "accuracy, ~15 %% faster end to end); a step raises at its end if an activation left fp16's range.  0: plain "
+                        "fp32 GEMMs.  auto: as 1, but make_cam, make_sem_seg and make_ins_seg notice such an activation per image, "
+                        "write nothing computed from it and compute that image again on the fp32 GEMMs (its files are those of 0, "
+                        "all others those of 1; one line per worker names the images).  The tune_* steps, run_train.py and "
+                        "run_train_cam.py keep the end-of-step check: auto behaves as 1 there.  (also IRN_SPLIT_GEMM)")
     p.add_argument("--step_timeout", default=0.0, type=float,
                    help="seconds a step may take in its worker processes before the pool is stopped and the step raises "
                         "(0 = no limit; also IRN_STEP_TIMEOUT_S)")
@@ -141,10 +162,7 @@ def main(argv=None):
                              "--%s: CAM training is run by `python run_train_cam.py`, not from here" % name)
     for d in (args.cam_out_dir, args.sem_seg_out_dir, args.ins_seg_out_dir) + ((args.ir_label_out_dir,) if args.cam_to_ir_label_pass else ()):
         os.makedirs(d, exist_ok=True)
-    if args.split_gemm is not None:
-        os.environ["IRN_SPLIT_GEMM"] = str(int(args.split_gemm))           # workers read it when they import the trunk
-        from irn_amd.net import resnet50 as _r50
-        _r50.SPLIT_GEMM = bool(args.split_gemm)
+    apply_split_gemm(args)
     if args.deterministic is not None:
         os.environ["IRN_DETERMINISTIC"] = str(int(args.deterministic))      # read by every process that sets MIOpen up (workers inherit it)
     pyutils.Logger(args.log_name + ".log")

@@ -38,10 +38,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.train_cam_pass:
         raise SystemExit("--train_cam_pass: CAM training is run by `python run_train_cam.py`, not from here")
-    if args.split_gemm is not None:
-        os.environ["IRN_SPLIT_GEMM"] = str(int(args.split_gemm))           # workers read it when they import the trunk
-        from irn_amd.net import resnet50 as _r50
-        _r50.SPLIT_GEMM = bool(args.split_gemm)
+    run_sample.apply_split_gemm(args, auto=False)       # training keeps the end-of-step fp16-range check: "auto" runs as 1
     if args.deterministic is not None:
         os.environ["IRN_DETERMINISTIC"] = str(int(args.deterministic))
     pyutils.Logger(args.log_name + ".log")

@@ -121,6 +121,19 @@ int irn_aff_loss_backward(const float *edge, const float *dp, const uint8_t *lab
 int irn_aff_loss_backward_ordered(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
                                   int radius, const float *coef, float *grad_edge, float *grad_dp, void *ws, size_t ws_bytes,
                                   void *stream);
+/* The same three calls for a dataset with another class count: labels >= ignore_from take no part, where the calls above
+ * have 21 (they are these calls with ignore_from = 21).  A dataset of C foreground classes passes C + 1, so that labels
+ * 1..C are classes.  Nothing else in the arithmetic depends on it: the loss only asks which labels are equal, which are 0
+ * and which are ignored.  ignore_from outside 1..255 gives IRN_ERR_ARG (labels are bytes and 255 is always void). */
+int irn_aff_loss_forward_ignore(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
+                                int radius, int ignore_from, double *sums, int64_t *counts, void *ws, size_t ws_bytes,
+                                void *stream);
+int irn_aff_loss_backward_ignore(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
+                                 int radius, int ignore_from, const float *coef, float *grad_edge, float *grad_dp, void *ws,
+                                 size_t ws_bytes, void *stream);
+int irn_aff_loss_backward_ordered_ignore(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
+                                         int radius, int ignore_from, const float *coef, float *grad_edge, float *grad_dp,
+                                         void *ws, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Random-walk context  (replaces misc/indexing.py:141-165 `propagate_to_edge` and everything it
@@ -732,6 +745,29 @@ int irn_mask_overlap(const uint8_t *masks_dev, int n, const uint8_t *inst_dev, i
                      void *stream);
 int irn_ir_label_confusion(const uint8_t *planes_dev, int t_count, const int32_t *fg_idx, int f, const int32_t *bg_idx,
                            int b, const uint8_t *gt_dev, int h, int w, int64_t *hist_dev, int64_t *bad_dev, void *stream);
+/* The same counts for a dataset with another class count.  n_classes (nc below) = classes including the
+ * background, 2 <= nc <= IRN_EVAL_MAX_CLASSES; the calls above are these calls with nc = IRN_EVAL_CLASSES,
+ * one kernel serves every count.  Everything above holds with 21 read as nc:
+ *   hist [nc+1][nc][t+1], conf [t][nc][nc], void [t][nc]; irn_label_confusion conf [nc][nc], void [nc];
+ *   irn_ir_label_confusion hist [f][b][nc+1][nc+1], the last row = GT 255, the last column = label 255.
+ *   GT g <= nc-1 is row g, 255 is row nc, anything else is bad; a key in 0..nc-2 is column key+1, any
+ *   other key is bad; a prediction or plane value >= nc is bad; at most nc-1 planes (k) per image, and
+ *   pred_255_as < nc.
+ * The cap is 80 foreground classes because the per-workgroup LDS tables are sized by it ((nc+1)*nc uint32
+ * bins, 26.6 KB at nc = 81); labels stay uint8 with 255 = void.  irn_ir_label_confusion_nc needs
+ * f*(nc+1)*nc + f*b*(nc+1) words of LDS per workgroup and runs the fg axis in as many launches as that takes
+ * (one for 16 x 16 at nc = 21, eight at nc = 81); the histogram does not depend on the grouping, and bad
+ * counts a pixel once.  nc outside its range, or k above nc-1, gives IRN_ERR_ARG before any device work. */
+#define IRN_EVAL_MAX_CLASSES 81
+int irn_cam_confusion_nc(const float *high_res_dev, const int64_t *keys_dev, int k, const uint8_t *gt_dev, int h, int w,
+                         const float *thres_dev, int t, int n_classes, int64_t *hist_dev, int64_t *bad_dev, void *stream);
+int irn_cam_confusion_reduce_nc(const int64_t *hist_dev, int t, int n_classes, int64_t *conf_dev, int64_t *void_dev,
+                                void *stream);
+int irn_label_confusion_nc(const uint8_t *pred_dev, const uint8_t *gt_dev, int h, int w, int pred_255_as, int n_classes,
+                           int64_t *conf_dev, int64_t *void_dev, int64_t *bad_dev, void *stream);
+int irn_ir_label_confusion_nc(const uint8_t *planes_dev, int t_count, const int32_t *fg_idx, int f, const int32_t *bg_idx,
+                              int b, const uint8_t *gt_dev, int h, int w, int n_classes, int64_t *hist_dev,
+                              int64_t *bad_dev, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Label threshold sweep  (step/make_sem_seg_labels.py:43-49 + step/eval_sem_seg.py:10-17 at T values
@@ -755,6 +791,16 @@ int irn_label_sweep_confusion(int n_images, const float *const *rw_dev, const in
                               const int64_t *const *keys_dev, const uint8_t *const *gt_dev,
                               const float *thres_dev, int t, int64_t *hist_dev, int64_t *bad_dev,
                               void *scratch_dev, void *stream);
+/* The same sweep at n_classes classes including the background (2..IRN_EVAL_MAX_CLASSES; the call above is this
+ * one at IRN_EVAL_CLASSES): c <= n_classes-1, hist [n_classes+1][n_classes][t+1], GT and key ranges as for
+ * irn_cam_confusion_nc.  An image has (t+1)*(n_classes+1)*c bins and a workgroup counts them in passes of at most
+ * 15 360 (60 KiB of LDS), so 80 channels at 256 thresholds take 110 passes per 4096 pixels where 20 channels
+ * take 8. */
+int irn_label_sweep_confusion_nc(int n_images, const float *const *rw_dev, const int32_t *c, const int32_t *h,
+                                 const int32_t *w, const int32_t *out_h, const int32_t *out_w,
+                                 const int64_t *const *keys_dev, const uint8_t *const *gt_dev,
+                                 const float *thres_dev, int t, int n_classes, int64_t *hist_dev, int64_t *bad_dev,
+                                 void *scratch_dev, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * COCO mask encoding  (replaces the pycococreatortools / pycocotools arithmetic behind

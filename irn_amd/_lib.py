@@ -39,6 +39,9 @@ _SIGS = {
     "irn_aff_loss_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "irn_aff_loss_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "irn_aff_loss_backward_ordered": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "irn_aff_loss_forward_ignore": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "irn_aff_loss_backward_ignore": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "irn_aff_loss_backward_ordered_ignore": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "irn_walk_create": (i32, [i32, C.POINTER(vp)]),
     "irn_walk_destroy": (i32, [vp]),
     "irn_walk_configure": (i32, [vp, i32, pi32, pi32, pi32, C.POINTER(sz)]),
@@ -115,6 +118,11 @@ _SIGS = {
     "irn_label_confusion": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "irn_mask_overlap": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "irn_label_sweep_confusion": (i32, [i32, ppv, pi32, pi32, pi32, pi32, pi32, ppv, ppv, vp, i32, vp, vp, vp, vp]),
+    "irn_ir_label_confusion_nc": (i32, [vp, i32, pi32, i32, pi32, i32, vp, i32, i32, i32, vp, vp, vp]),
+    "irn_cam_confusion_nc": (i32, [vp, vp, i32, vp, i32, i32, vp, i32, i32, vp, vp, vp]),
+    "irn_cam_confusion_reduce_nc": (i32, [vp, i32, i32, vp, vp, vp]),
+    "irn_label_confusion_nc": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "irn_label_sweep_confusion_nc": (i32, [i32, ppv, pi32, pi32, pi32, pi32, pi32, ppv, ppv, vp, i32, i32, vp, vp, vp, vp]),
     "irn_mask_rle_scratch_bytes": (sz, [i32, i32, i32]),
     "irn_mask_rle_count": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "irn_mask_rle_emit": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),

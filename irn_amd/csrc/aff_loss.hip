@@ -23,7 +23,8 @@ namespace irn {
 
 namespace {
 
-constexpr int kIgnoreFrom = 21;      // labels >= 21 take no part (voc12/dataloader.py:94)
+// ignore_from, a launch argument of the three kernels: labels >= ignore_from take no part (voc12/dataloader.py:94 has 21,
+// the 20 VOC classes; a dataset of C classes passes C + 1).  Labels are bytes and 255 is always void: 1 <= ignore_from <= 255.
 constexpr int kPartWords = 8;        // per workgroup: 5 fp64 sums, 3 int64 counts
 
 struct PairAcc {
@@ -70,9 +71,9 @@ __device__ __forceinline__ void stage(const float *__restrict__ edge, const floa
 // Terms of the pair (source, source + (dy, dx)) whose path maximum is m.  a: the source label (255 for a thread outside the
 // source rectangle), s0 / s1: displacement at the source, `o`: tile offset of the destination relative to the source.
 __device__ __forceinline__ void pair_terms(PairAcc &acc, const Tiles &T, int src, int o, float m, int a, float s0, float s1,
-                                           float dy, float dx) {
+                                           float dy, float dx, int ignore_from) {
     const int b = T.lab[src + o];
-    const bool valid = a < kIgnoreFrom && b < kIgnoreFrom;
+    const bool valid = a < ignore_from && b < ignore_from;
     const bool pos = valid && a == b, neg = valid && a != b;
     const float aff = 1.0f - m;
     // -log(aff + 1e-5) for an equal pair, -log(1 + 1e-5 - aff) for an unequal one: one logarithm per pair
@@ -94,7 +95,7 @@ __global__ __launch_bounds__(256) void aff_loss_forward_kernel(const float *__re
                                                                int radius, int n_dirs, const int *__restrict__ dir_start8,
                                                                const int *__restrict__ cell_off8,
                                                                const int *__restrict__ dir_dy, const int *__restrict__ dir_dx,
-                                                               double *__restrict__ part) {
+                                                               int ignore_from, double *__restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int halo = (R ? R : radius) - 1;
     const int LW = AFF_TW + 2 * halo, LH = AFF_TH + halo, cells = LH * LW;
@@ -119,7 +120,7 @@ __global__ __launch_bounds__(256) void aff_loss_forward_kernel(const float *__re
         static_for<kPaths<R>.n_dirs>([&](auto id) __attribute__((always_inline)) {
             constexpr int d = decltype(id)::value;
             constexpr int dy = kPaths<R>.dy[d], dx = kPaths<R>.dx[d];
-            pair_terms(acc, T, src, dy * LW + dx, path_max<R, d>(tb), a, s0, s1, (float)dy, (float)dx);
+            pair_terms(acc, T, src, dy * LW + dx, path_max<R, d>(tb), a, s0, s1, (float)dy, (float)dx, ignore_from);
         });
     } else {
         const float *tb = t_edge + src;
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(256) void aff_loss_forward_kernel(const float *__re
                 m1 = max3(max3(m1, tb[ob.x], tb[ob.y]), tb[ob.z], tb[ob.w]);
             }
             const int dy = dir_dy[d], dx = dir_dx[d];
-            pair_terms(acc, T, src, dy * LW + dx, max3(m0, m1, m1), a, s0, s1, (float)dy, (float)dx);
+            pair_terms(acc, T, src, dy * LW + dx, max3(m0, m1, m1), a, s0, s1, (float)dy, (float)dx, ignore_from);
         }
     }
 
@@ -197,14 +198,18 @@ __device__ __forceinline__ float sgn(float v) { return (float)((v > 0.f) - (v < 
 // Backward.  Table-driven for every radius, over the path cells in the reference's order: the gradient of a path maximum
 // goes to the FIRST cell that attains it (max_pool2d's rule, the same as affinity_backward_kernel), and that order is the
 // path table's, not the raster order of the compile-time tables.
+// IGN: the ignore threshold as a constant (the instantiation for 21, the default of every caller without a class list: with the
+// threshold in a register this kernel measured 3 % slower), or 0 = the launch argument.
+template <int IGN>
 __global__ __launch_bounds__(256) void aff_loss_backward_kernel(const float *__restrict__ edge, const float *__restrict__ dp,
                                                                 const unsigned char *__restrict__ label, int hp, int wp,
                                                                 int radius, int n_dirs, const int *__restrict__ dir_start,
                                                                 const int *__restrict__ cell_dy, const int *__restrict__ cell_dx,
                                                                 const int *__restrict__ dir_dy, const int *__restrict__ dir_dx,
-                                                                const float *__restrict__ coef, float *__restrict__ grad_edge,
-                                                                float *__restrict__ grad_dp) {
+                                                                const float *__restrict__ coef, int ignore_arg,
+                                                                float *__restrict__ grad_edge, float *__restrict__ grad_dp) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int ignore_from = IGN ? IGN : ignore_arg;
     const int halo = radius - 1;
     const int LW = AFF_TW + 2 * halo, LH = AFF_TH + halo, cells = LH * LW;
     float *t_edge = lds, *t_dp0 = lds + cells, *t_dp1 = lds + 2 * cells;
@@ -222,7 +227,7 @@ __global__ __launch_bounds__(256) void aff_loss_backward_kernel(const float *__r
     const bool inside = ty0 + ly < sh && tx0 + lx < sw;
     const int src = ly * LW + lx + halo;
     const int a = inside ? (int)t_lab[src] : 255;
-    if (a < kIgnoreFrom) {
+    if (a < ignore_from) {
         const float c_pos = a == 0 ? coef[0] : coef[1], c_neg = coef[2];
         const float c_fg = coef[3], c_bg = coef[4];
         const float s0 = t_dp0[src], s1 = t_dp1[src];
@@ -231,7 +236,7 @@ __global__ __launch_bounds__(256) void aff_loss_backward_kernel(const float *__r
             const int dy = dir_dy[d], dx = dir_dx[d];
             const int o = dy * LW + dx;
             const int b = t_lab[src + o];
-            if (b >= kIgnoreFrom) continue;
+            if (b >= ignore_from) continue;
             const int k0 = dir_start[d], k1 = dir_start[d + 1];
             float m = -INFINITY;
             int arg = 0;
@@ -311,7 +316,7 @@ __global__ __launch_bounds__(256) void aff_loss_backward_ordered_kernel(
     const float *__restrict__ edge, const float *__restrict__ dp, const unsigned char *__restrict__ label, int hp, int wp,
     int radius, int n_dirs, const int *__restrict__ dir_start, const int *__restrict__ cell_dy,
     const int *__restrict__ cell_dx, const int *__restrict__ dir_dy, const int *__restrict__ dir_dx,
-    const float *__restrict__ coef, float *__restrict__ grad_edge, float *__restrict__ grad_dp) {
+    const float *__restrict__ coef, int ignore_from, float *__restrict__ grad_edge, float *__restrict__ grad_dp) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int halo = radius - 1;
     const int LW = AFF_TW + 2 * halo, LH = AFF_TH + 2 * halo, cells = LH * LW;
@@ -335,7 +340,7 @@ __global__ __launch_bounds__(256) void aff_loss_backward_ordered_kernel(
     const float e_bg = c_bgp / (aff + 1e-5f), e_fg = c_fgp / (aff + 1e-5f), e_neg = -c_neg / (1.00001f - aff);
     const int lc = t_lab[ctr];
     const float q0 = t_dp0[ctr], q1 = t_dp1[ctr];
-    const bool c_is_src = cy < sy1 && cx >= sx0 && cx < sx1 && lc < kIgnoreFrom;
+    const bool c_is_src = cy < sy1 && cx >= sx0 && cx < sx1 && lc < ignore_from;
     float acc_e = 0.f, acc0 = 0.f, acc1 = 0.f;
     for (int d = 0; d < n_dirs; ++d) {
         const int dy = dir_dy[d], dx = dir_dx[d];
@@ -346,7 +351,7 @@ __global__ __launch_bounds__(256) void aff_loss_backward_ordered_kernel(
             acc0 += lc > 0 ? c_fg * sgn(p0 - fy) : c_bg * sgn(p0);
             acc1 += lc > 0 ? c_fg * sgn(p1 - fx) : c_bg * sgn(p1);
         }
-        if (lc < kIgnoreFrom && cy - dy >= 0 && cy - dy < sy1 && cx - dx >= sx0 && cx - dx < sx1 && (int)t_lab[ctr - o] == lc) {
+        if (lc < ignore_from && cy - dy >= 0 && cy - dy < sy1 && cx - dx >= sx0 && cx - dx < sx1 && (int)t_lab[ctr - o] == lc) {
             // c the destination of (c - dir, d): - g, chosen by the source's label (equal to c's)
             const float p0 = t_dp0[ctr - o] - q0, p1 = t_dp1[ctr - o] - q1;
             acc0 -= lc > 0 ? c_fg * sgn(p0 - fy) : c_bg * sgn(p0);
@@ -359,7 +364,7 @@ __global__ __launch_bounds__(256) void aff_loss_backward_ordered_kernel(
             if (sy < 0 || sy >= sy1 || sx < sx0 || sx >= sx1) continue;
             const int s = ctr - (ky * LW + kx);
             const int a = t_lab[s], b = t_lab[s + o];
-            if (a >= kIgnoreFrom || b >= kIgnoreFrom) continue;
+            if (a >= ignore_from || b >= ignore_from) continue;
             bool first = true;
             for (int j = k0; j < k1 && first; ++j) {
                 const float v = t_edge[s + cell_dy[j] * LW + cell_dx[j]];
@@ -380,8 +385,10 @@ int n_tiles(int hp, int wp, int radius) {
 }
 
 // everything that can be refused before a device is touched
-int check_args(const char *who, bool pointers, int batch, int hp, int wp, int radius, const void *ws, size_t ws_bytes) {
+int check_args(const char *who, bool pointers, int batch, int hp, int wp, int radius, int ignore_from, const void *ws,
+               size_t ws_bytes) {
     if (!pointers || !ws) return fail(IRN_ERR_ARG, "%s: null pointer", who);
+    if (ignore_from < 1 || ignore_from > 255) return fail(IRN_ERR_ARG, "%s: ignore_from %d outside 1..255", who, ignore_from);
     if (batch < 1 || batch > 65535) return fail(IRN_ERR_ARG, "%s: batch must be in [1, 65535]", who);
     if (radius < 2 || radius > IRN_MAX_RADIUS) return fail(IRN_ERR_ARG, "%s: radius must be in [2,%d]", who, IRN_MAX_RADIUS);
     if (hp <= radius - 1 || wp <= 2 * (radius - 1))
@@ -405,10 +412,12 @@ extern "C" size_t irn_aff_loss_workspace_bytes(int batch, int hp, int wp, int ra
     return (size_t)batch * n_tiles(hp, wp, radius) * kPartWords * sizeof(double);
 }
 
-extern "C" int irn_aff_loss_forward(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
-                                    int radius, double *sums, int64_t *counts, void *ws, size_t ws_bytes, void *stream_) {
+extern "C" int irn_aff_loss_forward_ignore(const float *edge, const float *dp, const uint8_t *label, int batch, int hp,
+                                           int wp, int radius, int ignore_from, double *sums, int64_t *counts, void *ws,
+                                           size_t ws_bytes, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (int rc = check_args("irn_aff_loss_forward", edge && dp && label && sums && counts, batch, hp, wp, radius, ws, ws_bytes))
+    if (int rc = check_args("irn_aff_loss_forward", edge && dp && label && sums && counts, batch, hp, wp, radius, ignore_from, ws,
+                            ws_bytes))
         return rc;
     const int tiles = n_tiles(hp, wp, radius), rf = radius - 1;
     const size_t lds = lds_bytes((AFF_TH + rf) * (AFF_TW + 2 * rf), false);
@@ -416,15 +425,15 @@ extern "C" int irn_aff_loss_forward(const float *edge, const float *dp, const ui
     double *part = (double *)ws;
     if (radius == 10) {
         hipLaunchKernelGGL(aff_loss_forward_kernel<10>, grid, dim3(256), lds, stream, edge, dp, label, hp, wp, radius, 0,
-                           nullptr, nullptr, nullptr, nullptr, part);
+                           nullptr, nullptr, nullptr, nullptr, ignore_from, part);
     } else if (radius == 5) {
         hipLaunchKernelGGL(aff_loss_forward_kernel<5>, grid, dim3(256), lds, stream, edge, dp, label, hp, wp, radius, 0,
-                           nullptr, nullptr, nullptr, nullptr, part);
+                           nullptr, nullptr, nullptr, nullptr, ignore_from, part);
     } else {
         const DeviceTable *tab = nullptr;
         if (int rc = get_device_table(radius, 0, &tab)) return rc;
         hipLaunchKernelGGL(aff_loss_forward_kernel<0>, grid, dim3(256), lds, stream, edge, dp, label, hp, wp, radius,
-                           tab->n_dirs, tab->dir_start8, tab->cell_off8, tab->dir_dy, tab->dir_dx, part);
+                           tab->n_dirs, tab->dir_start8, tab->cell_off8, tab->dir_dy, tab->dir_dx, ignore_from, part);
     }
     IRN_LAUNCH_CHECK("aff_loss_forward_kernel");
     hipLaunchKernelGGL(aff_loss_finish_kernel, dim3(1), dim3(256), 0, stream, (const double *)part, tiles * batch, sums,
@@ -433,12 +442,18 @@ extern "C" int irn_aff_loss_forward(const float *edge, const float *dp, const ui
     return IRN_OK;
 }
 
-extern "C" int irn_aff_loss_backward(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
-                                     int radius, const float *coef, float *grad_edge, float *grad_dp, void *ws,
-                                     size_t ws_bytes, void *stream_) {
+extern "C" int irn_aff_loss_forward(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
+                                    int radius, double *sums, int64_t *counts, void *ws, size_t ws_bytes, void *stream_) {
+    return irn_aff_loss_forward_ignore(edge, dp, label, batch, hp, wp, radius, IRN_EVAL_CLASSES, sums, counts, ws, ws_bytes,
+                                       stream_);
+}
+
+extern "C" int irn_aff_loss_backward_ignore(const float *edge, const float *dp, const uint8_t *label, int batch, int hp,
+                                            int wp, int radius, int ignore_from, const float *coef, float *grad_edge,
+                                            float *grad_dp, void *ws, size_t ws_bytes, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (int rc = check_args("irn_aff_loss_backward", edge && dp && label && coef && grad_edge && grad_dp, batch, hp, wp,
-                            radius, ws, ws_bytes))
+                            radius, ignore_from, ws, ws_bytes))
         return rc;
     const DeviceTable *tab = nullptr;
     if (int rc = get_device_table(radius, 0, &tab)) return rc;
@@ -446,19 +461,29 @@ extern "C" int irn_aff_loss_backward(const float *edge, const float *dp, const u
     const size_t n = (size_t)batch * hp * wp;
     IRN_HIP_TRY(hipMemsetAsync(grad_edge, 0, sizeof(float) * n, stream));
     IRN_HIP_TRY(hipMemsetAsync(grad_dp, 0, sizeof(float) * 2 * n, stream));
-    hipLaunchKernelGGL(aff_loss_backward_kernel, dim3(n_tiles(hp, wp, radius), batch), dim3(256),
+    const auto kernel = ignore_from == IRN_EVAL_CLASSES ? aff_loss_backward_kernel<IRN_EVAL_CLASSES> : aff_loss_backward_kernel<0>;
+    hipLaunchKernelGGL(kernel, dim3(n_tiles(hp, wp, radius), batch), dim3(256),
                        lds_bytes((AFF_TH + rf) * (AFF_TW + 2 * rf), true), stream, edge, dp, label, hp, wp, radius, tab->n_dirs,
-                       tab->dir_start, tab->cell_dy, tab->cell_dx, tab->dir_dy, tab->dir_dx, coef, grad_edge, grad_dp);
+                       tab->dir_start, tab->cell_dy, tab->cell_dx, tab->dir_dy, tab->dir_dx, coef, ignore_from, grad_edge,
+                       grad_dp);
     IRN_LAUNCH_CHECK("aff_loss_backward_kernel");
     return IRN_OK;
 }
 
-extern "C" int irn_aff_loss_backward_ordered(const float *edge, const float *dp, const uint8_t *label, int batch, int hp,
-                                             int wp, int radius, const float *coef, float *grad_edge, float *grad_dp,
-                                             void *ws, size_t ws_bytes, void *stream_) {
+extern "C" int irn_aff_loss_backward(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
+                                     int radius, const float *coef, float *grad_edge, float *grad_dp, void *ws,
+                                     size_t ws_bytes, void *stream_) {
+    return irn_aff_loss_backward_ignore(edge, dp, label, batch, hp, wp, radius, IRN_EVAL_CLASSES, coef, grad_edge, grad_dp, ws,
+                                        ws_bytes, stream_);
+}
+
+extern "C" int irn_aff_loss_backward_ordered_ignore(const float *edge, const float *dp, const uint8_t *label, int batch,
+                                                    int hp, int wp, int radius, int ignore_from, const float *coef,
+                                                    float *grad_edge, float *grad_dp, void *ws, size_t ws_bytes,
+                                                    void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (int rc = check_args("irn_aff_loss_backward_ordered", edge && dp && label && coef && grad_edge && grad_dp, batch, hp,
-                            wp, radius, ws, ws_bytes))
+                            wp, radius, ignore_from, ws, ws_bytes))
         return rc;
     const DeviceTable *tab = nullptr;
     if (int rc = get_device_table(radius, 0, &tab)) return rc;
@@ -466,8 +491,15 @@ extern "C" int irn_aff_loss_backward_ordered(const float *edge, const float *dp,
     // tiles of output cells over the whole grid: every cell of both gradients is stored once, nothing is cleared first
     hipLaunchKernelGGL(aff_loss_backward_ordered_kernel, dim3(cdiv(hp, AFF_TH) * cdiv(wp, AFF_TW), batch), dim3(256),
                        lds_bytes((AFF_TH + 2 * rf) * (AFF_TW + 2 * rf), false), stream, edge, dp, label, hp, wp, radius,
-                       tab->n_dirs, tab->dir_start, tab->cell_dy, tab->cell_dx, tab->dir_dy, tab->dir_dx, coef, grad_edge,
-                       grad_dp);
+                       tab->n_dirs, tab->dir_start, tab->cell_dy, tab->cell_dx, tab->dir_dy, tab->dir_dx, coef, ignore_from,
+                       grad_edge, grad_dp);
     IRN_LAUNCH_CHECK("aff_loss_backward_ordered_kernel");
     return IRN_OK;
+}
+
+extern "C" int irn_aff_loss_backward_ordered(const float *edge, const float *dp, const uint8_t *label, int batch, int hp,
+                                             int wp, int radius, const float *coef, float *grad_edge, float *grad_dp,
+                                             void *ws, size_t ws_bytes, void *stream_) {
+    return irn_aff_loss_backward_ordered_ignore(edge, dp, label, batch, hp, wp, radius, IRN_EVAL_CLASSES, coef, grad_edge,
+                                                grad_dp, ws, ws_bytes, stream_);
 }

@@ -8,19 +8,20 @@
 // histogram of irn_cam_confusion is counted by thres_hist.hpp, the code the label sweep (label.hip) counts with.
 #include "thres_hist.hpp"
 
+#include <algorithm>
 #include <cmath>
 
 using irn::cdiv;
 using irn::fail;
 namespace thist = irn::thist;
-using thist::add64, thist::gt_row, thist::kRows, thist::kMaxKeys;
+using thist::add64, thist::gt_row, thist::kMaxKeys, thist::classes_ok;
 
 namespace {
 
 constexpr int TPB = 256;                  // threads per block
 constexpr int PPT = 16;                   // pixels per thread (kept in registers by the CAM kernel)
 constexpr int PIX = TPB * PPT;            // pixels per block: bin counts stay below 2^32
-constexpr int NC = IRN_EVAL_CLASSES;      // 21 classes (background + 20)
+// ncls, everywhere below: classes including the background, a launch argument (2..IRN_EVAL_MAX_CLASSES)
 constexpr int CAP = 16384;                // LDS bins of one pass of the CAM kernel (64 KiB)
 static_assert(TPB == thist::kThreads, "thres_hist.hpp counts with blocks of this size");
 
@@ -30,14 +31,15 @@ static_assert(TPB == thist::kThreads, "thres_hist.hpp counts with blocks of this
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(TPB) k_cam_hist(const float *__restrict__ cam, const int64_t *__restrict__ keys, int k,
                                                   const uint8_t *__restrict__ gt, int n, const float *__restrict__ thres,
-                                                  int t, int64_t *__restrict__ hist, int64_t *__restrict__ bad) {
+                                                  int t, int ncls, int64_t *__restrict__ hist,
+                                                  int64_t *__restrict__ bad) {
     __shared__ uint32_t bins[CAP];
     __shared__ float th[IRN_EVAL_MAX_THRES];
     __shared__ int col[kMaxKeys];
     __shared__ uint32_t nbad;
     const int tid = threadIdx.x;
     if (k == 0 && tid == 0) col[0] = 0;
-    uint32_t local_bad = thist::stage(thres, t, keys, k, blockIdx.x == 0, th, col, &nbad);
+    uint32_t local_bad = thist::stage(thres, t, keys, k, blockIdx.x == 0, ncls, th, col, &nbad);
 
     const int kc = k > 0 ? k : 1;
     uint32_t bin[PPT];
@@ -47,13 +49,13 @@ __global__ void __launch_bounds__(TPB) k_cam_hist(const float *__restrict__ cam,
         bin[i] = thist::kSkip;
         const int p = base + i * TPB;
         if (p >= n) continue;
-        const int row = gt_row(gt[p]);
+        const int row = gt_row(gt[p], ncls);
         if (row < 0) {
             ++local_bad;
             continue;
         }
         if (k == 0) {
-            bin[i] = thist::bin_of(0, row, 0, kc);
+            bin[i] = thist::bin_of(0, row, 0, kc, ncls);
             continue;
         }
         float m = cam[p];
@@ -71,18 +73,18 @@ __global__ void __launch_bounds__(TPB) k_cam_hist(const float *__restrict__ cam,
             ++local_bad;
             continue;
         }
-        bin[i] = thist::bin_of(thist::count_below(th, t, m), row, c, kc);
+        bin[i] = thist::bin_of(thist::count_below(th, t, m), row, c, kc, ncls);
     }
-    local_bad += thist::count(bin, bins, CAP, (uint32_t)(t + 1) * kRows * (uint32_t)kc, kc, col, t, hist);
+    local_bad += thist::count(bin, bins, CAP, (uint32_t)(t + 1) * (uint32_t)(ncls + 1) * (uint32_t)kc, kc, col, t, ncls, hist);
     thist::flush_bad(local_bad, &nbad, bad);
 }
 
-// hist [22][21][t+1] -> conf [t][21][21] (+ void [t][21]).  One thread per (row, column) of the histogram: a pixel of
+// hist [ncls+1][ncls][t+1] -> conf [t][ncls][ncls] (+ void [t][ncls]).  One thread per (row, column) of the histogram: a pixel of
 // column c >= 1 and count j predicts c at thresholds 0..j-1 and 0 from j on; column 0 predicts 0 throughout.
-__global__ void __launch_bounds__(TPB) k_cam_reduce(const int64_t *__restrict__ hist, int t, int64_t *__restrict__ conf,
-                                                    int64_t *__restrict__ void_) {
+__global__ void __launch_bounds__(TPB) k_cam_reduce(const int64_t *__restrict__ hist, int t, int NC,
+                                                    int64_t *__restrict__ conf, int64_t *__restrict__ void_) {
     const int id = blockIdx.x * TPB + threadIdx.x;
-    if (id >= kRows * NC) return;
+    if (id >= (NC + 1) * NC) return;
     const int row = id / NC, c = id % NC;
     if (row == NC && !void_) return;
     const int64_t *h = hist + (size_t)id * (t + 1);
@@ -102,15 +104,16 @@ __global__ void __launch_bounds__(TPB) k_cam_reduce(const int64_t *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// label confusion: bins [22][21] per block
+// label confusion: bins [ncls+1][ncls] per block, in dynamic LDS sized by the call
 // ---------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(TPB) k_label_hist(const uint8_t *__restrict__ pred, const uint8_t *__restrict__ gt, int n,
-                                                    int map255, int64_t *__restrict__ conf, int64_t *__restrict__ void_,
-                                                    int64_t *__restrict__ bad) {
-    __shared__ uint32_t bins[kRows * NC];
+                                                    int map255, int NC, int64_t *__restrict__ conf,
+                                                    int64_t *__restrict__ void_, int64_t *__restrict__ bad) {
+    extern __shared__ uint32_t bins[];
     __shared__ uint32_t nbad;
     const int tid = threadIdx.x;
-    for (int b = tid; b < kRows * NC; b += TPB) bins[b] = 0;
+    const int n_bins = (NC + 1) * NC;
+    for (int b = tid; b < n_bins; b += TPB) bins[b] = 0;
     if (tid == 0) nbad = 0;
     __syncthreads();
     uint32_t local_bad = 0;
@@ -119,7 +122,7 @@ __global__ void __launch_bounds__(TPB) k_label_hist(const uint8_t *__restrict__ 
     for (int i = 0; i < PPT; ++i) {
         const int p = base + i * TPB;
         if (p >= n) continue;
-        const int row = gt_row(gt[p]);
+        const int row = gt_row(gt[p], NC);
         int q = pred[p];
         if (q == 255 && map255 >= 0) q = map255;
         if (row < 0 || q >= NC) {
@@ -130,7 +133,7 @@ __global__ void __launch_bounds__(TPB) k_label_hist(const uint8_t *__restrict__ 
     }
     if (local_bad) atomicAdd(&nbad, local_bad);
     __syncthreads();
-    for (int b = tid; b < kRows * NC; b += TPB) {
+    for (int b = tid; b < n_bins; b += TPB) {
         const uint32_t v = bins[b];
         if (!v) continue;
         if (b < NC * NC) add64(conf + b, v);
@@ -184,15 +187,23 @@ __global__ void __launch_bounds__(TPB) k_mask_overlap(const uint8_t *__restrict_
 // ---------------------------------------------------------------------------------------------------------------------
 // IR-label grid confusion: every (fg, bg) pair of a threshold grid from the CRF label planes, no label map written.
 // The label of pair (i, j) is fgv if fgv != 0, else 0 if bgv == 0, else 255.  A pixel with fgv != 0 is in the same cell
-// for every j, and one with fgv == 0 is in column 0 or 21 by j alone, so a block counts
-//     az[i][row][v]   pixels whose plane fg[i] reads v (v = 0..20)
+// for every j, and one with fgv == 0 is in column 0 or ncls by j alone, so a block counts
+//     az[i][row][v]   pixels whose plane fg[i] reads v (v = 0..ncls-1)
 //     un[i][j][row]   those of them with v == 0 whose plane bg[j] is not 0 (the unsure ones)
-// as uint32 in LDS (f*22*21 + f*b*22 words, sized by the call's f and b: 51 KiB at 16 x 16, 1.8 KiB at 2 x 2), f + (number
-// of unsure pairs) atomics per pixel instead of f*b, and expands them when it flushes: column v >= 1 of every j gets
-// az[i][row][v], column 21 gets un, column 0 gets az[i][row][0] - un.
+// as uint32 in LDS (f*(ncls+1)*ncls + f*b*(ncls+1) words, sized by the launch's f and b: 51 KiB at 16 x 16 and 21 classes,
+// 1.8 KiB at 2 x 2), f + (number of unsure pairs) atomics per pixel instead of f*b, and expands them when it flushes:
+// column v >= 1 of every j gets az[i][row][v], column ncls gets un, column 0 gets az[i][row][0] - un.
+// A launch counts the fg values i0 .. i0+f-1 of the call's grid: the host gives one launch as many as fit kIrLdsBytes
+// (all 16 at 21 classes, 2 at 81) and loops over the rest.  Every cell of hist belongs to one fg value, so the grouping
+// cannot change a count; the out-of-range pixels are the same in every launch and only the first one reports them.
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr int IR_MAX = IRN_CRF_MAX_SWEEP;     // planes, and pairs per axis
-constexpr int IR_COLS = NC + 1;               // columns of hist: labels 0..20 and 255
+constexpr size_t kIrLdsBytes = 65536 - 64;    // dynamic LDS of a launch: what a workgroup gets without an attribute, less nbad
+
+// words of LDS a launch over f fg values needs
+constexpr size_t ir_lds_words(int f, int b, int ncls) { return (size_t)f * (ncls + 1) * ncls + (size_t)f * b * (ncls + 1); }
+static_assert(ir_lds_words(IR_MAX, IR_MAX, IRN_EVAL_CLASSES) * 4 <= kIrLdsBytes, "a 16 x 16 grid at 21 classes is one launch");
+static_assert(ir_lds_words(1, IR_MAX, IRN_EVAL_MAX_CLASSES) * 4 <= kIrLdsBytes, "one fg value always fits");
 
 struct PairIdx {
     uint8_t fg[IR_MAX], bg[IR_MAX];
@@ -206,12 +217,17 @@ __device__ __forceinline__ uint32_t load4(const uint8_t *__restrict__ q, int val
     return v;
 }
 
-__global__ void __launch_bounds__(TPB) k_ir_label_hist(const uint8_t *__restrict__ planes, int t_count, PairIdx idx, int f,
-                                                       int b, const uint8_t *__restrict__ gt, int n,
+// KNC: the class count as a constant (the instantiation for IRN_EVAL_CLASSES: with run-time divisors in the flush a 16 x 16
+// grid measured 2.6 % slower), or 0 = the launch argument.
+template <int KNC>
+__global__ void __launch_bounds__(TPB) k_ir_label_hist(const uint8_t *__restrict__ planes, int t_count, PairIdx idx, int i0,
+                                                       int f, int b, int ncls, const uint8_t *__restrict__ gt, int n,
                                                        int64_t *__restrict__ hist, int64_t *__restrict__ bad) {
     extern __shared__ uint32_t lds[];
     __shared__ uint32_t nbad;
     const int tid = threadIdx.x;
+    const int NC = KNC ? KNC : ncls;
+    const int kRows = NC + 1, IR_COLS = NC + 1;   // rows: GT 0..ncls-1 and void; columns: labels 0..ncls-1 and 255
     const int n_az = f * kRows * NC, n_un = f * b * kRows;
     uint32_t *az = lds, *un = lds + n_az;
     for (int c = tid; c < n_az + n_un; c += TPB) lds[c] = 0;
@@ -240,7 +256,7 @@ __global__ void __launch_bounds__(TPB) k_ir_label_hist(const uint8_t *__restrict
         uint32_t unsure[4];                   // bit j: plane bg[j] is not 0
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-            row[k] = gt_row((uint8_t)(gw >> (8 * k)));
+            row[k] = gt_row((uint8_t)(gw >> (8 * k)), NC);
             if (k < valid && (row[k] < 0 || ((skip >> k) & 1u))) {
                 ++local_bad;
                 row[k] = -1;
@@ -253,7 +269,7 @@ __global__ void __launch_bounds__(TPB) k_ir_label_hist(const uint8_t *__restrict
             for (int k = 0; k < 4; ++k) unsure[k] |= ((~zero[k] >> idx.bg[j]) & 1u) << j;
         }
         for (int i = 0; i < f; ++i) {
-            const int ti = idx.fg[i];
+            const int ti = idx.fg[i0 + i];
             const uint32_t w = load4(planes + (size_t)ti * n + p, valid);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -274,7 +290,7 @@ __global__ void __launch_bounds__(TPB) k_ir_label_hist(const uint8_t *__restrict
         if (!cnt) continue;
         const int v = c % NC, ir = c / NC, r = ir % kRows, i = ir / kRows;
         for (int j = 0; j < b; ++j) {
-            int64_t *cell = hist + (((size_t)i * b + j) * kRows + r) * IR_COLS;
+            int64_t *cell = hist + (((size_t)(i0 + i) * b + j) * kRows + r) * IR_COLS;
             if (v) {
                 add64(cell + v, cnt);
                 continue;
@@ -284,50 +300,78 @@ __global__ void __launch_bounds__(TPB) k_ir_label_hist(const uint8_t *__restrict
             if (u) add64(cell + NC, u);
         }
     }
-    if (tid == 0 && nbad) add64(bad, nbad);
+    if (tid == 0 && nbad && i0 == 0) add64(bad, nbad);
 }
 
 bool pixels_ok(int h, int w) { return h >= 1 && w >= 1 && (int64_t)h * w <= (int64_t)0x7fffffff - PIX; }
 
 }  // namespace
 
-extern "C" int irn_cam_confusion(const float *high_res_dev, const int64_t *keys_dev, int k, const uint8_t *gt_dev, int h,
-                                 int w, const float *thres_dev, int t, int64_t *hist_dev, int64_t *bad_dev, void *stream) {
-    if (!gt_dev || !thres_dev || !hist_dev || !bad_dev || k < 0 || k > kMaxKeys || (k > 0 && (!high_res_dev || !keys_dev)) ||
+// Every entry with a class count refuses one outside 2..IRN_EVAL_MAX_CLASSES by name; the entries without the argument are
+// the same calls at IRN_EVAL_CLASSES.
+extern "C" int irn_cam_confusion_nc(const float *high_res_dev, const int64_t *keys_dev, int k, const uint8_t *gt_dev, int h,
+                                    int w, const float *thres_dev, int t, int n_classes, int64_t *hist_dev, int64_t *bad_dev,
+                                    void *stream) {
+    if (!classes_ok(n_classes))
+        return fail(IRN_ERR_ARG, "irn_cam_confusion: n_classes %d outside 2..%d", n_classes, IRN_EVAL_MAX_CLASSES);
+    if (!gt_dev || !thres_dev || !hist_dev || !bad_dev || k < 0 || k > n_classes - 1 || (k > 0 && (!high_res_dev || !keys_dev)) ||
         t < 1 || t > IRN_EVAL_MAX_THRES || !pixels_ok(h, w))
         return fail(IRN_ERR_ARG, "irn_cam_confusion: bad argument (k=%d, h=%d, w=%d, t=%d; 0 <= k <= %d, 1 <= t <= %d)",
-                    k, h, w, t, kMaxKeys, IRN_EVAL_MAX_THRES);
+                    k, h, w, t, n_classes - 1, IRN_EVAL_MAX_THRES);
     const int n = h * w;
     hipLaunchKernelGGL(k_cam_hist, dim3(cdiv(n, PIX)), dim3(TPB), 0, (hipStream_t)stream, high_res_dev, keys_dev, k, gt_dev,
-                       n, thres_dev, t, hist_dev, bad_dev);
+                       n, thres_dev, t, n_classes, hist_dev, bad_dev);
     IRN_LAUNCH_CHECK("k_cam_hist");
+    return IRN_OK;
+}
+
+extern "C" int irn_cam_confusion(const float *high_res_dev, const int64_t *keys_dev, int k, const uint8_t *gt_dev, int h,
+                                 int w, const float *thres_dev, int t, int64_t *hist_dev, int64_t *bad_dev, void *stream) {
+    return irn_cam_confusion_nc(high_res_dev, keys_dev, k, gt_dev, h, w, thres_dev, t, IRN_EVAL_CLASSES, hist_dev, bad_dev,
+                                stream);
+}
+
+extern "C" int irn_cam_confusion_reduce_nc(const int64_t *hist_dev, int t, int n_classes, int64_t *conf_dev,
+                                           int64_t *void_dev, void *stream) {
+    if (!classes_ok(n_classes))
+        return fail(IRN_ERR_ARG, "irn_cam_confusion_reduce: n_classes %d outside 2..%d", n_classes, IRN_EVAL_MAX_CLASSES);
+    if (!hist_dev || !conf_dev || t < 1 || t > IRN_EVAL_MAX_THRES)
+        return fail(IRN_ERR_ARG, "irn_cam_confusion_reduce: bad argument (t=%d)", t);
+    hipLaunchKernelGGL(k_cam_reduce, dim3(cdiv((n_classes + 1) * n_classes, TPB)), dim3(TPB), 0, (hipStream_t)stream, hist_dev,
+                       t, n_classes, conf_dev, void_dev);
+    IRN_LAUNCH_CHECK("k_cam_reduce");
     return IRN_OK;
 }
 
 extern "C" int irn_cam_confusion_reduce(const int64_t *hist_dev, int t, int64_t *conf_dev, int64_t *void_dev,
                                         void *stream) {
-    if (!hist_dev || !conf_dev || t < 1 || t > IRN_EVAL_MAX_THRES)
-        return fail(IRN_ERR_ARG, "irn_cam_confusion_reduce: bad argument (t=%d)", t);
-    hipLaunchKernelGGL(k_cam_reduce, dim3(cdiv(kRows * NC, TPB)), dim3(TPB), 0, (hipStream_t)stream, hist_dev, t, conf_dev,
-                       void_dev);
-    IRN_LAUNCH_CHECK("k_cam_reduce");
+    return irn_cam_confusion_reduce_nc(hist_dev, t, IRN_EVAL_CLASSES, conf_dev, void_dev, stream);
+}
+
+extern "C" int irn_label_confusion_nc(const uint8_t *pred_dev, const uint8_t *gt_dev, int h, int w, int pred_255_as,
+                                      int n_classes, int64_t *conf_dev, int64_t *void_dev, int64_t *bad_dev, void *stream) {
+    if (!classes_ok(n_classes))
+        return fail(IRN_ERR_ARG, "irn_label_confusion: n_classes %d outside 2..%d", n_classes, IRN_EVAL_MAX_CLASSES);
+    if (!pred_dev || !gt_dev || !conf_dev || !bad_dev || pred_255_as >= n_classes || !pixels_ok(h, w))
+        return fail(IRN_ERR_ARG, "irn_label_confusion: bad argument (h=%d, w=%d, pred_255_as=%d)", h, w, pred_255_as);
+    const int n = h * w;
+    const size_t lds = sizeof(uint32_t) * (n_classes + 1) * n_classes;          // 26.6 KB at 81 classes
+    hipLaunchKernelGGL(k_label_hist, dim3(cdiv(n, PIX)), dim3(TPB), lds, (hipStream_t)stream, pred_dev, gt_dev, n,
+                       pred_255_as, n_classes, conf_dev, void_dev, bad_dev);
+    IRN_LAUNCH_CHECK("k_label_hist");
     return IRN_OK;
 }
 
 extern "C" int irn_label_confusion(const uint8_t *pred_dev, const uint8_t *gt_dev, int h, int w, int pred_255_as,
                                    int64_t *conf_dev, int64_t *void_dev, int64_t *bad_dev, void *stream) {
-    if (!pred_dev || !gt_dev || !conf_dev || !bad_dev || pred_255_as >= NC || !pixels_ok(h, w))
-        return fail(IRN_ERR_ARG, "irn_label_confusion: bad argument (h=%d, w=%d, pred_255_as=%d)", h, w, pred_255_as);
-    const int n = h * w;
-    hipLaunchKernelGGL(k_label_hist, dim3(cdiv(n, PIX)), dim3(TPB), 0, (hipStream_t)stream, pred_dev, gt_dev, n,
-                       pred_255_as, conf_dev, void_dev, bad_dev);
-    IRN_LAUNCH_CHECK("k_label_hist");
-    return IRN_OK;
+    return irn_label_confusion_nc(pred_dev, gt_dev, h, w, pred_255_as, IRN_EVAL_CLASSES, conf_dev, void_dev, bad_dev, stream);
 }
 
-extern "C" int irn_ir_label_confusion(const uint8_t *planes_dev, int t_count, const int32_t *fg_idx, int f,
-                                      const int32_t *bg_idx, int b, const uint8_t *gt_dev, int h, int w, int64_t *hist_dev,
-                                      int64_t *bad_dev, void *stream) {
+extern "C" int irn_ir_label_confusion_nc(const uint8_t *planes_dev, int t_count, const int32_t *fg_idx, int f,
+                                         const int32_t *bg_idx, int b, const uint8_t *gt_dev, int h, int w, int n_classes,
+                                         int64_t *hist_dev, int64_t *bad_dev, void *stream) {
+    if (!classes_ok(n_classes))
+        return fail(IRN_ERR_ARG, "irn_ir_label_confusion: n_classes %d outside 2..%d", n_classes, IRN_EVAL_MAX_CLASSES);
     if (t_count < 1 || t_count > IR_MAX)
         return fail(IRN_ERR_ARG, "irn_ir_label_confusion: t_count %d outside 1..%d", t_count, IR_MAX);
     if (f < 1 || f > IR_MAX || b < 1 || b > IR_MAX)
@@ -349,11 +393,23 @@ extern "C" int irn_ir_label_confusion(const uint8_t *planes_dev, int t_count, co
     if (!planes_dev || !gt_dev || !hist_dev || !bad_dev)
         return fail(IRN_ERR_ARG, "irn_ir_label_confusion: a null pointer (planes, gt, hist or bad)");
     const int n = h * w;
-    const size_t lds = (size_t)(f * kRows * NC + f * b * kRows) * sizeof(uint32_t);
-    hipLaunchKernelGGL(k_ir_label_hist, dim3(cdiv(n, PIX)), dim3(TPB), lds, (hipStream_t)stream, planes_dev, t_count, idx, f,
-                       b, gt_dev, n, hist_dev, bad_dev);
-    IRN_LAUNCH_CHECK("k_ir_label_hist");
+    // fg values per launch: as many as fit the LDS of a workgroup (>= 1 by the static_assert above)
+    const int per = (int)std::min<size_t>((size_t)f, kIrLdsBytes / (ir_lds_words(1, b, n_classes) * sizeof(uint32_t)));
+    for (int i0 = 0; i0 < f; i0 += per) {
+        const int fi = std::min(per, f - i0);
+        const auto kernel = n_classes == IRN_EVAL_CLASSES ? k_ir_label_hist<IRN_EVAL_CLASSES> : k_ir_label_hist<0>;
+        hipLaunchKernelGGL(kernel, dim3(cdiv(n, PIX)), dim3(TPB), ir_lds_words(fi, b, n_classes) * sizeof(uint32_t),
+                           (hipStream_t)stream, planes_dev, t_count, idx, i0, fi, b, n_classes, gt_dev, n, hist_dev, bad_dev);
+        IRN_LAUNCH_CHECK("k_ir_label_hist");
+    }
     return IRN_OK;
+}
+
+extern "C" int irn_ir_label_confusion(const uint8_t *planes_dev, int t_count, const int32_t *fg_idx, int f,
+                                      const int32_t *bg_idx, int b, const uint8_t *gt_dev, int h, int w, int64_t *hist_dev,
+                                      int64_t *bad_dev, void *stream) {
+    return irn_ir_label_confusion_nc(planes_dev, t_count, fg_idx, f, bg_idx, b, gt_dev, h, w, IRN_EVAL_CLASSES, hist_dev,
+                                     bad_dev, stream);
 }
 
 extern "C" int irn_mask_overlap(const uint8_t *masks_dev, int n, const uint8_t *inst_dev, int g, int h, int w,

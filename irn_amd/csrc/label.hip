@@ -226,7 +226,8 @@ __global__ __launch_bounds__(256) void label_argmax_kernel(const LabelJob *__res
 // irn_cam_confusion (eval.hip), reduced by irn_cam_confusion_reduce.  A NaN score wins at every threshold as it does in
 // the epilogue (torch.argmax): c* = the first NaN channel, j = t.  Scores: `group_of` / `group_scores`, the functions
 // `label_argmax_kernel` calls, on the maximum of `upsample_max_kernel`.
-// Counting: thres_hist.hpp, shared with eval.hip.  An image has (t + 1) * 22 * c bins (113 080 at c = 20, t = 256), so a
+// Counting: thres_hist.hpp, shared with eval.hip.  An image has (t + 1) * (ncls + 1) * c bins (113 080 at 21 classes,
+// c = 20, t = 256; 1 685 920 at 81 classes, c = 80), so a
 // chunk's bins (4096 pixels) stay in registers and are counted in passes over bin ranges of `cap` (the dynamic LDS the
 // host sized for the call: one pass for a typical grid).
 // ---------------------------------------------------------------------------------------------
@@ -235,19 +236,30 @@ constexpr int kSweepChunk = 256 * kSweepGroups;          // groups per chunk (40
 constexpr int kSweepCap = 15360;                         // most LDS bins per pass (60 KiB; thresholds and columns follow)
 static_assert(thist::kThreads == 256, "thres_hist.hpp counts with blocks of this size");
 
+// dynamic LDS of label_sweep_kernel: bins[cap], th[IRN_EVAL_MAX_THRES], col[kMaxKeys] (80 columns), nbad
+constexpr size_t sweep_lds_bytes(int cap) {
+    return sizeof(uint32_t) * cap + sizeof(float) * IRN_EVAL_MAX_THRES + sizeof(int) * thist::kMaxKeys + sizeof(uint32_t);
+}
+static_assert(sweep_lds_bytes(kSweepCap) <= 65536, "the sweep's LDS must fit what a launch gets without an attribute");
+
+// KNC: the class count as a constant (the instantiation for IRN_EVAL_CLASSES, where the row arithmetic of thres_hist.hpp then
+// folds as it did when it was a constant), or 0 = the launch argument.
+template <int KNC>
 __global__ __launch_bounds__(256) void label_sweep_kernel(const LabelJob *__restrict__ jobs, const float *__restrict__ thres,
-                                                          int t, int cap, int64_t *__restrict__ hist, int64_t *__restrict__ bad) {
+                                                          int t, int cap, int ncls_arg, int64_t *__restrict__ hist,
+                                                          int64_t *__restrict__ bad) {
     extern __shared__ __attribute__((aligned(16))) uint32_t sweep_lds[];
+    const int ncls = KNC ? KNC : ncls_arg;
     uint32_t *bins = sweep_lds;                                       // [cap], cap a multiple of 4
     float *th = reinterpret_cast<float *>(sweep_lds + cap);           // [IRN_EVAL_MAX_THRES]
     int *col = reinterpret_cast<int *>(th + IRN_EVAL_MAX_THRES);      // [thist::kMaxKeys]
     uint32_t *nbad = reinterpret_cast<uint32_t *>(col + thist::kMaxKeys);
     const LabelJob J = jobs[blockIdx.y];
-    uint32_t local_bad = thist::stage(thres, t, J.keys, J.c, blockIdx.x == 0 && blockIdx.y == 0, th, col, nbad);
+    uint32_t local_bad = thist::stage(thres, t, J.keys, J.c, blockIdx.x == 0 && blockIdx.y == 0, ncls, th, col, nbad);
 
     const unsigned gw = (unsigned)(J.ow + 3) >> 2, groups = gw * (unsigned)J.oh;
     const unsigned chunks = (groups + kSweepChunk - 1) / kSweepChunk;
-    const uint32_t nbins = (uint32_t)(t + 1) * thist::kRows * (uint32_t)J.c;
+    const uint32_t nbins = (uint32_t)(t + 1) * (uint32_t)(ncls + 1) * (uint32_t)J.c;
     const float gmax = dec_ordered(*J.max_slot);
     for (unsigned chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x) {
         uint32_t bin[4 * kSweepGroups];
@@ -283,17 +295,17 @@ __global__ __launch_bounds__(256) void label_sweep_kernel(const LabelJob *__rest
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 if (q >= G.nq) continue;
-                const int row = thist::gt_row(gv[q]);
+                const int row = thist::gt_row(gv[q], ncls);
                 if (row < 0) {
-                    ++local_bad;                                       // GT 21..254
+                    ++local_bad;                                       // GT ncls..254
                     continue;
                 }
                 const int lo = thist::count_below(th, t, m[q]);
                 const int j = nanc[q] >= 0 ? t : lo, cq = nanc[q] >= 0 ? nanc[q] : cs[q];
-                bin[4 * i + q] = thist::bin_of(j, row, cq, J.c);
+                bin[4 * i + q] = thist::bin_of(j, row, cq, J.c, ncls);
             }
         }
-        local_bad += thist::count(bin, bins, (uint32_t)cap, nbins, J.c, col, t, hist);
+        local_bad += thist::count(bin, bins, (uint32_t)cap, nbins, J.c, col, t, ncls, hist);
     }
     thist::flush_bad(local_bad, nbad, bad);
 }
@@ -437,12 +449,14 @@ extern "C" int irn_label_epilogue(int n_images, const float *const *rw_dev, cons
     return scratch_release(stream);
 }
 
-extern "C" int irn_label_sweep_confusion(int n_images, const float *const *rw_dev, const int32_t *c, const int32_t *h,
-                                         const int32_t *w, const int32_t *out_h, const int32_t *out_w,
-                                         const int64_t *const *keys_dev, const uint8_t *const *gt_dev,
-                                         const float *thres_dev, int t, int64_t *hist_dev, int64_t *bad_dev,
-                                         void *scratch_dev, void *stream_) {
+extern "C" int irn_label_sweep_confusion_nc(int n_images, const float *const *rw_dev, const int32_t *c, const int32_t *h,
+                                            const int32_t *w, const int32_t *out_h, const int32_t *out_w,
+                                            const int64_t *const *keys_dev, const uint8_t *const *gt_dev,
+                                            const float *thres_dev, int t, int n_classes, int64_t *hist_dev,
+                                            int64_t *bad_dev, void *scratch_dev, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
+    if (!thist::classes_ok(n_classes))
+        return fail(IRN_ERR_ARG, "irn_label_sweep_confusion: n_classes %d outside 2..%d", n_classes, IRN_EVAL_MAX_CLASSES);
     if (n_images < 1 || n_images > 65535 || !rw_dev || !c || !h || !w || !out_h || !out_w || !keys_dev || !gt_dev || !thres_dev ||
         !hist_dev || !bad_dev || !scratch_dev || t < 1 || t > IRN_EVAL_MAX_THRES)
         return fail(IRN_ERR_ARG, "irn_label_sweep_confusion: bad argument (n_images=%d, t=%d; 1 <= t <= %d)", n_images, t,
@@ -452,21 +466,31 @@ extern "C" int irn_label_sweep_confusion(int n_images, const float *const *rw_de
                         gt_dev, scratch_dev, B);
     if (rc) return rc;
     for (int i = 0; i < n_images; ++i)                                // the sweep's own conditions, before anything is enqueued
-        if (c[i] > thist::kMaxKeys || !keys_dev[i] || !gt_dev[i])
+        if (c[i] > n_classes - 1 || !keys_dev[i] || !gt_dev[i])
             return fail(IRN_ERR_ARG, "irn_label_sweep_confusion: image %d: c=%d (at most %d), keys and ground truth are required", i,
-                        c[i], thist::kMaxKeys);
+                        c[i], n_classes - 1);
     rc = launch_max_passes(B, scratch_dev, stream);
     if (rc) return rc;
     // LDS bins for the call's largest image, at most kSweepCap per pass; at most 128 chunks of 4096 pixels per image and
     // launch row (a 1040 x 528 image strides once)
-    const long nbins = (long)(t + 1) * thist::kRows * B.max_c;
+    const long nbins = (long)(t + 1) * (n_classes + 1) * B.max_c;
     const int cap = (int)std::min<long>((nbins + 3) / 4 * 4, kSweepCap);
-    const size_t lds = sizeof(uint32_t) * cap + sizeof(float) * IRN_EVAL_MAX_THRES + sizeof(int) * thist::kMaxKeys + sizeof(uint32_t);
+    const size_t lds = sweep_lds_bytes(cap);
     const int bx = (int)std::min<long>(((B.max_px + 3) / 4 + kSweepChunk - 1) / kSweepChunk + 1, 128);
-    hipLaunchKernelGGL(label_sweep_kernel, dim3(bx, n_images), dim3(256), lds, stream, B.dev, thres_dev, t, cap, hist_dev,
-                       bad_dev);
+    const auto kernel = n_classes == IRN_EVAL_CLASSES ? label_sweep_kernel<IRN_EVAL_CLASSES> : label_sweep_kernel<0>;
+    hipLaunchKernelGGL(kernel, dim3(bx, n_images), dim3(256), lds, stream, B.dev, thres_dev, t, cap, n_classes,
+                       hist_dev, bad_dev);
     IRN_LAUNCH_CHECK("label_sweep_kernel");
     return scratch_release(stream);
+}
+
+extern "C" int irn_label_sweep_confusion(int n_images, const float *const *rw_dev, const int32_t *c, const int32_t *h,
+                                         const int32_t *w, const int32_t *out_h, const int32_t *out_w,
+                                         const int64_t *const *keys_dev, const uint8_t *const *gt_dev,
+                                         const float *thres_dev, int t, int64_t *hist_dev, int64_t *bad_dev,
+                                         void *scratch_dev, void *stream_) {
+    return irn_label_sweep_confusion_nc(n_images, rw_dev, c, h, w, out_h, out_w, keys_dev, gt_dev, thres_dev, t, IRN_EVAL_CLASSES,
+                                        hist_dev, bad_dev, scratch_dev, stream_);
 }
 
 extern "C" int irn_cam_merge(int n_scales, const float *const *src_dev, const int32_t *hs, const int32_t *ws, int n_classes,

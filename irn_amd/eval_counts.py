@@ -11,8 +11,17 @@ import torch
 from ._host import accumulator, u8_map
 from ._lib import _need_cuda, _stream, check, lib
 
-EVAL_CLASSES = 21                     # background + 20 VOC classes
+EVAL_CLASSES = 21                     # background + 20 VOC classes: the default class count everywhere
+EVAL_MAX_CLASSES = 81                 # IRN_EVAL_MAX_CLASSES: background + 80
 EVAL_MAX_THRES = 256                  # IRN_EVAL_MAX_THRES
+
+
+def eval_classes(n_classes, who):
+    """`n_classes` (classes including the background) as an int in 2..EVAL_MAX_CLASSES, or a ValueError naming `who`."""
+    nc = int(n_classes)
+    if nc != n_classes or not 2 <= nc <= EVAL_MAX_CLASSES:
+        raise ValueError("%s: n_classes %s outside 2..%d (background included)" % (who, n_classes, EVAL_MAX_CLASSES))
+    return nc
 
 
 def _i64_zeros(shape, dev):
@@ -35,12 +44,14 @@ def _thres_tensor(thres, dev):
     return th, int(th.numel())
 
 
-def cam_confusion(high_res, keys, gt, thres, hist=None, bad=None):
+def cam_confusion(high_res, keys, gt, thres, hist=None, bad=None, n_classes=EVAL_CLASSES):
     """step/eval_cam.py:14-19 + the confusion count for one image at every threshold of `thres` in one pass.
 
     high_res: GPU fp32 [K,H,W] (K >= 0), keys: 0-based classes [K], gt: uint8 [H,W] (255 = void), thres: GPU fp32 [T] from
     `eval_thresholds` (or anything it takes).  Adds into hist int64 [22,21,T+1] (row 21 = void GT, include/irn_hip.h) and
-    bad int64 [1]; returns (hist, bad).  `cam_confusion_matrices(hist)` turns the histogram into the T matrices."""
+    bad int64 [1]; returns (hist, bad).  `cam_confusion_matrices(hist)` turns the histogram into the T matrices.
+    n_classes (nc: classes including the background, 2..81): hist is [nc+1,nc,T+1], keys are 0..nc-2, GT 0..nc-1 or 255."""
+    nc = eval_classes(n_classes, "cam_confusion")
     _need_cuda(high_res, "high_res")
     dev = high_res.device
     g = u8_map(gt, dev, "gt")
@@ -49,50 +60,52 @@ def cam_confusion(high_res, keys, gt, thres, hist=None, bad=None):
     k = int(cams.shape[0]) if cams.dim() == 3 else -1
     if k < 0 or (k and tuple(cams.shape[1:]) != (h, w)):
         raise ValueError("cam_confusion: high_res %s for a GT of %dx%d" % (tuple(cams.shape), h, w))
-    if k > EVAL_CLASSES - 1:
-        raise ValueError("cam_confusion: %d CAM planes (at most %d)" % (k, EVAL_CLASSES - 1))
+    if k > nc - 1:
+        raise ValueError("cam_confusion: %d CAM planes (at most %d)" % (k, nc - 1))
     ks = torch.as_tensor(keys).to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
     if ks.numel() != k:
         raise ValueError("cam_confusion: %d keys for %d CAM planes" % (ks.numel(), k))
     th, t = _thres_tensor(thres, dev)
-    hist = accumulator(hist, (EVAL_CLASSES + 1, EVAL_CLASSES, t + 1), dev, "hist")
+    hist = accumulator(hist, (nc + 1, nc, t + 1), dev, "hist")
     bad = accumulator(bad, (1,), dev, "bad")
     with torch.cuda.device(dev):
-        check(lib.irn_cam_confusion(cams.data_ptr() if k else None, ks.data_ptr() if k else None, k, g.data_ptr(), h, w,
-                                    th.data_ptr(), t, hist.data_ptr(), bad.data_ptr(), _stream()))
+        check(lib.irn_cam_confusion_nc(cams.data_ptr() if k else None, ks.data_ptr() if k else None, k, g.data_ptr(), h, w,
+                                       th.data_ptr(), t, nc, hist.data_ptr(), bad.data_ptr(), _stream()))
     return hist, bad
 
 
-def cam_confusion_matrices(hist):
+def cam_confusion_matrices(hist, n_classes=EVAL_CLASSES):
     """hist int64 [22,21,T+1] of `cam_confusion` -> (conf int64 [T,21,21] (row = GT, column = prediction), void int64
-    [T,21] (predictions at GT-255 pixels)), on the GPU."""
+    [T,21] (predictions at GT-255 pixels)), on the GPU; with n_classes = nc, [nc+1,nc,T+1] -> [T,nc,nc] and [T,nc]."""
+    nc = eval_classes(n_classes, "cam_confusion_matrices")
     _need_cuda(hist, "hist")
     t = int(hist.shape[2]) - 1
-    hist = accumulator(hist, (EVAL_CLASSES + 1, EVAL_CLASSES, t + 1), hist.device, "hist")
-    conf = _i64_zeros((t, EVAL_CLASSES, EVAL_CLASSES), hist.device)
-    void = _i64_zeros((t, EVAL_CLASSES), hist.device)
+    hist = accumulator(hist, (nc + 1, nc, t + 1), hist.device, "hist")
+    conf = _i64_zeros((t, nc, nc), hist.device)
+    void = _i64_zeros((t, nc), hist.device)
     with torch.cuda.device(hist.device):
-        check(lib.irn_cam_confusion_reduce(hist.data_ptr(), t, conf.data_ptr(), void.data_ptr(), _stream()))
+        check(lib.irn_cam_confusion_reduce_nc(hist.data_ptr(), t, nc, conf.data_ptr(), void.data_ptr(), _stream()))
     return conf, void
 
 
-def label_confusion(pred, gt, conf=None, bad=None, pred_255_as=0, void=None):
+def label_confusion(pred, gt, conf=None, bad=None, pred_255_as=0, void=None, n_classes=EVAL_CLASSES):
     """step/eval_sem_seg.py:14-17 for one image: pred, gt uint8 [H,W] GPU tensors (pred 255 reads as `pred_255_as`; None =
     out of range).  Adds into conf int64 [21,21], void int64 [21] (predictions at GT-255 pixels) and bad int64 [1];
-    returns (conf, void, bad)."""
+    returns (conf, void, bad).  With n_classes = nc (background included): conf [nc,nc], void [nc], values 0..nc-1."""
+    nc = eval_classes(n_classes, "label_confusion")
     _need_cuda(pred, "pred")
     dev = pred.device
     p = u8_map(pred, dev, "pred")
     g = u8_map(gt, dev, "gt")
     if p.shape != g.shape:
         raise ValueError("label_confusion: prediction %s for a GT of %s" % (tuple(p.shape), tuple(g.shape)))
-    conf = accumulator(conf, (EVAL_CLASSES, EVAL_CLASSES), dev, "conf")
-    void = accumulator(void, (EVAL_CLASSES,), dev, "void")
+    conf = accumulator(conf, (nc, nc), dev, "conf")
+    void = accumulator(void, (nc,), dev, "void")
     bad = accumulator(bad, (1,), dev, "bad")
     h, w = g.shape
     with torch.cuda.device(dev):
-        check(lib.irn_label_confusion(p.data_ptr(), g.data_ptr(), h, w, -1 if pred_255_as is None else int(pred_255_as),
-                                      conf.data_ptr(), void.data_ptr(), bad.data_ptr(), _stream()))
+        check(lib.irn_label_confusion_nc(p.data_ptr(), g.data_ptr(), h, w, -1 if pred_255_as is None else int(pred_255_as),
+                                         nc, conf.data_ptr(), void.data_ptr(), bad.data_ptr(), _stream()))
     return conf, void, bad
 
 
@@ -122,12 +135,14 @@ def mask_overlap(masks, inst_map, n_inst, bad=None):
     return inter, area_pred, area_gt
 
 
-def ir_label_confusion(planes, fg_idx, bg_idx, gt, hist=None, bad=None):
+def ir_label_confusion(planes, fg_idx, bg_idx, gt, hist=None, bad=None, n_classes=EVAL_CLASSES):
     """step/cam_to_ir_label.py:36-39 + the confusion count for every (fg, bg) pair of a threshold grid, from the planes of
     `crf_label_sweep`: planes uint8 [T,H,W] (GPU), fg_idx [F] / bg_idx [B] plane numbers (1..16 each, repeats allowed), gt
     uint8 [H,W] (255 = void).  Pair (i, j) labels a pixel planes[fg_idx[i]] where that is not 0, else 0 where
     planes[bg_idx[j]] is 0 too, else 255.  Adds into hist int64 [F,B,22,22] (row = GT, 21 = void; column = label, 21 = 255)
-    and bad int64 [1]; returns (hist, bad).  No label map is written."""
+    and bad int64 [1]; returns (hist, bad).  No label map is written.  With n_classes = nc (background included): hist
+    [F,B,nc+1,nc+1], plane values 0..nc-1; a grid too large for one workgroup's LDS is counted in several launches."""
+    nc = eval_classes(n_classes, "ir_label_confusion")
     _need_cuda(planes, "planes")
     dev = planes.device
     if planes.dtype != torch.uint8 or planes.dim() != 3:
@@ -139,10 +154,10 @@ def ir_label_confusion(planes, fg_idx, bg_idx, gt, hist=None, bad=None):
         raise ValueError("ir_label_confusion: planes %s for a GT of %s" % (tuple(pl.shape), tuple(g.shape)))
     fg = np.ascontiguousarray(np.asarray(fg_idx, np.int32).reshape(-1))
     bg = np.ascontiguousarray(np.asarray(bg_idx, np.int32).reshape(-1))
-    hist = accumulator(hist, (fg.size, bg.size, EVAL_CLASSES + 1, EVAL_CLASSES + 1), dev, "hist")
+    hist = accumulator(hist, (fg.size, bg.size, nc + 1, nc + 1), dev, "hist")
     bad = accumulator(bad, (1,), dev, "bad")
     pi32 = C.POINTER(C.c_int32)
     with torch.cuda.device(dev):
-        check(lib.irn_ir_label_confusion(pl.data_ptr(), t, fg.ctypes.data_as(pi32), int(fg.size), bg.ctypes.data_as(pi32),
-                                         int(bg.size), g.data_ptr(), h, w, hist.data_ptr(), bad.data_ptr(), _stream()))
+        check(lib.irn_ir_label_confusion_nc(pl.data_ptr(), t, fg.ctypes.data_as(pi32), int(fg.size), bg.ctypes.data_as(pi32),
+                                            int(bg.size), g.data_ptr(), h, w, nc, hist.data_ptr(), bad.data_ptr(), _stream()))
     return hist, bad

@@ -6,7 +6,7 @@ import torch
 
 from ._host import accumulator
 from ._lib import _need_cuda, _stream, check, i32_array, lib, ptr_array
-from .eval_counts import EVAL_CLASSES, EVAL_MAX_THRES, _thres_tensor
+from .eval_counts import EVAL_CLASSES, EVAL_MAX_THRES, _thres_tensor, eval_classes
 
 
 def _label_inputs(rws, out_sizes, keys):
@@ -68,7 +68,7 @@ def label_epilogue(rws, out_sizes, bg_thres, keys=None, want_labels=True, want_a
     return out
 
 
-def label_sweep_confusion(rws, out_sizes, keys, gts, thres, hist=None, bad=None):
+def label_sweep_confusion(rws, out_sizes, keys, gts, thres, hist=None, bad=None, n_classes=EVAL_CLASSES):
     """`label_epilogue` + `label_confusion` at every background threshold of `thres` in one pass, for a batch (no label
     map and no upsampled tensor is written), by the epilogue's own score functions and `cam_confusion`'s counting code.
 
@@ -76,7 +76,9 @@ def label_sweep_confusion(rws, out_sizes, keys, gts, thres, hist=None, bad=None)
     (255 = void), or ONE flat uint8 GPU buffer that holds the maps of `out_sizes` back to back; thres: GPU fp32 [T] from
     `eval_thresholds` (or anything it takes).  Adds into hist int64 [22,21,T+1] — the layout of `cam_confusion`, so
     `cam_confusion_matrices(hist)` gives the T matrices `label_confusion` counts on the labels of each threshold — and
-    bad int64 [1]; returns (hist, bad).  Everything is checked before the launch: a refusal leaves hist / bad untouched."""
+    bad int64 [1]; returns (hist, bad).  Everything is checked before the launch: a refusal leaves hist / bad untouched.
+    With n_classes = nc (background included, 2..81): at most nc-1 channels per image and hist [nc+1,nc,T+1]."""
+    nc = eval_classes(n_classes, "label_sweep_confusion")
     n = len(rws)
     if n < 1 or len(out_sizes) != n or len(keys) != n:
         raise ValueError("label_sweep_confusion: %d score maps, %d sizes, %d key lists" % (n, len(out_sizes), len(keys)))
@@ -108,8 +110,8 @@ def label_sweep_confusion(rws, out_sizes, keys, gts, thres, hist=None, bad=None)
             gs.append(g.contiguous())
         gt_ptrs = [g.data_ptr() for g in gs]
     for i, (r, k) in enumerate(zip(rs, ks)):
-        if not 1 <= r.shape[0] <= EVAL_CLASSES - 1:
-            raise ValueError("label_sweep_confusion: image %d has %d channels (1..%d)" % (i, r.shape[0], EVAL_CLASSES - 1))
+        if not 1 <= r.shape[0] <= nc - 1:
+            raise ValueError("label_sweep_confusion: image %d has %d channels (1..%d)" % (i, r.shape[0], nc - 1))
         if not (1 <= sizes[i][0] <= 4 * r.shape[1] and 1 <= sizes[i][1] <= 4 * r.shape[2]):
             raise ValueError("label_sweep_confusion: image %d: output %s from a %dx%d map" % (i, sizes[i], r.shape[1], r.shape[2]))
         if k.numel() != r.shape[0]:
@@ -117,14 +119,14 @@ def label_sweep_confusion(rws, out_sizes, keys, gts, thres, hist=None, bad=None)
     th, t = _thres_tensor(thres, dev)
     if not 1 <= t <= EVAL_MAX_THRES:
         raise ValueError("label_sweep_confusion: %d thresholds (1..%d)" % (t, EVAL_MAX_THRES))
-    hist = accumulator(hist, (EVAL_CLASSES + 1, EVAL_CLASSES, t + 1), dev, "hist")
+    hist = accumulator(hist, (nc + 1, nc, t + 1), dev, "hist")
     bad = accumulator(bad, (1,), dev, "bad")
     scratch = torch.empty(max(n, 64), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        check(lib.irn_label_sweep_confusion(
+        check(lib.irn_label_sweep_confusion_nc(
             n, ptr_array([r.data_ptr() for r in rs]), i32_array([r.shape[0] for r in rs]), i32_array([r.shape[1] for r in rs]),
             i32_array([r.shape[2] for r in rs]), i32_array([s[0] for s in sizes]), i32_array([s[1] for s in sizes]),
-            ptr_array([k.data_ptr() for k in ks]), ptr_array(gt_ptrs), th.data_ptr(), t, hist.data_ptr(), bad.data_ptr(),
+            ptr_array([k.data_ptr() for k in ks]), ptr_array(gt_ptrs), th.data_ptr(), t, nc, hist.data_ptr(), bad.data_ptr(),
             scratch.data_ptr(), _stream()))
     return hist, bad
 

@@ -3,7 +3,7 @@ cam_confusion / label_confusion / mask_overlap).
 
     observed_classes(conf, void)      the size chainercv's growing confusion matrix reaches
     iou_from_confusion(conf, void)    calc_semantic_segmentation_confusion + the iou of step/eval_cam.py:22-28
-    sem_seg_scores(conf, void)        step/eval_sem_seg.py:19-31 (fp / fn / iou of the [:21, :21] matrix)
+    sem_seg_scores(conf, void)        step/eval_sem_seg.py:19-31 (fp / fn / iou of the [:nc, :nc] matrix; the reference has nc = 21)
     ir_label_scores(hist)             step/tune_ir_label.py: accuracy, coverage and all-pixel iou of one IR-label grid point
     instance_ap_voc(records)          eval_instance_segmentation_voc(iou_thresh=0.5): calc_instance_segmentation_voc_prec_rec
                                       + calc_detection_voc_ap(use_07_metric=False), from per-image overlap counts
@@ -38,9 +38,11 @@ def iou_from_confusion(conf, void=None):
 
 
 def sem_seg_scores(conf, void=None):
-    """step/eval_sem_seg.py:19-29 on the [:21, :21] matrix -> dict fp, fn, iou (float64 arrays) and the matrix."""
+    """step/eval_sem_seg.py:19-29 on the [:nc, :nc] matrix -> dict fp, fn, iou (float64 arrays) and the matrix.  nc is the
+    size of the matrix given (the class count it was counted with, background included; 21 in the reference)."""
+    nc = np.asarray(conf).shape[0]
     conf, _ = iou_from_confusion(conf, void)
-    conf = conf[:21, :21]
+    conf = conf[:nc, :nc]
     gtj = conf.sum(axis=1)
     resj = conf.sum(axis=0)
     gtjresj = np.diag(conf)
@@ -53,19 +55,20 @@ def sem_seg_scores(conf, void=None):
 
 
 def ir_label_scores(hist):
-    """Scores of one (fg, bg) point of step/tune_ir_label.py from hist int64 [22,22] of ops.ir_label_confusion (row = GT,
-    21 = void; column = IR label, 21 = 255 unsure) -> dict
-      iou, miou     sem_seg_scores of the [:21, :21] matrix: the accuracy on the confident pixels
+    """Scores of one (fg, bg) point of step/tune_ir_label.py from hist int64 [nc+1,nc+1] of ops.ir_label_confusion (row =
+    GT, nc = void; column = IR label, nc = 255 unsure; nc = 21 by default, taken from the histogram's size) -> dict
+      iou, miou     sem_seg_scores of the [:nc, :nc] matrix: the accuracy on the confident pixels
       coverage      the share of the non-void pixels that get a label
       iou_all, miou_all   per class diag / (GT pixels, unsure ones included, + labelled pixels - diag): unsure pixels count
                     as misses."""
     hist = np.asarray(hist, np.int64)
-    conf, void = hist[:21, :21], hist[21, :21]
+    nc = hist.shape[0] - 1
+    conf, void = hist[:nc, :nc], hist[nc, :nc]
     s = sem_seg_scores(conf, void)
     diag = np.diag(conf)
     with np.errstate(divide="ignore", invalid="ignore"):
-        coverage = conf.sum() / hist[:21, :].sum()
-        iou_all = diag / (hist[:21, :].sum(axis=1) + conf.sum(axis=0) - diag)
+        coverage = conf.sum() / hist[:nc, :].sum()
+        iou_all = diag / (hist[:nc, :].sum(axis=1) + conf.sum(axis=0) - diag)
     return {"iou": s["iou"], "miou": nanmean(s["iou"]), "coverage": float(coverage), "iou_all": iou_all,
             "miou_all": nanmean(iou_all)}
 

@@ -203,7 +203,7 @@ class _AffinityDisplacementSums(torch.autograd.Function):
     maxima, pair classes and signs from them."""
 
     @staticmethod
-    def forward(ctx, edge, dp, label, radius, ordered=False):
+    def forward(ctx, edge, dp, label, radius, ordered=False, ignore_from=21):
         b, hp, wp = label.shape
         need = lib.irn_aff_loss_workspace_bytes(b, hp, wp, radius)
         if need == 0:
@@ -213,35 +213,37 @@ class _AffinityDisplacementSums(torch.autograd.Function):
         sums = torch.empty(5, dtype=torch.float64, device=edge.device)
         counts = torch.empty(3, dtype=torch.int64, device=edge.device)
         with torch.cuda.device(edge.device):
-            check(lib.irn_aff_loss_forward(edge.data_ptr(), dp.data_ptr(), label.data_ptr(), b, hp, wp, radius,
-                                           sums.data_ptr(), counts.data_ptr(), ws.data_ptr(), need, _stream()))
+            check(lib.irn_aff_loss_forward_ignore(edge.data_ptr(), dp.data_ptr(), label.data_ptr(), b, hp, wp, radius,
+                                                  ignore_from, sums.data_ptr(), counts.data_ptr(), ws.data_ptr(), need,
+                                                  _stream()))
         ctx.save_for_backward(edge, dp, label)
-        ctx.geom = (radius, ws, bool(ordered))
+        ctx.geom = (radius, ws, bool(ordered), ignore_from)
         ctx.mark_non_differentiable(counts)
         return sums, counts
 
     @staticmethod
     def backward(ctx, grad_sums, _grad_counts):
         edge, dp, label = ctx.saved_tensors
-        radius, ws, ordered = ctx.geom
+        radius, ws, ordered, ignore_from = ctx.geom
         b, hp, wp = label.shape
         coef = grad_sums.to(torch.float32).contiguous()          # stays on the device: nothing synchronises
         grad_edge = torch.empty_like(edge)
         grad_dp = torch.empty_like(dp)
-        backward = lib.irn_aff_loss_backward_ordered if ordered else lib.irn_aff_loss_backward
+        backward = lib.irn_aff_loss_backward_ordered_ignore if ordered else lib.irn_aff_loss_backward_ignore
         with torch.cuda.device(edge.device):
-            check(backward(edge.data_ptr(), dp.data_ptr(), label.data_ptr(), b, hp, wp, radius, coef.data_ptr(),
+            check(backward(edge.data_ptr(), dp.data_ptr(), label.data_ptr(), b, hp, wp, radius, ignore_from, coef.data_ptr(),
                            grad_edge.data_ptr(), grad_dp.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
-        return grad_edge, grad_dp, None, None, None
+        return grad_edge, grad_dp, None, None, None, None
 
 
-def affinity_displacement_sums(edge, dp, label, radius, ordered=False):
+def affinity_displacement_sums(edge, dp, label, radius, ordered=False, n_classes=20):
     """The five sums and three counts that the IRNet training losses are formed from (reference
     net/resnet50_irn.py:198-213 + step/train_irn.py:58-64 + voc12/dataloader.py:80-106), in one pass over the three maps:
     no [B, |S|, N] tensor is written, forward or backward (include/irn_hip.h, irn_aff_loss_forward).
 
     ``edge``: GPU float [B, Hp, Wp] (or [B, 1, Hp, Wp]), already through the sigmoid; ``dp``: GPU float [B, 2, Hp, Wp];
-    ``label``: GPU uint8 [B, Hp, Wp], 0 background, 1..20 a class, >= 21 ignore.  Returns ``(sums, counts)``: fp64 [5]
+    ``label``: GPU uint8 [B, Hp, Wp], 0 background, 1..n_classes a class (``n_classes``: the dataset's foreground
+    classes, 1..80), anything above ignored.  Returns ``(sums, counts)``: fp64 [5]
     (bg / fg positive-affinity loss, negative-affinity loss, fg / bg displacement loss) and int64 [3] (bg, fg, neg
     pairs), both on the device.  Differentiable w.r.t. ``edge`` and ``dp``.  ``ordered``: the backward is the gather
     (irn_aff_loss_backward_ordered) — bit-identical gradients for identical inputs, whatever an image is batched with —
@@ -251,12 +253,14 @@ def affinity_displacement_sums(edge, dp, label, radius, ordered=False):
     _need_cuda(label, "label")
     if label.dtype != torch.uint8 or label.dim() != 3:
         raise ValueError("affinity_displacement_sums: label must be uint8 [B, Hp, Wp]")
+    if not 1 <= int(n_classes) <= 80:
+        raise ValueError("affinity_displacement_sums: n_classes %s outside 1..80" % (n_classes,))
     b, hp, wp = label.shape
     if edge.numel() != b * hp * wp or tuple(dp.shape) != (b, 2, hp, wp):
         raise ValueError("affinity_displacement_sums: edge %s and dp %s do not fit label %s"
                          % (tuple(edge.shape), tuple(dp.shape), tuple(label.shape)))
     return _AffinityDisplacementSums.apply(edge.reshape(b, hp, wp).contiguous().float(), dp.contiguous().float(),
-                                           label.contiguous(), int(radius), bool(ordered))
+                                           label.contiguous(), int(radius), bool(ordered), int(n_classes) + 1)
 
 
 def affinity_sparse2dense(affinity_sparse, ind_from, ind_to, n_vertices):

@@ -234,19 +234,21 @@ class AffinityDisplacementLoss(Net):
         pair_disp = self.to_pair_displacement(dp_out)
         return pos_aff_loss, neg_aff_loss, self.to_displacement_loss(pair_disp), torch.abs(pair_disp)
 
-    def fused_losses(self, x, label, trunk="autograd"):
+    def fused_losses(self, x, label, trunk="autograd", n_classes=20):
         """The four scalar losses of a training step (reference step/train_irn.py:58-64: positive affinity, negative
         affinity, foreground displacement, background displacement) from the images ``x`` and the reduced IR label maps
         ``label`` (uint8 [B, Hp, Wp]) — `forward(x, True)` followed by the masked sums, without any [B, |S|, N] tensor.
         ``trunk``: "autograd" runs the frozen trunk inside the autograd graph as the reference does (`Net.forward`),
-        "inference" under `no_grad` on the inference path (`Net.forward_train`)."""
+        "inference" under `no_grad` on the inference path (`Net.forward_train`).  ``n_classes``: the dataset's foreground
+        classes; labels above it are ignored."""
         from ..misc import indexing
         if trunk not in ("autograd", "inference"):
             raise ValueError("fused_losses: trunk is 'autograd' or 'inference', got %r" % (trunk,))
         edge_out, dp_out = Net.forward_train(self, x) if trunk == "inference" else Net.forward(self, x)
         # reproducible mode: the gather backward, the same bits every time; otherwise the faster scatter with float atomics
         s, n = indexing.affinity_displacement_sums(torch.sigmoid(edge_out), dp_out, label, self.path_index.radius,
-                                                   ordered=_r50.DETERMINISTIC is True)
+                                                   ordered=_r50.DETERMINISTIC is True, n_classes=n_classes)
+        self.last_pair_counts = n            # int64 [3] on the device: (bg, fg, neg) pairs of this batch
         n = n.to(torch.float64)
         pos_aff_loss = s[0] / (n[0] + 1e-5) / 2 + s[1] / (n[1] + 1e-5) / 2
         neg_aff_loss = s[2] / (n[2] + 1e-5)

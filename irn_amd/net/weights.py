@@ -34,9 +34,9 @@ def random_resnet50_state(seed=0):
     return _fill(ResNet50Trunk(strides=(2, 2, 2, 1)), seed).state_dict()
 
 
-def random_cam_state(seed=1):
+def random_cam_state(seed=1, n_classes=20):
     from .resnet50_cam import CAM
-    return _fill(CAM(), seed).state_dict()
+    return _fill(CAM(n_classes=n_classes), seed).state_dict()
 
 
 def random_irn_state(seed=2):

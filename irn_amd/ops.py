@@ -42,7 +42,7 @@ from .augment import (AUGMENT_DESC_WORDS, AUGMENT_LABEL_DESC_WORDS, AugmentTable
 from .bn_act import bn_act, bn_act_, bn_act_backward, bn_fold, bn_param_grads, stem_pool, upsample_bilinear
 from .cocomask import mask_rle, rle_decode, rle_from_string, rle_to_string
 from .crf import CRF_GT_PROB, CRF_MAX_SWEEP, CRF_T, crf_filter, crf_inference_label, crf_ir_label, crf_label_sweep
-from .eval_counts import (EVAL_CLASSES, EVAL_MAX_THRES, cam_confusion, cam_confusion_matrices, eval_thresholds, ir_label_confusion,
+from .eval_counts import (EVAL_CLASSES, EVAL_MAX_CLASSES, EVAL_MAX_THRES, cam_confusion, cam_confusion_matrices, eval_thresholds, ir_label_confusion,
                           label_confusion, mask_overlap)
 from .gemm import (conv1x1_algo_count, conv1x1_nhwc, conv3x3_split, gemm16_algo_count, gemm16_nhwc, gemm_ranks, gemm_ranks16,
                    gemm_ranks3x3, split16, split16_pad, split_overflowed, split_weight, split_weight_3x3)

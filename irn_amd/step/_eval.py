@@ -48,8 +48,9 @@ def check_shape(id, what, shape, gt_shape):
         raise ValueError("%s: %s %s does not match the ground truth %s" % (id, what, tuple(shape), tuple(gt_shape)))
 
 
-def raise_if_bad(bad, what):
+def raise_if_bad(bad, what, n_fg=20):
+    """`n_fg`: the foreground classes the counts were taken with (`_classes.num_classes(args)`)."""
     n = int(bad.item())
     if n:
-        raise ValueError("%s: %d value(s) out of range (GT outside 0..20 and 255, a NaN CAM, a class key outside 0..19, "
-                         "a prediction above 20 or an instance id above the count)" % (what, n))
+        raise ValueError("%s: %d value(s) out of range (GT outside 0..%d and 255, a NaN CAM, a class key outside 0..%d, "
+                         "a prediction above %d or an instance id above the count)" % (what, n, n_fg, n_fg - 1, n_fg))

@@ -7,6 +7,7 @@ ONCE per process and device list and serve every later step (`WorkerPool`): a HI
 the CAMs `make_cam` left in device memory (`_stores.CamStore`) survive from one step of `run_sample.py` to the next.  The step
 API is unchanged: `step.X.run(args)` works on its own and returns when every shard is done."""
 import atexit
+import functools
 import importlib
 import os
 import pickle
@@ -36,16 +37,21 @@ class ModelSpec:
     keeps it on its device for later steps that name the same checkpoint — make_sem_seg_labels and make_ins_seg_labels
     share one EdgeDisplacement."""
 
-    def __init__(self, network, cls_name, path, strict):
+    def __init__(self, network, cls_name, path, strict, n_classes=None):
+        """`n_classes`: the class count a network that has one (the CAM classifier) is built with; None: its default."""
         self.network, self.cls_name, self.path, self.strict = network, cls_name, os.path.abspath(path), bool(strict)
+        self.n_classes = None if n_classes is None else int(n_classes)
 
     def key(self):
         st = os.stat(self.path)
-        return (self.network, self.cls_name, self.path, self.strict, st.st_mtime_ns, st.st_size)
+        return (self.network, self.cls_name, self.path, self.strict, st.st_mtime_ns, st.st_size, self.n_classes)
 
     def build(self):
         from ..net import weights
-        return weights.load_checkpoint(getattr(import_network(self.network), self.cls_name), self.path, strict=self.strict)
+        factory = getattr(import_network(self.network), self.cls_name)
+        if self.n_classes is not None:
+            factory = functools.partial(factory, n_classes=self.n_classes)
+        return weights.load_checkpoint(factory, self.path, strict=self.strict)
 
 
 _MODELS = {}          # per process: ModelSpec.key() -> network (on this worker's device once a step has used it)

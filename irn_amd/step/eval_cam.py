@@ -17,7 +17,7 @@ import torch
 from .. import ops
 from ..misc import evaluation
 from ..voc12 import eval_data
-from . import _eval
+from . import _classes, _eval
 
 
 def _thresholds(args):
@@ -30,6 +30,7 @@ def run(args):
     ids = eval_data.seg_ids(args.voc12_root, args.chainer_eval_set)
     req, th32 = _thresholds(args)
     dev = _eval.device()
+    c = _classes.num_classes(args)
 
     def load(id):
         gt = eval_data.class_label(args.voc12_root, id)
@@ -47,11 +48,11 @@ def run(args):
         hist = bad = None
         for id, it in _eval.items(ids, load, args):
             hist, bad = ops.cam_confusion(it["high_res"].to(dev, non_blocking=True), it["keys"].to(dev),
-                                          it["gt"].to(dev, non_blocking=True), th, hist, bad)
+                                          it["gt"].to(dev, non_blocking=True), th, hist, bad, n_classes=c + 1)
         if hist is None:
             raise ValueError("eval_cam: the split %s lists no images" % args.chainer_eval_set)
-        conf, void = ops.cam_confusion_matrices(hist)
-        _eval.raise_if_bad(bad, "eval_cam")
+        conf, void = ops.cam_confusion_matrices(hist, n_classes=c + 1)
+        _eval.raise_if_bad(bad, "eval_cam", c)
         conf, void = conf.cpu().numpy(), void.cpu().numpy()
 
     mious = {}

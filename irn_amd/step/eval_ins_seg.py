@@ -17,7 +17,7 @@ import torch
 from .. import ops
 from ..misc import evaluation
 from ..voc12 import eval_data
-from . import _eval
+from . import _classes, _eval
 
 
 def load_rle(path):
@@ -34,9 +34,10 @@ def load_rle(path):
 def run(args):
     ids = eval_data.seg_ids(args.voc12_root, args.chainer_eval_set)
     dev = _eval.device()
+    c = _classes.num_classes(args)
 
     def load(id):
-        inst_map, inst_class = eval_data.instance_label(args.voc12_root, id)
+        inst_map, inst_class = eval_data.instance_label(args.voc12_root, id, n_fg=c)
         path = os.path.join(args.ins_seg_out_dir, id + ".npy")
         rle_path = os.path.join(args.ins_seg_out_dir, id + ".rle.npz")
         if not os.path.exists(path) and os.path.exists(rle_path):
@@ -65,7 +66,7 @@ def run(args):
                             "gt_class": it["inst_class"].numpy()})
         if not records:
             raise ValueError("eval_ins_seg: the split %s lists no images" % args.chainer_eval_set)
-        _eval.raise_if_bad(bad, "eval_ins_seg")
+        _eval.raise_if_bad(bad, "eval_ins_seg", c)
         flat = torch.cat(counts).cpu().numpy()                 # every image's counts in one copy
     pos = 0
     for rec in records:

@@ -2,7 +2,7 @@
 
 Reads  args.voc12_root (ImageSets/Segmentation/<args.chainer_eval_set>.txt, SegmentationClass/<id>.png),
        args.sem_seg_out_dir/<id>.png
-Prints fp[0] fn[0], the mean fp / fn of the classes 1..20 and {'iou': ..., 'miou': ...} in the reference's format;
+Prints fp[0] fn[0], the mean fp / fn of the classes 1..C (C = --num_classes, 20 by default) and {'iou': ..., 'miou': ...} in the reference's format;
 returns the {'iou', 'miou'} dict.
 
 Prediction 255 reads as 0 (step/eval_sem_seg.py:14); the confusion is counted per image on the device
@@ -17,12 +17,13 @@ from PIL import Image
 from .. import ops
 from ..misc import evaluation
 from ..voc12 import eval_data
-from . import _eval
+from . import _classes, _eval
 
 
 def run(args):
     ids = eval_data.seg_ids(args.voc12_root, args.chainer_eval_set)
     dev = _eval.device()
+    c = _classes.num_classes(args)
 
     def load(id):
         gt = eval_data.class_label(args.voc12_root, id)
@@ -34,10 +35,10 @@ def run(args):
         conf = void = bad = None
         for id, it in _eval.items(ids, load, args):
             conf, void, bad = ops.label_confusion(it["pred"].to(dev, non_blocking=True), it["gt"].to(dev, non_blocking=True),
-                                                  conf, bad, pred_255_as=0, void=void)
+                                                  conf, bad, pred_255_as=0, void=void, n_classes=c + 1)
         if conf is None:
             raise ValueError("eval_sem_seg: the split %s lists no images" % args.chainer_eval_set)
-        _eval.raise_if_bad(bad, "eval_sem_seg")
+        _eval.raise_if_bad(bad, "eval_sem_seg", c)
         conf, void = conf.cpu().numpy(), void.cpu().numpy()
 
     s = evaluation.sem_seg_scores(conf, void)

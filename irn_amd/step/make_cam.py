@@ -20,11 +20,11 @@ import torch
 
 from ..misc import torchutils
 from ..voc12 import dataloader as voc12_dataloader
-from . import _io, _pool, _report, _split_auto, _stores
+from . import _classes, _io, _pool, _report, _split_auto, _stores
 
 
 def merge_scales(outputs, size, label):
-    """outputs: per-scale GPU [20,hs,ws] activation maps -> (keys, cam [K,ceil(H/4),ceil(W/4)],
+    """outputs: per-scale GPU [C,hs,ws] activation maps (C classes) -> (keys, cam [K,ceil(H/4),ceil(W/4)],
     high_res [K,H,W]) — step/make_cam.py:38-52 in two launches of libirn_hip.so (irn_cam_merge).
     GPU tensors only (the torch-op restatement the tests compare with lives in oracle/torch_mirrors.py)."""
     from .. import ops
@@ -164,11 +164,13 @@ def _work(process_id, model, dataset, args):
 
 
 def run(args):
-    model = _pool.ModelSpec(args.cam_network, "CAM", args.cam_weights_name + ".pth", strict=True)   # built by the worker(s)
+    c = _classes.num_classes(args)
+    model = _pool.ModelSpec(args.cam_network, "CAM", args.cam_weights_name + ".pth", strict=True,
+                            n_classes=None if c == _classes.VOC_CLASSES else c)   # built by the worker(s); a --cam_network of the user's own need not know the argument
     n_gpus = _pool.n_gpus_or_raise(args)
     scales = tuple(float(s) for s in args.cam_scales)
     dataset = voc12_dataloader.VOC12ClassificationDatasetMSF(args.train_list, voc12_root=args.voc12_root,
-                                                             scales=scales, raw=_io.device_preprocess(args))
+                                                             scales=scales, raw=_io.device_preprocess(args), n_classes=c)
     names = [voc12_dataloader.decode_int_filename(v) for v in dataset.img_name_list]
     dataset = torchutils.split_dataset(dataset, n_gpus)
     os.makedirs(args.cam_out_dir, exist_ok=True)

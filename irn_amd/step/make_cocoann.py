@@ -23,7 +23,8 @@ Three deliberate differences from the reference:
    dict with a str "counts" through).  Polygons are out of scope.
 2. Annotation ids are unique over the file (1, 2, 3, ... in output order).  The reference restarts at 1 for every image
    (:36), and COCO readers index annotations by id.
-3. Categories are generated (the 20 VOC classes, id 1..20 in class order, supercategory "none"), not copied from
+3. Categories are generated (the 20 VOC classes, id 1..20 in class order, supercategory "none"; with --num_classes C the
+   names of --class_names, or class_1 .. class_C, id 1..C), not copied from
    pascal_val2012.json (:16, a file the reference does not ship), and category_id = class + 1 so that it points into
    them; the reference passes the 0-based class through.
 """
@@ -36,15 +37,15 @@ from PIL import Image
 
 from .. import ops
 from ..voc12 import dataloader
-from . import _eval
+from . import _classes, _eval
 
 CATEGORIES = ("aeroplane", "bicycle", "bird", "boat", "bottle", "bus", "car", "cat", "chair", "cow", "diningtable", "dog",
               "horse", "motorbike", "person", "pottedplant", "sheep", "sofa", "train", "tvmonitor")
 MIN_SCORE = 1e-5                      # step/make_cocoann.py:39
 
 
-def categories():
-    return [{"supercategory": "none", "id": i + 1, "name": name} for i, name in enumerate(CATEGORIES)]
+def categories(names=CATEGORIES):
+    return [{"supercategory": "none", "id": i + 1, "name": name} for i, name in enumerate(names)]
 
 
 def annotation(ann_id, img_id, cls, area, bbox, height, width, counts):
@@ -53,11 +54,11 @@ def annotation(ann_id, img_id, cls, area, bbox, height, width, counts):
             "width": width, "height": height}
 
 
-def rle_record_kept(rec, height, width, name=None):
+def rle_record_kept(rec, height, width, name=None, n_classes=len(CATEGORIES)):
     """One <name>.rle.npz record (a mapping with the arrays `ops.detect_instance_rle_batch` returns), checked against a
     JPEG of height x width.  -> {"class" int64 [K], "counts" int64 [total], "offsets" int64 [K+1], "area" int64 [K], "bbox"
     int32 [K,4]} of the K detections that stay (score >= MIN_SCORE), "low" (the number dropped) and "n" (all of them).
-    Needs no device.  Errors name the image when `name` is given."""
+    Needs no device.  Errors name the image when `name` is given; `n_classes`: the dataset's foreground classes."""
     cls, score = np.asarray(rec["class"]).reshape(-1).astype(np.int64), np.asarray(rec["score"]).reshape(-1)
     counts, offsets = np.asarray(rec["counts"]).reshape(-1).astype(np.int64), np.asarray(rec["offsets"]).reshape(-1).astype(np.int64)
     area, bbox = np.asarray(rec["area"]).reshape(-1).astype(np.int64), np.asarray(rec["bbox"]).reshape(-1, 4).astype(np.int32)
@@ -71,8 +72,8 @@ def rle_record_kept(rec, height, width, name=None):
         raise ValueError("%srun lengths of size %s do not match the %dx%d (height x width) JPEG" % (who, size, height, width))
     if offsets[0] != 0 or (np.diff(offsets) < 1).any() or offsets[n] != len(counts):
         raise ValueError("%soffsets do not partition the %d run lengths" % (who, len(counts)))
-    if n and (cls.min() < 0 or cls.max() >= len(CATEGORIES)):
-        raise ValueError("%sclass outside 0..%d" % (who, len(CATEGORIES) - 1))
+    if n and (cls.min() < 0 or cls.max() >= n_classes):
+        raise ValueError("%sclass outside 0..%d" % (who, n_classes - 1))
     keep = np.flatnonzero(~(score < MIN_SCORE))
     parts = [counts[offsets[i]:offsets[i + 1]] for i in keep]
     for i, c in zip(keep, parts):
@@ -103,6 +104,8 @@ def rle_record_annotations(rec, img_id, height, width, first_id, name=None):
 def run(args):
     names = [dataloader.decode_int_filename(v) for v in dataloader.load_img_name_list(args.infer_list)]
     dev = _eval.device()
+    class_names = _classes.class_names(args)          # refusals (a missing file, a wrong line count) before any image is read
+    c = len(class_names)
 
     def load(name):
         with Image.open(dataloader.get_img_path(name, args.voc12_root)) as im:
@@ -113,7 +116,7 @@ def run(args):
         rle_path = os.path.join(args.ins_seg_out_dir, name + ".rle.npz")
         if not found and os.path.exists(rle_path):
             with np.load(rle_path, allow_pickle=False) as z:
-                kept = rle_record_kept(z, height, width)               # (the loader names the image of an error)
+                kept = rle_record_kept(z, height, width, n_classes=c)               # (the loader names the image of an error)
             return {"rle": np.int64(1), "class": kept["class"], "counts": kept["counts"], "offsets": kept["offsets"],
                     "area": kept["area"], "bbox": kept["bbox"], "size": np.int64([height, width]),
                     "low": np.int64(kept["low"]), "found": np.int64(kept["n"] > 0)}
@@ -128,15 +131,15 @@ def run(args):
                 if m.shape != (len(cls), height, width):
                     raise ValueError("masks %s do not match the %d detections of a %dx%d (height x width) JPEG"
                                      % (m.shape, len(cls), height, width))
-                if cls.min() < 0 or cls.max() >= len(CATEGORIES):
-                    raise ValueError("class outside 0..%d" % (len(CATEGORIES) - 1))
+                if cls.min() < 0 or cls.max() >= c:
+                    raise ValueError("class outside 0..%d" % (c - 1))
                 keep = ~(score < MIN_SCORE)
                 low = int(len(cls) - keep.sum())
                 mask, cls = m[keep], cls[keep]
         return {"mask": np.ascontiguousarray(mask), "class": cls, "size": np.int64([height, width]),
                 "low": np.int64(low), "found": np.int64(found), "rle": np.int64(0)}
 
-    out = {"images": [], "annotations": [], "categories": categories(), "type": "instances"}
+    out = {"images": [], "annotations": [], "categories": categories(class_names), "type": "instances"}
     stats = {"images": 0, "annotations": 0, "skipped_low_score": 0, "without_detections": 0}
     with torch.cuda.device(dev):
         for name, it in _eval.items(names, load, args):

@@ -31,20 +31,22 @@ from ..misc import pyutils, torchutils
 from ..net import weights
 from ..net.resnet50_cam import Net
 from ..voc12 import dataloader
+from . import _classes
 
 MAX_LOADER_WORKERS = 8
 PRINT_EVERY = 100
 
 
 def build_model(args):
-    model = Net()
+    c = _classes.num_classes(args)
+    model = Net(n_classes=c)
     init = getattr(args, "cam_init_weights", None)
     if init:
         state = torch.load(init, map_location="cpu", weights_only=True)
         if "conv1.weight" in state:          # a bare trunk: its keys are the `resnet50.` ones (the stages alias them)
             state = {"resnet50." + k: v for k, v in state.items() if not k.startswith("fc.")}
     else:
-        state = weights.random_cam_state()
+        state = weights.random_cam_state(n_classes=c)
     model.load_state_dict(state, strict=False)
     return model
 
@@ -56,11 +58,13 @@ def device_augment(args):
 def make_datasets(args, seed):
     """(train, val) datasets as step/train_cam.py:44-52 configures them; raw items when the batch is built on the GPU."""
     raw = device_augment(args)
+    c = _classes.num_classes(args)
     train = dataloader.VOC12ClassificationDataset(args.train_list, voc12_root=args.voc12_root,
                                                   resize_long=tuple(getattr(args, "cam_resize_long", (320, 640))), hor_flip=True,
-                                                  crop_size=args.cam_crop_size, crop_method="random", raw=raw, seed=seed)
+                                                  crop_size=args.cam_crop_size, crop_method="random", raw=raw, seed=seed,
+                                                  n_classes=c)
     val = dataloader.VOC12ClassificationDataset(args.val_list, voc12_root=args.voc12_root, crop_size=args.cam_crop_size,
-                                                raw=raw, seed=seed)
+                                                raw=raw, seed=seed, n_classes=c)
     return train, val
 
 

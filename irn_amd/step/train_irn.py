@@ -34,6 +34,7 @@ from ..misc import indexing, pyutils, torchutils
 from ..net import weights
 from ..net.resnet50_irn import AffinityDisplacementLoss
 from ..voc12 import dataloader
+from . import _classes
 
 MAX_LOADER_WORKERS = 8
 
@@ -106,9 +107,13 @@ def check_split_overflow(trunk):
                                "`run_train.py --split_gemm 0` (IRN_SPLIT_GEMM=0): the fp32 GEMMs have no such limit.")
 
 
-def train_step(model, optimizer, img, label, trunk="autograd"):
-    """One optimisation step on a batch already on the device; returns the four losses as a device tensor [4]."""
-    parts = model.fused_losses(img, label) if trunk == "autograd" else model.fused_losses(img, label, trunk=trunk)
+def train_step(model, optimizer, img, label, trunk="autograd", n_classes=20):
+    """One optimisation step on a batch already on the device; returns the four losses as a device tensor [4].  `n_classes`:
+    the dataset's foreground classes (labels above it are ignored by the loss)."""
+    kw = {} if trunk == "autograd" else {"trunk": trunk}
+    if n_classes != 20:
+        kw["n_classes"] = n_classes
+    parts = model.fused_losses(img, label, **kw)
     pos_aff_loss, neg_aff_loss, dp_fg_loss, dp_bg_loss = parts
     total_loss = (pos_aff_loss + neg_aff_loss) / 2 + (dp_fg_loss + dp_bg_loss) / 2
     optimizer.zero_grad()
@@ -130,7 +135,8 @@ def displacement_mean(model, loader, device):
 
 
 def run(args):
-    """Returns {'first_losses': [4 floats], 'steps': int}: the losses of the first step and the steps taken."""
+    """Returns {'first_losses': [4 floats], 'first_counts': [bg, fg, neg pairs of the first batch], 'steps': int}: the losses
+    and pair counts of the first step and the steps taken."""
     # the mode only, before the model is built or a convolution runs
     with _tuned.process_mode():
         if irn_trunk(args) == "inference":
@@ -149,6 +155,7 @@ def _run(args):
     model = build_model(args, path_index)
 
     trunk = irn_trunk(args)
+    n_classes = _classes.num_classes(args)
     train_dataset, infer_dataset = make_datasets(args, seed)
     max_step = (len(train_dataset) // args.irn_batch_size) * args.irn_num_epoches
     if max_step == 0:
@@ -163,15 +170,16 @@ def _run(args):
     model = model.to(device)
     model.train()
     timer = pyutils.Timer()
-    first, pending = None, []
+    first, first_counts, pending = None, None, []
     for ep in range(args.irn_num_epoches):
         print("Epoch %d/%d" % (ep + 1, args.irn_num_epoches))
         train_dataset.set_epoch(ep)
         for it, pack in enumerate(_loader(train_dataset, args, True, seed + ep)):
             img, label = device_batch(pack, args.irn_crop_size, device)
-            pending.append(train_step(model, optimizer, img, label, trunk))
+            pending.append(train_step(model, optimizer, img, label, trunk, n_classes))
             if first is None:
                 first = [float(v) for v in pending[0].cpu()]
+                first_counts = [int(v) for v in model.last_pair_counts.cpu()]
             if (optimizer.global_step - 1) % 50 == 0:
                 timer.update_progress(optimizer.global_step / max_step)
                 mean = torch.stack(pending).mean(0).cpu()          # the one read-back per 50 steps
@@ -198,4 +206,4 @@ def _run(args):
         os.makedirs(out_dir, exist_ok=True)
     torch.save(model.to("cpu").state_dict(), args.irn_weights_name)      # (on the host: the aliased entries stay one storage)
     torch.cuda.empty_cache()
-    return {"first_losses": first, "steps": optimizer.global_step}
+    return {"first_losses": first, "first_counts": first_counts, "steps": optimizer.global_step}

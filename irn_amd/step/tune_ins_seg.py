@@ -29,7 +29,7 @@ from .. import ops
 from ..misc import evaluation
 from ..voc12 import dataloader as voc12_dataloader
 from ..voc12 import eval_data
-from . import _eval, _io, _labels, _report, _stores, make_ins_seg_labels
+from . import _classes, _eval, _io, _labels, _report, _stores, make_ins_seg_labels
 from .tune_sem_seg import grid_axes as _grid_axes
 from .tune_sem_seg import pick_best
 
@@ -98,9 +98,10 @@ def run(args):
     if not ids:
         raise ValueError("tune_ins_seg: the split %s lists no images" % args.chainer_eval_set)
     dev = _eval.device()
+    c = _classes.num_classes(args)
 
     def load(id):
-        inst_map, inst_class = eval_data.instance_label(args.voc12_root, id)
+        inst_map, inst_class = eval_data.instance_label(args.voc12_root, id, n_fg=c)
         img = np.array(Image.open(voc12_dataloader.get_img_path(id, args.voc12_root)).convert("RGB"))
         _eval.check_shape(id, "image", img.shape[:2], inst_map.shape)
         return {"inst_map": inst_map, "inst_class": inst_class, "image": img}
@@ -124,6 +125,6 @@ def run(args):
         if pend:
             _count(model, walker, pend, axes, records, bad, args)
         _labels.end_walk(walker)             # before the read-backs and checks, which still belong inside the mode
-        _eval.raise_if_bad(bad, "tune_ins_seg")
+        _eval.raise_if_bad(bad, "tune_ins_seg", c)
         _report.check_split_overflow("tune_ins_seg")
     return report(records, axes, configured)

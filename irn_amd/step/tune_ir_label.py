@@ -7,7 +7,7 @@ Reads  args.voc12_root (ImageSets/Segmentation/<args.chainer_eval_set>.txt, JPEG
        args.tune_conf_fg_thres, args.tune_conf_bg_thres (more values per axis)
 Prints the configured point's {'iou', 'miou', 'coverage', 'miou_all'}, one `fg .. bg .. miou .. coverage .. miou_all ..` line
        per grid point and the best one (highest miou_all); returns the configured point's dict + 'grid' {(fg, bg): miou_all},
-       'scores' {(fg, bg): dict of evaluation.ir_label_scores}, 'hist' (numpy int64 [F,B,22,22]) and 'best'.  Writes nothing.
+       'scores' {(fg, bg): dict of evaluation.ir_label_scores}, 'hist' (numpy int64 [F,B,22,22]; [F,B,C+2,C+2] with --num_classes C) and 'best'.  Writes nothing.
 
 IR labels are mined on args.train_list, but ground truth exists only for the segmentation split, so the ids of
 args.chainer_eval_set are scored (eval_cam makes the same choice).  The IR label of a pixel is fg if fg != 0, else 0 if bg == 0,
@@ -28,7 +28,7 @@ from .. import ops
 from ..misc import evaluation
 from ..voc12 import dataloader as voc12_dataloader
 from ..voc12 import eval_data
-from . import _eval, _io
+from . import _classes, _eval, _io
 
 MAX_AXIS = 16                         # values per axis (irn_ir_label_confusion)
 MAX_THRES = ops.CRF_MAX_SWEEP         # distinct thresholds over both axes together: CRFs per image
@@ -66,7 +66,7 @@ def pick_best(grid):
 
 
 def report(hist, fgs, bgs, configured):
-    """Scores of every grid point from hist int64 [F,B,22,22], printed in the step's format; returns the step's dict."""
+    """Scores of every grid point from hist int64 [F,B,nc+1,nc+1], printed in the step's format; returns the step's dict."""
     scores = {(fg, bg): evaluation.ir_label_scores(hist[i, j]) for i, fg in enumerate(fgs) for j, bg in enumerate(bgs)}
     grid = {point: s["miou_all"] for point, s in scores.items()}
     here = scores[configured]
@@ -89,6 +89,7 @@ def run(args):
     if not ids:
         raise ValueError("tune_ir_label: the split %s lists no images" % args.chainer_eval_set)
     dev = _eval.device()
+    c = _classes.num_classes(args)
 
     def load(id):
         gt = eval_data.class_label(args.voc12_root, id)
@@ -107,7 +108,7 @@ def run(args):
         hist = bad = None
         for id, it in _eval.items(ids, load, args):
             planes = ops.crf_label_sweep(_io.upload(it["image"]), _io.upload(it["high_res"]), _io.upload(it["keys"]), th32)
-            hist, bad = ops.ir_label_confusion(planes, fg_idx, bg_idx, _io.upload(it["gt"]), hist, bad)
-        _eval.raise_if_bad(bad, "tune_ir_label")
+            hist, bad = ops.ir_label_confusion(planes, fg_idx, bg_idx, _io.upload(it["gt"]), hist, bad, n_classes=c + 1)
+        _eval.raise_if_bad(bad, "tune_ir_label", c)
         hist = hist.cpu().numpy()
     return report(hist, fgs, bgs, configured)

@@ -23,7 +23,7 @@ from .. import ops
 from ..misc import evaluation
 from ..voc12 import dataloader as voc12_dataloader
 from ..voc12 import eval_data
-from . import _eval, _io, _labels, _report, _stores
+from . import _classes, _eval, _io, _labels, _report, _stores
 
 MAX_PAIRS = 64                        # (beta, exp_times) pairs = walks per batch
 
@@ -60,7 +60,7 @@ def pick_best(grid):
 
 
 def report(conf, void, axes, configured):
-    """Scores of every grid point from conf int64 [P,T,21,21] / void int64 [P,T,21] (pairs in beta-major order), printed in
+    """Scores of every grid point from conf int64 [P,T,nc,nc] / void int64 [P,T,nc] (nc = --num_classes + 1; pairs in beta-major order), printed in
     the step's format; returns the step's dict."""
     betas, exps, req, _ = axes
     grid, ious = {}, {}
@@ -83,7 +83,7 @@ def report(conf, void, axes, configured):
     return out
 
 
-def _count(model, walker, pend, pairs, th, hist, bad, args):
+def _count(model, walker, pend, pairs, th, hist, bad, args, nc):
     """One batch: the boundary maps once, then per (beta, exp_times) a walk and the count of every threshold."""
     _labels.edges_for(model, pend, _labels.irn_batch(args), **_labels.edge_store_kw(model, args))
     edges, cams = [p["edge"] for p in pend], [p["cam"] for p in pend]
@@ -94,7 +94,7 @@ def _count(model, walker, pend, pairs, th, hist, bad, args):
         # before the count, not after: the count adds into an accumulator and cannot be redone once a fallback re-run has
         # replaced the walk's outputs
         walker.sync()
-        _, bad = ops.label_sweep_confusion(rws, sizes, keys, gts, th, hist[p], bad)
+        _, bad = ops.label_sweep_confusion(rws, sizes, keys, gts, th, hist[p], bad, n_classes=nc)
     pend.clear()
     return bad
 
@@ -108,6 +108,7 @@ def run(args):
     if not ids:
         raise ValueError("tune_sem_seg: the split %s lists no images" % args.chainer_eval_set)
     dev = _eval.device()
+    nc = _classes.num_classes(args) + 1
 
     def load(id):
         gt = eval_data.class_label(args.voc12_root, id)
@@ -118,7 +119,7 @@ def run(args):
     with _labels.tuning(args, dev) as (model, walker):
         batch = _labels.walk_batch(args, 64)
         th = torch.from_numpy(th32).to(dev)
-        hist = torch.zeros((len(pairs), ops.EVAL_CLASSES + 1, ops.EVAL_CLASSES, len(th32) + 1), dtype=torch.int64, device=dev)
+        hist = torch.zeros((len(pairs), nc + 1, nc, len(th32) + 1), dtype=torch.int64, device=dev)
         bad = torch.zeros(1, dtype=torch.int64, device=dev)
         cam_run = _stores.current_cam_run(args.cam_out_dir)
         pend = []
@@ -130,12 +131,12 @@ def run(args):
             p.update(img=ops.msf_pack(_io.upload(it["image"]), (1.0,))[0], gt=it["gt"])
             pend.append(p)
             if len(pend) == batch:
-                bad = _count(model, walker, pend, pairs, th, hist, bad, args)
+                bad = _count(model, walker, pend, pairs, th, hist, bad, args, nc)
         if pend:
-            bad = _count(model, walker, pend, pairs, th, hist, bad, args)
+            bad = _count(model, walker, pend, pairs, th, hist, bad, args, nc)
         _labels.end_walk(walker)             # before the read-backs and checks, which still belong inside the mode
-        _eval.raise_if_bad(bad, "tune_sem_seg")
-        conf, void = zip(*(ops.cam_confusion_matrices(hist[p]) for p in range(len(pairs))))
+        _eval.raise_if_bad(bad, "tune_sem_seg", nc - 1)
+        conf, void = zip(*(ops.cam_confusion_matrices(hist[p], n_classes=nc) for p in range(len(pairs))))
         conf, void = torch.stack(conf).cpu().numpy(), torch.stack(void).cpu().numpy()
         _report.check_split_overflow("tune_sem_seg")
     return report(conf, void, axes, configured)

@@ -5,7 +5,7 @@ voc12/dataloader.py pieces the label-generation steps use:
     VOC12ClassificationDatasetMSF (:175-205)
 
 JPEGs are decoded with PIL (the reference's imageio call decodes through PIL as well).  The
-image-level labels come from ``cls_labels.npy`` ({int id -> float32[20]}); pass ``cls_labels=`` or
+image-level labels come from ``cls_labels.npy`` ({int id -> float32[C]}, C = 20 for VOC; ``n_classes=C`` checks the rows); pass ``cls_labels=`` or
 keep the file next to the image lists as the reference does.
 
 The two datasets of the IRNet training step are here as well: ``VOC12ImageDataset`` (:109-156, the top-left crops of
@@ -42,6 +42,23 @@ def load_img_name_list(dataset_path):
         return np.asarray([int(line.strip().replace("_", "")) for line in f if line.strip()], np.int64)
 
 
+def load_label_list(img_name_list_path, img_name_list, cls_labels=None, n_classes=None):
+    """float32 [N, C]: the image-level labels of the list, from `cls_labels` or from cls_labels.npy beside the list file.
+    With `n_classes` every row must have that length: a label file made for another class list is an error that names the
+    file and both numbers."""
+    path = "cls_labels"
+    if cls_labels is None:
+        path = os.path.join(os.path.dirname(os.path.abspath(img_name_list_path)), "cls_labels.npy")
+        cls_labels = np.load(path, allow_pickle=True).item()
+    rows = [np.asarray(cls_labels[int(n)], np.float32).reshape(-1) for n in img_name_list]
+    if n_classes is not None:
+        for n, row in zip(img_name_list, rows):
+            if row.size != int(n_classes):
+                raise ValueError("%s: the label of image %s has %d entries, --num_classes is %d"
+                                 % (path, decode_int_filename(n), row.size, int(n_classes)))
+    return np.array(rows, np.float32)
+
+
 def get_img_path(img_name, voc12_root):
     if not isinstance(img_name, str):
         img_name = decode_int_filename(img_name)
@@ -75,7 +92,7 @@ class VOC12ClassificationDataset(Dataset):
     `classification_collate`: the images are ragged."""
 
     def __init__(self, img_name_list_path, voc12_root, resize_long=None, hor_flip=False, crop_size=None, crop_method=None,
-                 cls_labels=None, raw=False, seed=0, img_normal=TorchvisionNormalize()):
+                 cls_labels=None, raw=False, seed=0, img_normal=TorchvisionNormalize(), n_classes=None):
         self.img_name_list = load_img_name_list(img_name_list_path)
         self.voc12_root = voc12_root
         self.resize_long = resize_long
@@ -88,10 +105,7 @@ class VOC12ClassificationDataset(Dataset):
         self.epoch = 0
         if raw and not crop_size:
             raise ValueError("VOC12ClassificationDataset: raw items are made for a fixed crop_size")
-        if cls_labels is None:
-            path = os.path.join(os.path.dirname(os.path.abspath(img_name_list_path)), "cls_labels.npy")
-            cls_labels = np.load(path, allow_pickle=True).item()
-        self.label_list = np.array([cls_labels[int(n)] for n in self.img_name_list], np.float32)
+        self.label_list = load_label_list(img_name_list_path, self.img_name_list, cls_labels, n_classes)
 
     def set_epoch(self, epoch):
         self.epoch = int(epoch)
@@ -163,7 +177,7 @@ class VOC12ClassificationDatasetMSF(Dataset):
     loader workers of the bicubic resizes."""
 
     def __init__(self, img_name_list_path, voc12_root, img_normal=TorchvisionNormalize(), scales=(1.0,),
-                 cls_labels=None, raw=False, skip_image=None):
+                 cls_labels=None, raw=False, skip_image=None, n_classes=None):
         self.img_name_list = load_img_name_list(img_name_list_path)
         self.voc12_root = voc12_root
         self.img_normal = img_normal
@@ -173,10 +187,7 @@ class VOC12ClassificationDatasetMSF(Dataset):
         # runs second takes the boundary / displacement maps from device memory): the item then carries an EMPTY uint8 tensor
         # and the size read from the file header — no JPEG decode, no upload
         self.skip_image = skip_image
-        if cls_labels is None:
-            path = os.path.join(os.path.dirname(os.path.abspath(img_name_list_path)), "cls_labels.npy")
-            cls_labels = np.load(path, allow_pickle=True).item()
-        self.label_list = np.array([cls_labels[int(n)] for n in self.img_name_list], np.float32)
+        self.label_list = load_label_list(img_name_list_path, self.img_name_list, cls_labels, n_classes)
 
     def __len__(self):
         return len(self.img_name_list)

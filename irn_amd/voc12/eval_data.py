@@ -16,7 +16,7 @@ import os
 import numpy as np
 from PIL import Image
 
-N_FG = 20
+N_FG = 20                             # VOC; a step with --num_classes passes its own
 
 
 def seg_ids(voc12_root, split):
@@ -36,7 +36,8 @@ def class_label(voc12_root, id):
     return _palette_png(os.path.join(voc12_root, "SegmentationClass", id + ".png"))
 
 
-def instance_label(voc12_root, id):
+def instance_label(voc12_root, id, n_fg=N_FG):
+    """`n_fg`: the dataset's foreground classes; an instance's class lies in 0..n_fg-1."""
     obj = _palette_png(os.path.join(voc12_root, "SegmentationObject", id + ".png"))
     cls = class_label(voc12_root, id)
     if obj.shape != cls.shape:
@@ -48,7 +49,7 @@ def instance_label(voc12_root, id):
     for g, oid in enumerate(ids):
         m = obj == oid
         lbl = int(np.unique(cls[m])[0]) - 1
-        if not 0 <= lbl < N_FG:
+        if not 0 <= lbl < n_fg:
             raise ValueError("%s: object %d has class %d (background or void)" % (id, int(oid), lbl))
         inst_map[m] = g + 1
         inst_class[g] = lbl

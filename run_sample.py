@@ -17,6 +17,7 @@ import argparse
 import os
 
 from irn_amd.misc import pyutils
+from irn_amd.step import _classes
 
 
 def _flag(v):
@@ -52,6 +53,7 @@ def build_parser():
     p.add_argument("--val_list", default="voc12/val.txt", type=str)
     p.add_argument("--infer_list", default="voc12/train.txt", type=str)
     p.add_argument("--chainer_eval_set", default="train", type=str)
+    _classes.add_arguments(p)              # --num_classes, --class_names
     p.add_argument("--cam_network", default="net.resnet50_cam", type=str)
     p.add_argument("--cam_scales", default=(1.0, 0.5, 1.5, 2.0), type=float, nargs="+")
     p.add_argument("--irn_network", default="net.resnet50_irn", type=str)
@@ -160,6 +162,8 @@ def main(argv=None):
             raise SystemExit("--train_irn_pass: IRNet training is run by `python run_train.py --train_irn_pass True`, not from here"
                              if name == "train_irn_pass" else
                              "--%s: CAM training is run by `python run_train_cam.py`, not from here" % name)
+    if args.class_names:
+        _classes.class_names(args)           # a missing file or a wrong line count, before any step has run
     for d in (args.cam_out_dir, args.sem_seg_out_dir, args.ins_seg_out_dir) + ((args.ir_label_out_dir,) if args.cam_to_ir_label_pass else ()):
         os.makedirs(d, exist_ok=True)
     apply_split_gemm(args)

@@ -12,6 +12,9 @@ each path the paths alternate, and the median of `--reps` passes is reported as 
   (b) the same for a 2 x 2 grid (4 thresholds against 4 calls)
   (c) `crf_label_sweep` at T = 2 against one `crf_ir_label`: what the chunked entry costs where it shares nothing more
   (d) `ir_label_confusion` alone, 4 x 4 and 16 x 16, on the planes of (a) / random planes of 16 thresholds
+  (e) with --classes80, INSTEAD of (a)-(d): the two counts at 81 classes (`n_classes=81`), figures only — `ir_label_confusion`
+      at 16 x 16 on random planes of the labels 1..80 (eight launches per image: the fg axis in groups of two), and
+      `label_sweep_confusion` of one 94 x 125 score map of 80 channels (375 x 500 output) at 16 thresholds
 
     python tools/tune_ir_label_bench.py [--images 64] [--reps 20] [--json-out profiles/tune_ir_label_bench.json]
 """
@@ -87,13 +90,37 @@ def alternate(paths, reps):
     return {name: float(np.median(v)) for name, v in ms.items()}
 
 
+def classes80(n, reps, dev):
+    rng = np.random.RandomState(0)
+    gts = [torch.from_numpy(rng.randint(0, 81, synth.voc_image_size(s)).astype(np.uint8)).to(dev) for s in range(n)]
+    planes = [torch.from_numpy(np.where(rng.rand(16, *g.shape) < 0.5, 0, rng.randint(1, 81, size=(16,) + tuple(g.shape))).astype(np.uint8))
+              .to(dev) for g in gts]
+    rw = torch.from_numpy(np.abs(rng.randn(80, 94, 125)).astype(np.float32)).to(dev)
+    gt = torch.from_numpy(rng.randint(0, 81, (375, 500)).astype(np.uint8)).to(dev)
+    keys, th = torch.arange(80, device=dev), ops.eval_thresholds(np.linspace(0.05, 0.8, 16), dev)
+    all16 = list(range(16))
+
+    def count():
+        hist = bad = None
+        for p, g in zip(planes, gts):
+            hist, bad = ops.ir_label_confusion(p, all16, all16, g, hist, bad, n_classes=81)
+    m = alternate({"ir": count, "sweep": lambda: ops.label_sweep_confusion([rw], [(375, 500)], [keys], [gt], th, n_classes=81)}, reps)
+    return {"metric": "81-class counts", "images": n, "reps": reps, "device": torch.cuda.get_device_name(0),
+            "ir_label_confusion_16x16_us_per_image": round(1e3 * m["ir"] / n, 2),
+            "label_sweep_confusion_80ch_375x500_t16_ms": round(m["sweep"], 3)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=64)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--json-out", default=os.path.join(ROOT, "profiles", "tune_ir_label_bench.json"))
+    ap.add_argument("--classes80", action="store_true", help="only (e): the 81-class counts")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
+    if a.classes80:
+        print(json.dumps(classes80(a.images, a.reps, dev)))
+        return
     items = _items(a.images, dev)
     n = len(items)
     res = {"metric": "tune_ir_label calls, ms per image (median of %d passes over %d images)" % (a.reps, n), "images": n,

@@ -17,52 +17,36 @@ and all T share the image's two lattices.  Per image `ops.crf_label_sweep` runs 
 `ops.ir_label_confusion` counts every pair from the T planes; the histogram stays on the device and comes back once
 (DESIGN.md §23).  A plane is bit-equal to what `ops.crf_ir_label` computes for that threshold, so a grid point's counts are
 those of the PNGs cam_to_ir_label would write there.  An image without class keys contributes its all-zero map, as
-cam_to_ir_label writes it.  Runs in the calling process on its current device like the evaluation steps (step/_eval.py)."""
+cam_to_ir_label writes it.  Runs in the calling process on its current device like the evaluation steps (step/_eval.py).
+The axis rules, the tie-breaking of `best` and the split reader are step/_tune.py's, shared with the walk tuners."""
+import functools
 import os
 
 import numpy as np
 import torch
-from PIL import Image
 
 from .. import ops
 from ..misc import evaluation
-from ..voc12 import dataloader as voc12_dataloader
 from ..voc12 import eval_data
-from . import _classes, _eval, _io
+from . import _classes, _eval, _io, _tune
 
 MAX_AXIS = 16                         # values per axis (irn_ir_label_confusion)
 MAX_THRES = ops.CRF_MAX_SWEEP         # distinct thresholds over both axes together: CRFs per image
+# ties go to the smaller fg, then the smaller bg
+pick_best = functools.partial(_tune.pick_best, tie_order=(0, 1))
 
 
 def grid_axes(args):
     """-> (fg values as requested, bg values as requested, all distinct thresholds ascending float32, fg plane numbers, bg
-    plane numbers): each axis holds its configured value, sorted and without repeats; values are told apart as float32 (the
-    seeds compare in float32) and the first spelling of a float32 value names it."""
-    axes = []
-    for what, conf, tune in (("foreground", "conf_fg_thres", "tune_conf_fg_thres"), ("background", "conf_bg_thres", "tune_conf_bg_thres")):
-        req = {}
-        for t in [float(getattr(args, conf))] + [float(t) for t in (getattr(args, tune, None) or ())]:
-            req.setdefault(float(np.float32(t)), t)
-        th32 = np.unique(np.asarray(list(req), np.float32))
-        if np.isnan(th32).any():
-            raise ValueError("tune_ir_label: a %s threshold is NaN" % what)
-        if th32.size > MAX_AXIS:
-            raise ValueError("tune_ir_label: %d %s thresholds (at most %d)" % (th32.size, what, MAX_AXIS))
-        axes.append(([req[float(t)] for t in th32], th32))
-    (fgs, fg32), (bgs, bg32) = axes
+    plane numbers): each axis is a `_tune.threshold_axis` that holds its configured value."""
+    (fgs, fg32), (bgs, bg32) = (
+        _tune.threshold_axis(getattr(args, "conf_%s_thres" % a), getattr(args, "tune_conf_%s_thres" % a, None), what, MAX_AXIS,
+                             "tune_ir_label") for a, what in (("fg", "foreground"), ("bg", "background")))
     th32 = np.unique(np.concatenate([fg32, bg32]))
     if th32.size > MAX_THRES:
         raise ValueError("tune_ir_label: %d distinct thresholds over both axes (at most %d: each is one CRF per image)"
                          % (th32.size, MAX_THRES))
     return fgs, bgs, th32, np.searchsorted(th32, fg32).astype(np.int32), np.searchsorted(th32, bg32).astype(np.int32)
-
-
-def pick_best(grid):
-    """The grid point of the highest score; ties go to the smaller fg, then the smaller bg (a NaN never wins against a number)."""
-    def rank(point):
-        m = grid[point]
-        return (m == m, m if m == m else 0.0, -point[0], -point[1])
-    return max(grid, key=rank)
 
 
 def report(hist, fgs, bgs, configured):
@@ -83,18 +67,15 @@ def report(hist, fgs, bgs, configured):
 
 def run(args):
     fgs, bgs, th32, fg_idx, bg_idx = grid_axes(args)          # refusals before any image is read
-    configured = (fgs[int(np.searchsorted(th32[fg_idx], np.float32(args.conf_fg_thres)))],
-                  bgs[int(np.searchsorted(th32[bg_idx], np.float32(args.conf_bg_thres)))])
-    ids = eval_data.seg_ids(args.voc12_root, args.chainer_eval_set)
-    if not ids:
-        raise ValueError("tune_ir_label: the split %s lists no images" % args.chainer_eval_set)
+    configured = (_tune.configured(fgs, th32[fg_idx], args.conf_fg_thres), _tune.configured(bgs, th32[bg_idx], args.conf_bg_thres))
+    ids = _tune.split_ids(args)
+    _tune.refuse_empty(ids, args, "tune_ir_label")
     dev = _eval.device()
     c = _classes.num_classes(args)
 
     def load(id):
         gt = eval_data.class_label(args.voc12_root, id)
-        img = np.array(Image.open(voc12_dataloader.get_img_path(id, args.voc12_root)).convert("RGB"))
-        _eval.check_shape(id, "image", img.shape[:2], gt.shape)
+        img = _tune.jpeg(args, id, gt.shape)
         cam = np.load(os.path.join(args.cam_out_dir, id + ".npy"), allow_pickle=True).item()
         keys = np.asarray(cam["keys"], np.int64).reshape(-1)
         if keys.size:

@@ -11,7 +11,11 @@ the same seed gives the same tensor on every box):
 * ``displacement_field`` dp[0]=dy, dp[1]=dx pointing at the nearest of m attractors
                          (reference step/make_ins_seg_labels.py:124)
 * ``voc_num_classes``    K drawn from the VOC12 image-level label histogram
+* ``blob_ground_truth``  class / object maps cut from CAM blobs, and ``write_voc_tree``: the VOC-layout tree of JPEGs, label
+                         PNGs, lists and CAM files that step-level tests and benches run on
 """
+import os
+
 import numpy as np
 from scipy import ndimage
 
@@ -128,6 +132,61 @@ def photo(h, w, seed=0):
         img[y0:y1, x0:x1] = rng.choice([0.0, 255.0], 3)
     img += rng.normal(0, 6, img.shape)
     return np.clip(np.rint(img), 0, 255).astype(np.uint8)
+
+
+def upsample4(cam, size):
+    """[K,gh,gw] on the stride-4 grid -> [K,H,W] of an image of `size`, nearest neighbour."""
+    return np.repeat(np.repeat(cam, 4, axis=1), 4, axis=2)[:, :size[0], :size[1]]
+
+
+def blob_ground_truth(cam, keys, fg_cut, void_cut, obj_ids=None):
+    """Ground truth cut from CAM planes [K,H,W] at label resolution -> (class map, object map or None), uint8 [H,W]: where the
+    highest plane (the first of equals) is above `fg_cut` its class `keys[plane] + 1` / its object `obj_ids[plane]` (one
+    instance per class), 255 (void) where it lies in (void_cut, fg_cut], 0 below."""
+    top, arg = cam.max(axis=0), cam.argmax(axis=0)
+
+    def cut(ids):
+        out = np.where(top > fg_cut, np.asarray(ids)[arg], 0).astype(np.uint8)
+        out[(top > void_cut) & (top <= fg_cut)] = 255
+        return out
+    return cut(np.asarray(keys) + 1), None if obj_ids is None else cut(obj_ids)
+
+
+def save_palette_png(path, arr):
+    """uint8 [H,W] as a palette ('P' mode) PNG, the way VOC ships its label maps."""
+    from PIL import Image
+    img = Image.fromarray(np.asarray(arr, np.uint8), mode="P")
+    img.putpalette([v for i in range(256) for v in ((i * 37) % 256, (i * 91) % 256, (i * 53) % 256)])
+    img.save(path)
+
+
+def write_voc_tree(root, specs, list_path, cam_dir=None, split="train", cls_labels=None):
+    """A VOC-layout tree under `root` from per-image specs {"name", "photo" (uint8 [H,W,3]), "quality" (of the JPEG), "keys",
+    "cls" (class map), optional "obj" (object map), optional "cam" (the dict of the CAM file)}: JPEGImages, SegmentationClass,
+    SegmentationObject where a spec has "obj", ImageSets/Segmentation/<split>.txt, the image list `list_path`, with
+    `cls_labels` = the class count a cls_labels.npy beside the list, and the CAM files in `cam_dir`.  -> the names."""
+    from PIL import Image
+    names = [s["name"] for s in specs]
+    dirs = ["JPEGImages", "SegmentationClass", "ImageSets/Segmentation"] + ["SegmentationObject"] * any("obj" in s for s in specs)
+    for d in [os.path.join(root, d) for d in dirs] + [os.path.dirname(list_path)] + [cam_dir] * (cam_dir is not None):
+        os.makedirs(d, exist_ok=True)
+    for s in specs:
+        Image.fromarray(s["photo"]).save(os.path.join(root, "JPEGImages", s["name"] + ".jpg"), quality=s["quality"])
+        save_palette_png(os.path.join(root, "SegmentationClass", s["name"] + ".png"), s["cls"])
+        if "obj" in s:
+            save_palette_png(os.path.join(root, "SegmentationObject", s["name"] + ".png"), s["obj"])
+        if "cam" in s:
+            np.save(os.path.join(cam_dir, s["name"] + ".npy"), s["cam"])
+    for path in (os.path.join(root, "ImageSets", "Segmentation", split + ".txt"), list_path):
+        with open(path, "w") as f:
+            f.write("\n".join(names) + "\n")
+    if cls_labels is not None:
+        labels = {}
+        for s in specs:
+            labels[int(s["name"].replace("_", ""))] = lab = np.zeros(cls_labels, np.float32)
+            lab[s["keys"]] = 1
+        np.save(os.path.join(os.path.dirname(list_path), "cls_labels.npy"), labels)
+    return names
 
 
 

@@ -214,8 +214,4 @@ def eval_ins_seg(root, split, ins_dir):
                                           iou_thresh=0.5)
 
 
-def save_p_png(path, arr):
-    """uint8 [H,W] as a palette ('P' mode) PNG, the way VOC ships its label maps."""
-    img = Image.fromarray(np.asarray(arr, np.uint8), mode="P")
-    img.putpalette([v for i in range(256) for v in ((i * 37) % 256, (i * 91) % 256, (i * 53) % 256)])
-    img.save(path)
+from irn_amd.synth import save_palette_png as save_p_png  # noqa: E402,F401  (the fixtures' writer, not a restatement)

@@ -13,6 +13,7 @@ from PIL import Image
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _cocomask_ref as R  # noqa: E402
+import _steps as S  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -245,23 +246,13 @@ def test_step_names_the_image_of_a_mask_of_the_wrong_shape(tmp_path):
 
 
 def test_run_sample_writes_the_file(tmp_path):
-    import run_sample
-    from irn_amd.misc import pyutils
-    from irn_amd.step import _common
     root, ins, names, _ = _make_tree(tmp_path)
     out = tmp_path / "coco.json"
-    stdout = sys.stdout
-    try:
-        res = run_sample.main(["--voc12_root", str(root), "--infer_list", str(tmp_path / "train.txt"), "--num_workers", "2",
-                               "--cam_out_dir", str(tmp_path / "cam"), "--sem_seg_out_dir", str(tmp_path / "sem"),
-                               "--ins_seg_out_dir", str(ins), "--log_name", str(tmp_path / "log"),
-                               "--make_cam_pass", "False", "--make_ins_seg_pass", "False", "--make_sem_seg_pass", "False",
-                               "--make_cocoann_pass", "True", "--cocoann_out", str(out)])
-    finally:
-        if isinstance(sys.stdout, pyutils.Logger):
-            sys.stdout.close()
-        sys.stdout = stdout
-        _common.shutdown_workers()
+    res = S.run_sample_main(["--voc12_root", str(root), "--infer_list", str(tmp_path / "train.txt"), "--num_workers", "2",
+                             "--cam_out_dir", str(tmp_path / "cam"), "--sem_seg_out_dir", str(tmp_path / "sem"),
+                             "--ins_seg_out_dir", str(ins), "--log_name", str(tmp_path / "log"),
+                             "--make_cam_pass", "False", "--make_ins_seg_pass", "False", "--make_sem_seg_pass", "False",
+                             "--make_cocoann_pass", "True", "--cocoann_out", str(out)])
     want, want_stats = R.cocoann(names, str(root), str(ins))
     assert res == {"make_cocoann": want_stats}
     assert json.load(open(out)) == want

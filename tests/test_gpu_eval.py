@@ -10,6 +10,7 @@ from PIL import Image
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _eval_ref as R  # noqa: E402
+import _steps as S  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -221,24 +222,14 @@ SWEEP = ["0.05", "0.1", "0.15", "0.2", "0.3", "0.45", "0.6"]
 
 
 def _run(tmp_path, root, tag, extra):
-    import run_sample
-    from irn_amd.misc import pyutils
-    from irn_amd.step import _common
     lst = str(tmp_path / "lists" / "train.txt")
-    stdout = sys.stdout
-    try:
-        return run_sample.main(["--voc12_root", str(root), "--train_list", lst, "--infer_list", lst, "--num_workers", "2",
-                                "--cam_weights_name", str(tmp_path / "res50_cam"),
-                                "--irn_weights_name", str(tmp_path / "res50_irn.pth"),
-                                "--cam_out_dir", str(tmp_path / tag / "cam"), "--sem_seg_out_dir", str(tmp_path / tag / "sem"),
-                                "--ins_seg_out_dir", str(tmp_path / tag / "ins"), "--log_name", str(tmp_path / tag),
-                                "--cam_scales", "1.0", "0.5", "--eval_cam_pass", "True", "--eval_ins_seg_pass", "True",
-                                "--eval_sem_seg_pass", "True", "--cam_eval_thres_sweep"] + SWEEP + extra)
-    finally:
-        if isinstance(sys.stdout, pyutils.Logger):
-            sys.stdout.close()
-        sys.stdout = stdout
-        _common.shutdown_workers()
+    return S.run_sample_main(["--voc12_root", str(root), "--train_list", lst, "--infer_list", lst, "--num_workers", "2",
+                              "--cam_weights_name", str(tmp_path / "res50_cam"),
+                              "--irn_weights_name", str(tmp_path / "res50_irn.pth"),
+                              "--cam_out_dir", str(tmp_path / tag / "cam"), "--sem_seg_out_dir", str(tmp_path / tag / "sem"),
+                              "--ins_seg_out_dir", str(tmp_path / tag / "ins"), "--log_name", str(tmp_path / tag),
+                              "--cam_scales", "1.0", "0.5", "--eval_cam_pass", "True", "--eval_ins_seg_pass", "True",
+                              "--eval_sem_seg_pass", "True", "--cam_eval_thres_sweep"] + SWEEP + extra)
 
 
 def _same(a, b):

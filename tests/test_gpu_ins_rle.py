@@ -16,6 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _cocomask_ref as R  # noqa: E402
+import _steps as S  # noqa: E402
 from test_ins_rle_cpu import edge_maps  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -213,25 +214,15 @@ def test_cpu_tensors_and_wrong_shapes_are_refused():
 # end to end through run_sample.py
 # ---------------------------------------------------------------------------------------------------------------------
 def _run(tmp_path, root, ins, out, extra):
-    import run_sample
-    from irn_amd.misc import pyutils
-    from irn_amd.step import _common
     lst = str(tmp_path / "lists" / "train.txt")
-    stdout = sys.stdout
-    try:
-        with _limit(900):
-            return run_sample.main(["--voc12_root", str(root), "--train_list", lst, "--infer_list", lst, "--num_workers", "2",
-                                    "--cam_weights_name", str(tmp_path / "res50_cam"),
-                                    "--irn_weights_name", str(tmp_path / "res50_irn.pth"),
-                                    "--cam_out_dir", str(tmp_path / "cam"), "--sem_seg_out_dir", str(tmp_path / "sem"),
-                                    "--ins_seg_out_dir", str(ins), "--log_name", str(tmp_path / ins.name),
-                                    "--cam_scales", "1.0", "0.5", "--make_sem_seg_pass", "False", "--eval_ins_seg_pass", "True",
-                                    "--make_cocoann_pass", "True", "--cocoann_out", str(out)] + extra)
-    finally:
-        if isinstance(sys.stdout, pyutils.Logger):
-            sys.stdout.close()
-        sys.stdout = stdout
-        _common.shutdown_workers()
+    with _limit(900):
+        return S.run_sample_main(["--voc12_root", str(root), "--train_list", lst, "--infer_list", lst, "--num_workers", "2",
+                                  "--cam_weights_name", str(tmp_path / "res50_cam"),
+                                  "--irn_weights_name", str(tmp_path / "res50_irn.pth"),
+                                  "--cam_out_dir", str(tmp_path / "cam"), "--sem_seg_out_dir", str(tmp_path / "sem"),
+                                  "--ins_seg_out_dir", str(ins), "--log_name", str(tmp_path / ins.name),
+                                  "--cam_scales", "1.0", "0.5", "--make_sem_seg_pass", "False", "--eval_ins_seg_pass", "True",
+                                  "--make_cocoann_pass", "True", "--cocoann_out", str(out)] + extra)
 
 
 def test_run_sample_in_both_formats_gives_the_same_coco_file_and_ap(tmp_path, monkeypatch):

@@ -15,6 +15,7 @@ from PIL import Image
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _eval_ref as R  # noqa: E402
+import _steps as S  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -27,43 +28,21 @@ KEYS = ([20, 45, 79], [3, 33], [25, 60, 70], [7, 21])          # every image has
 def _make_voc(tmp):
     """JPEGs and ground truth (class and object maps) of four images from Gaussian blobs, a void band where they fade."""
     from irn_amd import synth
-    root = tmp / "voc"
-    for d in ("JPEGImages", "SegmentationClass", "SegmentationObject", "ImageSets/Segmentation"):
-        (root / d).mkdir(parents=True)
-    (tmp / "lists").mkdir()
     rng = np.random.RandomState(0)
-    names, labels = [], {}
+    specs = []
     for i, keys in enumerate(KEYS):
-        name = "2008_%06d" % (i + 1)
         h, w = ((96, 128), (113, 150))[i % 2]
         img = (rng.rand(h // 8 + 1, w // 8 + 1, 3) * 255).astype(np.uint8)
-        Image.fromarray(img).resize((w, h), Image.BICUBIC).save(root / "JPEGImages" / (name + ".jpg"), quality=95)
         keys = np.asarray(keys, np.int64)
-        gh, gw = synth.grid_of((h, w))
-        cam = synth.cam_blobs(len(keys), gh, gw, seed=40 + i)
-        up = np.repeat(np.repeat(cam, 4, axis=1), 4, axis=2)[:, :h, :w]
-        top, arg = up.max(axis=0), up.argmax(axis=0)
-        gt = np.where(top > 0.45, keys[arg] + 1, 0).astype(np.uint8)
-        gt[(top > 0.35) & (top <= 0.45)] = 255
-        obj = np.where(top > 0.45, arg + 1, 0).astype(np.uint8)                # one instance per class
-        obj[gt == 255] = 255
-        R.save_p_png(root / "SegmentationClass" / (name + ".png"), gt)
-        R.save_p_png(root / "SegmentationObject" / (name + ".png"), obj)
-        lab = np.zeros(C, np.float32)
-        lab[keys] = 1
-        labels[int(name.replace("_", ""))] = lab
-        names.append(name)
-    (root / "ImageSets" / "Segmentation" / "train.txt").write_text("\n".join(names) + "\n")
-    (tmp / "lists" / "train.txt").write_text("\n".join(names) + "\n")
-    np.save(tmp / "lists" / "cls_labels.npy", labels)
-    return root, names
+        cam = synth.cam_blobs(len(keys), *synth.grid_of((h, w)), seed=40 + i)
+        gt, obj = synth.blob_ground_truth(synth.upsample4(cam, (h, w)), keys, 0.45, 0.35, obj_ids=np.arange(len(keys)) + 1)
+        specs.append({"name": "2008_%06d" % (i + 1), "photo": np.asarray(Image.fromarray(img).resize((w, h), Image.BICUBIC)),
+                      "quality": 95, "keys": keys, "cls": gt, "obj": obj})
+    return tmp / "voc", synth.write_voc_tree(tmp / "voc", specs, tmp / "lists" / "train.txt", cls_labels=C)
 
 
 def _run(tree, passes, extra=()):
     """run_sample.main with exactly the passes named."""
-    import run_sample
-    from irn_amd.misc import pyutils
-    from irn_amd.step import _common
     tmp, lst = tree["tmp"], str(tree["tmp"] / "lists" / "train.txt")
     argv = ["--voc12_root", str(tree["root"]), "--train_list", lst, "--infer_list", lst, "--num_workers", "2",
             "--worker_devices", "0", "--num_classes", str(C), "--cam_scales", "1.0", "0.5",
@@ -75,14 +54,7 @@ def _run(tree, passes, extra=()):
     for name in passes:
         if name not in ("make_cam", "make_ins_seg", "make_sem_seg"):
             argv += ["--%s_pass" % name, "True"]
-    stdout = sys.stdout
-    try:
-        return run_sample.main(argv + list(extra))
-    finally:
-        if isinstance(sys.stdout, pyutils.Logger):
-            sys.stdout.close()
-        sys.stdout = stdout
-        _common.shutdown_workers()
+    return S.run_sample_main(argv + list(extra))
 
 
 @pytest.fixture(scope="module")

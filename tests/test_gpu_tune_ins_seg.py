@@ -11,7 +11,7 @@ import torch
 from PIL import Image
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import _eval_ref as R  # noqa: E402
+import _steps as S  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -25,57 +25,27 @@ def _make_voc(tmp):
     image, a void band where the blobs fade; one GT instance per class), so that detections meet instances whatever the
     random IRNet does."""
     from irn_amd import synth
-    root = tmp / "voc"
-    for d in ("JPEGImages", "SegmentationClass", "SegmentationObject", "ImageSets/Segmentation"):
-        (root / d).mkdir(parents=True)
-    (tmp / "cam").mkdir()
-    (tmp / "lists").mkdir()
     rng = np.random.RandomState(0)
-    names, labels = [], {}
+    specs = []
     for i in range(N_IMAGES):
-        name = "2008_%06d" % (i + 1)
         h, w = ((96, 128), (113, 150))[i % 2]
         img = (rng.rand(h // 8 + 1, w // 8 + 1, 3) * 255).astype(np.uint8)
-        Image.fromarray(img).resize((w, h), Image.BICUBIC).save(root / "JPEGImages" / (name + ".jpg"), quality=95)
         k = 2 + i % 2
         keys = np.sort(rng.choice(20, k, replace=False)).astype(np.int64)
-        gh, gw = synth.grid_of((h, w))
-        cam = synth.cam_blobs(k, gh, gw, seed=40 + i)
-        np.save(tmp / "cam" / (name + ".npy"), {"keys": torch.from_numpy(keys), "cam": torch.from_numpy(cam)})
-        up = np.repeat(np.repeat(cam, 4, axis=1), 4, axis=2)[:, :h, :w]
-        top = up.max(axis=0)
-        cls = np.where(top > 0.45, keys[up.argmax(axis=0)] + 1, 0).astype(np.uint8)
-        obj = np.where(top > 0.45, 2 * up.argmax(axis=0) + 3, 0).astype(np.uint8)         # object ids 3, 5, 7: one per class
-        cls[(top > 0.35) & (top <= 0.45)] = 255
-        obj[(top > 0.35) & (top <= 0.45)] = 255
-        R.save_p_png(root / "SegmentationClass" / (name + ".png"), cls)
-        R.save_p_png(root / "SegmentationObject" / (name + ".png"), obj)
-        lab = np.zeros(20, np.float32)
-        lab[keys] = 1
-        labels[int(name.replace("_", ""))] = lab
-        names.append(name)
-    (root / "ImageSets" / "Segmentation" / "train.txt").write_text("\n".join(names) + "\n")
-    (tmp / "lists" / "train.txt").write_text("\n".join(names) + "\n")
-    np.save(tmp / "lists" / "cls_labels.npy", labels)
-    return root, names
+        cam = synth.cam_blobs(k, *synth.grid_of((h, w)), seed=40 + i)
+        cls, obj = synth.blob_ground_truth(synth.upsample4(cam, (h, w)), keys, 0.45, 0.35, obj_ids=2 * np.arange(k) + 3)   # 3, 5, 7
+        specs.append({"name": "2008_%06d" % (i + 1), "photo": np.asarray(Image.fromarray(img).resize((w, h), Image.BICUBIC)),
+                      "quality": 95, "keys": keys, "cls": cls, "obj": obj,
+                      "cam": {"keys": torch.from_numpy(keys), "cam": torch.from_numpy(cam)}})
+    return tmp / "voc", synth.write_voc_tree(tmp / "voc", specs, tmp / "lists" / "train.txt", cam_dir=tmp / "cam", cls_labels=20)
 
 
 def _run(tmp_path, root, ins_dir, extra):
-    import run_sample
-    from irn_amd.misc import pyutils
-    from irn_amd.step import _common
     lst = str(tmp_path / "lists" / "train.txt")
-    stdout = sys.stdout
-    try:
-        return run_sample.main(["--voc12_root", str(root), "--infer_list", lst, "--num_workers", "2", "--worker_devices", "0",
-                                "--irn_weights_name", str(tmp_path / "res50_irn.pth"), "--cam_out_dir", str(tmp_path / "cam"),
-                                "--sem_seg_out_dir", str(tmp_path / "sem"), "--ins_seg_out_dir", str(ins_dir),
-                                "--log_name", str(tmp_path / "log"), "--make_cam_pass", "False", "--make_sem_seg_pass", "False"] + extra)
-    finally:
-        if isinstance(sys.stdout, pyutils.Logger):
-            sys.stdout.close()
-        sys.stdout = stdout
-        _common.shutdown_workers()
+    return S.run_sample_main(["--voc12_root", str(root), "--infer_list", lst, "--num_workers", "2", "--worker_devices", "0",
+                              "--irn_weights_name", str(tmp_path / "res50_irn.pth"), "--cam_out_dir", str(tmp_path / "cam"),
+                              "--sem_seg_out_dir", str(tmp_path / "sem"), "--ins_seg_out_dir", str(ins_dir),
+                              "--log_name", str(tmp_path / "log"), "--make_cam_pass", "False", "--make_sem_seg_pass", "False"] + extra)
 
 
 def test_grid_points_equal_the_label_and_eval_steps(tmp_path, capsys):

@@ -15,6 +15,7 @@ from PIL import Image
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _densecrf_ref as R  # noqa: E402
 import _eval_ref as E  # noqa: E402
+import _steps as S  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -244,50 +245,28 @@ def _make_voc(tmp, n, no_keys=()):
     tests/test_gpu_tune_sem_seg.py: CAMs and GT come from the same Gaussian blobs (2-3 classes per image, a void band where the
     blobs fade).  Images listed in `no_keys` get a CAM file without class keys."""
     from irn_amd import synth
-    root = tmp / "voc"
-    for d in ("JPEGImages", "SegmentationClass", "ImageSets/Segmentation"):
-        (root / d).mkdir(parents=True)
-    (tmp / "cam").mkdir()
-    (tmp / "lists").mkdir()
     rng = np.random.RandomState(0)
-    names = []
+    specs = []
     for i in range(n):
-        name = "2008_%06d" % (i + 1)
         h, w = ((96, 128), (113, 150))[i % 2]
-        Image.fromarray(synth.photo(h, w, seed=60 + i)).save(root / "JPEGImages" / (name + ".jpg"), quality=95)
         k = 2 + i % 2
         keys = np.sort(rng.choice(20, k, replace=False)).astype(np.int64)
         cam = synth.cam_blobs(k, h, w, seed=40 + i)
-        top = cam.max(axis=0)
-        gt = np.where(top > 0.4, keys[cam.argmax(axis=0)] + 1, 0).astype(np.uint8)
-        gt[(top > 0.32) & (top <= 0.4)] = 255
-        E.save_p_png(root / "SegmentationClass" / (name + ".png"), gt)
+        gt = synth.blob_ground_truth(cam, keys, 0.4, 0.32)[0]
         if i in no_keys:
             keys, cam = keys[:0], cam[:0]
-        np.save(tmp / "cam" / (name + ".npy"), {"keys": keys, "high_res": cam})
-        names.append(name)
-    (root / "ImageSets" / "Segmentation" / "train.txt").write_text("\n".join(names) + "\n")
-    (tmp / "lists" / "train.txt").write_text("\n".join(names) + "\n")
-    return root, names
+        specs.append({"name": "2008_%06d" % (i + 1), "photo": synth.photo(h, w, seed=60 + i), "quality": 95, "keys": keys, "cls": gt,
+                      "cam": {"keys": keys, "high_res": cam}})
+    return tmp / "voc", synth.write_voc_tree(tmp / "voc", specs, tmp / "lists" / "train.txt", cam_dir=tmp / "cam")
 
 
 def _run(tmp_path, root, ir_dir, extra):
-    import run_sample
-    from irn_amd.misc import pyutils
-    from irn_amd.step import _common
     lst = str(tmp_path / "lists" / "train.txt")
-    stdout = sys.stdout
-    try:
-        return run_sample.main(["--voc12_root", str(root), "--train_list", lst, "--infer_list", lst, "--num_workers", "2",
-                                "--worker_devices", "0", "--cam_out_dir", str(tmp_path / "cam"), "--ir_label_out_dir", str(ir_dir),
-                                "--sem_seg_out_dir", str(tmp_path / "sem"), "--ins_seg_out_dir", str(tmp_path / "ins"),
-                                "--log_name", str(tmp_path / "log"), "--make_cam_pass", "False", "--make_ins_seg_pass", "False",
-                                "--make_sem_seg_pass", "False"] + extra)
-    finally:
-        if isinstance(sys.stdout, pyutils.Logger):
-            sys.stdout.close()
-        sys.stdout = stdout
-        _common.shutdown_workers()
+    return S.run_sample_main(["--voc12_root", str(root), "--train_list", lst, "--infer_list", lst, "--num_workers", "2",
+                              "--worker_devices", "0", "--cam_out_dir", str(tmp_path / "cam"), "--ir_label_out_dir", str(ir_dir),
+                              "--sem_seg_out_dir", str(tmp_path / "sem"), "--ins_seg_out_dir", str(tmp_path / "ins"),
+                              "--log_name", str(tmp_path / "log"), "--make_cam_pass", "False", "--make_ins_seg_pass", "False",
+                              "--make_sem_seg_pass", "False"] + extra)
 
 
 def _read_gt(root, name):

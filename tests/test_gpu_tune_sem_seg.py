@@ -10,7 +10,7 @@ import torch
 from PIL import Image
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import _eval_ref as R  # noqa: E402
+import _steps as S  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -23,54 +23,26 @@ def _make_voc(tmp):
     """JPEGs, CAM files and ground truth of N_IMAGES images; CAMs and GT come from the same Gaussian blobs (2-3 classes per
     image, a void band where the blobs fade), so that labels of several classes exist whatever the random IRNet does."""
     from irn_amd import synth
-    root = tmp / "voc"
-    for d in ("JPEGImages", "SegmentationClass", "ImageSets/Segmentation"):
-        (root / d).mkdir(parents=True)
-    (tmp / "cam").mkdir()
-    (tmp / "lists").mkdir()
     rng = np.random.RandomState(0)
-    names, labels = [], {}
+    specs = []
     for i in range(N_IMAGES):
-        name = "2008_%06d" % (i + 1)
         h, w = ((96, 128), (113, 150))[i % 2]
         img = (rng.rand(h // 8 + 1, w // 8 + 1, 3) * 255).astype(np.uint8)
-        Image.fromarray(img).resize((w, h), Image.BICUBIC).save(root / "JPEGImages" / (name + ".jpg"), quality=95)
         k = 2 + i % 2
         keys = np.sort(rng.choice(20, k, replace=False)).astype(np.int64)
-        gh, gw = synth.grid_of((h, w))
-        cam = synth.cam_blobs(k, gh, gw, seed=40 + i)
-        np.save(tmp / "cam" / (name + ".npy"), {"keys": torch.from_numpy(keys), "cam": torch.from_numpy(cam)})
-        up = np.repeat(np.repeat(cam, 4, axis=1), 4, axis=2)[:, :h, :w]
-        top = up.max(axis=0)
-        gt = np.where(top > 0.45, keys[up.argmax(axis=0)] + 1, 0).astype(np.uint8)
-        gt[(top > 0.35) & (top <= 0.45)] = 255
-        R.save_p_png(root / "SegmentationClass" / (name + ".png"), gt)
-        lab = np.zeros(20, np.float32)
-        lab[keys] = 1
-        labels[int(name.replace("_", ""))] = lab
-        names.append(name)
-    (root / "ImageSets" / "Segmentation" / "train.txt").write_text("\n".join(names) + "\n")
-    (tmp / "lists" / "train.txt").write_text("\n".join(names) + "\n")
-    np.save(tmp / "lists" / "cls_labels.npy", labels)
-    return root, names
+        cam = synth.cam_blobs(k, *synth.grid_of((h, w)), seed=40 + i)
+        specs.append({"name": "2008_%06d" % (i + 1), "photo": np.asarray(Image.fromarray(img).resize((w, h), Image.BICUBIC)),
+                      "quality": 95, "keys": keys, "cls": synth.blob_ground_truth(synth.upsample4(cam, (h, w)), keys, 0.45, 0.35)[0],
+                      "cam": {"keys": torch.from_numpy(keys), "cam": torch.from_numpy(cam)}})
+    return tmp / "voc", synth.write_voc_tree(tmp / "voc", specs, tmp / "lists" / "train.txt", cam_dir=tmp / "cam", cls_labels=20)
 
 
 def _run(tmp_path, root, sem_dir, extra):
-    import run_sample
-    from irn_amd.misc import pyutils
-    from irn_amd.step import _common
     lst = str(tmp_path / "lists" / "train.txt")
-    stdout = sys.stdout
-    try:
-        return run_sample.main(["--voc12_root", str(root), "--infer_list", lst, "--num_workers", "2", "--worker_devices", "0",
-                                "--irn_weights_name", str(tmp_path / "res50_irn.pth"), "--cam_out_dir", str(tmp_path / "cam"),
-                                "--sem_seg_out_dir", str(sem_dir), "--ins_seg_out_dir", str(tmp_path / "ins"),
-                                "--log_name", str(tmp_path / "log"), "--make_cam_pass", "False", "--make_ins_seg_pass", "False"] + extra)
-    finally:
-        if isinstance(sys.stdout, pyutils.Logger):
-            sys.stdout.close()
-        sys.stdout = stdout
-        _common.shutdown_workers()
+    return S.run_sample_main(["--voc12_root", str(root), "--infer_list", lst, "--num_workers", "2", "--worker_devices", "0",
+                              "--irn_weights_name", str(tmp_path / "res50_irn.pth"), "--cam_out_dir", str(tmp_path / "cam"),
+                              "--sem_seg_out_dir", str(sem_dir), "--ins_seg_out_dir", str(tmp_path / "ins"),
+                              "--log_name", str(tmp_path / "log"), "--make_cam_pass", "False", "--make_ins_seg_pass", "False"] + extra)
 
 
 def test_grid_points_equal_the_label_and_eval_steps(tmp_path, capsys):

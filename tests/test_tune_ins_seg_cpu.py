@@ -59,8 +59,8 @@ def _records(shift):
 def test_report_prints_the_eval_line_then_the_grid_then_the_best(capsys):
     from irn_amd.misc import evaluation
     from irn_amd.step import tune_ins_seg as T
-    from irn_amd.step import tune_sem_seg
-    assert T.pick_best is tune_sem_seg.pick_best
+    from irn_amd.step import _tune, tune_sem_seg
+    assert T.pick_best.func is _tune.pick_best and T.pick_best.keywords == tune_sem_seg.pick_best.keywords
     axes = T.grid_axes(_args(tune_beta=[6], tune_ins_bg_thres=[0.4]))          # pairs (6, 8), (10, 8); thresholds 0.25, 0.4
     points = [(6.0, 8, 0.25), (6.0, 8, 0.4), (10.0, 8, 0.25), (10.0, 8, 0.4)]
     records = {p: _records(s) for p, s in zip(points, (0, 20, 20, 0))}         # the two better points tie
@@ -105,17 +105,10 @@ def test_numpy_restatement_on_a_hand_made_map():
 
 
 def _main(tmp_path, extra):
-    import run_sample
-    from irn_amd.misc import pyutils
-    stdout = sys.stdout
-    try:
-        return run_sample.main(["--voc12_root", str(tmp_path), "--log_name", str(tmp_path / "log"), "--cam_out_dir", str(tmp_path / "cam"),
-                                "--sem_seg_out_dir", str(tmp_path / "sem"), "--ins_seg_out_dir", str(tmp_path / "ins"),
-                                "--make_cam_pass", "False", "--make_ins_seg_pass", "False", "--make_sem_seg_pass", "False"] + extra)
-    finally:
-        if isinstance(sys.stdout, pyutils.Logger):
-            sys.stdout.close()
-        sys.stdout = stdout
+    import _steps
+    return _steps.run_sample_main(["--voc12_root", str(tmp_path), "--log_name", str(tmp_path / "log"), "--cam_out_dir", str(tmp_path / "cam"),
+                                   "--sem_seg_out_dir", str(tmp_path / "sem"), "--ins_seg_out_dir", str(tmp_path / "ins"),
+                                   "--make_cam_pass", "False", "--make_ins_seg_pass", "False", "--make_sem_seg_pass", "False"] + extra)
 
 
 def test_command_line(tmp_path, monkeypatch):

@@ -78,17 +78,10 @@ def test_report_prints_the_eval_lines_then_the_grid_then_the_best(capsys):
 
 
 def _main(tmp_path, extra):
-    import run_sample
-    from irn_amd.misc import pyutils
-    stdout = sys.stdout
-    try:
-        return run_sample.main(["--voc12_root", str(tmp_path), "--log_name", str(tmp_path / "log"), "--cam_out_dir", str(tmp_path / "cam"),
-                                "--sem_seg_out_dir", str(tmp_path / "sem"), "--ins_seg_out_dir", str(tmp_path / "ins"),
-                                "--make_cam_pass", "False", "--make_ins_seg_pass", "False", "--make_sem_seg_pass", "False"] + extra)
-    finally:
-        if isinstance(sys.stdout, pyutils.Logger):
-            sys.stdout.close()
-        sys.stdout = stdout
+    import _steps
+    return _steps.run_sample_main(["--voc12_root", str(tmp_path), "--log_name", str(tmp_path / "log"), "--cam_out_dir", str(tmp_path / "cam"),
+                                   "--sem_seg_out_dir", str(tmp_path / "sem"), "--ins_seg_out_dir", str(tmp_path / "ins"),
+                                   "--make_cam_pass", "False", "--make_ins_seg_pass", "False", "--make_sem_seg_pass", "False"] + extra)
 
 
 def test_command_line(tmp_path, monkeypatch):

@@ -35,50 +35,25 @@ BETAS, EXPS = [6.0, 14.0], [6]                      # + the configured 10 / 8: 3
 THRES = [round(0.05 + 0.1 * i, 2) for i in range(8)]         # 0.05 .. 0.75, holds the configured 0.25
 
 
-def _save_p(path, arr):
-    from PIL import Image
-    img = Image.fromarray(arr, mode="P")
-    img.putpalette([v for j in range(256) for v in (j, j, j)])
-    img.save(path)
-
-
 def make_tree(root, n):
     """-> [(name, size, keys, cam, inst_map, n_inst)]; writes JPEGImages, SegmentationClass, SegmentationObject, the split,
     the image list with its cls_labels.npy, the CAM files and the IRNet checkpoint under `root`."""
-    from PIL import Image
-
     from irn_amd.net import weights
-    for d in ("JPEGImages", "SegmentationClass", "SegmentationObject", "ImageSets/Segmentation", "cam"):
-        os.makedirs(os.path.join(root, d))
-    items, labels = [], {}
+    items, specs = [], []
     for i in range(n):
         name = "2008_%06d" % (i + 1)
         h, w = synth.voc_image_size(i)
-        gh, gw = synth.grid_of((h, w))
         k = synth.voc_num_classes(i)
-        keys, cam = synth.voc_keys(k, i), synth.cam_blobs(k, gh, gw, i)
-        Image.fromarray(synth.photo(h, w, seed=i)).save(os.path.join(root, "JPEGImages", name + ".jpg"), quality=90)
-        np.save(os.path.join(root, "cam", name + ".npy"), {"keys": torch.from_numpy(keys), "cam": torch.from_numpy(cam)})
-        up = np.repeat(np.repeat(cam, 4, axis=1), 4, axis=2)[:, :h, :w]
-        top, arg = up.max(axis=0), up.argmax(axis=0)
-        cls = np.where(top > 0.45, keys[arg] + 1, 0).astype(np.uint8)
-        obj = np.where(top > 0.45, arg + 1, 0).astype(np.uint8)
-        cls[(top > 0.35) & (top <= 0.45)] = 255
-        obj[(top > 0.35) & (top <= 0.45)] = 255
-        _save_p(os.path.join(root, "SegmentationClass", name + ".png"), cls)
-        _save_p(os.path.join(root, "SegmentationObject", name + ".png"), obj)
+        keys, cam = synth.voc_keys(k, i), synth.cam_blobs(k, *synth.grid_of((h, w)), i)
+        cls, obj = synth.blob_ground_truth(synth.upsample4(cam, (h, w)), keys, 0.45, 0.35, obj_ids=np.arange(k) + 1)
+        specs.append({"name": name, "photo": synth.photo(h, w, seed=i), "quality": 90, "keys": keys, "cls": cls, "obj": obj,
+                      "cam": {"keys": torch.from_numpy(keys), "cam": torch.from_numpy(cam)}})
         ids = [v for v in np.unique(obj) if v not in (0, 255)]
         inst = np.zeros((h, w), np.uint8)
         for g, v in enumerate(ids):
             inst[obj == v] = g + 1
-        lab = np.zeros(20, np.float32)
-        lab[keys] = 1
-        labels[int(name.replace("_", ""))] = lab
         items.append((name, (h, w), keys, cam, inst, len(ids)))
-    for path in (os.path.join(root, "ImageSets", "Segmentation", "train.txt"), os.path.join(root, "train.txt")):
-        with open(path, "w") as f:
-            f.write("\n".join(it[0] for it in items) + "\n")
-    np.save(os.path.join(root, "cls_labels.npy"), labels)
+    synth.write_voc_tree(root, specs, os.path.join(root, "train.txt"), cam_dir=os.path.join(root, "cam"), cls_labels=20)
     torch.save(weights.random_irn_state(2), os.path.join(root, "res50_irn.pth"))
     return items
 

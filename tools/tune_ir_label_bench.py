@@ -41,9 +41,7 @@ def _items(n, dev):
         h, w = synth.voc_image_size(s)
         k = synth.voc_num_classes(s)
         cam, keys = synth.cam_blobs(k, h, w, seed=s), synth.voc_keys(k, s)
-        top = cam.max(axis=0)
-        gt = np.where(top > 0.4, keys[cam.argmax(axis=0)] + 1, 0).astype(np.uint8)
-        gt[(top > 0.32) & (top <= 0.4)] = 255
+        gt, _ = synth.blob_ground_truth(cam, keys, 0.4, 0.32)
         out.append(tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (synth.photo(h, w, seed=s), cam, keys, gt)))
     return out
 

@@ -40,6 +40,10 @@ extern "C" {
 
 #define IRN_MAX_RADIUS 16
 
+/* The version of this header's argument lists.  irn_version() returns the IRN_ABI_VERSION the library was built with, and
+ * it moves whenever an entry's arguments change: a binding that finds another value has loaded a library of another commit
+ * (irn_amd/_lib.py refuses to import it). */
+#define IRN_ABI_VERSION 101
 int irn_version(void);
 const char *irn_last_error(void);
 
@@ -85,9 +89,11 @@ int irn_pair_displacement_backward(const float *grad_out_dev, int batch, int cha
 /* Fused affinity / displacement loss of IRNet training (replaces, for the training step, the chain
  * net/resnet50_irn.py:198-213 + step/train_irn.py:58-64 + voc12/dataloader.py:80-106 without writing any
  * [batch, |S|, N] tensor).  edge: dev fp32 [batch, hp, wp], already through the sigmoid; dp: dev fp32
- * [batch, 2, hp, wp]; label: dev uint8 [batch, hp, wp], 0 = background, 1..20 = a class, >= 21 = ignore.
+ * [batch, 2, hp, wp]; label: dev uint8 [batch, hp, wp], 0 = background, 1..ignore_from-1 = a class, >= ignore_from = ignore
+ * (a dataset of C foreground classes passes C + 1; the usual value is IRN_EVAL_CLASSES = 21).  Nothing else in the arithmetic
+ * depends on it: the loss only asks which labels are equal, which are 0 and which are ignored.
  * Geometry as irn_edge_to_affinity / irn_pair_displacement: with rf = radius-1, source cell (y, rf+x), y < hp-rf,
- * x < wp-2rf, pairs with (y+dy_d, rf+x+dx_d).  With a, b the labels of the two cells: valid = a<21 && b<21,
+ * x < wp-2rf, pairs with (y+dy_d, rf+x+dx_d).  With a, b the labels of the two cells: valid = a<ignore_from && b<ignore_from,
  * bg = valid && a==b==0, fg = valid && a==b>0, neg = valid && a!=b; aff = 1 - max of edge over path(d);
  * pd_c = dp_c[src] - dp_c[dst]:
  *   sums[0] = sum bg * -log(aff+1e-5)        sums[1] = sum fg * -log(aff+1e-5)     sums[2] = sum neg * -log(1+1e-5-aff)
@@ -111,29 +117,17 @@ int irn_pair_displacement_backward(const float *grad_out_dev, int batch, int cha
  * irn_aff_loss_backward by the order of the additions only, and costs more (it re-walks a path for each of its cells).
  * ws: irn_aff_loss_workspace_bytes(batch, hp, wp, radius) bytes of device memory (0 = bad geometry); the backward
  * checks it like the forward and leaves it untouched.  Null pointers, batch outside [1, 65535], radius outside
- * [2, IRN_MAX_RADIUS] (the path table's range), hp <= rf or wp <= 2 rf give IRN_ERR_ARG, a workspace that is too
- * small IRN_ERR_STATE, all before any device is touched. */
+ * [2, IRN_MAX_RADIUS] (the path table's range), hp <= rf or wp <= 2 rf, ignore_from outside 1..255 (labels are bytes and
+ * 255 is always void) give IRN_ERR_ARG, a workspace that is too small IRN_ERR_STATE, all before any device is touched. */
 size_t irn_aff_loss_workspace_bytes(int batch, int hp, int wp, int radius);
 int irn_aff_loss_forward(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp, int radius,
-                         double *sums, int64_t *counts, void *ws, size_t ws_bytes, void *stream);
+                         int ignore_from, double *sums, int64_t *counts, void *ws, size_t ws_bytes, void *stream);
 int irn_aff_loss_backward(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp, int radius,
-                          const float *coef, float *grad_edge, float *grad_dp, void *ws, size_t ws_bytes, void *stream);
+                          int ignore_from, const float *coef, float *grad_edge, float *grad_dp, void *ws, size_t ws_bytes,
+                          void *stream);
 int irn_aff_loss_backward_ordered(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
-                                  int radius, const float *coef, float *grad_edge, float *grad_dp, void *ws, size_t ws_bytes,
-                                  void *stream);
-/* The same three calls for a dataset with another class count: labels >= ignore_from take no part, where the calls above
- * have 21 (they are these calls with ignore_from = 21).  A dataset of C foreground classes passes C + 1, so that labels
- * 1..C are classes.  Nothing else in the arithmetic depends on it: the loss only asks which labels are equal, which are 0
- * and which are ignored.  ignore_from outside 1..255 gives IRN_ERR_ARG (labels are bytes and 255 is always void). */
-int irn_aff_loss_forward_ignore(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
-                                int radius, int ignore_from, double *sums, int64_t *counts, void *ws, size_t ws_bytes,
-                                void *stream);
-int irn_aff_loss_backward_ignore(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
-                                 int radius, int ignore_from, const float *coef, float *grad_edge, float *grad_dp, void *ws,
-                                 size_t ws_bytes, void *stream);
-int irn_aff_loss_backward_ordered_ignore(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
-                                         int radius, int ignore_from, const float *coef, float *grad_edge, float *grad_dp,
-                                         void *ws, size_t ws_bytes, void *stream);
+                                  int radius, int ignore_from, const float *coef, float *grad_edge, float *grad_dp, void *ws,
+                                  size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Random-walk context  (replaces misc/indexing.py:141-165 `propagate_to_edge` and everything it
@@ -437,17 +431,24 @@ int irn_conv1x1_nhwc(const float *x_dev, const float *w_dev, const float *bias_d
  * irn_split16: x dev fp32 [n_pixels, n_channels] (channels-last activation, n_channels a multiple of 8, 16-byte aligned)
  *   -> out dev fp16 [n_pixels, 3 n_channels] = [hi | hi | lo'] per pixel.  With scale / shift (dev fp32 [n_channels], both or
  *   neither) the element is first y = x * scale[c] + shift[c] (one fmaf, the FixedBatchNorm of the 3x3 convolution in front,
- *   net/resnet50.py:40-42) and, with relu, max(y, 0) — the fp32 tensor is read once and never written back.  overflow_dev
- *   (dev uint32, may be NULL) has bit 0 set when an element was beyond fp16's range (|y| > 65504) or NaN: the caller's
- *   signal that this activation needs the fp32 path.
+ *   net/resnet50.py:40-42) and, with relu, max(y, 0) — the fp32 tensor is read once and never written back.  flags_dev
+ *   (dev uint32) gets bit 0 set (atomicOr; the other bits are left alone) when an element was beyond fp16's range
+ *   (|y| > 65504, y = the value that is split) or NaN: the caller's signal that this activation needs the fp32 path.  The
+ *   caller zeroes it and reads it behind the stream.  pixels_per_sample = 0, the usual value: flags_dev is ONE word for the
+ *   call and may be NULL.  pixels_per_sample >= 1: the overflow is attributed PER SAMPLE (a sample = one leading row of the
+ *   network input) — flags_dev is dev uint32 [n_pixels / pixels_per_sample], never NULL, row r flags word
+ *   r / pixels_per_sample and the words of other samples are left alone; n_pixels must be a multiple of pixels_per_sample.
+ *   The fp16 output does not depend on pixels_per_sample.
  * irn_gemm16_nhwc: a16 dev fp16 [m, k] (irn_split16's output, k = 3 cin), b16 dev fp16 [cout, k] = [w_hi | w_lo | w_hi 2^-11] of
  *   the batch-norm-folded weight scaled by 2^p (prepared by the caller in double precision), alpha = 2^-p:
  *       out = act(alpha a16 . b16^T + bias (+ residual)),  fp32 [m, cout]; algo_rank / workspace as irn_conv1x1_nhwc. */
 int irn_split16(const float *x_dev, const float *scale_dev, const float *shift_dev, int relu, void *out_dev, int64_t n_pixels,
-                int n_channels, unsigned *overflow_dev, void *stream);
+                int n_channels, int64_t pixels_per_sample, unsigned *flags_dev, void *stream);
 /* The same pass between a dense map [n_images, h, w, n_channels] and its zero-bordered form [n_images, h+2, w+2, .] (pixel (n, y, x)
  * at row n (h+2)(w+2) + (y+1)(w+2) + x+1): in_padded = x is the bordered fp32 form (interior read), out_padded = out is the
- * bordered fp16 form (interior split from the pixels, border rows written as zeros: the buffer needs no preparation).  On the
+ * bordered fp16 form (interior split from the pixels, border rows written as zeros: the buffer needs no preparation).
+ * per_sample = 0, the usual value: flags_dev is one word for the call (may be NULL); per_sample != 0: one word per image, dev
+ * uint32 [n_images], never NULL (irn_split16's pixels_per_sample = h w); border rows flag nothing and are never read.  On the
  * bordered form a 3x3 / pad 1 / stride 1 convolution (conv2 of Bottleneck.forward, net/resnet50.py:40) is NINE fp16 GEMMs that
  * accumulate over row-shifted views of one operand — tap (ky, kx) reads row r + (ky-1)(w+2) + (kx-1):
  * irn_conv3x3_split_gemm: a16 dev fp16 = the bordered operand [n (h+2)(w+2), 3 cin] with (w+3) rows of valid memory in front of
@@ -457,19 +458,8 @@ int irn_split16(const float *x_dev, const float *scale_dev, const float *shift_d
  *   side) and THREE GEMMs over K = 9 cin — the taps (ky, 0..2) of a pixel are three consecutive memory rows, so a kernel row's
  *   operand is the same buffer read with leading dimension 3 cin and 9 cin columns.  algo_rank / workspace as irn_conv1x1_nhwc. */
 int irn_split16_pad(const float *x_dev, const float *scale_dev, const float *shift_dev, int relu, void *out_dev, int64_t n_images,
-                    int h, int w, int n_channels, int in_padded, int out_padded, unsigned *overflow_dev, void *stream);
-/* The same two passes with the overflow attributed PER SAMPLE (a sample = one leading row of the network input: n_pixels /
- * pixels_per_sample of them in the dense form, n_images in the padded form): flags_dev is dev uint32 [n_samples], never NULL, and
- * bit 0 of flags_dev[s] is set (atomicOr; the other bits and the words of other samples are left alone) when an element of sample
- * s failed the same test on the same value — |y| > 65504 or NaN, y = the value that is split, after scale / shift / relu.  Sample
- * of a row: row / pixels_per_sample (dense; n_pixels must be a multiple of pixels_per_sample), the image index n (padded, either
- * direction); border rows of the bordered output are written as zeros and flag nothing, border rows of a bordered input are never
- * read.  The fp16 output is bit for bit that of irn_split16 / irn_split16_pad, which keep their single flag word; the caller
- * zeroes flags_dev and reads it behind the stream — a set bit means "this sample needs the fp32 path", the others do not. */
-int irn_split16_samples(const float *x_dev, const float *scale_dev, const float *shift_dev, int relu, void *out_dev, int64_t n_pixels,
-                        int n_channels, int64_t pixels_per_sample, unsigned *flags_dev, void *stream);
-int irn_split16_pad_samples(const float *x_dev, const float *scale_dev, const float *shift_dev, int relu, void *out_dev, int64_t n_images,
-                            int h, int w, int n_channels, int in_padded, int out_padded, unsigned *flags_dev, void *stream);
+                    int h, int w, int n_channels, int in_padded, int out_padded, int per_sample, unsigned *flags_dev,
+                    void *stream);
 int irn_conv3x3_split_gemm(const void *a16_dev, const void *w16_dev, float *out_dev, int64_t n_images, int h, int w, int cin, int cout,
                            float alpha, int row_fused, int algo_rank, void *workspace_dev, size_t workspace_bytes, void *stream);
 int irn_gemm16_algo_count(int64_t m, int k, int cout, int has_bias, int has_residual, int relu, size_t workspace_bytes,
@@ -503,23 +493,15 @@ int irn_upsample_bilinear_backward(const float *grad_out_dev, const float *out_d
 
 /* ---------------------------------------------------------------------------------------------
  * Instance front-end
- *   irn_find_centroids   replaces step/make_ins_seg_labels.py:18-56
+ *   irn_find_centroids_batch   replaces step/make_ins_seg_labels.py:18-56
  *       dp dev [2,h,w] -> centroids dev int32 [2,h,w]; float32 state, float64 increment in the
  *       reference's operation order, no FMA contraction, round-half-even at the end.
- *   irn_cluster_centroids replaces step/make_ins_seg_labels.py:58-75 (+ misc/imutils.py:182-190):
+ *   irn_cluster_centroids_batch replaces step/make_ins_seg_labels.py:58-75 (+ misc/imutils.py:182-190):
  *       weak = |dp| < thres; 4-connected components numbered in raster order of first pixel;
  *       label at each pixel's centroid; renumbered 0..K-1 ascending.
- *       -> cluster_map dev int32 [h,w], *k_out (host) = K.  Synchronises `stream` (K is returned).
- *       scratch: irn_cluster_scratch_bytes(h, w) bytes.
- * ------------------------------------------------------------------------------------------- */
-int irn_find_centroids(const float *dp_dev, int h, int w, int iterations, int32_t *centroids_dev,
-                       void *stream);
-size_t irn_cluster_scratch_bytes(int h, int w);
-int irn_cluster_centroids(const int32_t *centroids_dev, const float *dp_dev, int h, int w, float thres,
-                          int32_t *cluster_map_dev, int *k_out, void *scratch_dev, void *stream);
-
-/* Batched forms (the loop over images of step/make_ins_seg_labels.py:119-133): HOST arrays of device pointers and
- * sizes, one launch sequence for the whole batch, and NOTHING synchronises — the instance counts stay on the device
+ *       -> cluster_map dev int32 [h,w], k_dev[i] = K.
+ * Both take a batch (the loop over images of step/make_ins_seg_labels.py:119-133; one image is a batch of one): HOST
+ * arrays of device pointers and sizes, one launch sequence for the whole batch, and NOTHING synchronises — the counts stay on the device
  * (k_dev: dev int32 [n_images]) and the caller fetches all of them with one transfer before it configures the walk
  * (c[i] = n_classes[i] * K[i]).  scratch: irn_cluster_batch_scratch_bytes. */
 int irn_find_centroids_batch(int n_images, const float *const *dp_dev, const int32_t *h, const int32_t *w,
@@ -542,26 +524,15 @@ int irn_label4(const uint8_t *mask_dev, int n, int h, int w, int32_t *labels_dev
  * rw_up dev fp32 [n_channels,h,w] (normalised scores), argmax dev int32 [h,w] (0 = background,
  * c+1 = channel c) -> one detection per 4-connected component of every channel's mask, ordered
  * channel ascending then raster order of the component's first pixel (skimage label order).
- *   _count : labels the components (state kept in `scratch`); *n_det_out (host) = number of
- *            detections.  Synchronises `stream`.
- *   _emit  : after _count with the same inputs and scratch: score[d] = area < min_area ? 0 :
- *            max(score * mask) (:96-99), channel[d] (index into the caller's class_id array), mask
- *            dev uint8 [n_det,h,w].  Only call with n_det >= 1.
- * scratch: irn_detect_scratch_bytes(n_channels, h, w).
+ *   _batch_count : labels the components of every image of a batch in one pass sequence (state kept in
+ *            `scratch`) and writes the detection counts to n_det_dev (dev int32 [n_images]).  Does NOT
+ *            synchronise: the caller reads the counts with one transfer and sizes the outputs.
+ *   _batch_emit  : after _batch_count with the same inputs and scratch plus the counts (host): score[d] =
+ *            area < min_area ? 0 : max(score * mask) (:96-99), channel[d] (index into the caller's class_id
+ *            array), mask dev uint8 [n_det,h,w].  Images with n_det[i] == 0 are skipped (their output
+ *            pointers may be NULL).  min_area: host [n_images].
+ * One image is a batch of one.  scratch: irn_detect_batch_scratch_bytes.
  * ------------------------------------------------------------------------------------------- */
-size_t irn_detect_scratch_bytes(int n_channels, int h, int w);
-int irn_detect_instance_count(const float *rw_up_dev, const int32_t *argmax_dev, int n_channels, int h, int w,
-                              int *n_det_out, void *scratch_dev, void *stream);
-int irn_detect_instance_emit(const float *rw_up_dev, const int32_t *argmax_dev, int n_channels, int h, int w, int n_det,
-                             double min_area, float *score_dev, int32_t *channel_dev, uint8_t *mask_dev,
-                             void *scratch_dev, void *stream);
-
-
-/* Batched forms: one labelling pass sequence for all images of a batch.  _batch_count writes the detection counts
- * to n_det_dev (dev int32 [n_images]) and does NOT synchronise; the caller reads them with one transfer, sizes the
- * outputs and calls _batch_emit with the same inputs and scratch plus the counts (host) — images with n_det[i] == 0
- * are skipped (their output pointers may be NULL).  min_area: host [n_images].
- * scratch: irn_detect_batch_scratch_bytes. */
 size_t irn_detect_batch_scratch_bytes(int n_images, const int32_t *n_channels, const int32_t *h, const int32_t *w);
 int irn_detect_instance_batch_count(int n_images, const float *const *rw_up_dev, const int32_t *const *argmax_dev,
                                     const int32_t *n_channels, const int32_t *h, const int32_t *w, int32_t *n_det_dev,
@@ -701,106 +672,86 @@ int irn_crf_label_sweep(const uint8_t *rgb_dev, const float *high_res_dev, const
  *                     step/eval_sem_seg.py:10-17 and step/eval_ins_seg.py:21-22)
  * Every output is an int64 count in caller-owned device memory that each call ADDS into, so one
  * accumulator can stay on the device for a whole split; integer counts are exact and independent
- * of launch order and block count.  GT values are 0..20, or 255 (void: not in a confusion row, but
+ * of launch order and block count.  n_classes (nc below) = classes including the background,
+ * 2 <= nc <= IRN_EVAL_MAX_CLASSES; the usual value is IRN_EVAL_CLASSES (VOC12's 21), and one kernel
+ * serves every count.  GT values are 0..nc-1, or 255 (void: not in a confusion row, but
  * counted in `void` when it is not NULL, so the caller can reproduce the size chainercv's growing
- * matrix reaches).  A value outside its documented range (GT 21..254, a NaN CAM, a class key outside
- * 0..19, a prediction above 20, unsorted thresholds, an instance id above g) is skipped and counted
- * in `bad_dev` (int64 [1]).  Nothing synchronises.
+ * matrix reaches).  A value outside its documented range (GT nc..254, a NaN CAM, a class key outside
+ * 0..nc-2, a prediction or plane value above nc-1, unsorted thresholds, an instance id above g) is
+ * skipped and counted in `bad_dev` (int64 [1]).  nc outside its range, or more than nc-1 planes (k)
+ * per image, gives IRN_ERR_ARG before any device work.  Nothing synchronises.
+ * The cap is 80 foreground classes because the per-workgroup LDS tables are sized by it ((nc+1)*nc
+ * uint32 bins, 26.6 KB at nc = 81); labels stay uint8 with 255 = void.
  *
  * irn_cam_confusion: step/eval_cam.py for one image at T thresholds in one pass.  high_res dev fp32
- *   [k][h][w] (k >= 0; may be NULL when k == 0), keys dev int64 [k] (0-based classes), gt dev uint8
- *   [h][w], thres dev fp32 [t] (ascending, 1 <= t <= IRN_EVAL_MAX_THRES).  Per pixel, with m the max
- *   over the k planes and c the first plane that reaches it, the prediction at threshold i is 0 if
+ *   [k][h][w] (0 <= k <= nc-1; may be NULL when k == 0), keys dev int64 [k] (0-based classes), gt dev
+ *   uint8 [h][w], thres dev fp32 [t] (ascending, 1 <= t <= IRN_EVAL_MAX_THRES).  Per pixel, with m the
+ *   max over the k planes and c the first plane that reaches it, the prediction at threshold i is 0 if
  *   k == 0 or m <= thres[i], else keys[c] + 1 (= argmax of [thres[i], high_res] through the padded
- *   keys).  hist dev int64 [22][21][t+1] receives the pixel at [row][keys[c]+1][j], j = number of
- *   thresholds < m (row 21 = GT 255; k == 0: column 0, j = 0).
- * irn_cam_confusion_reduce: hist -> conf dev int64 [t][21][21] (row = GT, column = prediction) and,
- *   when not NULL, void dev int64 [t][21] (predictions at GT-255 pixels); adds into both.
+ *   keys).  hist dev int64 [nc+1][nc][t+1] receives the pixel at [row][keys[c]+1][j], j = number of
+ *   thresholds < m (row nc = GT 255; k == 0: column 0, j = 0).
+ * irn_cam_confusion_reduce: hist -> conf dev int64 [t][nc][nc] (row = GT, column = prediction) and,
+ *   when not NULL, void dev int64 [t][nc] (predictions at GT-255 pixels); adds into both.
  * irn_label_confusion: step/eval_sem_seg.py.  pred, gt dev uint8 [h][w]; pred 255 reads as
- *   pred_255_as when that is in 0..20 (< 0: 255 is out of range).  conf dev int64 [21][21],
- *   void dev int64 [21] (may be NULL).
+ *   pred_255_as when that is in 0..nc-1 (< 0: 255 is out of range).  conf dev int64 [nc][nc],
+ *   void dev int64 [nc] (may be NULL).
  * irn_mask_overlap: the mask_iou counts of step/eval_ins_seg.py.  masks dev uint8 [n][h][w] (nonzero =
  *   in the mask; may be NULL when n == 0), inst dev uint8 [h][w] (0 = no instance, 1..g = instance).
  *   inter dev int64 [n][g] (pixels in mask i and instance j+1), area_pred dev int64 [n], area_gt dev
  *   int64 [g]; n == 0 and g == 0 are valid (the arrays of size 0 may be NULL).
  * irn_ir_label_confusion: step/cam_to_ir_label.py:36-39 + the confusion count for every (fg, bg) pair of
  *   a threshold grid, from the planes of irn_crf_label_sweep; no IR label map is written.  planes dev
- *   uint8 [t_count][h][w] (1 <= t_count <= IRN_CRF_MAX_SWEEP; values 0..20), fg_idx HOST int32 [f] and
+ *   uint8 [t_count][h][w] (1 <= t_count <= IRN_CRF_MAX_SWEEP; values 0..nc-1), fg_idx HOST int32 [f] and
  *   bg_idx HOST int32 [b] (1 <= f, b <= 16; plane numbers in [0, t_count), repeats allowed), gt dev uint8
  *   [h][w].  Per pixel and pair, with fgv = planes[fg_idx[i]] and bgv = planes[bg_idx[j]], the label is
  *   fgv if fgv != 0, else 0 if bgv == 0, else 255, and the pixel is one count in hist dev int64
- *   [f][b][22][22] at [i][j][row][col]: row = GT 0..20 or 21 for GT 255, col = label 0..20 or 21 for
- *   255.  A GT of 21..254, or a value above 20 in ANY of the t_count planes, skips the pixel for every
- *   pair and counts once in bad.  Bad arguments give IRN_ERR_ARG before any device work.
+ *   [f][b][nc+1][nc+1] at [i][j][row][col]: row = GT 0..nc-1 or nc for GT 255, col = label 0..nc-1 or nc
+ *   for 255.  A GT of nc..254, or a value above nc-1 in ANY of the t_count planes, skips the pixel for
+ *   every pair and counts once in bad.  It needs f*(nc+1)*nc + f*b*(nc+1) words of LDS per workgroup and
+ *   runs the fg axis in as many launches as that takes (one for 16 x 16 at nc = 21, eight at nc = 81); the
+ *   histogram does not depend on the grouping.  Bad arguments give IRN_ERR_ARG before any device work.
  * ------------------------------------------------------------------------------------------- */
 #define IRN_EVAL_CLASSES 21
+#define IRN_EVAL_MAX_CLASSES 81
 #define IRN_EVAL_MAX_THRES 256
 int irn_cam_confusion(const float *high_res_dev, const int64_t *keys_dev, int k, const uint8_t *gt_dev, int h, int w,
-                      const float *thres_dev, int t, int64_t *hist_dev, int64_t *bad_dev, void *stream);
-int irn_cam_confusion_reduce(const int64_t *hist_dev, int t, int64_t *conf_dev, int64_t *void_dev, void *stream);
-int irn_label_confusion(const uint8_t *pred_dev, const uint8_t *gt_dev, int h, int w, int pred_255_as,
+                      const float *thres_dev, int t, int n_classes, int64_t *hist_dev, int64_t *bad_dev, void *stream);
+int irn_cam_confusion_reduce(const int64_t *hist_dev, int t, int n_classes, int64_t *conf_dev, int64_t *void_dev,
+                             void *stream);
+int irn_label_confusion(const uint8_t *pred_dev, const uint8_t *gt_dev, int h, int w, int pred_255_as, int n_classes,
                         int64_t *conf_dev, int64_t *void_dev, int64_t *bad_dev, void *stream);
 int irn_mask_overlap(const uint8_t *masks_dev, int n, const uint8_t *inst_dev, int g, int h, int w,
                      int64_t *inter_dev, int64_t *area_pred_dev, int64_t *area_gt_dev, int64_t *bad_dev,
                      void *stream);
 int irn_ir_label_confusion(const uint8_t *planes_dev, int t_count, const int32_t *fg_idx, int f, const int32_t *bg_idx,
-                           int b, const uint8_t *gt_dev, int h, int w, int64_t *hist_dev, int64_t *bad_dev, void *stream);
-/* The same counts for a dataset with another class count.  n_classes (nc below) = classes including the
- * background, 2 <= nc <= IRN_EVAL_MAX_CLASSES; the calls above are these calls with nc = IRN_EVAL_CLASSES,
- * one kernel serves every count.  Everything above holds with 21 read as nc:
- *   hist [nc+1][nc][t+1], conf [t][nc][nc], void [t][nc]; irn_label_confusion conf [nc][nc], void [nc];
- *   irn_ir_label_confusion hist [f][b][nc+1][nc+1], the last row = GT 255, the last column = label 255.
- *   GT g <= nc-1 is row g, 255 is row nc, anything else is bad; a key in 0..nc-2 is column key+1, any
- *   other key is bad; a prediction or plane value >= nc is bad; at most nc-1 planes (k) per image, and
- *   pred_255_as < nc.
- * The cap is 80 foreground classes because the per-workgroup LDS tables are sized by it ((nc+1)*nc uint32
- * bins, 26.6 KB at nc = 81); labels stay uint8 with 255 = void.  irn_ir_label_confusion_nc needs
- * f*(nc+1)*nc + f*b*(nc+1) words of LDS per workgroup and runs the fg axis in as many launches as that takes
- * (one for 16 x 16 at nc = 21, eight at nc = 81); the histogram does not depend on the grouping, and bad
- * counts a pixel once.  nc outside its range, or k above nc-1, gives IRN_ERR_ARG before any device work. */
-#define IRN_EVAL_MAX_CLASSES 81
-int irn_cam_confusion_nc(const float *high_res_dev, const int64_t *keys_dev, int k, const uint8_t *gt_dev, int h, int w,
-                         const float *thres_dev, int t, int n_classes, int64_t *hist_dev, int64_t *bad_dev, void *stream);
-int irn_cam_confusion_reduce_nc(const int64_t *hist_dev, int t, int n_classes, int64_t *conf_dev, int64_t *void_dev,
-                                void *stream);
-int irn_label_confusion_nc(const uint8_t *pred_dev, const uint8_t *gt_dev, int h, int w, int pred_255_as, int n_classes,
-                           int64_t *conf_dev, int64_t *void_dev, int64_t *bad_dev, void *stream);
-int irn_ir_label_confusion_nc(const uint8_t *planes_dev, int t_count, const int32_t *fg_idx, int f, const int32_t *bg_idx,
-                              int b, const uint8_t *gt_dev, int h, int w, int n_classes, int64_t *hist_dev,
-                              int64_t *bad_dev, void *stream);
+                           int b, const uint8_t *gt_dev, int h, int w, int n_classes, int64_t *hist_dev, int64_t *bad_dev,
+                           void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Label threshold sweep  (step/make_sem_seg_labels.py:43-49 + step/eval_sem_seg.py:10-17 at T values
  * of sem_seg_bg_thres in one pass; no label map and no [c,out_h,out_w] tensor is written).
  * Images, sizes, keys and scratch (n_images * 4 bytes) as for irn_label_epilogue; keys are required
- * and c <= 20.  gt_dev[i]: dev uint8 [out_h][out_w], 255 = void, ANY alignment (a batch's maps may be
+ * and c <= nc-1, nc = n_classes as for irn_cam_confusion (usually IRN_EVAL_CLASSES), GT and key ranges
+ * likewise.  gt_dev[i]: dev uint8 [out_h][out_w], 255 = void, ANY alignment (a batch's maps may be
  * packed back to back).  thres dev fp32 [t], ascending, 1 <= t <= IRN_EVAL_MAX_THRES.
  * Per output pixel, with v_c the score irn_label_epilogue compares (x4 bilinear upsample of channel
  * c divided by the image's global maximum): if some v_c is NaN, c* is the first such channel and
  * j = t (the epilogue, like torch.argmax, takes a NaN for the maximum: the pixel is keys[c*]+1 at
  * every threshold); otherwise c* is the first channel that reaches the maximum m and j the number
  * of thresholds < m (thres[i] == m is background: the epilogue compares with a strict >).  The
- * pixel is one count in hist dev int64 [22][21][t+1] at [row][keys[c*]+1][j] — the layout of
+ * pixel is one count in hist dev int64 [nc+1][nc][t+1] at [row][keys[c*]+1][j] — the layout of
  * irn_cam_confusion, so irn_cam_confusion_reduce turns hist into the T confusion matrices, each
  * equal to irn_label_confusion of the labels irn_label_epilogue writes at that threshold.
- * hist and bad (int64 [1]) are added into; GT 21..254 and a key outside 0..19 are skipped and
+ * hist and bad (int64 [1]) are added into; GT nc..254 and a key outside 0..nc-2 are skipped and
  * counted per pixel, a NaN or descending threshold once per call.  Nothing synchronises.
+ * An image has (t+1)*(nc+1)*c bins and a workgroup counts them in passes of at most 15 360 (60 KiB of
+ * LDS), so 80 channels at 256 thresholds take 110 passes per 4096 pixels where 20 channels take 8.
  * ------------------------------------------------------------------------------------------- */
 int irn_label_sweep_confusion(int n_images, const float *const *rw_dev, const int32_t *c, const int32_t *h,
                               const int32_t *w, const int32_t *out_h, const int32_t *out_w,
                               const int64_t *const *keys_dev, const uint8_t *const *gt_dev,
-                              const float *thres_dev, int t, int64_t *hist_dev, int64_t *bad_dev,
+                              const float *thres_dev, int t, int n_classes, int64_t *hist_dev, int64_t *bad_dev,
                               void *scratch_dev, void *stream);
-/* The same sweep at n_classes classes including the background (2..IRN_EVAL_MAX_CLASSES; the call above is this
- * one at IRN_EVAL_CLASSES): c <= n_classes-1, hist [n_classes+1][n_classes][t+1], GT and key ranges as for
- * irn_cam_confusion_nc.  An image has (t+1)*(n_classes+1)*c bins and a workgroup counts them in passes of at most
- * 15 360 (60 KiB of LDS), so 80 channels at 256 thresholds take 110 passes per 4096 pixels where 20 channels
- * take 8. */
-int irn_label_sweep_confusion_nc(int n_images, const float *const *rw_dev, const int32_t *c, const int32_t *h,
-                                 const int32_t *w, const int32_t *out_h, const int32_t *out_w,
-                                 const int64_t *const *keys_dev, const uint8_t *const *gt_dev,
-                                 const float *thres_dev, int t, int n_classes, int64_t *hist_dev, int64_t *bad_dev,
-                                 void *scratch_dev, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * COCO mask encoding  (replaces the pycococreatortools / pycocotools arithmetic behind

@@ -22,6 +22,14 @@ if not os.path.exists(LIB_PATH):
 
 lib = C.CDLL(LIB_PATH)
 
+# The bindings below are by name only, so a library built from another commit would be called with argument lists it
+# does not have.  IRN_ABI_VERSION of include/irn_hip.h moves with every such change; this is the value _SIGS is written for.
+ABI_VERSION = 101
+lib.irn_version.restype, lib.irn_version.argtypes = C.c_int, []
+if lib.irn_version() != ABI_VERSION:
+    raise ImportError("irn_amd: %s reports ABI version %d, these bindings need %d — it was built from another commit; "
+                      "rebuild it with `make -C irn_amd/csrc`" % (LIB_PATH, lib.irn_version(), ABI_VERSION))
+
 vp, i32, f32, sz, i64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 pi32 = C.POINTER(C.c_int32)
 ppv = C.POINTER(C.c_void_p)
@@ -36,12 +44,9 @@ _SIGS = {
     "irn_pair_displacement": (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
     "irn_pair_displacement_backward": (i32, [vp, i32, i32, i32, i32, i32, vp, vp]),
     "irn_aff_loss_workspace_bytes": (sz, [i32, i32, i32, i32]),
-    "irn_aff_loss_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
-    "irn_aff_loss_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
-    "irn_aff_loss_backward_ordered": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
-    "irn_aff_loss_forward_ignore": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
-    "irn_aff_loss_backward_ignore": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
-    "irn_aff_loss_backward_ordered_ignore": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "irn_aff_loss_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
+    "irn_aff_loss_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "irn_aff_loss_backward_ordered": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "irn_walk_create": (i32, [i32, C.POINTER(vp)]),
     "irn_walk_destroy": (i32, [vp]),
     "irn_walk_configure": (i32, [vp, i32, pi32, pi32, pi32, C.POINTER(sz)]),
@@ -75,27 +80,19 @@ _SIGS = {
     "irn_conv1x1_workspace_bytes": (sz, []),
     "irn_conv1x1_algo_count": (i32, [i64, i32, i32, i32, i32, i32, sz, C.POINTER(i32)]),
     "irn_conv1x1_nhwc": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp, sz, vp]),
-    "irn_split16": (i32, [vp, vp, vp, i32, vp, i64, i32, vp, vp]),
-    "irn_split16_pad": (i32, [vp, vp, vp, i32, vp, i64, i32, i32, i32, i32, i32, vp, vp]),
-    "irn_split16_samples": (i32, [vp, vp, vp, i32, vp, i64, i32, i64, vp, vp]),
-    "irn_split16_pad_samples": (i32, [vp, vp, vp, i32, vp, i64, i32, i32, i32, i32, i32, vp, vp]),
+    "irn_split16": (i32, [vp, vp, vp, i32, vp, i64, i32, i64, vp, vp]),
+    "irn_split16_pad": (i32, [vp, vp, vp, i32, vp, i64, i32, i32, i32, i32, i32, i32, vp, vp]),
     "irn_conv3x3_split_gemm": (i32, [vp, vp, vp, i64, i32, i32, i32, i32, f32, i32, i32, vp, sz, vp]),
     "irn_gemm16_algo_count": (i32, [i64, i32, i32, i32, i32, i32, sz, C.POINTER(i32)]),
     "irn_gemm16_nhwc": (i32, [vp, vp, vp, vp, vp, i64, i32, i32, i32, f32, i32, vp, sz, vp]),
     "irn_stem_pool": (i32, [vp, vp, vp, i64, i32, i32, i32, vp, vp]),
     "irn_upsample_bilinear": (i32, [vp, i64, i32, i32, i32, i32, vp, vp]),
     "irn_upsample_bilinear_backward": (i32, [vp, vp, i64, i32, i32, i32, i32, vp, vp]),
-    "irn_find_centroids": (i32, [vp, i32, i32, i32, vp, vp]),
-    "irn_cluster_scratch_bytes": (sz, [i32, i32]),
-    "irn_cluster_centroids": (i32, [vp, vp, i32, i32, f32, vp, C.POINTER(i32), vp, vp]),
     "irn_find_centroids_batch": (i32, [i32, ppv, pi32, pi32, i32, ppv, vp]),
     "irn_cluster_batch_scratch_bytes": (sz, [i32, pi32, pi32]),
     "irn_cluster_centroids_batch": (i32, [i32, ppv, ppv, pi32, pi32, f32, ppv, vp, vp, vp]),
     "irn_ccl_scratch_bytes": (sz, [i32, i32, i32]),
     "irn_label4": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
-    "irn_detect_scratch_bytes": (sz, [i32, i32, i32]),
-    "irn_detect_instance_count": (i32, [vp, vp, i32, i32, i32, C.POINTER(i32), vp, vp]),
-    "irn_detect_instance_emit": (i32, [vp, vp, i32, i32, i32, i32, C.c_double, vp, vp, vp, vp, vp]),
     "irn_detect_batch_scratch_bytes": (sz, [i32, pi32, pi32, pi32]),
     "irn_detect_instance_batch_count": (i32, [i32, ppv, ppv, pi32, pi32, pi32, vp, vp, vp]),
     "irn_detect_instance_batch_emit": (i32, [i32, ppv, ppv, pi32, pi32, pi32, pi32, C.POINTER(C.c_double), ppv, ppv, ppv, vp, vp]),
@@ -112,17 +109,12 @@ _SIGS = {
     "irn_crf_ir_label": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, i32, f32, vp, vp, sz, vp]),
     "irn_crf_sweep_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "irn_crf_label_sweep": (i32, [vp, vp, vp, i32, i32, i32, C.POINTER(f32), i32, i32, f32, vp, vp, sz, vp]),
-    "irn_ir_label_confusion": (i32, [vp, i32, pi32, i32, pi32, i32, vp, i32, i32, vp, vp, vp]),
-    "irn_cam_confusion": (i32, [vp, vp, i32, vp, i32, i32, vp, i32, vp, vp, vp]),
-    "irn_cam_confusion_reduce": (i32, [vp, i32, vp, vp, vp]),
-    "irn_label_confusion": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp]),
     "irn_mask_overlap": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
-    "irn_label_sweep_confusion": (i32, [i32, ppv, pi32, pi32, pi32, pi32, pi32, ppv, ppv, vp, i32, vp, vp, vp, vp]),
-    "irn_ir_label_confusion_nc": (i32, [vp, i32, pi32, i32, pi32, i32, vp, i32, i32, i32, vp, vp, vp]),
-    "irn_cam_confusion_nc": (i32, [vp, vp, i32, vp, i32, i32, vp, i32, i32, vp, vp, vp]),
-    "irn_cam_confusion_reduce_nc": (i32, [vp, i32, i32, vp, vp, vp]),
-    "irn_label_confusion_nc": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
-    "irn_label_sweep_confusion_nc": (i32, [i32, ppv, pi32, pi32, pi32, pi32, pi32, ppv, ppv, vp, i32, i32, vp, vp, vp, vp]),
+    "irn_ir_label_confusion": (i32, [vp, i32, pi32, i32, pi32, i32, vp, i32, i32, i32, vp, vp, vp]),
+    "irn_cam_confusion": (i32, [vp, vp, i32, vp, i32, i32, vp, i32, i32, vp, vp, vp]),
+    "irn_cam_confusion_reduce": (i32, [vp, i32, i32, vp, vp, vp]),
+    "irn_label_confusion": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "irn_label_sweep_confusion": (i32, [i32, ppv, pi32, pi32, pi32, pi32, pi32, ppv, ppv, vp, i32, i32, vp, vp, vp, vp]),
     "irn_mask_rle_scratch_bytes": (sz, [i32, i32, i32]),
     "irn_mask_rle_count": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "irn_mask_rle_emit": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),

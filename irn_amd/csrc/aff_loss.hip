@@ -412,9 +412,9 @@ extern "C" size_t irn_aff_loss_workspace_bytes(int batch, int hp, int wp, int ra
     return (size_t)batch * n_tiles(hp, wp, radius) * kPartWords * sizeof(double);
 }
 
-extern "C" int irn_aff_loss_forward_ignore(const float *edge, const float *dp, const uint8_t *label, int batch, int hp,
-                                           int wp, int radius, int ignore_from, double *sums, int64_t *counts, void *ws,
-                                           size_t ws_bytes, void *stream_) {
+extern "C" int irn_aff_loss_forward(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
+                                    int radius, int ignore_from, double *sums, int64_t *counts, void *ws, size_t ws_bytes,
+                                    void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (int rc = check_args("irn_aff_loss_forward", edge && dp && label && sums && counts, batch, hp, wp, radius, ignore_from, ws,
                             ws_bytes))
@@ -442,15 +442,9 @@ extern "C" int irn_aff_loss_forward_ignore(const float *edge, const float *dp, c
     return IRN_OK;
 }
 
-extern "C" int irn_aff_loss_forward(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
-                                    int radius, double *sums, int64_t *counts, void *ws, size_t ws_bytes, void *stream_) {
-    return irn_aff_loss_forward_ignore(edge, dp, label, batch, hp, wp, radius, IRN_EVAL_CLASSES, sums, counts, ws, ws_bytes,
-                                       stream_);
-}
-
-extern "C" int irn_aff_loss_backward_ignore(const float *edge, const float *dp, const uint8_t *label, int batch, int hp,
-                                            int wp, int radius, int ignore_from, const float *coef, float *grad_edge,
-                                            float *grad_dp, void *ws, size_t ws_bytes, void *stream_) {
+extern "C" int irn_aff_loss_backward(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
+                                     int radius, int ignore_from, const float *coef, float *grad_edge, float *grad_dp,
+                                     void *ws, size_t ws_bytes, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (int rc = check_args("irn_aff_loss_backward", edge && dp && label && coef && grad_edge && grad_dp, batch, hp, wp,
                             radius, ignore_from, ws, ws_bytes))
@@ -470,17 +464,9 @@ extern "C" int irn_aff_loss_backward_ignore(const float *edge, const float *dp, 
     return IRN_OK;
 }
 
-extern "C" int irn_aff_loss_backward(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
-                                     int radius, const float *coef, float *grad_edge, float *grad_dp, void *ws,
-                                     size_t ws_bytes, void *stream_) {
-    return irn_aff_loss_backward_ignore(edge, dp, label, batch, hp, wp, radius, IRN_EVAL_CLASSES, coef, grad_edge, grad_dp, ws,
-                                        ws_bytes, stream_);
-}
-
-extern "C" int irn_aff_loss_backward_ordered_ignore(const float *edge, const float *dp, const uint8_t *label, int batch,
-                                                    int hp, int wp, int radius, int ignore_from, const float *coef,
-                                                    float *grad_edge, float *grad_dp, void *ws, size_t ws_bytes,
-                                                    void *stream_) {
+extern "C" int irn_aff_loss_backward_ordered(const float *edge, const float *dp, const uint8_t *label, int batch, int hp,
+                                             int wp, int radius, int ignore_from, const float *coef, float *grad_edge,
+                                             float *grad_dp, void *ws, size_t ws_bytes, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (int rc = check_args("irn_aff_loss_backward_ordered", edge && dp && label && coef && grad_edge && grad_dp, batch, hp,
                             wp, radius, ignore_from, ws, ws_bytes))
@@ -495,11 +481,4 @@ extern "C" int irn_aff_loss_backward_ordered_ignore(const float *edge, const flo
                        grad_edge, grad_dp);
     IRN_LAUNCH_CHECK("aff_loss_backward_ordered_kernel");
     return IRN_OK;
-}
-
-extern "C" int irn_aff_loss_backward_ordered(const float *edge, const float *dp, const uint8_t *label, int batch, int hp,
-                                             int wp, int radius, const float *coef, float *grad_edge, float *grad_dp,
-                                             void *ws, size_t ws_bytes, void *stream_) {
-    return irn_aff_loss_backward_ordered_ignore(edge, dp, label, batch, hp, wp, radius, IRN_EVAL_CLASSES, coef, grad_edge,
-                                                grad_dp, ws, ws_bytes, stream_);
 }

@@ -307,7 +307,7 @@ int launch_affinity(const AffJob *jobs_dev, int n_jobs, int max_sh, int max_sw, 
 // ------------------------------------------------------------------------------------------------
 using namespace irn;
 
-extern "C" int irn_version(void) { return 100; }
+extern "C" int irn_version(void) { return IRN_ABI_VERSION; }
 
 extern "C" const char *irn_last_error(void) { return last_error_slot().c_str(); }
 

@@ -307,11 +307,10 @@ bool pixels_ok(int h, int w) { return h >= 1 && w >= 1 && (int64_t)h * w <= (int
 
 }  // namespace
 
-// Every entry with a class count refuses one outside 2..IRN_EVAL_MAX_CLASSES by name; the entries without the argument are
-// the same calls at IRN_EVAL_CLASSES.
-extern "C" int irn_cam_confusion_nc(const float *high_res_dev, const int64_t *keys_dev, int k, const uint8_t *gt_dev, int h,
-                                    int w, const float *thres_dev, int t, int n_classes, int64_t *hist_dev, int64_t *bad_dev,
-                                    void *stream) {
+// Every entry with a class count refuses one outside 2..IRN_EVAL_MAX_CLASSES by name.
+extern "C" int irn_cam_confusion(const float *high_res_dev, const int64_t *keys_dev, int k, const uint8_t *gt_dev, int h,
+                                 int w, const float *thres_dev, int t, int n_classes, int64_t *hist_dev, int64_t *bad_dev,
+                                 void *stream) {
     if (!classes_ok(n_classes))
         return fail(IRN_ERR_ARG, "irn_cam_confusion: n_classes %d outside 2..%d", n_classes, IRN_EVAL_MAX_CLASSES);
     if (!gt_dev || !thres_dev || !hist_dev || !bad_dev || k < 0 || k > n_classes - 1 || (k > 0 && (!high_res_dev || !keys_dev)) ||
@@ -325,14 +324,8 @@ extern "C" int irn_cam_confusion_nc(const float *high_res_dev, const int64_t *ke
     return IRN_OK;
 }
 
-extern "C" int irn_cam_confusion(const float *high_res_dev, const int64_t *keys_dev, int k, const uint8_t *gt_dev, int h,
-                                 int w, const float *thres_dev, int t, int64_t *hist_dev, int64_t *bad_dev, void *stream) {
-    return irn_cam_confusion_nc(high_res_dev, keys_dev, k, gt_dev, h, w, thres_dev, t, IRN_EVAL_CLASSES, hist_dev, bad_dev,
-                                stream);
-}
-
-extern "C" int irn_cam_confusion_reduce_nc(const int64_t *hist_dev, int t, int n_classes, int64_t *conf_dev,
-                                           int64_t *void_dev, void *stream) {
+extern "C" int irn_cam_confusion_reduce(const int64_t *hist_dev, int t, int n_classes, int64_t *conf_dev,
+                                        int64_t *void_dev, void *stream) {
     if (!classes_ok(n_classes))
         return fail(IRN_ERR_ARG, "irn_cam_confusion_reduce: n_classes %d outside 2..%d", n_classes, IRN_EVAL_MAX_CLASSES);
     if (!hist_dev || !conf_dev || t < 1 || t > IRN_EVAL_MAX_THRES)
@@ -343,13 +336,8 @@ extern "C" int irn_cam_confusion_reduce_nc(const int64_t *hist_dev, int t, int n
     return IRN_OK;
 }
 
-extern "C" int irn_cam_confusion_reduce(const int64_t *hist_dev, int t, int64_t *conf_dev, int64_t *void_dev,
-                                        void *stream) {
-    return irn_cam_confusion_reduce_nc(hist_dev, t, IRN_EVAL_CLASSES, conf_dev, void_dev, stream);
-}
-
-extern "C" int irn_label_confusion_nc(const uint8_t *pred_dev, const uint8_t *gt_dev, int h, int w, int pred_255_as,
-                                      int n_classes, int64_t *conf_dev, int64_t *void_dev, int64_t *bad_dev, void *stream) {
+extern "C" int irn_label_confusion(const uint8_t *pred_dev, const uint8_t *gt_dev, int h, int w, int pred_255_as,
+                                   int n_classes, int64_t *conf_dev, int64_t *void_dev, int64_t *bad_dev, void *stream) {
     if (!classes_ok(n_classes))
         return fail(IRN_ERR_ARG, "irn_label_confusion: n_classes %d outside 2..%d", n_classes, IRN_EVAL_MAX_CLASSES);
     if (!pred_dev || !gt_dev || !conf_dev || !bad_dev || pred_255_as >= n_classes || !pixels_ok(h, w))
@@ -362,14 +350,9 @@ extern "C" int irn_label_confusion_nc(const uint8_t *pred_dev, const uint8_t *gt
     return IRN_OK;
 }
 
-extern "C" int irn_label_confusion(const uint8_t *pred_dev, const uint8_t *gt_dev, int h, int w, int pred_255_as,
-                                   int64_t *conf_dev, int64_t *void_dev, int64_t *bad_dev, void *stream) {
-    return irn_label_confusion_nc(pred_dev, gt_dev, h, w, pred_255_as, IRN_EVAL_CLASSES, conf_dev, void_dev, bad_dev, stream);
-}
-
-extern "C" int irn_ir_label_confusion_nc(const uint8_t *planes_dev, int t_count, const int32_t *fg_idx, int f,
-                                         const int32_t *bg_idx, int b, const uint8_t *gt_dev, int h, int w, int n_classes,
-                                         int64_t *hist_dev, int64_t *bad_dev, void *stream) {
+extern "C" int irn_ir_label_confusion(const uint8_t *planes_dev, int t_count, const int32_t *fg_idx, int f,
+                                      const int32_t *bg_idx, int b, const uint8_t *gt_dev, int h, int w, int n_classes,
+                                      int64_t *hist_dev, int64_t *bad_dev, void *stream) {
     if (!classes_ok(n_classes))
         return fail(IRN_ERR_ARG, "irn_ir_label_confusion: n_classes %d outside 2..%d", n_classes, IRN_EVAL_MAX_CLASSES);
     if (t_count < 1 || t_count > IR_MAX)
@@ -403,13 +386,6 @@ extern "C" int irn_ir_label_confusion_nc(const uint8_t *planes_dev, int t_count,
         IRN_LAUNCH_CHECK("k_ir_label_hist");
     }
     return IRN_OK;
-}
-
-extern "C" int irn_ir_label_confusion(const uint8_t *planes_dev, int t_count, const int32_t *fg_idx, int f,
-                                      const int32_t *bg_idx, int b, const uint8_t *gt_dev, int h, int w, int64_t *hist_dev,
-                                      int64_t *bad_dev, void *stream) {
-    return irn_ir_label_confusion_nc(planes_dev, t_count, fg_idx, f, bg_idx, b, gt_dev, h, w, IRN_EVAL_CLASSES, hist_dev,
-                                     bad_dev, stream);
 }
 
 extern "C" int irn_mask_overlap(const uint8_t *masks_dev, int n, const uint8_t *inst_dev, int g, int h, int w,

@@ -576,14 +576,6 @@ extern "C" int irn_find_centroids_batch(int n_images, const float *const *dp_dev
     return scratch_release(stream);
 }
 
-extern "C" int irn_find_centroids(const float *dp_dev, int h, int w, int iterations, int32_t *centroids_dev,
-                                  void *stream_) {
-    if (!dp_dev || !centroids_dev || h < 1 || w < 1 || iterations < 0)
-        return fail(IRN_ERR_ARG, "irn_find_centroids: bad argument");
-    const int32_t hh = h, ww = w;
-    return irn_find_centroids_batch(1, &dp_dev, &hh, &ww, iterations, &centroids_dev, stream_);
-}
-
 extern "C" size_t irn_ccl_scratch_bytes(int n, int h, int w) {
     if (n < 1 || h < 1 || w < 1) return 0;
     return round_up(sizeof(int) * 2 * (size_t)n * h * w, 256);
@@ -620,10 +612,10 @@ extern "C" int irn_label4(const uint8_t *mask_dev, int n, int h, int w, int32_t 
     return scratch_release(stream);
 }
 
-// scratch of one image in irn_cluster_centroids[_batch]:
-//   [parent npx][rank npx] int32, [picked npx] int32, [present npx+2] int32, [K slot of the single-image form]
+// scratch of one image in irn_cluster_centroids_batch:
+//   [parent npx][rank npx] int32, [picked npx] int32, [present npx+2] int32, [one spare block]
 //   (each 256-byte aligned)
-extern "C" size_t irn_cluster_scratch_bytes(int h, int w) {
+static size_t cluster_scratch_bytes(int h, int w) {
     if (h < 1 || w < 1) return 0;
     const size_t npx = (size_t)h * w;
     return round_up(4 * npx, 256) * 3 + round_up(4 * (npx + 2), 256) + 256;
@@ -632,7 +624,7 @@ extern "C" size_t irn_cluster_scratch_bytes(int h, int w) {
 extern "C" size_t irn_cluster_batch_scratch_bytes(int n_images, const int32_t *h, const int32_t *w) {
     if (n_images < 1 || !h || !w) return 0;
     size_t total = 0;
-    for (int i = 0; i < n_images; ++i) total += irn_cluster_scratch_bytes(h[i], w[i]);
+    for (int i = 0; i < n_images; ++i) total += cluster_scratch_bytes(h[i], w[i]);
     return total;
 }
 
@@ -663,7 +655,7 @@ extern "C" int irn_cluster_centroids_batch(int n_images, const int32_t *const *c
         J.k_out = k_dev + i;
         J.h = h[i];
         J.w = w[i];
-        s += irn_cluster_scratch_bytes(h[i], w[i]);
+        s += cluster_scratch_bytes(h[i], w[i]);
         max_n = std::max(max_n, (int)npx);
     }
     ClusterJob *jd = nullptr;
@@ -687,26 +679,9 @@ extern "C" int irn_cluster_centroids_batch(int n_images, const int32_t *const *c
     return scratch_release(stream);
 }
 
-extern "C" int irn_cluster_centroids(const int32_t *centroids_dev, const float *dp_dev, int h, int w, float thres,
-                                     int32_t *cluster_map_dev, int *k_out, void *scratch_dev, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!centroids_dev || !dp_dev || !cluster_map_dev || !k_out || !scratch_dev || h < 1 || w < 1)
-        return fail(IRN_ERR_ARG, "irn_cluster_centroids: bad argument");
-    int32_t *k_dev = (int32_t *)((char *)scratch_dev + irn_cluster_scratch_bytes(h, w) - 256);   // the K slot
-    const int32_t hh = h, ww = w;
-    int rc = irn_cluster_centroids_batch(1, &centroids_dev, &dp_dev, &hh, &ww, thres, &cluster_map_dev, k_dev, scratch_dev,
-                                         stream_);
-    if (rc) return rc;
-    int32_t k = 0;
-    IRN_HIP_TRY(hipMemcpyAsync(&k, k_dev, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    IRN_HIP_TRY(hipStreamSynchronize(stream));
-    *k_out = k;
-    return IRN_OK;
-}
-
 // scratch of one image in irn_detect_instance_*: [parent npx][prov npx][newid npx][area npx][score_bits npx] int32,
 //                                                 [keys npx] int64, [counter]
-extern "C" size_t irn_detect_scratch_bytes(int n_channels, int h, int w) {
+static size_t detect_scratch_bytes(int n_channels, int h, int w) {
     if (n_channels < 1 || h < 1 || w < 1) return 0;
     const size_t npx = (size_t)h * w;
     return round_up(4 * npx, 256) * 5 + round_up(8 * npx, 256) + 256;
@@ -716,12 +691,12 @@ extern "C" size_t irn_detect_batch_scratch_bytes(int n_images, const int32_t *n_
                                                  const int32_t *w) {
     if (n_images < 1 || !n_channels || !h || !w) return 0;
     size_t total = 0;
-    for (int i = 0; i < n_images; ++i) total += irn_detect_scratch_bytes(n_channels[i], h[i], w[i]);
+    for (int i = 0; i < n_images; ++i) total += detect_scratch_bytes(n_channels[i], h[i], w[i]);
     return total;
 }
 
 namespace {
-// carve the per-image scratch; `counter` = the last 256-byte block (single-image API) unless the caller supplies one
+// carve the per-image scratch; `counter` = the last 256-byte block unless the caller supplies one
 void det_carve(DetJob &J, char *b, size_t npx) {
     const size_t a = round_up(4 * npx, 256);
     J.parent = (int *)b;
@@ -751,7 +726,7 @@ int det_fill_jobs(const char *who, int n_images, const float *const *rw_up_dev, 
         J.h = h[i];
         J.w = w[i];
         det_carve(J, s, (size_t)h[i] * w[i]);
-        s += irn_detect_scratch_bytes(n_channels[i], h[i], w[i]);
+        s += detect_scratch_bytes(n_channels[i], h[i], w[i]);
         *max_n = std::max(*max_n, h[i] * w[i]);
     }
     return IRN_OK;
@@ -1376,32 +1351,4 @@ extern "C" int irn_argmax_rethreshold_batch(int n_images, const float *const *rw
     hipLaunchKernelGGL(argmax_rethreshold_kernel, dim3(cdiv(max_n, 256), n_images), dim3(256), 0, stream, jd, thres);
     IRN_LAUNCH_CHECK("argmax_rethreshold_kernel");
     return scratch_release(stream);
-}
-
-extern "C" int irn_detect_instance_count(const float *rw_up_dev, const int32_t *argmax_dev, int n_channels, int h,
-                                         int w, int *n_det_out, void *scratch_dev, void *stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (!rw_up_dev || !argmax_dev || !n_det_out || !scratch_dev || n_channels < 1 || n_channels > 65535 || h < 1 || w < 1)
-        return fail(IRN_ERR_ARG, "irn_detect_instance_count: bad argument");
-    const int32_t cc = n_channels, hh = h, ww = w;
-    // the counter of the single-image form is the last block of its own scratch
-    int32_t *counter = (int32_t *)((char *)scratch_dev + irn_detect_scratch_bytes(n_channels, h, w) - 256);
-    int rc = irn_detect_instance_batch_count(1, &rw_up_dev, &argmax_dev, &cc, &hh, &ww, counter, scratch_dev, stream_);
-    if (rc) return rc;
-    int32_t n_det = 0;
-    IRN_HIP_TRY(hipMemcpyAsync(&n_det, counter, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    IRN_HIP_TRY(hipStreamSynchronize(stream));
-    *n_det_out = n_det;
-    return IRN_OK;
-}
-
-extern "C" int irn_detect_instance_emit(const float *rw_up_dev, const int32_t *argmax_dev, int n_channels, int h, int w,
-                                        int n_det, double min_area, float *score_dev, int32_t *channel_dev,
-                                        uint8_t *mask_dev, void *scratch_dev, void *stream_) {
-    if (!rw_up_dev || !argmax_dev || !score_dev || !channel_dev || !mask_dev || !scratch_dev || n_channels < 1 || h < 1 ||
-        w < 1 || n_det < 1)
-        return fail(IRN_ERR_ARG, "irn_detect_instance_emit: bad argument");
-    const int32_t cc = n_channels, hh = h, ww = w, nd = n_det;
-    return irn_detect_instance_batch_emit(1, &rw_up_dev, &argmax_dev, &cc, &hh, &ww, &nd, &min_area, &score_dev,
-                                          &channel_dev, &mask_dev, scratch_dev, stream_);
 }

@@ -449,11 +449,11 @@ extern "C" int irn_label_epilogue(int n_images, const float *const *rw_dev, cons
     return scratch_release(stream);
 }
 
-extern "C" int irn_label_sweep_confusion_nc(int n_images, const float *const *rw_dev, const int32_t *c, const int32_t *h,
-                                            const int32_t *w, const int32_t *out_h, const int32_t *out_w,
-                                            const int64_t *const *keys_dev, const uint8_t *const *gt_dev,
-                                            const float *thres_dev, int t, int n_classes, int64_t *hist_dev,
-                                            int64_t *bad_dev, void *scratch_dev, void *stream_) {
+extern "C" int irn_label_sweep_confusion(int n_images, const float *const *rw_dev, const int32_t *c, const int32_t *h,
+                                         const int32_t *w, const int32_t *out_h, const int32_t *out_w,
+                                         const int64_t *const *keys_dev, const uint8_t *const *gt_dev,
+                                         const float *thres_dev, int t, int n_classes, int64_t *hist_dev,
+                                         int64_t *bad_dev, void *scratch_dev, void *stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     if (!thist::classes_ok(n_classes))
         return fail(IRN_ERR_ARG, "irn_label_sweep_confusion: n_classes %d outside 2..%d", n_classes, IRN_EVAL_MAX_CLASSES);
@@ -482,15 +482,6 @@ extern "C" int irn_label_sweep_confusion_nc(int n_images, const float *const *rw
                        hist_dev, bad_dev);
     IRN_LAUNCH_CHECK("label_sweep_kernel");
     return scratch_release(stream);
-}
-
-extern "C" int irn_label_sweep_confusion(int n_images, const float *const *rw_dev, const int32_t *c, const int32_t *h,
-                                         const int32_t *w, const int32_t *out_h, const int32_t *out_w,
-                                         const int64_t *const *keys_dev, const uint8_t *const *gt_dev,
-                                         const float *thres_dev, int t, int64_t *hist_dev, int64_t *bad_dev,
-                                         void *scratch_dev, void *stream_) {
-    return irn_label_sweep_confusion_nc(n_images, rw_dev, c, h, w, out_h, out_w, keys_dev, gt_dev, thres_dev, t, IRN_EVAL_CLASSES,
-                                        hist_dev, bad_dev, scratch_dev, stream_);
 }
 
 extern "C" int irn_cam_merge(int n_scales, const float *const *src_dev, const int32_t *hs, const int32_t *ws, int n_classes,

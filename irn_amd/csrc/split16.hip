@@ -84,7 +84,7 @@ __global__ __launch_bounds__(kThreads) void split16_kernel(const float *__restri
         lo[k] = (_Float16)((v[k] - (float)h) * 2048.f);
         bad |= !(fabsf(v[k]) <= kFp16Max);               // beyond fp16's range, or NaN
     }
-    // rows_per_sample != 0: `overflow` is one word per sample (irn_split16_samples); `row` counts the rows the threads enumerate,
+    // rows_per_sample != 0: `overflow` is one word per sample; `row` counts the rows the threads enumerate,
     // so a sample is rows_per_sample of them in either form.  The division exists in this rare branch only — in front of the
     // stores, where `row` is alive anyway (behind them it would cost the plain kernel two registers).
     if (bad && overflow) atomicOr(rows_per_sample ? overflow + row / rows_per_sample : overflow, 1u);
@@ -110,7 +110,7 @@ int split16_launch(const float *x_dev, const float *scale_dev, const float *shif
     int64_t rows = n_pixels;                       // rows the threads enumerate: the bordered form's when it is the output
     if (pm.out_pad) rows = n_pixels / ((int64_t)pm.h * pm.w) * (pm.h + 2) * (pm.w + 2);
     // per-sample flags (pixels_per_sample > 0): whole samples only, so that every enumerated row has a flag word of its own sample
-    if (pixels_per_sample < 0 || pixels_per_sample >= (1ll << 31)) return fail(IRN_ERR_ARG, "irn_split16: pixels_per_sample must be in [1, 2^31)");
+    if (pixels_per_sample < 0 || pixels_per_sample >= (1ll << 31)) return fail(IRN_ERR_ARG, "irn_split16: pixels_per_sample must be in [0, 2^31)");
     if (pixels_per_sample && !overflow_dev) return fail(IRN_ERR_ARG, "irn_split16: per-sample flags need flags_dev");
     if (pixels_per_sample && n_pixels % pixels_per_sample) return fail(IRN_ERR_ARG, "irn_split16: n_pixels must be a multiple of pixels_per_sample");
     unsigned rps = (unsigned)pixels_per_sample;
@@ -132,33 +132,17 @@ int split16_launch(const float *x_dev, const float *scale_dev, const float *shif
 }  // namespace irn
 
 extern "C" int irn_split16(const float *x_dev, const float *scale_dev, const float *shift_dev, int relu, void *out_dev,
-                           int64_t n_pixels, int n_channels, unsigned *overflow_dev, void *stream) {
-    return irn::split16_launch(x_dev, scale_dev, shift_dev, relu, out_dev, n_pixels, n_channels, overflow_dev, 0, stream, irn::PadMap{0u, 0u, 0, 0});
-}
-
-extern "C" int irn_split16_samples(const float *x_dev, const float *scale_dev, const float *shift_dev, int relu, void *out_dev,
-                                   int64_t n_pixels, int n_channels, int64_t pixels_per_sample, unsigned *flags_dev, void *stream) {
-    if (pixels_per_sample < 1 || !flags_dev) return irn::fail(IRN_ERR_ARG, "irn_split16_samples: pixels_per_sample >= 1 and flags_dev are needed");
+                           int64_t n_pixels, int n_channels, int64_t pixels_per_sample, unsigned *flags_dev, void *stream) {
     return irn::split16_launch(x_dev, scale_dev, shift_dev, relu, out_dev, n_pixels, n_channels, flags_dev, pixels_per_sample, stream,
                                irn::PadMap{0u, 0u, 0, 0});
 }
 
 extern "C" int irn_split16_pad(const float *x_dev, const float *scale_dev, const float *shift_dev, int relu, void *out_dev,
-                               int64_t n_images, int h, int w, int n_channels, int in_padded, int out_padded, unsigned *overflow_dev,
-                               void *stream) {
+                               int64_t n_images, int h, int w, int n_channels, int in_padded, int out_padded, int per_sample,
+                               unsigned *flags_dev, void *stream) {
     using namespace irn;
     if (n_images < 0 || h < 1 || w < 1) return fail(IRN_ERR_ARG, "irn_split16_pad: n_images >= 0, h, w >= 1");
     if ((int64_t)n_images * (h + 2) * (w + 2) * n_channels >= (1ll << 31)) return fail(IRN_ERR_ARG, "irn_split16_pad: at most 2^31 - 1 padded elements per call");
-    return split16_launch(x_dev, scale_dev, shift_dev, relu, out_dev, n_images * h * w, n_channels, overflow_dev, 0, stream,
-                          PadMap{(unsigned)h, (unsigned)w, in_padded ? 1 : 0, out_padded ? 1 : 0});
-}
-
-extern "C" int irn_split16_pad_samples(const float *x_dev, const float *scale_dev, const float *shift_dev, int relu, void *out_dev,
-                                       int64_t n_images, int h, int w, int n_channels, int in_padded, int out_padded, unsigned *flags_dev,
-                                       void *stream) {
-    using namespace irn;
-    if (n_images < 0 || h < 1 || w < 1 || !flags_dev) return fail(IRN_ERR_ARG, "irn_split16_pad_samples: n_images >= 0, h, w >= 1 and flags_dev are needed");
-    if ((int64_t)n_images * (h + 2) * (w + 2) * n_channels >= (1ll << 31)) return fail(IRN_ERR_ARG, "irn_split16_pad_samples: at most 2^31 - 1 padded elements per call");
-    return split16_launch(x_dev, scale_dev, shift_dev, relu, out_dev, n_images * h * w, n_channels, flags_dev, (int64_t)h * w, stream,
-                          PadMap{(unsigned)h, (unsigned)w, in_padded ? 1 : 0, out_padded ? 1 : 0});
+    return split16_launch(x_dev, scale_dev, shift_dev, relu, out_dev, n_images * h * w, n_channels, flags_dev,
+                          per_sample ? (int64_t)h * w : 0, stream, PadMap{(unsigned)h, (unsigned)w, in_padded ? 1 : 0, out_padded ? 1 : 0});
 }

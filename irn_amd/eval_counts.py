@@ -69,8 +69,8 @@ def cam_confusion(high_res, keys, gt, thres, hist=None, bad=None, n_classes=EVAL
     hist = accumulator(hist, (nc + 1, nc, t + 1), dev, "hist")
     bad = accumulator(bad, (1,), dev, "bad")
     with torch.cuda.device(dev):
-        check(lib.irn_cam_confusion_nc(cams.data_ptr() if k else None, ks.data_ptr() if k else None, k, g.data_ptr(), h, w,
-                                       th.data_ptr(), t, nc, hist.data_ptr(), bad.data_ptr(), _stream()))
+        check(lib.irn_cam_confusion(cams.data_ptr() if k else None, ks.data_ptr() if k else None, k, g.data_ptr(), h, w,
+                                    th.data_ptr(), t, nc, hist.data_ptr(), bad.data_ptr(), _stream()))
     return hist, bad
 
 
@@ -84,7 +84,7 @@ def cam_confusion_matrices(hist, n_classes=EVAL_CLASSES):
     conf = _i64_zeros((t, nc, nc), hist.device)
     void = _i64_zeros((t, nc), hist.device)
     with torch.cuda.device(hist.device):
-        check(lib.irn_cam_confusion_reduce_nc(hist.data_ptr(), t, nc, conf.data_ptr(), void.data_ptr(), _stream()))
+        check(lib.irn_cam_confusion_reduce(hist.data_ptr(), t, nc, conf.data_ptr(), void.data_ptr(), _stream()))
     return conf, void
 
 
@@ -104,8 +104,8 @@ def label_confusion(pred, gt, conf=None, bad=None, pred_255_as=0, void=None, n_c
     bad = accumulator(bad, (1,), dev, "bad")
     h, w = g.shape
     with torch.cuda.device(dev):
-        check(lib.irn_label_confusion_nc(p.data_ptr(), g.data_ptr(), h, w, -1 if pred_255_as is None else int(pred_255_as),
-                                         nc, conf.data_ptr(), void.data_ptr(), bad.data_ptr(), _stream()))
+        check(lib.irn_label_confusion(p.data_ptr(), g.data_ptr(), h, w, -1 if pred_255_as is None else int(pred_255_as),
+                                      nc, conf.data_ptr(), void.data_ptr(), bad.data_ptr(), _stream()))
     return conf, void, bad
 
 
@@ -158,6 +158,6 @@ def ir_label_confusion(planes, fg_idx, bg_idx, gt, hist=None, bad=None, n_classe
     bad = accumulator(bad, (1,), dev, "bad")
     pi32 = C.POINTER(C.c_int32)
     with torch.cuda.device(dev):
-        check(lib.irn_ir_label_confusion_nc(pl.data_ptr(), t, fg.ctypes.data_as(pi32), int(fg.size), bg.ctypes.data_as(pi32),
-                                            int(bg.size), g.data_ptr(), h, w, nc, hist.data_ptr(), bad.data_ptr(), _stream()))
+        check(lib.irn_ir_label_confusion(pl.data_ptr(), t, fg.ctypes.data_as(pi32), int(fg.size), bg.ctypes.data_as(pi32),
+                                         int(bg.size), g.data_ptr(), h, w, nc, hist.data_ptr(), bad.data_ptr(), _stream()))
     return hist, bad

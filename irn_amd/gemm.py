@@ -200,7 +200,7 @@ def split16(x, scale=None, shift=None, relu=False, flags=None):
     """fp32 channels-last activation [N, C, H, W] -> fp16 [N*H*W, 3C] = [hi | hi | lo'] per pixel (irn_split16), the A operand
     of `gemm16_nhwc`; with `scale` / `shift` (fp32 [C]) the inference batch norm (+ ReLU) of the convolution that produced
     `x` is applied on the way (reference net/resnet50.py:40-42) and `x` is never written back.  `flags` (int32 [N], or the
-    tensor of an enclosing `sample_flags`): the overflow is recorded per sample there (irn_split16_samples) and the
+    tensor of an enclosing `sample_flags`): the overflow is recorded per sample there (pixels_per_sample = H*W) and the
     process-wide flag is left alone; the fp16 result is the same bits."""
     _need_cuda(x, "x")
     _need_cl(x, "split16: x")
@@ -218,21 +218,18 @@ def split16(x, scale=None, shift=None, relu=False, flags=None):
         flags = _SAMPLE_FLAGS[0]
     sp, tp = None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr()
     with torch.cuda.device(x.device):
-        per = max(1, (2 ** 31 - 1) // c)
+        per = max(1, (2 ** 31 - 1) // c)                 # at most 2^31 - 1 elements per call
+        pps = 0                                          # pixels per sample; 0 = the one process-wide word
         if flags is not None:
             _need_flags(flags, n, x.device, "split16")
             pps = h * w_
             per = per // pps * pps                       # whole samples per call
             if per == 0:
                 raise ValueError("split16: a sample of %d x %d elements; per-sample flags need fewer than 2^31 per sample" % (pps, c))
-            for i in range(0, m, per):
-                check(lib.irn_split16_samples(x.data_ptr() + 4 * i * c, sp, tp, 1 if relu else 0, out.data_ptr() + 2 * i * 3 * c, min(per, m - i), c,
-                                              pps, flags.data_ptr() + 4 * (i // pps), _stream()))
-            return out
-        for i in range(0, m, per):                       # at most 2^31 - 1 elements per call
-            rows = min(per, m - i)
-            check(lib.irn_split16(x.data_ptr() + 4 * i * c, sp, tp, 1 if relu else 0, out.data_ptr() + 2 * i * 3 * c, rows, c,
-                                  _split_flag(x.device).data_ptr(), _stream()))
+        for i in range(0, m, per):
+            word = _split_flag(x.device).data_ptr() if flags is None else flags.data_ptr() + 4 * (i // pps)
+            check(lib.irn_split16(x.data_ptr() + 4 * i * c, sp, tp, 1 if relu else 0, out.data_ptr() + 2 * i * 3 * c, min(per, m - i), c,
+                                  pps, word, _stream()))
     return out
 
 
@@ -302,7 +299,7 @@ def split16_pad(x, shape, scale=None, shift=None, relu=False, in_padded=False, o
     in_padded: `x` is the bordered fp32 form [n (h+2)(w+2), c] (a `conv3x3_split` result), the result is the dense fp16
     [n h w, 3c]; `out` given (a bordered fp16 buffer's interior view, borders already zero): `x` is a dense channels-last fp32
     tensor and the split goes into the bordered form, zero border rows included.  `flags`: as in `split16`, one word per image
-    (irn_split16_pad_samples)."""
+    (per_sample = 1)."""
     n, c, h, w_ = (int(v) for v in shape)
     _need_cuda(x, "x")
     if c % 8:
@@ -324,10 +321,10 @@ def split16_pad(x, shape, scale=None, shift=None, relu=False, in_padded=False, o
     if flags is not None:
         _need_flags(flags, n, x.device, "split16_pad")
     with torch.cuda.device(x.device):
-        fn = lib.irn_split16_pad if flags is None else lib.irn_split16_pad_samples
-        check(fn(x.data_ptr(), None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr(),
-                 1 if relu else 0, out.data_ptr(), n, h, w_, c, 1 if in_padded else 0, 1 if out_padded else 0,
-                 (_split_flag(x.device) if flags is None else flags).data_ptr(), _stream()))
+        check(lib.irn_split16_pad(
+            x.data_ptr(), None if scale is None else scale.data_ptr(), None if shift is None else shift.data_ptr(),
+            1 if relu else 0, out.data_ptr(), n, h, w_, c, 1 if in_padded else 0, 1 if out_padded else 0,
+            0 if flags is None else 1, (_split_flag(x.device) if flags is None else flags).data_ptr(), _stream()))
     return out
 
 

@@ -15,32 +15,17 @@ from ._lib import _need_cuda, _stream, check, i32_array, lib, ptr_array
 
 def find_centroids_with_refinement(displacement, iterations=300):
     """dp GPU fp32 [2,h,w] -> GPU int32 [2,h,w] (cy, cx); bit-identical to the reference's numpy
-    (step/make_ins_seg_labels.py:18-56)."""
-    _need_cuda(displacement, "displacement")
-    dp = displacement.contiguous().float()
-    _, h, w = dp.shape
-    out = torch.empty((2, h, w), dtype=torch.int32, device=dp.device)
-    with torch.cuda.device(dp.device):
-        check(lib.irn_find_centroids(dp.data_ptr(), h, w, int(iterations), out.data_ptr(), _stream()))
-    return out
+    (step/make_ins_seg_labels.py:18-56).  A batch of one."""
+    return find_centroids_batch([displacement], iterations)[0]
 
 
 def cluster_centroids(centroids, displacement, thres=2.5, as_one_hot=False):
     """-> (cluster_map GPU int32 [h,w] with values 0..K-1, K).  With ``as_one_hot`` returns the
-    reference's bool [K,h,w] instead (step/make_ins_seg_labels.py:58-75)."""
-    _need_cuda(centroids, "centroids")
-    dp = displacement.contiguous().float()
-    cen = centroids.to(torch.int32).contiguous()
-    _, h, w = dp.shape
-    cmap = torch.empty((h, w), dtype=torch.int32, device=dp.device)
-    scratch = torch.empty(lib.irn_cluster_scratch_bytes(h, w), dtype=torch.uint8, device=dp.device)
-    k = C.c_int()
-    with torch.cuda.device(dp.device):
-        check(lib.irn_cluster_centroids(cen.data_ptr(), dp.data_ptr(), h, w, float(thres), cmap.data_ptr(),
-                                        C.byref(k), scratch.data_ptr(), _stream()))
+    reference's bool [K,h,w] instead (step/make_ins_seg_labels.py:58-75).  A batch of one."""
+    (cmap,), (k,) = cluster_centroids_batch([centroids], [displacement], thres)
     if as_one_hot:
-        return (cmap[None] == torch.arange(k.value, device=dp.device, dtype=torch.int32)[:, None, None])
-    return cmap, k.value
+        return (cmap[None] == torch.arange(k, device=cmap.device, dtype=torch.int32)[:, None, None])
+    return cmap, k
 
 
 def find_centroids_batch(displacements, iterations=300):
@@ -109,44 +94,19 @@ def detect_instance(rw_up, argmax, class_ids, n_channels, max_fragment_size=0):
     class_ids: int64 [C'] (np.repeat(keys, K)).  Every 4-connected component of every channel's
     mask becomes a detection: score = max(rw_up[c] over the component), or 0 when it has fewer than
     max_fragment_size pixels.  Labelling, areas, scores and the [N,H,W] masks are produced by
-    libirn_hip.so (irn_detect_instance_count / _emit): one pass over the class map, one 4-byte sync
-    for N, one transfer of the result.  Returns the reference's numpy dict {'score','mask','class'}
+    libirn_hip.so (irn_detect_instance_batch_count / _emit, a batch of one): one pass over the class map,
+    one 4-byte sync for N, one transfer of the result.  Returns the reference's numpy dict {'score','mask','class'}
     in its order (channel ascending, component ascending by first pixel).  Raises ValueError when
     nothing is detected (the reference crashes in np.stack([]) — SURVEY.md §3.5)."""
     _need_cuda(rw_up, "rw_up")
     _need_cuda(argmax, "argmax")
-    dev = rw_up.device
-    sc = rw_up.contiguous().float()
-    am = argmax.to(torch.int32).contiguous()
-    n_channels = int(n_channels)
-    h, w = am.shape
-    if sc.shape != (n_channels, h, w):
-        raise ValueError("rw_up must be [%d,%d,%d], got %s" % (n_channels, h, w, tuple(sc.shape)))
-    class_ids = np.asarray(class_ids)
-    npx = h * w
-    scratch = cached("det_scratch", dev, lib.irn_detect_scratch_bytes(n_channels, h, w), torch.uint8)
-    n = C.c_int()
-    with torch.cuda.device(dev):
-        check(lib.irn_detect_instance_count(sc.data_ptr(), am.data_ptr(), n_channels, h, w, C.byref(n),
-                                            scratch.data_ptr(), _stream()))
-        nd = n.value
-        if nd == 0:
-            raise ValueError(_NOTHING)
-        # one packed device buffer [score fp32 | channel int32 | masks uint8] -> one transfer into pinned memory
-        # (a pageable .cpu() of the masks plus fresh allocations cost 3.6 ms per 512^2 image: 10x the rest of the step)
-        head = 8 * nd
-        packed = cached("det_out", dev, head + nd * npx, torch.uint8)
-        base = packed.data_ptr()
-        check(lib.irn_detect_instance_emit(sc.data_ptr(), am.data_ptr(), n_channels, h, w, nd, float(max_fragment_size),
-                                           base, base + 4 * nd, base + head, scratch.data_ptr(), _stream()))
-        host = cached("det_host", "pinned", head + nd * npx, torch.uint8)
-        host[:head + nd * npx].copy_(packed[:head + nd * npx], non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-    raw = host.numpy()
-    score = raw[:4 * nd].view(np.float32).copy()
-    chan = raw[4 * nd:head].view(np.int32)
-    mask = raw[head:head + nd * npx].view(np.bool_).reshape(nd, h, w).copy()
-    return {"score": score, "mask": mask, "class": class_ids[chan]}
+    h, w = argmax.shape
+    if tuple(rw_up.shape) != (int(n_channels), h, w):
+        raise ValueError("rw_up must be [%d,%d,%d], got %s" % (n_channels, h, w, tuple(rw_up.shape)))
+    found = detect_instance_batch([rw_up], [argmax], [class_ids], [n_channels], [max_fragment_size])[0]
+    if isinstance(found, ValueError):
+        raise found
+    return found
 
 
 _NOTHING = "detect_instance: no foreground pixel in any channel"
@@ -261,8 +221,7 @@ class PendingDetections(_PendingBatch):
 
 
 def detect_instance_batch(rw_ups, argmaxes, class_ids, n_channels, max_fragment_sizes, timings=None, deferred=False):
-    """detect_instance for a batch of images with two host round trips in total (the per-image form has three per
-    image): one 4-byte-per-image transfer of the detection counts, one packed transfer of every image's
+    """detect_instance for a batch of images with two host round trips in total: one 4-byte-per-image transfer of the detection counts, one packed transfer of every image's
     {score, channel, masks} (irn_detect_instance_batch_count / _emit).  Arguments are lists (one entry per image) of
     what `detect_instance` takes.  Returns a list with, per image, the reference's numpy dict or — for an image without
     any foreground pixel — the ValueError `detect_instance` would raise.  With `deferred=True` the packed transfer is

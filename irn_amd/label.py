@@ -123,7 +123,7 @@ def label_sweep_confusion(rws, out_sizes, keys, gts, thres, hist=None, bad=None,
     bad = accumulator(bad, (1,), dev, "bad")
     scratch = torch.empty(max(n, 64), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        check(lib.irn_label_sweep_confusion_nc(
+        check(lib.irn_label_sweep_confusion(
             n, ptr_array([r.data_ptr() for r in rs]), i32_array([r.shape[0] for r in rs]), i32_array([r.shape[1] for r in rs]),
             i32_array([r.shape[2] for r in rs]), i32_array([s[0] for s in sizes]), i32_array([s[1] for s in sizes]),
             ptr_array([k.data_ptr() for k in ks]), ptr_array(gt_ptrs), th.data_ptr(), t, nc, hist.data_ptr(), bad.data_ptr(),

@@ -213,9 +213,9 @@ class _AffinityDisplacementSums(torch.autograd.Function):
         sums = torch.empty(5, dtype=torch.float64, device=edge.device)
         counts = torch.empty(3, dtype=torch.int64, device=edge.device)
         with torch.cuda.device(edge.device):
-            check(lib.irn_aff_loss_forward_ignore(edge.data_ptr(), dp.data_ptr(), label.data_ptr(), b, hp, wp, radius,
-                                                  ignore_from, sums.data_ptr(), counts.data_ptr(), ws.data_ptr(), need,
-                                                  _stream()))
+            check(lib.irn_aff_loss_forward(edge.data_ptr(), dp.data_ptr(), label.data_ptr(), b, hp, wp, radius,
+                                           ignore_from, sums.data_ptr(), counts.data_ptr(), ws.data_ptr(), need,
+                                           _stream()))
         ctx.save_for_backward(edge, dp, label)
         ctx.geom = (radius, ws, bool(ordered), ignore_from)
         ctx.mark_non_differentiable(counts)
@@ -229,7 +229,7 @@ class _AffinityDisplacementSums(torch.autograd.Function):
         coef = grad_sums.to(torch.float32).contiguous()          # stays on the device: nothing synchronises
         grad_edge = torch.empty_like(edge)
         grad_dp = torch.empty_like(dp)
-        backward = lib.irn_aff_loss_backward_ordered_ignore if ordered else lib.irn_aff_loss_backward_ignore
+        backward = lib.irn_aff_loss_backward_ordered if ordered else lib.irn_aff_loss_backward
         with torch.cuda.device(edge.device):
             check(backward(edge.data_ptr(), dp.data_ptr(), label.data_ptr(), b, hp, wp, radius, ignore_from, coef.data_ptr(),
                            grad_edge.data_ptr(), grad_dp.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))

@@ -117,10 +117,10 @@ def test_c_entries_refuse_bad_arguments_before_any_device():
         assert L.irn_aff_loss_workspace_bytes(*bad) == 0
 
     def fwd(edge=one, dp=one, label=one, batch=2, hp=33, wp=47, radius=5, sums=one, counts=one, ws=one, ws_bytes=need):
-        return L.irn_aff_loss_forward(edge, dp, label, batch, hp, wp, radius, sums, counts, ws, ws_bytes, None)
+        return L.irn_aff_loss_forward(edge, dp, label, batch, hp, wp, radius, 21, sums, counts, ws, ws_bytes, None)
 
     def bwd(edge=one, dp=one, label=one, batch=2, hp=33, wp=47, radius=5, coef=one, ge=one, gd=one, ws=one, ws_bytes=need):
-        return L.irn_aff_loss_backward(edge, dp, label, batch, hp, wp, radius, coef, ge, gd, ws, ws_bytes, None)
+        return L.irn_aff_loss_backward(edge, dp, label, batch, hp, wp, radius, 21, coef, ge, gd, ws, ws_bytes, None)
 
     for call, pointers in ((fwd, ("edge", "dp", "label", "sums", "counts", "ws")),
                            (bwd, ("edge", "dp", "label", "coef", "ge", "gd", "ws"))):

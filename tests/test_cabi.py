@@ -3,6 +3,9 @@ host-only entry points (path tables, argument validation) behave."""
 import ctypes as C
 import os
 import re
+import shutil
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -27,11 +30,29 @@ def test_every_declared_symbol_is_exported_and_bound():
 
 def test_version_and_error_string():
     assert _lib.lib.irn_version() >= 100
+    src = open(os.path.join(ROOT, "include", "irn_hip.h")).read()
+    assert _lib.lib.irn_version() == int(re.search(r"#define\s+IRN_ABI_VERSION\s+(\d+)", src).group(1)) == _lib.ABI_VERSION
     nd, nc = C.c_int(), C.c_int()
     assert _lib.lib.irn_path_count(1, C.byref(nd), C.byref(nc)) == 1          # IRN_ERR_ARG
     assert b"radius" in _lib.lib.irn_last_error()
     with pytest.raises(_lib.IrnHipError):
         _lib.check(_lib.lib.irn_path_count(99, C.byref(nd), C.byref(nc)))
+
+
+def test_a_library_of_another_abi_version_is_refused_at_import(tmp_path):
+    """`IRN_HIP_LIB` pointing at a library that reports another `irn_version()` (here: one that exports nothing else and
+    says 100) makes `import irn_amd._lib` fail with an ImportError that names the file, the value found and the value needed
+    — before any entry is bound to an argument list the library may not have."""
+    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
+    assert cc, "no host C compiler"
+    c_file, so = tmp_path / "stale.c", tmp_path / "libstale.so"
+    c_file.write_text("int irn_version(void) {\n    return 100;\n}\n")
+    subprocess.check_call([cc, "-shared", "-fPIC", "-o", str(so), str(c_file)])
+    child = subprocess.run([sys.executable, "-c", "import irn_amd._lib"], cwd=ROOT, env=dict(os.environ, IRN_HIP_LIB=str(so)),
+                           capture_output=True, text=True)
+    assert child.returncode != 0
+    assert "ImportError" in child.stderr and str(so) in child.stderr
+    assert "ABI version 100" in child.stderr and "need %d" % _lib.ABI_VERSION in child.stderr
 
 
 @pytest.mark.parametrize("r", [2, 3, 5, 7, 10])
@@ -119,3 +140,7 @@ def test_argument_validation_of_the_newer_entry_points():
     assert L.irn_pair_displacement(one, 1, 2, 4, 27, 5, one, None) == 1       # grid smaller than the radius
     assert b"too small" in L.irn_last_error()
     assert L.irn_pair_displacement_backward(one, 40000, 2, 20, 27, 5, one, None) == 1    # batch * channels > 65535
+    # per-sample overflow flags need their words: refused by irn_split16 itself, whichever form asks
+    assert L.irn_split16(one, None, None, 0, one, 128, 8, 64, None, None) == 1 and b"flags_dev" in L.irn_last_error()
+    assert L.irn_split16(one, None, None, 0, one, 100, 8, 64, one, None) == 1 and b"multiple of pixels_per_sample" in L.irn_last_error()
+    assert L.irn_split16_pad(one, None, None, 0, one, 2, 8, 8, 8, 0, 1, 1, None, None) == 1 and b"flags_dev" in L.irn_last_error()

@@ -230,17 +230,17 @@ def test_c_entries_reject_bad_arguments():
     """Argument checks run before anything touches the GPU: IRN_ERR_ARG on a machine without one too."""
     from irn_amd._lib import lib
     p = 16                                                  # any non-null pointer value: never dereferenced here
-    assert lib.irn_cam_confusion(p, p, 1, p, 4, 4, p, 0, p, p, None) == 1              # t < 1
-    assert lib.irn_cam_confusion(p, p, 1, p, 4, 4, p, 257, p, p, None) == 1            # t over the cap
-    assert lib.irn_cam_confusion(p, p, 21, p, 4, 4, p, 1, p, p, None) == 1             # k over 20
-    assert lib.irn_cam_confusion(None, None, 1, p, 4, 4, p, 1, p, p, None) == 1        # k > 0 without planes
-    assert lib.irn_cam_confusion(p, p, 1, p, 0, 4, p, 1, p, p, None) == 1              # empty image
-    assert lib.irn_cam_confusion(p, p, 1, p, 4, 4, p, 1, None, p, None) == 1           # no accumulator
-    assert lib.irn_cam_confusion_reduce(p, 0, p, None, None) == 1
-    assert lib.irn_cam_confusion_reduce(None, 1, p, None, None) == 1
-    assert lib.irn_label_confusion(p, p, 4, -1, 0, p, None, p, None) == 1
-    assert lib.irn_label_confusion(p, None, 4, 4, 0, p, None, p, None) == 1
-    assert lib.irn_label_confusion(p, p, 4, 4, 21, p, None, p, None) == 1
+    assert lib.irn_cam_confusion(p, p, 1, p, 4, 4, p, 0, 21, p, p, None) == 1              # t < 1
+    assert lib.irn_cam_confusion(p, p, 1, p, 4, 4, p, 257, 21, p, p, None) == 1            # t over the cap
+    assert lib.irn_cam_confusion(p, p, 21, p, 4, 4, p, 1, 21, p, p, None) == 1             # k over 20
+    assert lib.irn_cam_confusion(None, None, 1, p, 4, 4, p, 1, 21, p, p, None) == 1        # k > 0 without planes
+    assert lib.irn_cam_confusion(p, p, 1, p, 0, 4, p, 1, 21, p, p, None) == 1              # empty image
+    assert lib.irn_cam_confusion(p, p, 1, p, 4, 4, p, 1, 21, None, p, None) == 1           # no accumulator
+    assert lib.irn_cam_confusion_reduce(p, 0, 21, p, None, None) == 1
+    assert lib.irn_cam_confusion_reduce(None, 1, 21, p, None, None) == 1
+    assert lib.irn_label_confusion(p, p, 4, -1, 0, 21, p, None, p, None) == 1
+    assert lib.irn_label_confusion(p, None, 4, 4, 0, 21, p, None, p, None) == 1
+    assert lib.irn_label_confusion(p, p, 4, 4, 21, 21, p, None, p, None) == 1
     assert lib.irn_mask_overlap(p, -1, p, 1, 4, 4, p, p, p, p, None) == 1
     assert lib.irn_mask_overlap(p, 1, p, 256, 4, 4, p, p, p, p, None) == 1
     assert lib.irn_mask_overlap(None, 2, p, 1, 4, 4, p, p, p, p, None) == 1

@@ -62,7 +62,7 @@ def _entry(inputs, radius, coef, entry="irn_aff_loss_backward_ordered"):
     ws = torch.empty(need, dtype=torch.uint8, device=_dev())
     co = torch.as_tensor(np.asarray(coef, np.float32), device=_dev())
     ge, gd = torch.full_like(edge, float("nan")), torch.full_like(dp, float("nan"))
-    check(getattr(lib, entry)(edge.data_ptr(), dp.data_ptr(), label.data_ptr(), b, hp, wp, radius, co.data_ptr(),
+    check(getattr(lib, entry)(edge.data_ptr(), dp.data_ptr(), label.data_ptr(), b, hp, wp, radius, 21, co.data_ptr(),
                               ge.data_ptr(), gd.data_ptr(), ws.data_ptr(), C.c_size_t(need), _stream()))
     torch.cuda.synchronize()
     return ge, gd

@@ -200,7 +200,7 @@ def test_refusals_leave_the_accumulators_untouched():
     scratch = torch.zeros(64, dtype=torch.int32, device=_dev())
     rc = lib.irn_label_sweep_confusion(2, ptr_array([r.data_ptr()] * 2), i32_array([3, 21]), i32_array([24, 24]), i32_array([20, 20]),
                                        i32_array([size[0]] * 2), i32_array([size[1]] * 2), ptr_array([k.data_ptr()] * 2),
-                                       ptr_array([g.data_ptr()] * 2), thd.data_ptr(), 2, hist.data_ptr(), bad.data_ptr(),
+                                       ptr_array([g.data_ptr()] * 2), thd.data_ptr(), 2, 21, hist.data_ptr(), bad.data_ptr(),
                                        scratch.data_ptr(), _stream())
     torch.cuda.synchronize()
     assert rc == 1 and b"image 1" in lib.irn_last_error()

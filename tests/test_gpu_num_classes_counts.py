@@ -297,9 +297,11 @@ def test_label_sweep_confusion(nc, t):
 
 
 # ------------------------------------------------------------------------------------------------
-# nc = 21: the entries without a class count are the same calls
+# nc = 21: the C entries with 21 passed explicitly are the wrappers called without a class count
 # ------------------------------------------------------------------------------------------------
 def test_old_entries_equal_the_new_ones_at_21_classes():
+    """The raw C entries, called through `lib` with n_classes = 21 written out, give the bits of the `ops` wrappers called
+    without `n_classes`: pins the argument's position in `_lib._SIGS` and the wrappers' default."""
     from irn_amd import ops
     from irn_amd._lib import _stream, check, i32_array, lib, ptr_array
     nc, size = 21, SIZES[1]
@@ -315,20 +317,20 @@ def test_old_entries_equal_the_new_ones_at_21_classes():
     cam_d, keys_d = _t(cam), _t(keys_a)
     hist, bad = zeros(nc + 1, nc, 257), zeros(1)
     check(lib.irn_cam_confusion(cam_d.data_ptr(), keys_d.data_ptr(), nc - 1, gt.data_ptr(), h, w, th.data_ptr(), 256,
-                                hist.data_ptr(), bad.data_ptr(), _stream()))
-    n_hist, n_bad = ops.cam_confusion(cam_d, keys_d, gt, th, n_classes=nc)
+                                21, hist.data_ptr(), bad.data_ptr(), _stream()))
+    n_hist, n_bad = ops.cam_confusion(cam_d, keys_d, gt, th)
     assert torch.equal(hist, n_hist) and torch.equal(bad, n_bad) and int(hist.sum()) > 0
 
     conf, void = zeros(256, nc, nc), zeros(256, nc)
-    check(lib.irn_cam_confusion_reduce(hist.data_ptr(), 256, conf.data_ptr(), void.data_ptr(), _stream()))
-    n_conf, n_void = ops.cam_confusion_matrices(hist, n_classes=nc)
+    check(lib.irn_cam_confusion_reduce(hist.data_ptr(), 256, 21, conf.data_ptr(), void.data_ptr(), _stream()))
+    n_conf, n_void = ops.cam_confusion_matrices(hist)
     assert torch.equal(conf, n_conf) and torch.equal(void, n_void)
 
     pred = _t(_pred(size, nc, 2))
     conf, void, bad = zeros(nc, nc), zeros(nc), zeros(1)
-    check(lib.irn_label_confusion(pred.data_ptr(), gt.data_ptr(), h, w, 0, conf.data_ptr(), void.data_ptr(), bad.data_ptr(),
+    check(lib.irn_label_confusion(pred.data_ptr(), gt.data_ptr(), h, w, 0, 21, conf.data_ptr(), void.data_ptr(), bad.data_ptr(),
                                   _stream()))
-    n_conf, n_void, n_bad = ops.label_confusion(pred, gt, n_classes=nc)
+    n_conf, n_void, n_bad = ops.label_confusion(pred, gt)
     assert torch.equal(conf, n_conf) and torch.equal(void, n_void) and torch.equal(bad, n_bad)
 
     planes = _t(_planes(size, nc, 3))
@@ -336,8 +338,8 @@ def test_old_entries_equal_the_new_ones_at_21_classes():
     pi32 = C.POINTER(C.c_int32)
     hist, bad = zeros(16, 16, nc + 1, nc + 1), zeros(1)
     check(lib.irn_ir_label_confusion(planes.data_ptr(), 16, idx.ctypes.data_as(pi32), 16, idx.ctypes.data_as(pi32), 16,
-                                     gt.data_ptr(), h, w, hist.data_ptr(), bad.data_ptr(), _stream()))
-    n_hist, n_bad = ops.ir_label_confusion(planes, idx, idx, gt, n_classes=nc)
+                                     gt.data_ptr(), h, w, 21, hist.data_ptr(), bad.data_ptr(), _stream()))
+    n_hist, n_bad = ops.ir_label_confusion(planes, idx, idx, gt)
     assert torch.equal(hist, n_hist) and torch.equal(bad, n_bad) and int(bad) > 0
 
     rw, out, keys, sgt = _sweep_items(nc)[0]
@@ -347,8 +349,8 @@ def test_old_entries_equal_the_new_ones_at_21_classes():
     scratch = torch.empty(64, dtype=torch.int32, device=dev)
     check(lib.irn_label_sweep_confusion(1, ptr_array([rw_d.data_ptr()]), i32_array([nc - 1]), i32_array([24]), i32_array([20]),
                                         i32_array([out[0]]), i32_array([out[1]]), ptr_array([keys_d.data_ptr()]),
-                                        ptr_array([sgt_d.data_ptr()]), sth.data_ptr(), 16, hist.data_ptr(), bad.data_ptr(),
+                                        ptr_array([sgt_d.data_ptr()]), sth.data_ptr(), 16, 21, hist.data_ptr(), bad.data_ptr(),
                                         scratch.data_ptr(), _stream()))
-    n_hist, n_bad = ops.label_sweep_confusion([rw_d], [out], [keys_d], [sgt_d], sth, n_classes=nc)
+    n_hist, n_bad = ops.label_sweep_confusion([rw_d], [out], [keys_d], [sgt_d], sth)
     torch.cuda.synchronize()
     assert torch.equal(hist, n_hist) and torch.equal(bad, n_bad) and int(hist.sum()) > 0

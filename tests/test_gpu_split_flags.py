@@ -1,4 +1,4 @@
-"""The fp16-range flag of the split pass, attributed per sample (irn_split16_samples, irn_split16_pad_samples;
+"""The fp16-range flag of the split pass, attributed per sample (irn_split16 with pixels_per_sample, irn_split16_pad with per_sample;
 irn_amd/csrc/split16.hip, irn_amd/gemm.py `sample_flags`, net/resnet50.run_rows): bit 0 of flags[s] is set exactly when a value of
 sample s — the value that is split, after batch norm and ReLU — is beyond 65504 or NaN; the fp16 output is the bits of the call
 without per-sample flags and the process-wide flag stays clear.

@@ -80,18 +80,18 @@ def test_entry_point_and_op_fail_loudly_without_gpu():
     L = _lib.lib
     one = C.c_void_p(64)                                                        # never dereferenced on these paths
     ptrs, i1 = _lib.ptr_array([64]), _lib.i32_array([1])
-    assert L.irn_label_sweep_confusion(0, ptrs, i1, i1, i1, i1, i1, ptrs, ptrs, one, 1, one, one, one, None) == 1
+    assert L.irn_label_sweep_confusion(0, ptrs, i1, i1, i1, i1, i1, ptrs, ptrs, one, 1, 21, one, one, one, None) == 1
     assert b"irn_label_sweep_confusion" in L.irn_last_error()
-    assert L.irn_label_sweep_confusion(1, ptrs, i1, i1, i1, i1, i1, ptrs, ptrs, one, 0, one, one, one, None) == 1      # t < 1
-    assert L.irn_label_sweep_confusion(1, ptrs, i1, i1, i1, i1, i1, ptrs, ptrs, one, 257, one, one, one, None) == 1    # t over the cap
-    assert L.irn_label_sweep_confusion(1, ptrs, _lib.i32_array([21]), i1, i1, i1, i1, ptrs, ptrs, one, 1, one, one, one, None) == 1
-    assert L.irn_label_sweep_confusion(1, ptrs, i1, i1, i1, _lib.i32_array([5]), i1, ptrs, ptrs, one, 1, one, one, one, None) == 1
-    assert L.irn_label_sweep_confusion(1, ptrs, i1, i1, i1, i1, i1, None, ptrs, one, 1, one, one, one, None) == 1      # no keys
-    assert L.irn_label_sweep_confusion(1, ptrs, i1, i1, i1, i1, i1, ptrs, _lib.ptr_array([None]), one, 1, one, one, one, None) == 1
-    assert L.irn_label_sweep_confusion(1, ptrs, i1, i1, i1, i1, i1, ptrs, ptrs, one, 1, None, one, one, None) == 1     # no accumulator
+    assert L.irn_label_sweep_confusion(1, ptrs, i1, i1, i1, i1, i1, ptrs, ptrs, one, 0, 21, one, one, one, None) == 1      # t < 1
+    assert L.irn_label_sweep_confusion(1, ptrs, i1, i1, i1, i1, i1, ptrs, ptrs, one, 257, 21, one, one, one, None) == 1    # t over the cap
+    assert L.irn_label_sweep_confusion(1, ptrs, _lib.i32_array([21]), i1, i1, i1, i1, ptrs, ptrs, one, 1, 21, one, one, one, None) == 1
+    assert L.irn_label_sweep_confusion(1, ptrs, i1, i1, i1, _lib.i32_array([5]), i1, ptrs, ptrs, one, 1, 21, one, one, one, None) == 1
+    assert L.irn_label_sweep_confusion(1, ptrs, i1, i1, i1, i1, i1, None, ptrs, one, 1, 21, one, one, one, None) == 1      # no keys
+    assert L.irn_label_sweep_confusion(1, ptrs, i1, i1, i1, i1, i1, ptrs, _lib.ptr_array([None]), one, 1, 21, one, one, one, None) == 1
+    assert L.irn_label_sweep_confusion(1, ptrs, i1, i1, i1, i1, i1, ptrs, ptrs, one, 1, 21, None, one, one, None) == 1     # no accumulator
     with pytest.raises(ValueError, match="GPU tensor"):
         ops.label_sweep_confusion([torch.zeros(1, 2, 2)], [(8, 8)], [[3]], [torch.zeros(8, 8, dtype=torch.uint8)], [0.25])
     if not torch.cuda.is_available():
         # valid arguments: the call reaches the device and reports it, no crash
-        assert L.irn_label_sweep_confusion(1, ptrs, i1, i1, i1, i1, i1, ptrs, ptrs, one, 1, one, one, one, None) == 2
+        assert L.irn_label_sweep_confusion(1, ptrs, i1, i1, i1, i1, i1, ptrs, ptrs, one, 1, 21, one, one, one, None) == 2
         assert L.irn_last_error()

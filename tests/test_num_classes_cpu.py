@@ -210,27 +210,27 @@ def test_new_entries_refuse_bad_class_counts_without_a_gpu():
     i32 = (C.c_int32 * 1)(4)
     ptrs = (C.c_void_p * 1)(64)
     for nc in (1, 82, 0, -5):
-        assert L.irn_cam_confusion_nc(one, one, 1, one, 4, 4, one, 1, nc, one, one, None) == 1
+        assert L.irn_cam_confusion(one, one, 1, one, 4, 4, one, 1, nc, one, one, None) == 1
         assert b"irn_cam_confusion" in L.irn_last_error() and b"n_classes" in L.irn_last_error()
-        assert L.irn_cam_confusion_reduce_nc(one, 1, nc, one, one, None) == 1
+        assert L.irn_cam_confusion_reduce(one, 1, nc, one, one, None) == 1
         assert b"irn_cam_confusion_reduce" in L.irn_last_error() and b"n_classes" in L.irn_last_error()
-        assert L.irn_label_confusion_nc(one, one, 4, 4, 0, nc, one, one, one, None) == 1
+        assert L.irn_label_confusion(one, one, 4, 4, 0, nc, one, one, one, None) == 1
         assert b"irn_label_confusion" in L.irn_last_error() and b"n_classes" in L.irn_last_error()
-        assert L.irn_ir_label_confusion_nc(one, 1, idx, 1, idx, 1, one, 4, 4, nc, one, one, None) == 1
+        assert L.irn_ir_label_confusion(one, 1, idx, 1, idx, 1, one, 4, 4, nc, one, one, None) == 1
         assert b"irn_ir_label_confusion" in L.irn_last_error() and b"n_classes" in L.irn_last_error()
-        assert L.irn_label_sweep_confusion_nc(1, ptrs, i32, i32, i32, i32, i32, ptrs, ptrs, one, 1, nc, one, one, one, None) == 1
+        assert L.irn_label_sweep_confusion(1, ptrs, i32, i32, i32, i32, i32, ptrs, ptrs, one, 1, nc, one, one, one, None) == 1
         assert b"irn_label_sweep_confusion" in L.irn_last_error() and b"n_classes" in L.irn_last_error()
     # channel counts above nc - 1, and a 255 mapped to a class that does not exist
-    assert L.irn_cam_confusion_nc(one, one, 2, one, 4, 4, one, 1, 2, one, one, None) == 1 and b"k=2" in L.irn_last_error()
-    assert L.irn_cam_confusion_nc(one, one, 81, one, 4, 4, one, 1, 81, one, one, None) == 1
-    assert L.irn_label_confusion_nc(one, one, 4, 4, 2, 2, one, one, one, None) == 1
+    assert L.irn_cam_confusion(one, one, 2, one, 4, 4, one, 1, 2, one, one, None) == 1 and b"k=2" in L.irn_last_error()
+    assert L.irn_cam_confusion(one, one, 81, one, 4, 4, one, 1, 81, one, one, None) == 1
+    assert L.irn_label_confusion(one, one, 4, 4, 2, 2, one, one, one, None) == 1
     two = (C.c_int32 * 1)(2)
-    assert L.irn_label_sweep_confusion_nc(1, ptrs, two, i32, i32, i32, i32, ptrs, ptrs, one, 1, 2, one, one, one, None) == 1
+    assert L.irn_label_sweep_confusion(1, ptrs, two, i32, i32, i32, i32, ptrs, ptrs, one, 1, 2, one, one, one, None) == 1
     assert b"at most 1" in L.irn_last_error()
     # the loss: ignore_from is a byte value below 255's void
     for bad in (0, 256, -1):
-        assert L.irn_aff_loss_forward_ignore(one, one, one, 1, 12, 21, 5, bad, one, one, one, 1 << 20, None) == 1
+        assert L.irn_aff_loss_forward(one, one, one, 1, 12, 21, 5, bad, one, one, one, 1 << 20, None) == 1
         assert b"ignore_from" in L.irn_last_error()
-        assert L.irn_aff_loss_backward_ignore(one, one, one, 1, 12, 21, 5, bad, one, one, one, one, 1 << 20, None) == 1
-        assert L.irn_aff_loss_backward_ordered_ignore(one, one, one, 1, 12, 21, 5, bad, one, one, one, one, 1 << 20, None) == 1
+        assert L.irn_aff_loss_backward(one, one, one, 1, 12, 21, 5, bad, one, one, one, one, 1 << 20, None) == 1
+        assert L.irn_aff_loss_backward_ordered(one, one, one, 1, 12, 21, 5, bad, one, one, one, one, 1 << 20, None) == 1
         assert b"irn_aff_loss_backward_ordered" in L.irn_last_error()

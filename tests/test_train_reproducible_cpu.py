@@ -36,7 +36,7 @@ def test_ordered_backward_refuses_bad_arguments_before_any_device():
     need = L.irn_aff_loss_workspace_bytes(2, 33, 47, 5)
 
     def bwd(edge=one, dp=one, label=one, batch=2, hp=33, wp=47, radius=5, coef=one, ge=one, gd=one, ws=one, ws_bytes=need):
-        return L.irn_aff_loss_backward_ordered(edge, dp, label, batch, hp, wp, radius, coef, ge, gd, ws, ws_bytes, None)
+        return L.irn_aff_loss_backward_ordered(edge, dp, label, batch, hp, wp, radius, 21, coef, ge, gd, ws, ws_bytes, None)
 
     for name in ("edge", "dp", "label", "coef", "ge", "gd", "ws"):
         assert bwd(**{name: None}) == 1, name

@@ -63,7 +63,7 @@ def _confusion(t_count, fg, bg):
     from irn_amd import _lib
     f = (C.c_int32 * max(len(fg), 1))(*fg)
     b = (C.c_int32 * max(len(bg), 1))(*bg)
-    rc = _lib.lib.irn_ir_label_confusion(None, t_count, f, len(fg), b, len(bg), None, 4, 4, None, None, None)
+    rc = _lib.lib.irn_ir_label_confusion(None, t_count, f, len(fg), b, len(bg), None, 4, 4, 21, None, None, None)
     return rc, _lib.lib.irn_last_error().decode()
 
 

@@ -65,7 +65,7 @@ def main():
     ge, gd = torch.empty_like(e), torch.empty_like(d)
 
     def backward_entry(entry):
-        return lambda: check(entry(e.data_ptr(), d.data_ptr(), lab.data_ptr(), b, g, g, r, coef.data_ptr(), ge.data_ptr(),
+        return lambda: check(entry(e.data_ptr(), d.data_ptr(), lab.data_ptr(), b, g, g, r, 21, coef.data_ptr(), ge.data_ptr(),
                                    gd.data_ptr(), ws.data_ptr(), ws.numel(), _stream()))
 
     def composed():

@@ -43,7 +43,7 @@ extern "C" {
 /* The version of this header's argument lists.  irn_version() returns the IRN_ABI_VERSION the library was built with, and
  * it moves whenever an entry's arguments change: a binding that finds another value has loaded a library of another commit
  * (irn_amd/_lib.py refuses to import it). */
-#define IRN_ABI_VERSION 101
+#define IRN_ABI_VERSION 102
 int irn_version(void);
 const char *irn_last_error(void);
 
@@ -782,6 +782,46 @@ int irn_mask_rle_count(const uint8_t *masks_dev, int n, int h, int w, int32_t *n
                        int32_t *bbox_dev, void *scratch_dev, void *stream);
 int irn_mask_rle_emit(const uint8_t *masks_dev, int n, int h, int w, const int64_t *offsets_dev,
                       uint32_t *counts_dev, void *scratch_dev, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * COCO mask polygons  (replaces pycococreatortools.create_annotation_info(..., tolerance=0) behind
+ *                      step/make_cocoann.py:43-44: per mask a list of polygons)
+ * masks as above.  The polygons are the boundary of the mask along pixel edges, not skimage's
+ * contours: vertex (x, y), 0 <= x <= w, 0 <= y <= h, is the top-left corner of pixel (x, y) (the
+ * coordinates of bbox).  Every side of a mask pixel whose neighbour across it is not in the mask is a
+ * directed unit edge with the mask on its right (top +x, right +y, bottom -x, left -y); an edge's
+ * successor is, at its head vertex, the right turn if that edge exists, else straight on, else the
+ * left turn.  The cycles of that map are the loops: a loop with a positive shoelace sum is the outer
+ * boundary of one 4-connected component, one with a negative sum a hole.  Outer loops are emitted,
+ * holes are counted.  A loop is its corners (the vertices where the direction changes), starting at
+ * its smallest vertex in (y, x) order, which it leaves in +x; a mask's loops come in the (y, x)
+ * order of their start vertices, masks in order.  Three calls on one stream, the scratch untouched
+ * in between, the caller reading one small array after each of the first two:
+ *
+ * irn_mask_polygon_edges: edge_offsets dev int32 [n+1], the boundary edges before every mask
+ *   ([n] = all of them).  The caller reads it: n_edges = edge_offsets[n], max_mask_edges = the
+ *   largest difference (the number of pointer-jumping rounds follows from it).
+ * irn_mask_polygon_count: n_loops, n_holes, n_vertices dev int32 [n] (outer loops, holes, corners of
+ *   the outer loops of every mask), written, not added into.  Given a smaller n_edges or
+ *   max_mask_edges than the masks have, it writes wrong numbers and nothing outside its buffers.
+ * irn_mask_polygon_emit: loop_sizes dev int32 [loops_room] (corners per outer loop) and xy dev int32
+ *   [xy_room][2] (the corners).  An element beyond loops_room or xy_room is not written.
+ * scratch: irn_mask_polygon_scratch_bytes(n, h, w) bytes for _edges and _count;
+ *   irn_mask_polygon_trace_scratch_bytes(n_edges) bytes (53 per edge) for _count and _emit, NULL when
+ *   n_edges == 0.  0 = bad argument, or nothing to do.
+ * Nothing synchronises.  8 + 2 * R launches with R = ceil(log2(max_mask_edges)) made even; no
+ * kernel waits for another workgroup or follows a chain.  n == 0 is valid.  1 <= h, w,
+ * h*w < 2^31 - 1 and 2*n*(h+1)*(w+1) < 2^31.  Integers only, one writer per output word.
+ * ------------------------------------------------------------------------------------------- */
+size_t irn_mask_polygon_scratch_bytes(int n, int h, int w);
+size_t irn_mask_polygon_trace_scratch_bytes(int n_edges);
+int irn_mask_polygon_edges(const uint8_t *masks_dev, int n, int h, int w, int32_t *edge_offsets_dev,
+                           void *scratch_dev, void *stream);
+int irn_mask_polygon_count(const uint8_t *masks_dev, int n, int h, int w, const int32_t *edge_offsets_dev,
+                           int n_edges, int max_mask_edges, int32_t *n_loops_dev, int32_t *n_holes_dev,
+                           int32_t *n_vertices_dev, void *scratch_dev, void *trace_scratch_dev, void *stream);
+int irn_mask_polygon_emit(int n_edges, int32_t *loop_sizes_dev, int64_t loops_room, int32_t *xy_dev,
+                          int64_t xy_room, void *trace_scratch_dev, void *stream);
 
 #ifdef __cplusplus
 }

@@ -24,7 +24,7 @@ lib = C.CDLL(LIB_PATH)
 
 # The bindings below are by name only, so a library built from another commit would be called with argument lists it
 # does not have.  IRN_ABI_VERSION of include/irn_hip.h moves with every such change; this is the value _SIGS is written for.
-ABI_VERSION = 101
+ABI_VERSION = 102
 lib.irn_version.restype, lib.irn_version.argtypes = C.c_int, []
 if lib.irn_version() != ABI_VERSION:
     raise ImportError("irn_amd: %s reports ABI version %d, these bindings need %d — it was built from another commit; "
@@ -118,6 +118,11 @@ _SIGS = {
     "irn_mask_rle_scratch_bytes": (sz, [i32, i32, i32]),
     "irn_mask_rle_count": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "irn_mask_rle_emit": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
+    "irn_mask_polygon_scratch_bytes": (sz, [i32, i32, i32]),
+    "irn_mask_polygon_trace_scratch_bytes": (sz, [i32]),
+    "irn_mask_polygon_edges": (i32, [vp, i32, i32, i32, vp, vp, vp]),
+    "irn_mask_polygon_count": (i32, [vp, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "irn_mask_polygon_emit": (i32, [i32, vp, i64, vp, i64, vp, vp]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -1,7 +1,8 @@
 """Host side of irn_amd/csrc/cocomask.hip: COCO mask encoding (step/make_cocoann.py) over include/irn_hip.h's
-irn_mask_rle_count / _emit.  The run lengths come from the GPU; pycocotools' string form of them (rleToString /
-rleFrString) is a few thousand counts per image and is made on the host, vectorised over the counts of a mask.
-`irn_amd.ops` re-exports the functions."""
+irn_mask_rle_count / _emit and irn_mask_polygon_edges / _count / _emit.  The run lengths come from the GPU; pycocotools'
+string form of them (rleToString / rleFrString) is a few thousand counts per image and is made on the host, vectorised
+over the counts of a mask.  The polygons (the mask's boundary along pixel edges) are traced on the GPU; `polygon_fill` is
+their inverse on the host.  `irn_amd.ops` re-exports the functions."""
 import numpy as np
 import torch
 
@@ -98,3 +99,87 @@ def rle_decode(counts, h, w):
         raise ValueError("rle_decode: the counts sum to %d, the mask has %d pixels" % (int(c.sum()), h * w))
     bits = np.repeat(np.arange(c.size) & 1, c).astype(bool)
     return np.ascontiguousarray(bits.reshape(w, h).T)
+
+
+def mask_polygons(masks):
+    """The boundary of masks bool / uint8 [N,H,W] on the GPU (nonzero = in the mask) along pixel edges, as closed integer
+    loops (include/irn_hip.h "COCO mask polygons"): vertex (x, y) is the top-left corner of pixel (x, y), the mask lies on
+    the right of every edge, and where two mask pixels touch only diagonally the loops keep them apart (4-connectivity).
+
+    Returns numpy arrays on the host: xy int32 [V,2], the corners of every outer loop (no vertex repeated at the end, each
+    loop from its smallest vertex in (y, x) order, leaving it in +x); loop_offsets int64 [L+1] (loop k is
+    xy[loop_offsets[k]:loop_offsets[k+1]]); mask_loops int64 [N+1] (mask i owns loops mask_loops[i]:mask_loops[i+1], in the
+    (y, x) order of their start vertices); holes int64 [N], the hole loops of every mask: counted, not emitted, since COCO
+    readers take the union of a segmentation's polygons.  Three synchronisations: the edge counts, the loop and corner
+    counts, the corners."""
+    _need_cuda(masks, "masks")
+    if not (masks.dim() == 3 and masks.dtype in (torch.uint8, torch.bool)):
+        raise ValueError("mask_polygons: masks must be a bool / uint8 [N,H,W] tensor, got %s %s" % (masks.dtype, tuple(masks.shape)))
+    dev = masks.device
+    m = (masks.view(torch.uint8) if masks.dtype == torch.bool else masks).contiguous()
+    n, h, w = (int(v) for v in m.shape)
+    empty = (np.zeros((0, 2), np.int32), np.zeros(1, np.int64), np.zeros(n + 1, np.int64), np.zeros(n, np.int64))
+    if n == 0:
+        return empty
+    nbytes = lib.irn_mask_polygon_scratch_bytes(n, h, w)
+    if nbytes == 0:
+        check(1)
+    scratch = cached("poly_scratch", dev, nbytes, torch.uint8)
+    # one device block for both small transfers: edge_offsets int32 [n+1] | n_loops | n_holes | n_vertices int32 [n] each
+    head = cached("poly_head", dev, 4 * n + 1, torch.int32)
+    host = cached("poly_head", "pinned", 4 * n + 1, torch.int32)
+    p_off = head.data_ptr()
+    p_loops, p_holes, p_verts = (p_off + 4 * (n + 1) + 4 * n * k for k in range(3))
+    with torch.cuda.device(dev):
+        check(lib.irn_mask_polygon_edges(m.data_ptr(), n, h, w, p_off, scratch.data_ptr(), _stream()))
+        read_back(head[:n + 1], host, side=False).synchronize()                # host round trip 1
+        edge_offsets = host[:n + 1].numpy().astype(np.int64)
+        n_edges, longest = int(edge_offsets[n]), int(np.diff(edge_offsets).max())
+        if n_edges == 0:
+            return empty
+        trace = cached("poly_trace", dev, lib.irn_mask_polygon_trace_scratch_bytes(n_edges), torch.uint8)
+        check(lib.irn_mask_polygon_count(m.data_ptr(), n, h, w, p_off, n_edges, longest, p_loops, p_holes, p_verts,
+                                         scratch.data_ptr(), trace.data_ptr(), _stream()))
+        read_back(head[n + 1:4 * n + 1], host, side=False).synchronize()       # host round trip 2
+        counts = host[:3 * n].numpy().astype(np.int64).reshape(3, n)
+        mask_loops = np.zeros(n + 1, np.int64)
+        np.cumsum(counts[0], out=mask_loops[1:])
+        holes = counts[1].copy()
+        n_loops, n_verts = int(mask_loops[n]), int(counts[2].sum())
+        out_dev = cached("poly_out", dev, n_loops + 2 * n_verts, torch.int32)
+        check(lib.irn_mask_polygon_emit(n_edges, out_dev.data_ptr(), n_loops, out_dev.data_ptr() + 4 * n_loops, n_verts,
+                                        trace.data_ptr(), _stream()))
+        out = torch.empty(n_loops + 2 * n_verts, dtype=torch.int32, pin_memory=True)   # the call's own, as in mask_rle
+        read_back(out_dev[:n_loops + 2 * n_verts], out, side=False).synchronize()      # host round trip 3
+    raw = out.numpy()
+    loop_offsets = np.zeros(n_loops + 1, np.int64)
+    np.cumsum(raw[:n_loops], out=loop_offsets[1:])
+    return raw[n_loops:].reshape(n_verts, 2), loop_offsets, mask_loops, holes
+
+
+def polygon_fill(xy, loop_offsets, h, w):
+    """The inverse of `mask_polygons` for one mask: bool [h,w], the union of the loops' fills.  Pixel (x, y) is inside a
+    loop iff an odd number of the loop's vertical edges at columns <= x span row y (its centre is sampled).  The union of a
+    mask's outer loops is the mask with its holes filled."""
+    xy = np.asarray(xy).astype(np.int64).reshape(-1, 2)
+    off = np.asarray(loop_offsets).astype(np.int64).reshape(-1)
+    if off.size < 1 or off[0] != 0 or (np.diff(off) < 0).any() or off[-1] != len(xy):
+        raise ValueError("polygon_fill: loop_offsets do not partition the %d vertices" % len(xy))
+    if len(xy) and (xy.min() < 0 or xy[:, 0].max() > w or xy[:, 1].max() > h):
+        raise ValueError("polygon_fill: a vertex outside the %dx%d (height x width) image" % (h, w))
+    out = np.zeros((h, w), bool)
+    for a, b in zip(off[:-1], off[1:]):
+        if b - a < 3:
+            continue
+        x, y = xy[a:b, 0], xy[a:b, 1]
+        x0, y0 = int(x.min()), int(y.min())
+        nx, ny = np.roll(x, -1), np.roll(y, -1)
+        ver = (x == nx) & (y != ny)                        # a vertical edge toggles, at its column, the rows it spans
+        rows, cols = int(y.max()) - y0, int(x.max()) - x0
+        ends = np.zeros((rows + 1, cols + 1), np.int64)
+        np.add.at(ends, (y[ver] - y0, x[ver] - x0), 1)
+        np.add.at(ends, (ny[ver] - y0, x[ver] - x0), 1)
+        toggles = np.cumsum(ends, axis=0) & 1              # parity along y: the rows between an edge's two ends
+        inside = (np.cumsum(toggles, axis=1) & 1).astype(bool)
+        out[y0:y0 + rows, x0:x0 + cols] |= inside[:rows, :cols]
+    return out

@@ -11,7 +11,7 @@ as `ops.X`, looked up at call time.
     crf.py          crf.hip        crf_filter, crf_inference_label, crf_ir_label, crf_label_sweep
     eval_counts.py  eval.hip       eval_thresholds, cam_confusion, cam_confusion_matrices, label_confusion, mask_overlap,
                                    ir_label_confusion
-    cocomask.py     cocomask.hip   mask_rle, rle_to_string, rle_from_string, rle_decode
+    cocomask.py     cocomask.hip   mask_rle, rle_to_string, rle_from_string, rle_decode, mask_polygons, polygon_fill
     gemm.py         conv1x1.cpp, split16.hip    the hipBLASLt convolutions of the trunk
     _host.py        what more than one of them needs: cached buffers, read_back, packed layouts and their staging
 
@@ -40,7 +40,7 @@ from ._lib import check, i32_array, lib, ptr_array
 from .augment import (AUGMENT_DESC_WORDS, AUGMENT_LABEL_DESC_WORDS, AugmentTables, LabelTables, augment_batch, augment_label_tables,
                       augment_pair_batch, augment_tables, nearest_plan)
 from .bn_act import bn_act, bn_act_, bn_act_backward, bn_fold, bn_param_grads, stem_pool, upsample_bilinear
-from .cocomask import mask_rle, rle_decode, rle_from_string, rle_to_string
+from .cocomask import mask_polygons, mask_rle, polygon_fill, rle_decode, rle_from_string, rle_to_string
 from .crf import CRF_GT_PROB, CRF_MAX_SWEEP, CRF_T, crf_filter, crf_inference_label, crf_ir_label, crf_label_sweep
 from .eval_counts import (EVAL_CLASSES, EVAL_MAX_CLASSES, EVAL_MAX_THRES, cam_confusion, cam_confusion_matrices, eval_thresholds, ir_label_confusion,
                           label_confusion, mask_overlap)

@@ -4,7 +4,8 @@ Reads  args.infer_list (image names, in list order), args.voc12_root/JPEGImages/
        args.ins_seg_out_dir/<name>.npy ({'score', 'mask', 'class'} of make_ins_seg_labels), or — when that file does not
        exist — <name>.rle.npz (its --ins_seg_format rle: the masks as run lengths, with area and bbox)
 Writes args.cocoann_out: {"images", "annotations", "categories", "type": "instances"}, what a Mask R-CNN trainer reads.
-Prints and returns {"images", "annotations", "skipped_low_score", "without_detections"}.
+Prints and returns {"images", "annotations", "skipped_low_score", "without_detections"}; with --cocoann_segmentation
+polygon also {"masks_with_holes", "holes"}.
 
 Per image the kept masks go to the device once and come back as run lengths, areas and boxes (`ops.mask_rle`,
 irn_amd/csrc/cocomask.hip); COCO's string form of the run lengths is made on the host.  A detection with score < 1e-5 is
@@ -18,9 +19,20 @@ license, coco_url and flickr_url; they are left out so that the same inputs alwa
 
 Three deliberate differences from the reference:
 
-1. RLE instead of polygons.  The reference asks pycococreatortools for polygons (tolerance 0, skimage find_contours).
-   Compressed RLE is exact where polygons are not, and every COCO reader accepts it in "segmentation" (annToRLE passes a
-   dict with a str "counts" through).  Polygons are out of scope.
+1. RLE by default, polygons on request.  The reference asks pycococreatortools for polygons (tolerance 0, skimage
+   find_contours).  Compressed RLE is exact and is what --cocoann_segmentation rle (the default) writes.  With
+   --cocoann_segmentation polygon "segmentation" is a list of polygons [[x0, y0, x1, y1, ...], ...] for the readers that
+   take nothing else (the Mask R-CNN code the IRN paper trained with).  They are defined exactly: the boundary of the
+   mask along pixel edges, vertex (x, y) = the top-left corner of pixel (x, y) (the coordinates of "bbox"), the mask on the
+   right of every edge, right turn before straight on before left turn, so that the loops follow the 4-connectivity of
+   make_ins_seg_labels' components; one polygon per outer loop, its corners only, from its smallest vertex in (y, x)
+   order, loops in the (y, x) order of those vertices (`ops.mask_polygons`, traced on the GPU).  Filling the loops gives
+   the mask back bit for bit, which is what the tests hold the kernels to.  They are not skimage's contours, because those
+   run through the midpoints of pixel edges in an order only skimage defines: nothing could be compared with them here.
+   Holes are counted ("masks_with_holes", "holes"), not written: a COCO reader takes the union of a segmentation's
+   polygons, so a hole loop could cut nothing out, and the polygons of a mask with holes describe it with the holes
+   filled, as the reference's do once a reader unions them.  "area" and "bbox" stay the true mask's.  An .rle.npz
+   record is decoded on the host and traced by the same kernels, so both input formats give the same bytes.
 2. Annotation ids are unique over the file (1, 2, 3, ... in output order).  The reference restarts at 1 for every image
    (:36), and COCO readers index annotations by id.
 3. Categories are generated (the 20 VOC classes, id 1..20 in class order, supercategory "none"; with --num_classes C the
@@ -48,10 +60,18 @@ def categories(names=CATEGORIES):
     return [{"supercategory": "none", "id": i + 1, "name": name} for i, name in enumerate(names)]
 
 
-def annotation(ann_id, img_id, cls, area, bbox, height, width, counts):
+def annotation(ann_id, img_id, cls, area, bbox, height, width, counts, polygons=None):
+    """`polygons`: the mask's outer loops as [[x0, y0, x1, y1, ...], ...] to write instead of the run lengths."""
+    seg = {"size": [height, width], "counts": ops.rle_to_string(counts)} if polygons is None else polygons
     return {"id": ann_id, "image_id": img_id, "category_id": int(cls) + 1, "iscrowd": 0, "area": int(area),
-            "bbox": [float(v) for v in bbox], "segmentation": {"size": [height, width], "counts": ops.rle_to_string(counts)},
-            "width": width, "height": height}
+            "bbox": [float(v) for v in bbox], "segmentation": seg, "width": width, "height": height}
+
+
+def polygon_lists(xy, loop_offsets, mask_loops):
+    """`ops.mask_polygons`' arrays as per mask a list of [x0, y0, x1, y1, ...] lists of Python ints."""
+    flat = np.asarray(xy).reshape(-1).tolist()
+    off = [2 * int(v) for v in loop_offsets]
+    return [[flat[off[k]:off[k + 1]] for k in range(int(a), int(b))] for a, b in zip(mask_loops[:-1], mask_loops[1:])]
 
 
 def rle_record_kept(rec, height, width, name=None, n_classes=len(CATEGORIES)):
@@ -86,10 +106,15 @@ def rle_record_kept(rec, height, width, name=None, n_classes=len(CATEGORIES)):
             "area": area[keep], "bbox": bbox[keep], "low": n - len(keep), "n": n}
 
 
-def annotations(kept, img_id, height, width, first_id):
+def annotations(kept, img_id, height, width, first_id, polygons=None):
     """The annotation dicts of one image from per-detection class, area, bbox and run lengths (counts / offsets) — from the
-    device's encoder for dense masks, from `rle_record_kept` for a stored record."""
+    device's encoder for dense masks, from `rle_record_kept` for a stored record.  `polygons`: (xy, loop_offsets,
+    mask_loops) of `ops.mask_polygons` for the same detections, written as the segmentations instead of the run lengths."""
     cls, counts, offsets = kept["class"], kept["counts"], kept["offsets"]
+    if polygons is not None:
+        lists = polygon_lists(*polygons)
+        return [annotation(first_id + i, img_id, cls[i], kept["area"][i], kept["bbox"][i], height, width, None, lists[i])
+                for i in range(len(cls))]
     return [annotation(first_id + i, img_id, cls[i], kept["area"][i], kept["bbox"][i], height, width,
                        counts[offsets[i]:offsets[i + 1]]) for i in range(len(cls))]
 
@@ -106,6 +131,7 @@ def run(args):
     dev = _eval.device()
     class_names = _classes.class_names(args)          # refusals (a missing file, a wrong line count) before any image is read
     c = len(class_names)
+    polygon = getattr(args, "cocoann_segmentation", "rle") == "polygon"
 
     def load(name):
         with Image.open(dataloader.get_img_path(name, args.voc12_root)) as im:
@@ -117,9 +143,14 @@ def run(args):
         if not found and os.path.exists(rle_path):
             with np.load(rle_path, allow_pickle=False) as z:
                 kept = rle_record_kept(z, height, width, n_classes=c)               # (the loader names the image of an error)
-            return {"rle": np.int64(1), "class": kept["class"], "counts": kept["counts"], "offsets": kept["offsets"],
-                    "area": kept["area"], "bbox": kept["bbox"], "size": np.int64([height, width]),
-                    "low": np.int64(kept["low"]), "found": np.int64(kept["n"] > 0)}
+            rec = {"rle": np.int64(1), "class": kept["class"], "counts": kept["counts"], "offsets": kept["offsets"],
+                   "area": kept["area"], "bbox": kept["bbox"], "size": np.int64([height, width]),
+                   "low": np.int64(kept["low"]), "found": np.int64(kept["n"] > 0)}
+            if polygon:                   # the tracer takes dense masks: decoded here, in the loader thread
+                off = kept["offsets"]
+                rec["mask"] = np.stack([ops.rle_decode(kept["counts"][off[i]:off[i + 1]], height, width)
+                                        for i in range(len(kept["class"]))]) if len(kept["class"]) else np.zeros((0, height, width), bool)
+            return rec
         if found:
             det = np.load(path, allow_pickle=True).item()
             cls, score = np.asarray(det["class"]).reshape(-1).astype(np.int64), np.asarray(det["score"]).reshape(-1)
@@ -141,6 +172,8 @@ def run(args):
 
     out = {"images": [], "annotations": [], "categories": categories(class_names), "type": "instances"}
     stats = {"images": 0, "annotations": 0, "skipped_low_score": 0, "without_detections": 0}
+    if polygon:
+        stats.update(masks_with_holes=0, holes=0)
     with torch.cuda.device(dev):
         for name, it in _eval.items(names, load, args):
             img_id = int(name[:4] + name[5:])
@@ -152,12 +185,19 @@ def run(args):
                 stats["without_detections"] += 1
             if len(cls) == 0:
                 continue
+            masks = it["mask"].to(dev, non_blocking=True) if polygon or not int(it["rle"]) else None
             if int(it["rle"]):          # an .rle.npz record holds what the encoder would compute: no upload, no kernel
                 kept = {k: it[k].numpy() for k in ("class", "counts", "offsets", "area", "bbox")}
             else:
-                counts, offsets, area, bbox = ops.mask_rle(it["mask"].to(dev, non_blocking=True))
+                counts, offsets, area, bbox = ops.mask_rle(masks)
                 kept = {"class": cls, "counts": counts, "offsets": offsets, "area": area, "bbox": bbox}
-            out["annotations"] += annotations(kept, img_id, height, width, len(out["annotations"]) + 1)
+            polygons = None
+            if polygon:
+                xy, loop_offsets, mask_loops, holes = ops.mask_polygons(masks)
+                polygons = (xy, loop_offsets, mask_loops)
+                stats["masks_with_holes"] += int((holes > 0).sum())
+                stats["holes"] += int(holes.sum())
+            out["annotations"] += annotations(kept, img_id, height, width, len(out["annotations"]) + 1, polygons)
     stats["images"], stats["annotations"] = len(out["images"]), len(out["annotations"])
     with open(args.cocoann_out, "w") as f:
         json.dump(out, f)

@@ -139,6 +139,10 @@ def build_parser():
                         "eval_ins_seg read either")
     p.add_argument("--cocoann_out", default="voc2012_train_custom.json", type=str,
                    help="make_cocoann: the COCO annotation file it writes (the reference hard-codes this name, step/make_cocoann.py:48)")
+    p.add_argument("--cocoann_segmentation", default="rle", choices=("rle", "polygon"),
+                   help="make_cocoann: rle = every mask as COCO's compressed run lengths; polygon = as the polygons of its "
+                        "outer boundary along pixel edges, integer corners, traced on the GPU (the reference writes skimage "
+                        "contours; irn_amd/step/make_cocoann.py says how these differ)")
     p.add_argument("--edge_out_dir", default=None, type=str,
                    help="verification aid (not in the reference): also write every image's boundary / displacement maps "
                         "(<name>.npy = {'edge' [1,h,w], 'dp' [2,h,w]}) as the label steps used them")

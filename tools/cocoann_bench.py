@@ -7,6 +7,14 @@ The detections are blob masks, not the output of make_ins_seg_labels: irn_amd/sy
 (thresholded `synth.cam_blobs`, upsampled from the stride-4 grid as the label step upsamples its walk), scores in (0, 1).
 
     python tools/cocoann_bench.py [--images 64] [--cpu-images 16]
+
+With --segmentation polygon it measures the polygon mode instead: the step's images/s in both modes, three
+runs of each, alternating; the three polygon entries alone between HIP events on masks that are already on the device, with
+the sizes a first call read back (median of 20 passes over the images); the bytes read back and the JSON bytes per image; and
+the plain-loop restatement (tests/_polygon_ref.py) on the host over --cpu-images of the images.  The result line is also
+appended to profiles/cocoann_polygon_bench.json.
+
+    python tools/cocoann_bench.py --segmentation polygon
 """
 import argparse
 import contextlib
@@ -56,9 +64,9 @@ def make_tree(root, n):
     return names, dense, n_masks
 
 
-def _args(root, out):
+def _args(root, out, segmentation="rle"):
     return argparse.Namespace(voc12_root=root, infer_list=os.path.join(root, "list.txt"), ins_seg_out_dir=os.path.join(root, "ins"),
-                              cocoann_out=out, num_workers=8)
+                              cocoann_out=out, num_workers=8, cocoann_segmentation=segmentation)
 
 
 def kernel_ms(fn):
@@ -111,11 +119,107 @@ def kernels_alone(names, root, reps=20):
     return ms / len(work) * 1e3, moved / (ms * 1e-3) / 1e9
 
 
+def polygon_kernels_alone(names, root, reps=20):
+    """The three polygon entries on every image's masks, resident on the device, with the edge, loop and corner counts of
+    a first `ops.mask_polygons` call: HIP-event time per image (no read-back inside), launches per image, bytes the step
+    reads back per image."""
+    from irn_amd import _lib, ops
+    L, dev = _lib.lib, torch.device("cuda", 0)
+    work, launches, back = [], 0, 0
+    for name in names:
+        det = np.load(os.path.join(root, "ins", name + ".npy"), allow_pickle=True).item()
+        m = torch.from_numpy(det["mask"]).to(dev).view(torch.uint8).contiguous()
+        n, h, w = m.shape
+        xy, loop_offsets, _, _ = ops.mask_polygons(m)
+        scratch = torch.empty(L.irn_mask_polygon_scratch_bytes(n, h, w), dtype=torch.uint8, device=dev)
+        head = torch.empty(4 * n + 1, dtype=torch.int32, device=dev)
+        _lib.check(L.irn_mask_polygon_edges(m.data_ptr(), n, h, w, head.data_ptr(), scratch.data_ptr(), _lib._stream()))
+        off = head[:n + 1].cpu().numpy().astype(np.int64)
+        n_edges, longest = int(off[n]), int(np.diff(off).max())
+        trace = torch.empty(max(L.irn_mask_polygon_trace_scratch_bytes(n_edges), 1), dtype=torch.uint8, device=dev)
+        n_loops, n_verts = len(loop_offsets) - 1, len(xy)
+        out = torch.empty(max(n_loops + 2 * n_verts, 1), dtype=torch.int32, device=dev)
+        work.append((m, n, h, w, head, scratch, trace, n_edges, longest, out, n_loops, n_verts))
+        rounds = int(np.ceil(np.log2(max(longest, 1))))
+        launches += 8 + 2 * (rounds + rounds % 2)
+        back += 4 * (n + 1) + 12 * n + 4 * (n_loops + 2 * n_verts)
+
+    def once():
+        for m, n, h, w, head, scratch, trace, n_edges, longest, out, n_loops, n_verts in work:
+            p = head.data_ptr()
+            _lib.check(L.irn_mask_polygon_edges(m.data_ptr(), n, h, w, p, scratch.data_ptr(), _lib._stream()))
+            _lib.check(L.irn_mask_polygon_count(m.data_ptr(), n, h, w, p, n_edges, longest, p + 4 * (n + 1), p + 4 * (2 * n + 1),
+                                                p + 4 * (3 * n + 1), scratch.data_ptr(), trace.data_ptr(), _lib._stream()))
+            _lib.check(L.irn_mask_polygon_emit(n_edges, out.data_ptr(), n_loops, out.data_ptr() + 4 * n_loops, n_verts,
+                                               trace.data_ptr(), _lib._stream()))
+    once()
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        once()
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    return float(np.median(times)) / len(work) * 1e3, launches / len(work), back / len(work)
+
+
+def polygon_main(a):
+    import _polygon_ref as P
+    from irn_amd.step import make_cocoann
+    torch.cuda.set_device(0)
+    res = {"metric": "make_cocoann polygon mode", "images": a.images, "device": torch.cuda.get_device_name(0)}
+    with tempfile.TemporaryDirectory() as root:
+        names, dense, n_masks = make_tree(root, a.images)
+        outs = {mode: os.path.join(root, mode + ".json") for mode in ("rle", "polygon")}
+
+        def go(mode):
+            with contextlib.redirect_stdout(io.StringIO()):
+                return make_cocoann.run(_args(root, outs[mode], mode))
+        stats = {mode: go(mode) for mode in outs}                  # warm: kernels loaded, page cache filled
+        rates = {mode: [] for mode in outs}
+        for _ in range(3):
+            for mode in outs:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                go(mode)
+                torch.cuda.synchronize()
+                rates[mode].append(round(a.images / (time.perf_counter() - t0), 1))
+        res["masks_per_image"] = round(n_masks / a.images, 2)
+        res["step_images_per_s"] = rates
+        res["masks_with_holes"], res["holes"] = stats["polygon"]["masks_with_holes"], stats["polygon"]["holes"]
+        coco = json.load(open(outs["polygon"]))
+        res["corners_per_image"] = round(sum(len(loop) // 2 for x in coco["annotations"] for loop in x["segmentation"]) / a.images, 1)
+        res["json_bytes_per_image"] = {mode: round(os.path.getsize(outs[mode]) / a.images, 1) for mode in outs}
+        res["dense_mask_bytes_per_image"] = round(dense / a.images, 1)
+        us, launches, back = polygon_kernels_alone(names, root)
+        res["kernels_alone_us_per_image"] = round(us, 2)
+        res["launches_per_image"] = round(launches, 1)
+        res["bytes_back_per_image"] = round(back, 1)
+        if a.cpu_images > 0:
+            sub = names[:a.cpu_images]
+            masks = [np.load(os.path.join(root, "ins", name + ".npy"), allow_pickle=True).item()["mask"] for name in sub]
+            t0 = time.perf_counter()
+            for m in masks:
+                P.mask_polygons(m)
+            res["restatement_images_per_s"] = round(len(sub) / (time.perf_counter() - t0), 3)
+            res["cpu_images"] = len(sub)
+    line = json.dumps(res)
+    os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+    with open(os.path.join(ROOT, "profiles", "cocoann_polygon_bench.json"), "a") as f:
+        f.write(line + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=64)
     ap.add_argument("--cpu-images", type=int, default=16)
+    ap.add_argument("--segmentation", choices=("rle", "polygon"), default="rle")
     a = ap.parse_args()
+    if a.segmentation == "polygon":
+        return polygon_main(a)
     import _cocomask_ref as R
     from irn_amd.step import make_cocoann
     torch.cuda.set_device(0)

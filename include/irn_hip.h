@@ -43,7 +43,7 @@ extern "C" {
 /* The version of this header's argument lists.  irn_version() returns the IRN_ABI_VERSION the library was built with, and
  * it moves whenever an entry's arguments change: a binding that finds another value has loaded a library of another commit
  * (irn_amd/_lib.py refuses to import it). */
-#define IRN_ABI_VERSION 102
+#define IRN_ABI_VERSION 103
 int irn_version(void);
 const char *irn_last_error(void);
 
@@ -726,6 +726,39 @@ int irn_mask_overlap(const uint8_t *masks_dev, int n, const uint8_t *inst_dev, i
 int irn_ir_label_confusion(const uint8_t *planes_dev, int t_count, const int32_t *fg_idx, int f, const int32_t *bg_idx,
                            int b, const uint8_t *gt_dev, int h, int w, int n_classes, int64_t *hist_dev, int64_t *bad_dev,
                            void *stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Boundary counts  (Boundary IoU, Cheng et al., CVPR 2021, and its detection form Boundary AP.  The
+ *                   reference has no such code: these replace the per-class / per-instance cv2.erode
+ *                   loop of the published measure; the definition is DESIGN.md "Boundary IoU")
+ * band(L, d) of a uint8 map L[h][w]: 1 at (y, x) iff the square window |dy| <= d, |dx| <= d around it
+ * leaves the image or holds a byte other than L[y][x]; for every value c that is (L == c) minus its
+ * erosion by a 3x3 kernel, d times, behind a one-pixel zero border.  All 256 bytes are labels, 254 and
+ * 255 included.  1 <= d <= IRN_BAND_MAX_D; the caller computes d per image
+ * (max(1, round(ratio * sqrt(h*h + w*w)))).  Integers only; counts are int64 that every call ADDS into,
+ * `bad` and n_classes (nc) are those of the evaluation counts above.  Null pointers, d or nc outside
+ * their ranges and non-positive sizes give IRN_ERR_ARG before any device work; nothing synchronises.
+ *
+ * irn_label_band: band dev uint8 [h][w] = band(map, d), written as 0 / 1.
+ * irn_label_boundary_counts: pred, gt dev uint8 [h][w]; pred 255 reads as pred_255_as first (as for
+ *   irn_label_confusion).  With P = band(pred, d), G = band(gt, d) (GT 255, void, is a label there) and
+ *   valid = gt != 255, counts dev int64 [nc][3] receives per class c
+ *     [c][0] #{valid & P & G & pred == c & gt == c}   [c][1] #{valid & P & pred == c}   [c][2] #{G & gt == c}
+ *   A pixel whose pred (after the mapping) is above nc-1 or whose gt is nc..254 goes to bad and into no count.
+ * irn_mask_boundary_overlap: masks dev uint8 [n][h][w] (nonzero = in the mask, each banded on its own as a
+ *   two-valued map, the band kept where the mask is set), inst dev uint8 [h][w] (0 = none, 1..g), as for
+ *   irn_mask_overlap.  inst_band dev uint8 [h][w] is caller-owned scratch the call fills with band(inst, d).
+ *   inter_b dev int64 [n][g] (pixels in mask i's band and in instance j+1's band), band_pred dev int64 [n],
+ *   band_gt dev int64 [g]; instance ids above g are counted in bad, once per pixel.  Sizes of 0 as for
+ *   irn_mask_overlap.
+ * ------------------------------------------------------------------------------------------- */
+#define IRN_BAND_MAX_D 64
+int irn_label_band(const uint8_t *map_dev, int h, int w, int d, uint8_t *band_dev, void *stream);
+int irn_label_boundary_counts(const uint8_t *pred_dev, const uint8_t *gt_dev, int h, int w, int d, int pred_255_as,
+                              int n_classes, int64_t *counts_dev, int64_t *bad_dev, void *stream);
+int irn_mask_boundary_overlap(const uint8_t *masks_dev, int n, const uint8_t *inst_dev, uint8_t *inst_band_dev, int g, int h,
+                              int w, int d, int64_t *inter_b_dev, int64_t *band_pred_dev, int64_t *band_gt_dev,
+                              int64_t *bad_dev, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Label threshold sweep  (step/make_sem_seg_labels.py:43-49 + step/eval_sem_seg.py:10-17 at T values

@@ -24,7 +24,7 @@ lib = C.CDLL(LIB_PATH)
 
 # The bindings below are by name only, so a library built from another commit would be called with argument lists it
 # does not have.  IRN_ABI_VERSION of include/irn_hip.h moves with every such change; this is the value _SIGS is written for.
-ABI_VERSION = 102
+ABI_VERSION = 103
 lib.irn_version.restype, lib.irn_version.argtypes = C.c_int, []
 if lib.irn_version() != ABI_VERSION:
     raise ImportError("irn_amd: %s reports ABI version %d, these bindings need %d — it was built from another commit; "
@@ -114,6 +114,9 @@ _SIGS = {
     "irn_cam_confusion": (i32, [vp, vp, i32, vp, i32, i32, vp, i32, i32, vp, vp, vp]),
     "irn_cam_confusion_reduce": (i32, [vp, i32, i32, vp, vp, vp]),
     "irn_label_confusion": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "irn_label_band": (i32, [vp, i32, i32, i32, vp, vp]),
+    "irn_label_boundary_counts": (i32, [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
+    "irn_mask_boundary_overlap": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]),
     "irn_label_sweep_confusion": (i32, [i32, ppv, pi32, pi32, pi32, pi32, pi32, ppv, ppv, vp, i32, i32, vp, vp, vp, vp]),
     "irn_mask_rle_scratch_bytes": (sz, [i32, i32, i32]),
     "irn_mask_rle_count": (i32, [vp, i32, i32, i32, vp, vp, vp, vp, vp]),

@@ -1,6 +1,7 @@
 // Evaluation counts on the GPU (include/irn_hip.h "Evaluation counts"): the confusion matrices behind
 // step/eval_cam.py and step/eval_sem_seg.py, the mask_iou counts behind step/eval_ins_seg.py, and the confusion matrices
-// of a whole fg x bg threshold grid of IR labels (step/tune_ir_label.py; not in the reference).
+// of a whole fg x bg threshold grid of IR labels (step/tune_ir_label.py; not in the reference), and the boundary bands and
+// band counts of Boundary IoU / Boundary AP (--boundary_iou_ratio of the two label evaluation steps; not in the reference).
 //
 // Every kernel privatises its counters in LDS (one uint32 per bin, at most 4096 pixels per block, so a bin cannot
 // overflow) and flushes the non-zero bins once per block with 64-bit integer atomics into the caller's int64
@@ -303,7 +304,240 @@ __global__ void __launch_bounds__(TPB) k_ir_label_hist(const uint8_t *__restrict
     if (tid == 0 && nbad && i0 == 0) add64(bad, nbad);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Boundary bands (Boundary IoU; not in the reference, DESIGN.md "Boundary IoU"): band(L, d)[y][x] = 1 iff the square
+// window |dy| <= d, |dx| <= d around (y, x) leaves the image or holds a byte other than L[y][x].  All 256 bytes are labels.
+//
+// A block owns a tile of BT_H x BT_W pixels and stages it with a halo of d cells in LDS (cells outside the image are told
+// by their coordinates, never by a value).  The window is separable: a row pass marks every cell of the tile's columns
+// (halo rows included) whose 2d+1 row segment is uniform and inside the image, a column pass marks the pixels whose 2d+1
+// marked cells above and below carry the pixel's value.  Both are run-length scans, one thread per row (then per column),
+// once in each direction: a cell's segment is uniform iff the run of equal cells that ends at it is longer than d from
+// both sides.  That is 2 reads per staged cell and pass whatever d is, at the price of few busy threads (BT_H + 2d of 256
+// in the row pass, BT_W in the column pass); the counting around it is what the rest of the block is for.
+// LDS of a launch, sized by its d: the haloed tile (pitch x (BT_H+2d) bytes), the row flags (68 x (BT_H+2d)) and the
+// tile's result (BT_H x BT_W): 10.8 KB at d = 12 (375x500 at ratio 0.02), 43.3 KB at the largest d, 64, where a block
+// stages 160 x 192 cells for its 32 x 64 pixels (15x the pixels; 2.4x at d = 12).  A 64 x 64 tile would stage 9x there but
+// take 53.5 KB and halve the blocks of an image.
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr int BT_W = 64, BT_H = 32;             // pixels of a tile
+constexpr int BPT = BT_W * BT_H / TPB;          // pixels per thread: column tid % BT_W, rows tid / BT_W + (TPB / BT_W) * i
+constexpr int BT_RSTEP = TPB / BT_W;
+constexpr int FLAG_PITCH = BT_W + 4;            // 17 words: the row pass writes one column from many rows
+static_assert(BPT * TPB == BT_W * BT_H && BT_RSTEP * BT_W == TPB && BPT <= 32, "a thread's pixels, and one bit for each");
+
+// bytes between two rows of the haloed tile: a multiple of 4 with an odd word count (threads of the row pass read one
+// column of many rows)
+__host__ __device__ constexpr int band_pitch(int d) {
+    const int p = (BT_W + 2 * d + 3) & ~3;
+    return (p / 4) % 2 == 0 ? p + 4 : p;
+}
+__host__ __device__ constexpr size_t band_lds_bytes(int d) {
+    return (size_t)(band_pitch(d) + FLAG_PITCH) * (BT_H + 2 * d) + BT_W * BT_H;
+}
+static_assert(band_lds_bytes(IRN_BAND_MAX_D) + 256 * 4 + 64 <= 65536, "the haloed tile of the largest d and the counters fit a workgroup");
+
+// how a kernel reads the bytes it bands
+struct AsLabel {
+    __device__ int operator()(uint8_t v) const { return v; }
+};
+struct Map255 {                                   // a prediction: 255 reads as `as` when that is >= 0
+    int as;
+    __device__ int operator()(uint8_t v) const { return v == 255 && as >= 0 ? as : (int)v; }
+};
+struct AsMask {                                   // a mask: two values
+    __device__ int operator()(uint8_t v) const { return v != 0; }
+};
+
+struct BandTile {
+    const uint8_t *tile;      // haloed values: pixel (ty, tx) of the tile at tile[(ty + d) * pitch + tx + d]
+    const uint8_t *inner;     // [BT_H][BT_W]: 1 = the whole window equals the pixel (not band)
+    int pitch, d;
+    __device__ int value(int ty, int tx) const { return tile[(ty + d) * pitch + tx + d]; }
+    __device__ bool band(int ty, int tx) const { return !inner[ty * BT_W + tx]; }
+};
+
+// length of the run of equal in-image values that ends at a cell; v < 0 = outside the image (or, in the column pass, a
+// cell whose row segment is not uniform)
+__device__ __forceinline__ int run_step(int run, int prev, int v) { return v < 0 ? 0 : (v == prev ? run + 1 : 1); }
+
+// Bands the tile at (x0, y0) of map[h][w], read through `read`, in `lds` (band_lds_bytes(d) bytes).  Every thread of the
+// block calls it; it starts and ends with a barrier, so a second call may follow once the first result is in registers.
+template <class Read>
+__device__ BandTile band_tile(const uint8_t *__restrict__ map, Read read, int h, int w, int d, int x0, int y0, uint8_t *lds) {
+    const int tid = threadIdx.x;
+    const int pitch = band_pitch(d), rows = BT_H + 2 * d, cols = BT_W + 2 * d;
+    uint8_t *tile = lds, *flag = lds + (size_t)pitch * rows, *inner = flag + (size_t)FLAG_PITCH * rows;
+    __syncthreads();
+    for (int r = tid / BT_W; r < rows; r += BT_RSTEP) {
+        const int y = y0 - d + r;
+        const bool row_in = y >= 0 && y < h;
+        for (int c = tid % BT_W; c < cols; c += BT_W) {
+            const int x = x0 - d + c;
+            tile[r * pitch + c] = row_in && x >= 0 && x < w ? (uint8_t)read(map[(size_t)y * w + x]) : 0;
+        }
+    }
+    __syncthreads();
+    for (int r = tid; r < rows; r += TPB) {
+        const int y = y0 - d + r;
+        const bool row_in = y >= 0 && y < h;
+        const uint8_t *t = tile + r * pitch;
+        uint8_t *f = flag + r * FLAG_PITCH;
+        int run = 0, prev = -1;
+        for (int c = 0; c < d + BT_W; ++c) {
+            const int x = x0 - d + c;
+            const int v = row_in && x >= 0 && x < w ? (int)t[c] : -1;
+            run = run_step(run, prev, v);
+            prev = v;
+            if (c >= d) f[c - d] = run > d;
+        }
+        run = 0, prev = -1;
+        for (int c = cols - 1; c >= d; --c) {
+            const int x = x0 - d + c;
+            const int v = row_in && x >= 0 && x < w ? (int)t[c] : -1;
+            run = run_step(run, prev, v);
+            prev = v;
+            if (c < d + BT_W) f[c - d] = f[c - d] && run > d;
+        }
+    }
+    __syncthreads();
+    for (int x = tid; x < BT_W; x += TPB) {
+        int run = 0, prev = -1;
+        for (int r = 0; r < d + BT_H; ++r) {
+            const int v = flag[r * FLAG_PITCH + x] ? (int)tile[r * pitch + x + d] : -1;
+            run = run_step(run, prev, v);
+            prev = v;
+            if (r >= d) inner[(r - d) * BT_W + x] = run > d;
+        }
+        run = 0, prev = -1;
+        for (int r = rows - 1; r >= d; --r) {
+            const int v = flag[r * FLAG_PITCH + x] ? (int)tile[r * pitch + x + d] : -1;
+            run = run_step(run, prev, v);
+            prev = v;
+            if (r < d + BT_H) inner[(r - d) * BT_W + x] = inner[(r - d) * BT_W + x] && run > d;
+        }
+    }
+    __syncthreads();
+    return {tile, inner, pitch, d};
+}
+
+__global__ void __launch_bounds__(TPB) k_label_band(const uint8_t *__restrict__ map, int h, int w, int d, int tiles_x,
+                                                    uint8_t *__restrict__ out) {
+    extern __shared__ uint32_t band_lds[];        // band_lds_bytes(d) bytes, here and in the two kernels below
+    const int x0 = (blockIdx.x % tiles_x) * BT_W, y0 = (blockIdx.x / tiles_x) * BT_H;
+    const BandTile b = band_tile(map, AsLabel{}, h, w, d, x0, y0, reinterpret_cast<uint8_t *>(band_lds));
+    const int tx = threadIdx.x % BT_W, x = x0 + tx;
+#pragma unroll
+    for (int i = 0; i < BPT; ++i) {
+        const int ty = threadIdx.x / BT_W + BT_RSTEP * i, y = y0 + ty;
+        if (y < h && x < w) out[(size_t)y * w + x] = b.band(ty, tx);
+    }
+}
+
+// Semantic boundary counts: the prediction's band first (values and band bits into registers), then the GT's in the same
+// LDS; bins [NC][3] = (both bands and the same class, prediction band, GT band).
+__global__ void __launch_bounds__(TPB) k_label_boundary(const uint8_t *__restrict__ pred, const uint8_t *__restrict__ gt, int h,
+                                                        int w, int d, int map255, int NC, int tiles_x,
+                                                        int64_t *__restrict__ counts, int64_t *__restrict__ bad) {
+    extern __shared__ uint32_t band_lds[];
+    __shared__ uint32_t bins[3 * IRN_EVAL_MAX_CLASSES];
+    __shared__ uint32_t nbad;
+    const int tid = threadIdx.x;
+    for (int b = tid; b < 3 * NC; b += TPB) bins[b] = 0;
+    if (tid == 0) nbad = 0;
+    uint8_t *lds = reinterpret_cast<uint8_t *>(band_lds);
+    const int x0 = (blockIdx.x % tiles_x) * BT_W, y0 = (blockIdx.x / tiles_x) * BT_H;
+    const int tx = tid % BT_W, x = x0 + tx;
+    uint8_t pv[BPT];
+    uint32_t pband = 0;
+    {
+        const BandTile p = band_tile(pred, Map255{map255}, h, w, d, x0, y0, lds);
+#pragma unroll
+        for (int i = 0; i < BPT; ++i) {
+            const int ty = tid / BT_W + BT_RSTEP * i;
+            pv[i] = (uint8_t)p.value(ty, tx);
+            pband |= (p.band(ty, tx) ? 1u : 0u) << i;
+        }
+    }
+    const BandTile g = band_tile(gt, AsLabel{}, h, w, d, x0, y0, lds);
+    uint32_t local_bad = 0;
+#pragma unroll
+    for (int i = 0; i < BPT; ++i) {
+        const int ty = tid / BT_W + BT_RSTEP * i;
+        if (y0 + ty >= h || x >= w) continue;
+        const int row = gt_row((uint8_t)g.value(ty, tx), NC), q = pv[i];
+        if (row < 0 || q >= NC) {
+            ++local_bad;
+            continue;
+        }
+        if (row == NC) continue;              // void: a label when the GT band was formed, counted nowhere
+        const bool pb = (pband >> i) & 1u, gb = g.band(ty, tx);
+        if (gb) atomicAdd(&bins[row * 3 + 2], 1u);
+        if (pb) atomicAdd(&bins[q * 3 + 1], 1u);
+        if (pb && gb && q == row) atomicAdd(&bins[row * 3], 1u);
+    }
+    if (local_bad) atomicAdd(&nbad, local_bad);
+    __syncthreads();
+    for (int b = tid; b < 3 * NC; b += TPB)
+        if (bins[b]) add64(counts + b, bins[b]);
+    if (tid == 0 && nbad) add64(bad, nbad);
+}
+
+// Instance boundary counts: block (x, y) counts the tile x by instance id, within the band of mask y that lies in the
+// instances' band (y < n_masks) or over the instances' band alone (y == n_masks: the GT band sizes, and the range check of
+// the instance map over every pixel, done once).  inst_band = band(inst, d), written by k_label_band before this launch.
+__global__ void __launch_bounds__(TPB) k_mask_boundary(const uint8_t *__restrict__ masks, int n_masks,
+                                                       const uint8_t *__restrict__ inst, const uint8_t *__restrict__ inst_band,
+                                                       int g, int h, int w, int d, int tiles_x, int64_t *__restrict__ inter_b,
+                                                       int64_t *__restrict__ band_pred, int64_t *__restrict__ band_gt,
+                                                       int64_t *__restrict__ bad) {
+    extern __shared__ uint32_t band_lds[];
+    __shared__ uint32_t cnt[256];
+    __shared__ uint32_t total;
+    const int tid = threadIdx.x;
+    const int m = blockIdx.y;
+    cnt[tid] = 0;
+    if (tid == 0) total = 0;
+    const int x0 = (blockIdx.x % tiles_x) * BT_W, y0 = (blockIdx.x / tiles_x) * BT_H;
+    const int tx = tid % BT_W, x = x0 + tx;
+    const bool is_mask = m < n_masks;
+    BandTile b{};
+    if (is_mask) b = band_tile(masks + (size_t)m * h * w, AsMask{}, h, w, d, x0, y0, reinterpret_cast<uint8_t *>(band_lds));
+    else __syncthreads();
+    uint32_t mine = 0;
+#pragma unroll
+    for (int i = 0; i < BPT; ++i) {
+        const int ty = tid / BT_W + BT_RSTEP * i, y = y0 + ty;
+        if (y >= h || x >= w) continue;
+        const size_t p = (size_t)y * w + x;
+        if (is_mask) {
+            if (!b.value(ty, tx) || !b.band(ty, tx)) continue;
+            ++mine;
+            const uint8_t id = inst[p];
+            if (id && inst_band[p]) atomicAdd(&cnt[id], 1u);
+        } else {
+            const uint8_t id = inst[p];
+            if (id && (id > g || inst_band[p])) atomicAdd(&cnt[id], 1u);
+        }
+    }
+    if (mine) atomicAdd(&total, mine);
+    __syncthreads();
+    const uint32_t v = cnt[tid];
+    if (tid >= 1 && v) {
+        if (tid > g) {
+            if (!is_mask) add64(bad, v);              // counted once, by the whole-image row
+        } else if (is_mask) {
+            add64(inter_b + (size_t)m * g + (tid - 1), v);
+        } else {
+            add64(band_gt + (tid - 1), v);
+        }
+    }
+    if (tid == 0 && is_mask && total) add64(band_pred + m, total);
+}
+
 bool pixels_ok(int h, int w) { return h >= 1 && w >= 1 && (int64_t)h * w <= (int64_t)0x7fffffff - PIX; }
+bool band_d_ok(int d) { return d >= 1 && d <= IRN_BAND_MAX_D; }
+int band_tiles(int h, int w) { return cdiv(w, BT_W) * cdiv(h, BT_H); }      // below h*w/2048 + h/32 + w/64 + 1: an int where pixels_ok holds
 
 }  // namespace
 
@@ -398,5 +632,45 @@ extern "C" int irn_mask_overlap(const uint8_t *masks_dev, int n, const uint8_t *
     hipLaunchKernelGGL(k_mask_overlap, dim3(cdiv(px, PIX), n + 1), dim3(TPB), 0, (hipStream_t)stream, masks_dev, n,
                        inst_dev, g, px, inter_dev, area_pred_dev, area_gt_dev, bad_dev);
     IRN_LAUNCH_CHECK("k_mask_overlap");
+    return IRN_OK;
+}
+
+// Boundary bands and the counts behind Boundary IoU / Boundary AP (include/irn_hip.h "Boundary counts").
+extern "C" int irn_label_band(const uint8_t *map_dev, int h, int w, int d, uint8_t *band_dev, void *stream) {
+    if (!band_d_ok(d)) return fail(IRN_ERR_ARG, "irn_label_band: d %d outside 1..%d", d, IRN_BAND_MAX_D);
+    if (!map_dev || !band_dev || !pixels_ok(h, w)) return fail(IRN_ERR_ARG, "irn_label_band: bad argument (h=%d, w=%d)", h, w);
+    hipLaunchKernelGGL(k_label_band, dim3(band_tiles(h, w)), dim3(TPB), band_lds_bytes(d), (hipStream_t)stream, map_dev, h, w, d,
+                       cdiv(w, BT_W), band_dev);
+    IRN_LAUNCH_CHECK("k_label_band");
+    return IRN_OK;
+}
+
+extern "C" int irn_label_boundary_counts(const uint8_t *pred_dev, const uint8_t *gt_dev, int h, int w, int d, int pred_255_as,
+                                         int n_classes, int64_t *counts_dev, int64_t *bad_dev, void *stream) {
+    if (!classes_ok(n_classes))
+        return fail(IRN_ERR_ARG, "irn_label_boundary_counts: n_classes %d outside 2..%d", n_classes, IRN_EVAL_MAX_CLASSES);
+    if (!band_d_ok(d)) return fail(IRN_ERR_ARG, "irn_label_boundary_counts: d %d outside 1..%d", d, IRN_BAND_MAX_D);
+    if (!pred_dev || !gt_dev || !counts_dev || !bad_dev || pred_255_as >= n_classes || !pixels_ok(h, w))
+        return fail(IRN_ERR_ARG, "irn_label_boundary_counts: bad argument (h=%d, w=%d, pred_255_as=%d)", h, w, pred_255_as);
+    hipLaunchKernelGGL(k_label_boundary, dim3(band_tiles(h, w)), dim3(TPB), band_lds_bytes(d), (hipStream_t)stream, pred_dev,
+                       gt_dev, h, w, d, pred_255_as, n_classes, cdiv(w, BT_W), counts_dev, bad_dev);
+    IRN_LAUNCH_CHECK("k_label_boundary");
+    return IRN_OK;
+}
+
+extern "C" int irn_mask_boundary_overlap(const uint8_t *masks_dev, int n, const uint8_t *inst_dev, uint8_t *inst_band_dev, int g,
+                                         int h, int w, int d, int64_t *inter_b_dev, int64_t *band_pred_dev,
+                                         int64_t *band_gt_dev, int64_t *bad_dev, void *stream) {
+    if (!band_d_ok(d)) return fail(IRN_ERR_ARG, "irn_mask_boundary_overlap: d %d outside 1..%d", d, IRN_BAND_MAX_D);
+    if (!inst_dev || !inst_band_dev || !bad_dev || n < 0 || n > 65534 || g < 0 || g > 255 ||
+        (n > 0 && (!masks_dev || !band_pred_dev)) || (g > 0 && !band_gt_dev) || (n > 0 && g > 0 && !inter_b_dev) || !pixels_ok(h, w))
+        return fail(IRN_ERR_ARG, "irn_mask_boundary_overlap: bad argument (n=%d, g=%d, h=%d, w=%d)", n, g, h, w);
+    const int tiles = band_tiles(h, w), tiles_x = cdiv(w, BT_W);
+    hipLaunchKernelGGL(k_label_band, dim3(tiles), dim3(TPB), band_lds_bytes(d), (hipStream_t)stream, inst_dev, h, w, d, tiles_x,
+                       inst_band_dev);
+    IRN_LAUNCH_CHECK("k_label_band");
+    hipLaunchKernelGGL(k_mask_boundary, dim3(tiles, n + 1), dim3(TPB), band_lds_bytes(d), (hipStream_t)stream, masks_dev, n,
+                       inst_dev, inst_band_dev, g, h, w, d, tiles_x, inter_b_dev, band_pred_dev, band_gt_dev, bad_dev);
+    IRN_LAUNCH_CHECK("k_mask_boundary");
     return IRN_OK;
 }

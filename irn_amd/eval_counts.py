@@ -1,6 +1,7 @@
 """Host side of irn_amd/csrc/eval.hip: the integer counts behind the evaluation steps (step/eval_cam.py,
 step/eval_sem_seg.py, step/eval_ins_seg.py of the reference): irn_cam_confusion, irn_label_confusion, irn_mask_overlap,
-and the grid count of step/tune_ir_label.py, irn_ir_label_confusion.
+the grid count of step/tune_ir_label.py, irn_ir_label_confusion, and the boundary bands and band counts of Boundary IoU /
+Boundary AP (irn_label_band, irn_label_boundary_counts, irn_mask_boundary_overlap; not in the reference).
 Accumulators are int64 GPU tensors that every call adds into; `bad` (int64 [1]) counts values outside the documented
 ranges and the caller raises when it is non-zero.  `irn_amd.ops` re-exports the functions."""
 import ctypes as C
@@ -161,3 +162,88 @@ def ir_label_confusion(planes, fg_idx, bg_idx, gt, hist=None, bad=None, n_classe
         check(lib.irn_ir_label_confusion(pl.data_ptr(), t, fg.ctypes.data_as(pi32), int(fg.size), bg.ctypes.data_as(pi32),
                                          int(bg.size), g.data_ptr(), h, w, nc, hist.data_ptr(), bad.data_ptr(), _stream()))
     return hist, bad
+
+
+BAND_MAX_D = 64                       # IRN_BAND_MAX_D
+
+
+def boundary_distance(h, w, ratio):
+    """The band width of Boundary IoU for an h x w image: max(1, round(ratio * diagonal)), in Python doubles with Python's
+    round (ties to even), as the published code computes it; 375x500 at 0.02 -> 12."""
+    return max(1, int(round(float(ratio) * (int(h) * int(h) + int(w) * int(w)) ** 0.5)))
+
+
+def _band_d(d, who):
+    if int(d) != d or not 1 <= int(d) <= BAND_MAX_D:
+        raise ValueError("%s: d %s outside 1..%d" % (who, d, BAND_MAX_D))
+    return int(d)
+
+
+def label_band(label_map, d):
+    """band(label_map, d) of DESIGN.md "Boundary IoU": label_map uint8 [H,W] on the GPU -> uint8 [H,W], 1 where the square
+    window of half-width d around the pixel leaves the image or holds another byte.  Every byte value is a label."""
+    _need_cuda(label_map, "label_map")
+    dev = label_map.device
+    m = u8_map(label_map, dev, "label_map")
+    d = _band_d(d, "label_band")
+    h, w = m.shape
+    out = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.irn_label_band(m.data_ptr(), h, w, d, out.data_ptr(), _stream()))
+    return out
+
+
+def label_boundary_counts(pred, gt, d, counts=None, bad=None, pred_255_as=0, n_classes=EVAL_CLASSES):
+    """The Boundary IoU counts of one image: pred, gt uint8 [H,W] GPU tensors as for `label_confusion`, d from
+    `boundary_distance`.  Adds into counts int64 [nc,3] — per class the pixels in both bands with pred == gt == c, those of
+    the prediction's band with pred == c and those of the GT's band with gt == c (void GT pixels are labels when the band is
+    formed and are counted nowhere) — and bad int64 [1]; returns (counts, bad)."""
+    nc = eval_classes(n_classes, "label_boundary_counts")
+    _need_cuda(pred, "pred")
+    dev = pred.device
+    p = u8_map(pred, dev, "pred")
+    g = u8_map(gt, dev, "gt")
+    if p.shape != g.shape:
+        raise ValueError("label_boundary_counts: prediction %s for a GT of %s" % (tuple(p.shape), tuple(g.shape)))
+    d = _band_d(d, "label_boundary_counts")
+    counts = accumulator(counts, (nc, 3), dev, "counts")
+    bad = accumulator(bad, (1,), dev, "bad")
+    h, w = g.shape
+    with torch.cuda.device(dev):
+        check(lib.irn_label_boundary_counts(p.data_ptr(), g.data_ptr(), h, w, d, -1 if pred_255_as is None else int(pred_255_as),
+                                            nc, counts.data_ptr(), bad.data_ptr(), _stream()))
+    return counts, bad
+
+
+def mask_boundary_overlap(masks, inst_map, n_inst, d, bad=None, inst_band=None):
+    """The Boundary AP counts of one image, arguments as for `mask_overlap`: every mask's band (the mask as a two-valued
+    map, kept where it is set) against the instances' bands (band(inst_map, d) where inst_map is not 0).  Returns (inter_b
+    int64 [N,G], band_pred int64 [N], band_gt int64 [G]) on the GPU; ids above n_inst are counted in bad int64 [1].
+    inst_band: a flat uint8 GPU tensor of at least H*W elements to use as scratch (one of its own otherwise); the call
+    leaves band(inst_map, d) in its head."""
+    _need_cuda(inst_map, "inst_map")
+    dev = inst_map.device
+    inst = u8_map(inst_map, dev, "inst_map")
+    h, w = inst.shape
+    if not (isinstance(masks, torch.Tensor) and masks.dim() == 3 and masks.dtype in (torch.uint8, torch.bool)):
+        raise ValueError("mask_boundary_overlap: masks must be a bool / uint8 [N,H,W] tensor")
+    m = masks.to(dev)
+    m = (m.view(torch.uint8) if m.dtype == torch.bool else m).contiguous()
+    n, g = int(m.shape[0]), int(n_inst)
+    if tuple(m.shape[1:]) != (h, w):
+        raise ValueError("mask_boundary_overlap: masks %s for an instance map of %dx%d" % (tuple(m.shape), h, w))
+    d = _band_d(d, "mask_boundary_overlap")
+    if inst_band is None:
+        inst_band = torch.empty(h * w, dtype=torch.uint8, device=dev)
+    elif not (isinstance(inst_band, torch.Tensor) and inst_band.is_cuda and inst_band.device == dev and inst_band.dtype == torch.uint8
+              and inst_band.dim() == 1 and inst_band.is_contiguous() and inst_band.numel() >= h * w):
+        raise ValueError("mask_boundary_overlap: inst_band must be a flat contiguous uint8 GPU tensor of at least %d elements on %s" % (h * w, dev))
+    bad = accumulator(bad, (1,), dev, "bad")
+    inter_b = _i64_zeros((n, g), dev)
+    band_pred = _i64_zeros((n,), dev)
+    band_gt = _i64_zeros((g,), dev)
+    with torch.cuda.device(dev):
+        check(lib.irn_mask_boundary_overlap(m.data_ptr() if n else None, n, inst.data_ptr(), inst_band.data_ptr(), g, h, w, d,
+                                            inter_b.data_ptr() if n and g else None, band_pred.data_ptr() if n else None,
+                                            band_gt.data_ptr() if g else None, bad.data_ptr(), _stream()))
+    return inter_b, band_pred, band_gt

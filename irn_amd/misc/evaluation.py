@@ -6,7 +6,9 @@ cam_confusion / label_confusion / mask_overlap).
     sem_seg_scores(conf, void)        step/eval_sem_seg.py:19-31 (fp / fn / iou of the [:nc, :nc] matrix; the reference has nc = 21)
     ir_label_scores(hist)             step/tune_ir_label.py: accuracy, coverage and all-pixel iou of one IR-label grid point
     instance_ap_voc(records)          eval_instance_segmentation_voc(iou_thresh=0.5): calc_instance_segmentation_voc_prec_rec
-                                      + calc_detection_voc_ap(use_07_metric=False), from per-image overlap counts
+                                      + calc_detection_voc_ap(use_07_metric=False), from per-image overlap counts; with
+                                      boundary=True matched on min(mask IoU, boundary IoU): Boundary AP (not in the reference)
+    boundary_iou_scores(counts)       Boundary IoU per class from the band counts of ops.label_boundary_counts (not in the reference)
 
 Everything here is numpy in the order of operations chainercv uses, so the floats equal what it computes from the masks.
 """
@@ -84,12 +86,25 @@ def mask_iou_from_counts(inter, area_a, area_b):
     return iou
 
 
-def instance_ap_voc(records, iou_thresh=0.5):
+def boundary_iou_scores(counts):
+    """Boundary IoU (Cheng et al., CVPR 2021) from counts int64 [nc,3] of ops.label_boundary_counts summed over a split
+    (per class: both bands and the same class, prediction band, GT band) -> {'biou': float64 [nc], 'mbiou'}:
+    biou = inter / (pband + gband - inter), nan for a class with no band pixel in either map; mbiou = nanmean."""
+    counts = np.asarray(counts, np.int64)
+    inter, pband, gband = counts[:, 0], counts[:, 1], counts[:, 2]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        biou = inter / (pband + gband - inter)
+    return {"biou": biou, "mbiou": nanmean(biou)}
+
+
+def instance_ap_voc(records, iou_thresh=0.5, boundary=False):
     """eval_instance_segmentation_voc(..., iou_thresh, use_07_metric=False) from counts -> {'ap': float64 [n_fg], 'map'}.
 
     records: one dict per image, in the split's order (the argsort tie order depends on it), with
       'pred_class' int [N], 'pred_score' [N] (as the detection file holds it), 'gt_class' int [G],
-      'inter' int [N,G], 'area_pred' int [N], 'area_gt' int [G]  (ops.mask_overlap)."""
+      'inter' int [N,G], 'area_pred' int [N], 'area_gt' int [G]  (ops.mask_overlap).
+    boundary: Boundary AP — a detection is matched on np.minimum(mask IoU, boundary IoU), the second from the records'
+      'inter_b' int [N,G], 'band_pred' int [N], 'band_gt' int [G]  (ops.mask_boundary_overlap); nothing else changes."""
     n_pos = defaultdict(int)
     score = defaultdict(list)
     match = defaultdict(list)
@@ -100,6 +115,10 @@ def instance_ap_voc(records, iou_thresh=0.5):
         inter = np.asarray(rec["inter"], np.int64).reshape(len(pred_label), len(gt_label))
         area_pred = np.asarray(rec["area_pred"], np.int64)
         area_gt = np.asarray(rec["area_gt"], np.int64)
+        if boundary:
+            inter_b = np.asarray(rec["inter_b"], np.int64).reshape(len(pred_label), len(gt_label))
+            band_pred = np.asarray(rec["band_pred"], np.int64)
+            band_gt = np.asarray(rec["band_gt"], np.int64)
         for l in np.unique(np.concatenate((pred_label, gt_label)).astype(int)):
             keep = np.flatnonzero(pred_label == l)
             ps = pred_score[keep]
@@ -114,6 +133,8 @@ def instance_ap_voc(records, iou_thresh=0.5):
                 match[l].extend((0,) * len(keep))
                 continue
             iou = mask_iou_from_counts(inter[np.ix_(keep, gsel)], area_pred[keep], area_gt[gsel])
+            if boundary:
+                iou = np.minimum(iou, mask_iou_from_counts(inter_b[np.ix_(keep, gsel)], band_pred[keep], band_gt[gsel]))
             gt_index = iou.argmax(axis=1)
             gt_index[iou.max(axis=1) < iou_thresh] = -1
             del iou

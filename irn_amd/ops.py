@@ -10,7 +10,8 @@ as `ops.X`, looked up at call time.
                                    detection_overlap_batch, argmax_rethreshold_batch, the Pending* results
     crf.py          crf.hip        crf_filter, crf_inference_label, crf_ir_label, crf_label_sweep
     eval_counts.py  eval.hip       eval_thresholds, cam_confusion, cam_confusion_matrices, label_confusion, mask_overlap,
-                                   ir_label_confusion
+                                   ir_label_confusion, boundary_distance, label_band, label_boundary_counts,
+                                   mask_boundary_overlap
     cocomask.py     cocomask.hip   mask_rle, rle_to_string, rle_from_string, rle_decode, mask_polygons, polygon_fill
     gemm.py         conv1x1.cpp, split16.hip    the hipBLASLt convolutions of the trunk
     _host.py        what more than one of them needs: cached buffers, read_back, packed layouts and their staging
@@ -42,8 +43,9 @@ from .augment import (AUGMENT_DESC_WORDS, AUGMENT_LABEL_DESC_WORDS, AugmentTable
 from .bn_act import bn_act, bn_act_, bn_act_backward, bn_fold, bn_param_grads, stem_pool, upsample_bilinear
 from .cocomask import mask_polygons, mask_rle, polygon_fill, rle_decode, rle_from_string, rle_to_string
 from .crf import CRF_GT_PROB, CRF_MAX_SWEEP, CRF_T, crf_filter, crf_inference_label, crf_ir_label, crf_label_sweep
-from .eval_counts import (EVAL_CLASSES, EVAL_MAX_CLASSES, EVAL_MAX_THRES, cam_confusion, cam_confusion_matrices, eval_thresholds, ir_label_confusion,
-                          label_confusion, mask_overlap)
+from .eval_counts import (BAND_MAX_D, EVAL_CLASSES, EVAL_MAX_CLASSES, EVAL_MAX_THRES, boundary_distance, cam_confusion, cam_confusion_matrices,
+                          eval_thresholds, ir_label_confusion, label_band, label_boundary_counts, label_confusion, mask_boundary_overlap,
+                          mask_overlap)
 from .gemm import (conv1x1_algo_count, conv1x1_nhwc, conv3x3_split, gemm16_algo_count, gemm16_nhwc, gemm_ranks, gemm_ranks16,
                    gemm_ranks3x3, split16, split16_pad, split_overflowed, split_weight, split_weight_3x3)
 from .gemm import sample_flags as split_sample_flags

@@ -48,6 +48,24 @@ def check_shape(id, what, shape, gt_shape):
         raise ValueError("%s: %s %s does not match the ground truth %s" % (id, what, tuple(shape), tuple(gt_shape)))
 
 
+def boundary_ratio(args):
+    """--boundary_iou_ratio as a float: 0 (also when the namespace has no such flag) = off; negative or nan is refused."""
+    r = float(getattr(args, "boundary_iou_ratio", 0) or 0)
+    if not r >= 0:
+        raise ValueError("--boundary_iou_ratio %s: a ratio of the image diagonal, 0 (off) or above" % r)
+    return r
+
+
+def boundary_d(id, shape, ratio):
+    """The band width of image `id` at `ratio`, or a ValueError naming both when it is beyond what the kernels take."""
+    from .. import ops
+    d = ops.boundary_distance(shape[0], shape[1], ratio)
+    if d > ops.BAND_MAX_D:
+        raise ValueError("%s: --boundary_iou_ratio %s gives a band of %d pixels on %dx%d (at most %d)"
+                         % (id, ratio, d, shape[0], shape[1], ops.BAND_MAX_D))
+    return d
+
+
 def raise_if_bad(bad, what, n_fg=20):
     """`n_fg`: the foreground classes the counts were taken with (`_classes.num_classes(args)`)."""
     n = int(bad.item())

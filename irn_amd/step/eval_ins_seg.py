@@ -8,6 +8,10 @@ Prints 0.5iou: {'ap': ..., 'map': ...} as the reference does; returns the dict.
 Per image the device counts |mask & instance|, |mask| and |instance| for every predicted mask and GT instance
 (`ops.mask_overlap`); the counts of the whole split come back in one copy, and chainercv's matching and VOC AP
 (iou_thresh 0.5, not the 07 metric) run on them in split order (`misc.evaluation.instance_ap_voc`).
+
+With --boundary_iou_ratio R > 0 (not in the reference) every image also gets its band counts (`ops.mask_boundary_overlap`, band
+width `ops.boundary_distance(h, w, R)`); they ride the same copy, and the step prints 0.5biou: {'ap': ..., 'map': ...} — Boundary
+AP, matched on min(mask IoU, boundary IoU) — after the reference's line and returns the dict with 'bap' and 'bmap' added.
 """
 import os
 
@@ -35,6 +39,8 @@ def run(args):
     ids = eval_data.seg_ids(args.voc12_root, args.chainer_eval_set)
     dev = _eval.device()
     c = _classes.num_classes(args)
+    ratio = _eval.boundary_ratio(args)
+    fields = (("inter", "ng"), ("area_pred", "n"), ("area_gt", "g")) + ((("inter_b", "ng"), ("band_pred", "n"), ("band_gt", "g")) if ratio else ())
 
     def load(id):
         inst_map, inst_class = eval_data.instance_label(args.voc12_root, id, n_fg=c)
@@ -57,11 +63,18 @@ def run(args):
     records, counts = [], []
     with torch.cuda.device(dev):
         bad = torch.zeros(1, dtype=torch.int64, device=dev)
+        inst_band = None
         for id, it in _eval.items(ids, load, args):
             g = int(it["inst_class"].numel())
-            inter, area_pred, area_gt = ops.mask_overlap(it["mask"].to(dev, non_blocking=True),
-                                                         it["inst_map"].to(dev, non_blocking=True), g, bad)
+            mask, inst_map = it["mask"].to(dev, non_blocking=True), it["inst_map"].to(dev, non_blocking=True)
+            inter, area_pred, area_gt = ops.mask_overlap(mask, inst_map, g, bad)
             counts += [inter.reshape(-1), area_pred, area_gt]
+            if ratio:
+                if inst_band is None or inst_band.numel() < inst_map.numel():
+                    inst_band = torch.empty(inst_map.numel(), dtype=torch.uint8, device=dev)
+                inter_b, band_pred, band_gt = ops.mask_boundary_overlap(mask, inst_map, g, _eval.boundary_d(id, inst_map.shape, ratio),
+                                                                        bad, inst_band)
+                counts += [inter_b.reshape(-1), band_pred, band_gt]
             records.append({"pred_class": it["class"].numpy(), "pred_score": it["score"].numpy(),
                             "gt_class": it["inst_class"].numpy()})
         if not records:
@@ -71,10 +84,14 @@ def run(args):
     pos = 0
     for rec in records:
         n, g = len(rec["pred_class"]), len(rec["gt_class"])
-        for key, size in (("inter", n * g), ("area_pred", n), ("area_gt", g)):
-            rec[key] = flat[pos:pos + size]
+        for key, shape in fields:
+            size = {"ng": n * g, "n": n, "g": g}[shape]
+            rec[key] = flat[pos:pos + size].reshape((n, g) if shape == "ng" else (size,))
             pos += size
-        rec["inter"] = rec["inter"].reshape(n, g)
     out = evaluation.instance_ap_voc(records, iou_thresh=0.5)
     print("0.5iou:", out)
+    if ratio:
+        b = evaluation.instance_ap_voc(records, iou_thresh=0.5, boundary=True)
+        print("0.5biou:", b)
+        out = dict(out, bap=b["ap"], bmap=b["map"])
     return out

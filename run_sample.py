@@ -36,6 +36,14 @@ def _split_gemm(v):
     return v if v == "auto" else int(v)
 
 
+def _ratio(v):
+    """--boundary_iou_ratio: a float that is 0 or above (nan is refused)."""
+    r = float(v)
+    if not r >= 0:
+        raise argparse.ArgumentTypeError("--boundary_iou_ratio: 0 (off) or a positive ratio of the image diagonal, got %r" % v)
+    return r
+
+
 def apply_split_gemm(args, auto=True):
     """--split_gemm into IRN_SPLIT_GEMM (workers read it when they import the trunk) and the trunk's module switches of this
     process; unset: both stay as the environment made them.  `auto` False: a command whose steps have no per-image fallback
@@ -78,6 +86,9 @@ def build_parser():
     p.add_argument("--cam_eval_thres_sweep", default=[], type=float, nargs="*",
                    help="eval_cam: more thresholds counted in the same pass (not in the reference; at most 255); prints the "
                         "miou of each and the best one")
+    p.add_argument("--boundary_iou_ratio", default=0.0, type=_ratio,
+                   help="eval_sem_seg, eval_ins_seg: also score Boundary IoU / Boundary AP (Cheng et al., CVPR 2021; not in the "
+                        "reference) on bands of round(R * image diagonal) pixels; 0 = off, the published value is 0.02")
     p.add_argument("--tune_beta", default=[], type=float, nargs="*",
                    help="tune_sem_seg: more values of --beta on the grid (not in the reference)")
     p.add_argument("--tune_exp_times", default=[], type=int, nargs="*",

@@ -43,7 +43,7 @@ extern "C" {
 /* The version of this header's argument lists.  irn_version() returns the IRN_ABI_VERSION the library was built with, and
  * it moves whenever an entry's arguments change: a binding that finds another value has loaded a library of another commit
  * (irn_amd/_lib.py refuses to import it). */
-#define IRN_ABI_VERSION 103
+#define IRN_ABI_VERSION 104
 int irn_version(void);
 const char *irn_last_error(void);
 
@@ -650,6 +650,18 @@ int irn_argmax_rethreshold_batch(int n_images, const float *const *rw_up_dev, co
  *   workspace: irn_crf_sweep_workspace_bytes(h, w, n_labels = k+1, t_count) (0 = unsupported): at most
  *   irn_crf_workspace_bytes(h, w, 32) + 4 * t_count * h * w bytes (+ alignment); the lattice value
  *   arrays do not grow with t_count.
+ * irn_crf_score_sweep: the CRF seeded with SCORES instead of labels (make_sem_seg_labels
+ *   --sem_seg_crf_iters, tune_sem_seg).  scores dev fp32 [c][h][w] (the rw_up of irn_label_epilogue),
+ *   thres HOST fp32 [t_count], 1 <= t_count <= IRN_CRF_MAX_SWEEP, strictly ascending, each >= 1e-5, no
+ *   NaN.  CRF i has l = c+1 labels with -U = log(max(s, 1e-5)), s = [thres[i], scores]; a pixel with a
+ *   NaN score has s' = 1 at its first NaN channel and 1e-5 at every other label.  Pairwise terms,
+ *   iterations and softmax are those above.  Plane i of planes dev uint8 [t_count][h][w] is the first
+ *   maximum of Q through the keys (0 = background, else keys[j]+1); q_dev (dev fp32
+ *   [t_count][c+1][h][w], may be NULL) receives Q.  Lattices are built once per call, the thresholds
+ *   run in chunks of max(1, 64 / (c+1)) CRFs and a plane does not depend on its chunk.  c == 0 writes
+ *   zeros (Q = 1) and needs no workspace.  c + 1 <= 32.  Bad arguments give IRN_ERR_ARG before any
+ *   device work, a short workspace IRN_ERR_STATE.  Nothing synchronises.
+ *   workspace: irn_crf_score_sweep_workspace_bytes(h, w, n_labels = c+1, t_count) (0 = unsupported).
  * ------------------------------------------------------------------------------------------- */
 #define IRN_CRF_MAX_SWEEP 16
 size_t irn_crf_filter_workspace_bytes(int n, int d, int channels);
@@ -665,6 +677,10 @@ int irn_crf_ir_label(const uint8_t *rgb_dev, const float *high_res_dev, const in
 size_t irn_crf_sweep_workspace_bytes(int h, int w, int n_labels, int t_count);
 int irn_crf_label_sweep(const uint8_t *rgb_dev, const float *high_res_dev, const int64_t *keys_dev, int k, int h, int w,
                         const float *thres, int t_count, int t, float gt_prob, uint8_t *planes_dev, void *ws,
+                        size_t ws_bytes, void *stream);
+size_t irn_crf_score_sweep_workspace_bytes(int h, int w, int n_labels, int t_count);
+int irn_crf_score_sweep(const uint8_t *rgb_dev, const float *scores_dev, const int64_t *keys_dev, int c, int h, int w,
+                        const float *thres, int t_count, int t, uint8_t *planes_dev, float *q_dev, void *ws,
                         size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------

@@ -24,7 +24,7 @@ lib = C.CDLL(LIB_PATH)
 
 # The bindings below are by name only, so a library built from another commit would be called with argument lists it
 # does not have.  IRN_ABI_VERSION of include/irn_hip.h moves with every such change; this is the value _SIGS is written for.
-ABI_VERSION = 103
+ABI_VERSION = 104
 lib.irn_version.restype, lib.irn_version.argtypes = C.c_int, []
 if lib.irn_version() != ABI_VERSION:
     raise ImportError("irn_amd: %s reports ABI version %d, these bindings need %d — it was built from another commit; "
@@ -109,6 +109,8 @@ _SIGS = {
     "irn_crf_ir_label": (i32, [vp, vp, vp, i32, i32, i32, f32, f32, i32, f32, vp, vp, sz, vp]),
     "irn_crf_sweep_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "irn_crf_label_sweep": (i32, [vp, vp, vp, i32, i32, i32, C.POINTER(f32), i32, i32, f32, vp, vp, sz, vp]),
+    "irn_crf_score_sweep_workspace_bytes": (sz, [i32, i32, i32, i32]),
+    "irn_crf_score_sweep": (i32, [vp, vp, vp, i32, i32, i32, C.POINTER(f32), i32, i32, vp, vp, vp, sz, vp]),
     "irn_mask_overlap": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "irn_ir_label_confusion": (i32, [vp, i32, pi32, i32, pi32, i32, vp, i32, i32, i32, vp, vp, vp]),
     "irn_cam_confusion": (i32, [vp, vp, i32, vp, i32, i32, vp, i32, i32, vp, vp, vp]),

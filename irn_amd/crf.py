@@ -10,6 +10,7 @@ from ._lib import _need_cuda, _stream, check, lib
 
 CRF_T, CRF_GT_PROB = 10, 0.7          # the reference's defaults (misc/imutils.py:156)
 CRF_MAX_SWEEP = 16                    # IRN_CRF_MAX_SWEEP
+CRF_SCORE_EPS = np.float32(1e-5)      # the clip of the score-seeded unary
 _CRF_WS = {}                          # (device index, stream) -> grow-only workspace of the CRF entries
 
 
@@ -153,3 +154,48 @@ def crf_label_sweep(img, high_res, keys, thres, t=CRF_T, gt_prob=CRF_GT_PROB, ou
                                       th.ctypes.data_as(C.POINTER(C.c_float)), n_t, int(t), float(gt_prob), out.data_ptr(),
                                       None if ws is None else ws.data_ptr(), nbytes, _stream()))
     return out
+
+
+def crf_score_sweep(img, scores, keys, thres, t=CRF_T, out=None, want_q=False):
+    """The dense CRF seeded with scores instead of labels, for one image at every background threshold of
+    `thres` (1..CRF_MAX_SWEEP values; cast to float32, strictly ascending after the cast, each >= CRF_SCORE_EPS): CRF i has
+    the labels [background, scores...] with -U = log(max([thres[i], scores], 1e-5)).  `scores`: GPU fp32 [C,H,W], the
+    `rw_up` of `label_epilogue`; `keys`: the 0-based class ids [C].  Plane i of the result, uint8 [T,H,W] on the GPU (`out`
+    when given), is the first maximum of Q through the keys: 0 background, key+1 otherwise — at t = 0 the label map of
+    `label_epilogue` at that threshold.  The lattices are built once per call.  With `want_q` also Q fp32 [T,C+1,H,W]."""
+    _need_cuda(scores, "scores")
+    dev = scores.device
+    rgb = _crf_rgb(img, dev)
+    h, w = rgb.shape[:2]
+    sc = scores.float().contiguous()
+    c = int(sc.shape[0]) if sc.dim() == 3 else 0
+    if sc.dim() != 3 or tuple(sc.shape[1:]) != (h, w):
+        raise ValueError("crf_score_sweep: scores %s for an image of %dx%d (fp32 [C,H,W])" % (tuple(sc.shape), h, w))
+    ks = torch.as_tensor(keys, device=dev).to(torch.int64).reshape(-1).contiguous()
+    if ks.numel() != c:
+        raise ValueError("crf_score_sweep: %d keys for %d score planes" % (ks.numel(), c))
+    th = np.ascontiguousarray(np.asarray(thres, np.float32).reshape(-1))
+    n_t = int(th.size)
+    if not 1 <= n_t <= CRF_MAX_SWEEP or np.isnan(th).any() or (np.diff(th) <= 0).any() or (th < CRF_SCORE_EPS).any():
+        raise ValueError("crf_score_sweep: 1..%d strictly ascending float32 thresholds of at least %g, got %s"
+                         % (CRF_MAX_SWEEP, CRF_SCORE_EPS, th))
+    if int(t) < 0:
+        raise ValueError("crf_score_sweep: t = %d iterations" % int(t))
+    if out is None:
+        out = torch.empty((n_t, h, w), dtype=torch.uint8, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == torch.uint8 and out.is_contiguous()
+              and tuple(out.shape) == (n_t, h, w)):
+        raise ValueError("crf_score_sweep: out must be a contiguous uint8 %s tensor on %s" % ((n_t, h, w), dev))
+    ws, nbytes = None, 0
+    with torch.cuda.device(dev):
+        if c:
+            nbytes = int(lib.irn_crf_score_sweep_workspace_bytes(h, w, c + 1, n_t))
+            if nbytes == 0:
+                raise ValueError("crf_score_sweep: unsupported size %dx%d with %d classes (at most %d)" % (h, w, c, 31))
+            ws = _crf_workspace(dev, nbytes)
+        q = torch.empty((n_t, c + 1, h, w), dtype=torch.float32, device=dev) if want_q else None
+        check(lib.irn_crf_score_sweep(rgb.data_ptr(), sc.data_ptr() if c else None, ks.data_ptr() if c else None, c, h, w,
+                                      th.ctypes.data_as(C.POINTER(C.c_float)), n_t, int(t), out.data_ptr(),
+                                      None if q is None else q.data_ptr(), None if ws is None else ws.data_ptr(), nbytes,
+                                      _stream()))
+    return (out, q) if want_q else out

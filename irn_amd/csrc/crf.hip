@@ -476,22 +476,45 @@ __device__ inline void softmax_row(float (&t)[MAX_LABELS], int l, float *__restr
         if (i < l) q[i] = t[i] * inv;
 }
 
+// Where a mean-field kernel takes -U from.  A source hands out one row per (crf, pixel); row(i, l) is -U of label i.
+// SeedUnary: unary_from_labels over lab [crf][pixel] (two values per row).  DenseUnary: the rows k_score_unary wrote,
+// fp32 [pixel][crf * l + label].
+struct SeedUnary {
+    const int32_t *lab;
+    Unary u;
+    struct Row {
+        int lp;
+        Unary u;
+        __device__ float operator()(int i, int) const { return (i == lp) ? u.neg_p : u.neg_n; }
+    };
+    __device__ Row row(int n, int, int, int crf, int p) const { return Row{lab[(size_t)crf * n + p], u}; }
+};
+
+struct DenseUnary {
+    const float *neg_u;
+    struct Row {
+        const float *r;
+        __device__ float operator()(int i, int l) const { return i < l ? r[i] : 0.0f; }
+    };
+    __device__ Row row(int, int ncrf, int l, int crf, int p) const { return Row{neg_u + ((size_t)p * ncrf + crf) * l}; }
+};
+
 // Q = softmax(-U) for every (pixel, crf); Q is [pixel][crf * l + label]
-__global__ void __launch_bounds__(TPB) k_q_init(const int32_t *__restrict__ lab, int n, int ncrf, int l, Unary u,
-                                                float *__restrict__ q) {
+template <class Src>
+__global__ void __launch_bounds__(TPB) k_q_init(Src src, int n, int ncrf, int l, float *__restrict__ q) {
     const int t = blockIdx.x * TPB + threadIdx.x;
     if (t >= n * ncrf) return;
     const int crf = t / n, p = t - crf * n;
-    const int lp = lab[(size_t)crf * n + p];
+    const typename Src::Row un = src.row(n, ncrf, l, crf, p);
     float row[MAX_LABELS];
 #pragma unroll
-    for (int i = 0; i < MAX_LABELS; i++) row[i] = (i == lp) ? u.neg_p : u.neg_n;
+    for (int i = 0; i < MAX_LABELS; i++) row[i] = un(i, l);
     softmax_row(row, l, q + (size_t)p * ncrf * l + (size_t)crf * l);
 }
 
 // one mean-field update: tmp = -U; tmp -= -3 K_gauss(Q); tmp -= -10 K_bilat(Q); Q = softmax(tmp)
-template <int DG, int DB>
-__global__ void __launch_bounds__(TPB) k_update(const int32_t *__restrict__ lab, int n, int ncrf, int l, Unary u,
+template <int DG, int DB, class Src>
+__global__ void __launch_bounds__(TPB) k_update(Src src, int n, int ncrf, int l,
                                                 const float *__restrict__ vg, const int32_t *__restrict__ og,
                                                 const float *__restrict__ bg, const float *__restrict__ ng, float ag,
                                                 const float *__restrict__ vb, const int32_t *__restrict__ ob,
@@ -523,15 +546,56 @@ __global__ void __launch_bounds__(TPB) k_update(const int32_t *__restrict__ lab,
             if (i < l) kb[i] += w * v[i] * ab;
     }
     const float sg = ng[p], sb = nb[p];
-    const int lp = lab[(size_t)crf * n + p];
+    const typename Src::Row un = src.row(n, ncrf, l, crf, p);
 #pragma unroll
     for (int i = 0; i < MAX_LABELS; i++) {
-        float x = (i == lp) ? u.neg_p : u.neg_n;
+        float x = un(i, l);
         x = x - (-GAUSS_COMPAT * (kg[i] * sg));
         x = x - (-BILAT_COMPAT * (kb[i] * sb));
         kg[i] = x;
     }
     softmax_row(kg, l, q + (size_t)p * c + ch0);
+}
+
+constexpr float SCORE_EPS = 1e-5f;     // the clip of pydensecrf's unary_from_softmax (a definition)
+
+// -U of the score-seeded CRFs of one chunk: s_0 = the CRF's threshold, s_i = scores[i-1]; -U_i =
+// log(max(s_i, eps)).  A pixel with a NaN score has s' = 1 at its first NaN channel and eps at every other label, the
+// background included.  neg_u is [pixel][crf * l + label]; only column 0 differs between the CRFs of a chunk.
+__global__ void __launch_bounds__(TPB) k_score_unary(const float *__restrict__ scores, int c, int n, Thresholds th, int ncrf,
+                                                     float *__restrict__ neg_u) {
+    const int p = blockIdx.x * TPB + threadIdx.x;
+    if (p >= n) return;
+    const int l = c + 1;
+    float *row = neg_u + (size_t)p * ncrf * l;
+    int first_nan = -1;
+    for (int i = 0; i < c; i++) {
+        const float v = scores[(size_t)i * n + p];
+        if (v != v && first_nan < 0) first_nan = i;
+        const float lg = logf(v != v ? SCORE_EPS : fmaxf(v, SCORE_EPS));
+        for (int crf = 0; crf < ncrf; crf++) row[crf * l + 1 + i] = lg;
+    }
+#pragma unroll
+    for (int crf = 0; crf < IRN_CRF_MAX_SWEEP; crf++)
+        if (crf < ncrf) row[crf * l] = logf(first_nan >= 0 ? SCORE_EPS : fmaxf(th.v[crf], SCORE_EPS));
+    if (first_nan >= 0) {               // the whole row again: eps at every label but the first NaN channel's
+        const float le = logf(SCORE_EPS);
+        for (int crf = 0; crf < ncrf; crf++)
+            for (int i = 0; i < c; i++) row[crf * l + 1 + i] = (i == first_nan) ? 0.0f : le;      // log(1) : log(eps)
+    }
+}
+
+// Q of every CRF of a chunk as planes: out [crf][label][pixel] (the tests' view of the sweep)
+__global__ void __launch_bounds__(TPB) k_q_planes(const float *__restrict__ q, int n, int c, float *__restrict__ out) {
+    const long total = (long)n * c;
+    for (long t = (long)blockIdx.x * TPB + threadIdx.x; t < total; t += (long)gridDim.x * TPB) {
+        const int p = (int)(t / c), ch = (int)(t - (long)p * c);
+        out[(size_t)ch * n + p] = q[t];
+    }
+}
+
+__global__ void __launch_bounds__(TPB) k_fill(float *__restrict__ out, long total, float v) {
+    for (long t = (long)blockIdx.x * TPB + threadIdx.x; t < total; t += (long)gridDim.x * TPB) out[t] = v;
 }
 
 // argmax of each crf's Q (first maximum), then any of: the labels (+ Q as [label][pixel]) of the first CRF, the
@@ -571,16 +635,18 @@ __global__ void __launch_bounds__(TPB) k_finish(const float *__restrict__ q, int
 struct CrfWs {
     float *feat_g, *feat_b, *q;
     int32_t *lab;
+    float *neg_u = nullptr;             // the dense unary of a score-seeded chunk, [pixel][ncrf * l]
     Lattice g, b;
 };
 
-size_t carve_crf(void *base, CrfWs &W, int h, int w, int l, int nseed = 2, int ncrf = 2) {
+size_t carve_crf(void *base, CrfWs &W, int h, int w, int l, int nseed = 2, int ncrf = 2, bool dense = false) {
     Carver cv(base);
     const int n = h * w, c = ncrf * l;
     W.feat_g = cv.take<float>((size_t)n * 2);
     W.feat_b = cv.take<float>((size_t)n * 5);
     W.lab = cv.take<int32_t>((size_t)n * nseed);
     W.q = cv.take<float>((size_t)n * c);
+    if (dense) W.neg_u = cv.take<float>((size_t)n * c);
     carve(cv, W.g, n, 2, c);
     carve(cv, W.b, n, 5, c);
     return cv.off;
@@ -617,24 +683,27 @@ int build_kernels(CrfWs &W, const uint8_t *rgb, int h, int w, int l, int t, hipS
     return IRN_OK;
 }
 
-// ... and the iterations of one chunk: ncrf CRFs seeded by lab [ncrf][n] as one filter over ncrf * l channels, into W.q.
+// ... and the iterations of one chunk: ncrf CRFs whose unary comes from `src` (seeds lab [ncrf][n], or the dense rows of
+// k_score_unary) as one filter over ncrf * l channels, into W.q.
 // A channel's values never meet another's, so a CRF's Q does not depend on which others share its chunk.
-int iterate_chunk(CrfWs &W, const int32_t *lab, int n, int ncrf, int l, int t, float gt_prob, hipStream_t s) {
-    const Unary u = unary_of(l, gt_prob);
+template <class Src>
+int iterate_chunk(CrfWs &W, Src src, int n, int ncrf, int l, int t, hipStream_t s) {
     const int c = ncrf * l;
-    k_q_init<<<cdiv(n * ncrf, TPB), TPB, 0, s>>>(lab, n, ncrf, l, u, W.q);
+    k_q_init<Src><<<cdiv(n * ncrf, TPB), TPB, 0, s>>>(src, n, ncrf, l, W.q);
     IRN_LAUNCH_CHECK("k_q_init");
     if (t <= 0 || l == 1) return IRN_OK;
     for (int it = 0; it < t; it++) {
         const float *vg = splat_blur(W.g, W.q, W.g.norm, c, s);
         const float *vb = splat_blur(W.b, W.q, W.b.norm, c, s);
-        k_update<2, 5><<<cdiv(n * ncrf, TPB), TPB, 0, s>>>(lab, n, ncrf, l, u, vg, W.g.offset, W.g.bary, W.g.norm,
-                                                            W.g.prm.alpha, vb, W.b.offset, W.b.bary, W.b.norm,
-                                                            W.b.prm.alpha, W.q);
+        k_update<2, 5, Src><<<cdiv(n * ncrf, TPB), TPB, 0, s>>>(src, n, ncrf, l, vg, W.g.offset, W.g.bary, W.g.norm,
+                                                                 W.g.prm.alpha, vb, W.b.offset, W.b.bary, W.b.norm,
+                                                                 W.b.prm.alpha, W.q);
         IRN_LAUNCH_CHECK("k_update");
     }
     return IRN_OK;
 }
+
+inline SeedUnary seeds(const int32_t *lab, int l, float gt_prob) { return SeedUnary{lab, unary_of(l, gt_prob)}; }
 
 }  // namespace
 
@@ -715,7 +784,7 @@ extern "C" int irn_crf_inference_label(const uint8_t *rgb_dev, const int32_t *la
     const int n = h * w;
     int rc;
     if ((rc = build_kernels(W, rgb_dev, h, w, n_labels, t, s)) ||
-        (rc = iterate_chunk(W, labels_dev, n, 1, n_labels, t, gt_prob, s)))
+        (rc = iterate_chunk(W, seeds(labels_dev, n_labels, gt_prob), n, 1, n_labels, t, s)))
         return rc;
     k_finish<<<cdiv(n, TPB), TPB, 0, s>>>(W.q, n, 1, n_labels, nullptr, labels_out_dev, q_dev, nullptr, nullptr);
     IRN_LAUNCH_CHECK("k_finish");
@@ -745,7 +814,7 @@ extern "C" int irn_crf_ir_label(const uint8_t *rgb_dev, const float *high_res_de
     k_prologue<<<cdiv(n, TPB), TPB, 0, s>>>(high_res_dev, k, n, th, 2, W.lab);
     IRN_LAUNCH_CHECK("k_prologue");
     int rc;
-    if ((rc = build_kernels(W, rgb_dev, h, w, l, t, s)) || (rc = iterate_chunk(W, W.lab, n, 2, l, t, gt_prob, s))) return rc;
+    if ((rc = build_kernels(W, rgb_dev, h, w, l, t, s)) || (rc = iterate_chunk(W, seeds(W.lab, l, gt_prob), n, 2, l, t, s))) return rc;
     k_finish<<<cdiv(n, TPB), TPB, 0, s>>>(W.q, n, 2, l, keys_dev, nullptr, nullptr, conf_dev, nullptr);
     IRN_LAUNCH_CHECK("k_finish");
     return IRN_OK;
@@ -795,10 +864,73 @@ extern "C" int irn_crf_label_sweep(const uint8_t *rgb_dev, const float *high_res
     for (int c0 = 0; c0 < t_count; c0 += chunk) {
         const int ncrf = std::min(chunk, t_count - c0);
         const int32_t *lab = W.lab + (size_t)c0 * n;
-        if ((rc = iterate_chunk(W, lab, n, ncrf, l, t, gt_prob, s))) return rc;
+        if ((rc = iterate_chunk(W, seeds(lab, l, gt_prob), n, ncrf, l, t, s))) return rc;
         k_finish<<<cdiv(n, TPB), TPB, 0, s>>>(W.q, n, ncrf, l, keys_dev, nullptr, nullptr, nullptr,
                                               planes_dev + (size_t)c0 * n);
         IRN_LAUNCH_CHECK("k_finish");
+    }
+    return IRN_OK;
+}
+
+extern "C" size_t irn_crf_score_sweep_workspace_bytes(int h, int w, int n_labels, int t_count) {
+    if (t_count < 1 || t_count > IRN_CRF_MAX_SWEEP || irn_crf_workspace_bytes(h, w, n_labels) == 0) return 0;
+    CrfWs W;
+    return carve_crf(nullptr, W, h, w, n_labels, 0, sweep_chunk(n_labels, t_count), true);
+}
+
+extern "C" int irn_crf_score_sweep(const uint8_t *rgb_dev, const float *scores_dev, const int64_t *keys_dev, int c, int h,
+                                   int w, const float *thres, int t_count, int t, uint8_t *planes_dev, float *q_dev, void *ws,
+                                   size_t ws_bytes, void *stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    if (t_count < 1 || t_count > IRN_CRF_MAX_SWEEP)
+        return fail(IRN_ERR_ARG, "irn_crf_score_sweep: t_count %d outside 1..%d", t_count, IRN_CRF_MAX_SWEEP);
+    if (!thres) return fail(IRN_ERR_ARG, "irn_crf_score_sweep: thres is a null pointer");
+    Thresholds th{};
+    for (int i = 0; i < t_count; i++) {
+        if (thres[i] != thres[i]) return fail(IRN_ERR_ARG, "irn_crf_score_sweep: threshold %d is NaN", i);
+        if (!(thres[i] >= SCORE_EPS))
+            return fail(IRN_ERR_ARG, "irn_crf_score_sweep: threshold %d is %g, below the unary's clip %g", i, (double)thres[i],
+                        (double)SCORE_EPS);
+        if (i > 0 && !(thres[i - 1] < thres[i]))
+            return fail(IRN_ERR_ARG, "irn_crf_score_sweep: thresholds not strictly ascending (%g then %g at %d)",
+                        (double)thres[i - 1], (double)thres[i], i);
+        th.v[i] = thres[i];
+    }
+    if (c < 0 || t < 0) return fail(IRN_ERR_ARG, "irn_crf_score_sweep: bad argument (c=%d, t=%d)", c, t);
+    const int l = c + 1;
+    if (!crf_args_ok(h, w, l, "irn_crf_score_sweep")) return IRN_ERR_ARG;
+    if (!rgb_dev || !planes_dev || (c > 0 && (!scores_dev || !keys_dev || !ws)))
+        return fail(IRN_ERR_ARG, "irn_crf_score_sweep: a null pointer (rgb, planes, or with c > 0 scores, keys, ws)");
+    const int n = h * w;
+    if (c == 0) {                       // no class keys: background everywhere, Q = 1
+        IRN_HIP_TRY(hipMemsetAsync(planes_dev, 0, (size_t)t_count * n, s));
+        if (q_dev) {
+            k_fill<<<grid_for((long)t_count * n), TPB, 0, s>>>(q_dev, (long)t_count * n, 1.0f);
+            IRN_LAUNCH_CHECK("k_fill");
+        }
+        return IRN_OK;
+    }
+    const size_t need = irn_crf_score_sweep_workspace_bytes(h, w, l, t_count);
+    if (ws_bytes < need) return fail(IRN_ERR_STATE, "irn_crf_score_sweep: workspace %zu < %zu bytes", ws_bytes, need);
+    const int chunk = sweep_chunk(l, t_count);
+    CrfWs W;
+    carve_crf(ws, W, h, w, l, 0, chunk, true);
+    int rc = build_kernels(W, rgb_dev, h, w, l, t, s);
+    if (rc) return rc;
+    for (int c0 = 0; c0 < t_count; c0 += chunk) {
+        const int ncrf = std::min(chunk, t_count - c0);
+        Thresholds tc{};
+        for (int i = 0; i < ncrf; i++) tc.v[i] = th.v[c0 + i];
+        k_score_unary<<<cdiv(n, TPB), TPB, 0, s>>>(scores_dev, c, n, tc, ncrf, W.neg_u);
+        IRN_LAUNCH_CHECK("k_score_unary");
+        if ((rc = iterate_chunk(W, DenseUnary{W.neg_u}, n, ncrf, l, t, s))) return rc;
+        k_finish<<<cdiv(n, TPB), TPB, 0, s>>>(W.q, n, ncrf, l, keys_dev, nullptr, nullptr, nullptr,
+                                              planes_dev + (size_t)c0 * n);
+        IRN_LAUNCH_CHECK("k_finish");
+        if (q_dev) {
+            k_q_planes<<<grid_for((long)n * ncrf * l), TPB, 0, s>>>(W.q, n, ncrf * l, q_dev + (size_t)c0 * l * n);
+            IRN_LAUNCH_CHECK("k_q_planes");
+        }
     }
     return IRN_OK;
 }

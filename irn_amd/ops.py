@@ -8,7 +8,8 @@ as `ops.X`, looked up at call time.
     bn_act.py       bn_act.hip     bn_act_, bn_fold, bn_param_grads, bn_act, bn_act_backward, stem_pool, upsample_bilinear
     instance.py     instance.hip   find_centroids*, cluster_centroids*, label4, detect_instance*, detect_batch_count,
                                    detection_overlap_batch, argmax_rethreshold_batch, the Pending* results
-    crf.py          crf.hip        crf_filter, crf_inference_label, crf_ir_label, crf_label_sweep
+    crf.py          crf.hip        crf_filter, crf_inference_label, crf_ir_label, crf_label_sweep,
+                                   crf_score_sweep
     eval_counts.py  eval.hip       eval_thresholds, cam_confusion, cam_confusion_matrices, label_confusion, mask_overlap,
                                    ir_label_confusion, boundary_distance, label_band, label_boundary_counts,
                                    mask_boundary_overlap
@@ -42,7 +43,8 @@ from .augment import (AUGMENT_DESC_WORDS, AUGMENT_LABEL_DESC_WORDS, AugmentTable
                       augment_pair_batch, augment_tables, nearest_plan)
 from .bn_act import bn_act, bn_act_, bn_act_backward, bn_fold, bn_param_grads, stem_pool, upsample_bilinear
 from .cocomask import mask_polygons, mask_rle, polygon_fill, rle_decode, rle_from_string, rle_to_string
-from .crf import CRF_GT_PROB, CRF_MAX_SWEEP, CRF_T, crf_filter, crf_inference_label, crf_ir_label, crf_label_sweep
+from .crf import (CRF_GT_PROB, CRF_MAX_SWEEP, CRF_SCORE_EPS, CRF_T, crf_filter, crf_inference_label, crf_ir_label,
+                  crf_label_sweep, crf_score_sweep)
 from .eval_counts import (BAND_MAX_D, EVAL_CLASSES, EVAL_MAX_CLASSES, EVAL_MAX_THRES, boundary_distance, cam_confusion, cam_confusion_matrices,
                           eval_thresholds, ir_label_confusion, label_band, label_boundary_counts, label_confusion, mask_boundary_overlap,
                           mask_overlap)

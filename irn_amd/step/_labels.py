@@ -43,6 +43,55 @@ def make_walker(args, default_radius):
     return walker
 
 
+def crf_iters(args):
+    """--sem_seg_crf_iters: mean-field iterations of the score-seeded CRF behind the semantic labels, 0 = off."""
+    return int(getattr(args, "sem_seg_crf_iters", 0) or 0)
+
+
+def check_crf(args, step, thres, loader=True):
+    """What a step with the CRF on refuses before any work: the CRF reads the decoded uint8 pixels on the device, which (for
+    a step that reads its images through the `loader`) only the raw loader items hand over, and its unary takes the
+    logarithm of the threshold."""
+    from .. import ops
+    if loader and not _io.device_preprocess(args):
+        raise ValueError("%s: --sem_seg_crf_iters %d needs the decoded image on the device, which --device_preprocess False "
+                         "does not hand over; turn one of the two off" % (step, crf_iters(args)))
+    if not np.float32(thres) >= ops.CRF_SCORE_EPS:
+        raise ValueError("%s: --sem_seg_crf_iters needs a background threshold of at least %g, got %r"
+                         % (step, ops.CRF_SCORE_EPS, thres))
+
+
+def rgb_pixels(p, raw, staging=None):
+    """Keep an image's decoded pixels for the CRF: `raw` (host uint8 [H,W,3]) goes to the device once, stays as p["rgb"] and
+    feeds the IRNet's input p["img"] — the same pixels for both, as in cam_to_ir_label."""
+    from .. import ops
+    p["rgb"] = _io.upload(raw, staging)
+    p["img"] = ops.msf_pack(p["rgb"], (1.0,))[0]
+
+
+def crf_planes(rws, sizes, keys, rgbs, names, thres, t, outs=None):
+    """The CRF's label maps of a batch of walks: the epilogue's normalised scores (`rw_up`) instead of its labels, then per
+    image one `crf_score_sweep` over the background thresholds `thres` -> uint8 [T,H,W] each, one at a time (a generator; into
+    `outs[i]` where given)."""
+    from .. import ops
+    ups = ops.label_epilogue(rws, sizes, float(thres[0]), want_labels=False, want_rw_up=True)["rw_up"]
+    for i, up in enumerate(ups):
+        if up.shape[0] > 31:
+            raise ValueError("%s: %d classes present, the CRF takes at most 31 per image" % (names[i], up.shape[0]))
+        yield ops.crf_score_sweep(rgbs[i], up, keys[i], thres, t=t, out=None if outs is None else outs[i])
+
+
+def crf_refine(rws, sizes, keys, rgbs, names, thres, t):
+    """The label maps of a batch with the CRF on, at the single threshold `thres`: each image's map in its stretch of ONE flat
+    uint8 buffer (what `label_epilogue(packed=True)` returns as 'labels_flat')."""
+    offs = np.concatenate([[0], np.cumsum([hh * ww for hh, ww in sizes])])
+    flat = torch.empty(int(offs[-1]), dtype=torch.uint8, device=rws[0].device)
+    outs = [flat[int(offs[i]):int(offs[i + 1])].view(1, hh, ww) for i, (hh, ww) in enumerate(sizes)]
+    for _ in crf_planes(rws, sizes, keys, rgbs, names, [thres], t, outs):
+        pass
+    return flat
+
+
 def irn_batch(args):
     return int(getattr(args, "irn_batch", 0) or 8)              # images per IRNet trunk pass
 
@@ -142,7 +191,11 @@ def redo_items(redo, w, args):
     """The redo list as `item`s (pixels decoded again by `edges_for`), in name order, with their CAMs as they are NOW — the
     fp32 one where make_cam recomputed the image too."""
     cam_run = _stores.current_cam_run(args.cam_out_dir)
-    return [item(name, size, w.dev, args, cam_run) for name, size in sorted(redo.items())]
+    todo = [item(name, size, w.dev, args, cam_run) for name, size in sorted(redo.items())]
+    if w.keep_rgb:
+        for p in todo:
+            rgb_pixels(p, torch.from_numpy(np.array(Image.open(p["stamp"][0]).convert("RGB"))))
+    return todo
 
 
 def skip_image_predicate(model, args, device):
@@ -202,17 +255,18 @@ def item(name, size, dev, args, cam_run):
 
 
 @contextlib.contextmanager
-def worker(process_id, model, dataset, args):
+def worker(process_id, model, dataset, args, keep_rgb=False):
     """One shard of a label step on its worker's device.  Walker (its context and device buffers) and writer are closed however
-    the block ends; the walk's fall-back count and the step's summary line come only after a block that ended well."""
+    the block ends; the walk's fall-back count and the step's summary line come only after a block that ended well.
+    `keep_rgb`: every item keeps its decoded pixels on the device (`rgb_pixels`), so no image's pixels are skipped."""
     model = build_model(model)
     dev = torch.device("cuda", _pool.worker_device(process_id, args))
     with _io.shard_io(process_id, dataset, args) as (databin, n_gpus, loader, writer), torch.no_grad(), torch.cuda.device(dev):
-        _io.set_skip_image(databin, skip_image_predicate(model, args, dev))
+        _io.set_skip_image(databin, None if keep_rgb else skip_image_predicate(model, args, dev))
         model.cuda()
         with contextlib.closing(make_walker(args, RADIUS)) as walker:
             yield types.SimpleNamespace(model=model, walker=walker, writer=writer, loader=loader, dev=dev, databin=databin,
-                                        n_gpus=n_gpus, process_id=process_id)
+                                        n_gpus=n_gpus, process_id=process_id, keep_rgb=keep_rgb)
             _report.WALK_STATS["fallback_runs"] += walker.fallback_runs
             _report.step_summary(process_id, walker)
 
@@ -243,8 +297,11 @@ def items(w, args):
         name = pack["name"][0]
         name = name if isinstance(name, str) else voc12_dataloader.decode_int_filename(name)
         p = item(name, (int(pack["size"][0]), int(pack["size"][1])), w.dev, args, cam_run)
-        imgs = _io.device_images(pack, (1.0,))
-        p["img"] = None if imgs is None else imgs[0]
+        if w.keep_rgb:
+            rgb_pixels(p, pack["img"][0], pack.pop("_staging", None))
+        else:
+            imgs = _io.device_images(pack, (1.0,))
+            p["img"] = None if imgs is None else imgs[0]
         yield p
         _io.progress(w.process_id, w.n_gpus, it, len(w.databin))
 

@@ -84,13 +84,14 @@ def batches(iterable, n):
         yield pend
 
 
-def run_walk(args, step, grid_axes, thres, load, gt_key, what, default_batch, counter):
+def run_walk(args, step, grid_axes, thres, load, gt_key, what, default_batch, counter, keep_rgb=False):
     """`run` of a walk tuner up to its report -> (what `finish` returns, axes, the configured point).
 
     grid_axes(args) -> `walk_axes`; `thres` names the configured threshold in `args`.  load(id, c) -> the image's ground truth
     and, under "image", its `jpeg`; the map under `gt_key` gives the image's size and an image without class keys has no
     `what` to score.  counter(axes, c, dev, bad) -> (count(model, walker, pend) for one batch of `_labels.item` dicts, which
     also hold what `load` returned; finish() for the read-backs once `bad` has been checked).  c = --num_classes.
+    `keep_rgb`: every item keeps its decoded pixels on the device under "rgb" (what the IRNet's input is packed from).
     Refusals come in this order: no split file, the grid, an empty split, no GPU — all before any image is read."""
     ids = split_ids(args)
     axes = grid_axes(args)
@@ -110,7 +111,10 @@ def run_walk(args, step, grid_axes, thres, load, gt_key, what, default_batch, co
                 if p["keys"].numel() == 0:
                     raise ValueError("%s: %s has no class key in %s: an image without a CAM has no %s to score"
                                      % (step, id, args.cam_out_dir, what))
-                p["img"] = ops.msf_pack(_io.upload(it.pop("image")), (1.0,))[0]
+                rgb = _io.upload(it.pop("image"))
+                if keep_rgb:
+                    p["rgb"] = rgb
+                p["img"] = ops.msf_pack(rgb, (1.0,))[0]
                 p.update(it)
                 yield p
         for pend in batches(items(), batch):

@@ -2,6 +2,7 @@
 
 Reads  args.irn_network, args.irn_weights_name, args.infer_list, args.voc12_root, args.cam_out_dir,
        args.beta, args.exp_times, args.sem_seg_bg_thres, args.num_workers
+       args.sem_seg_crf_iters (not in the reference; 0 = off)
 Writes args.sem_seg_out_dir/<name>.png  uint8 [H,W] (0 = background, class+1 otherwise)
 
 Per image (step/make_sem_seg_labels.py:28-51): EdgeDisplacement forward (PyTorch-ROCm) -> edge; the image's CAM —
@@ -9,7 +10,9 @@ from the device store when make_cam ran in this process, else from its file; ran
 affinities and the label epilogue run in libirn_hip.so.  Unlike the reference's batch-1 loop the IRNet forward runs
 `irn_batch` images per pass (default 8) and the walk is issued for `walk_batch` images at a time (default 64) so one
 launch fills the GPU for several rounds; results per image are unchanged.  `args.radius` (default 5 = the
-reference's hard-coded value) selects the walk radius.
+reference's hard-coded value) selects the walk radius.  With `args.sem_seg_crf_iters` T > 0 the epilogue hands its normalised
+scores to a dense CRF of T mean-field iterations whose unary is their logarithm (`ops.crf_score_sweep`), one
+call per image on the pixels the IRNet saw; the read-back, the writers and the files' format stay as they are.
 """
 import os
 
@@ -27,9 +30,16 @@ def _save_png(path, label):
 
 def _start_copy(batch, args):
     """Label epilogue of the batch's walk; its maps (views of one device buffer) leave for the host as ONE copy into page-locked
-    memory on the copy stream, behind everything enqueued so far; `_collect` waits for it when the next batch is already queued."""
-    flat = batch["flat"] = ops.label_epilogue(batch["rws"], batch["sizes"], float(args.sem_seg_bg_thres), keys=batch["keys"],
-                                              packed=True)["labels_flat"]
+    memory on the copy stream, behind everything enqueued so far; `_collect` waits for it when the next batch is already queued.
+    With `--sem_seg_crf_iters` the maps are the CRF's (`_labels.crf_refine`), in the same buffer layout."""
+    t = _labels.crf_iters(args)
+    if t:
+        flat = _labels.crf_refine(batch["rws"], batch["sizes"], batch["keys"], batch["rgbs"], batch["names"],
+                                  float(args.sem_seg_bg_thres), t)
+    else:
+        flat = ops.label_epilogue(batch["rws"], batch["sizes"], float(args.sem_seg_bg_thres), keys=batch["keys"],
+                                  packed=True)["labels_flat"]
+    batch["flat"] = flat
     batch["staging"] = _io.PINNED.take(flat.numel())
     batch["done"] = ops.read_back(flat, batch["staging"], side=True)      # (behind the batch's flag words, if any: `_enqueue`)
 
@@ -42,7 +52,8 @@ def _enqueue(model, walker, pend, args, auto=False):
     _labels.edges_for(model, pend, _labels.irn_batch(args), auto=auto, **kw)
     rws = walker([p["edge"] for p in pend], [p["cam"] for p in pend], beta=float(args.beta), exp_times=int(args.exp_times))
     batch = {"names": [p["name"] for p in pend], "rws": rws, "sizes": [p["size"] for p in pend], "keys": [p["keys_dev"] for p in pend],
-             "flags": _labels.flag_read(pend) if auto else None, "store": kw.get("store")}
+             "flags": _labels.flag_read(pend) if auto else None, "store": kw.get("store"),
+             "rgbs": [p.get("rgb") for p in pend]}
     _start_copy(batch, args)
     pend.clear()
     return batch
@@ -72,7 +83,7 @@ def _collect(walker, batch, args, writer, redo=None):
 
 def _work(process_id, model, dataset, args):
     batch = _labels.walk_batch(args, 64)    # 64 VOC-size images = 3-4 rounds of the resident walk
-    with _labels.worker(process_id, model, dataset, args) as w:
+    with _labels.worker(process_id, model, dataset, args, keep_rgb=_labels.crf_iters(args) > 0) as w:
         # a batch is enqueued and left running while the loop gathers the next one (decoded images from the loader
         # threads, their uploads, the CAMs); it is collected just before the next batch is enqueued
         pend, running = [], None
@@ -107,5 +118,7 @@ def _work(process_id, model, dataset, args):
 
 
 def run(args):
+    if _labels.crf_iters(args):
+        _labels.check_crf(args, "make_sem_seg_labels", args.sem_seg_bg_thres)
     _labels.run_step(_work, args.sem_seg_out_dir, args)
     torch.cuda.empty_cache()

@@ -44,6 +44,14 @@ def _ratio(v):
     return r
 
 
+def _crf_iters(v):
+    """--sem_seg_crf_iters: an integer that is 0 or above."""
+    t = int(v)
+    if t < 0:
+        raise argparse.ArgumentTypeError("--sem_seg_crf_iters: 0 (off) or a number of mean-field iterations, got %r" % v)
+    return t
+
+
 def apply_split_gemm(args, auto=True):
     """--split_gemm into IRN_SPLIT_GEMM (workers read it when they import the trunk) and the trunk's module switches of this
     process; unset: both stay as the environment made them.  `auto` False: a command whose steps have no per-image fallback
@@ -69,6 +77,11 @@ def build_parser():
     p.add_argument("--exp_times", default=8, type=int)
     p.add_argument("--ins_seg_bg_thres", default=0.25, type=float)
     p.add_argument("--sem_seg_bg_thres", default=0.25, type=float)
+    p.add_argument("--sem_seg_crf_iters", default=0, type=_crf_iters,
+                   help="make_sem_seg_labels, tune_sem_seg: refine the labels by a dense CRF whose unary is the log of the walk's "
+                        "scores and of --sem_seg_bg_thres (not in the reference; DESIGN.md §29); mean-field iterations, 0 = off, "
+                        "10 is the usual count.  Needs device preprocessing, a threshold of at least 1e-5 and at most 31 classes "
+                        "per image; tune_sem_seg then takes at most 16 thresholds")
     p.add_argument("--radius", default=5, type=int,
                    help="random-walk radius of the label steps (not a flag of the reference, which hard-codes 5 at "
                         "step/make_sem_seg_labels.py:41 and step/make_ins_seg_labels.py:135; 10 = BASELINE configs[2])")

@@ -43,7 +43,7 @@ extern "C" {
 /* The version of this header's argument lists.  irn_version() returns the IRN_ABI_VERSION the library was built with, and
  * it moves whenever an entry's arguments change: a binding that finds another value has loaded a library of another commit
  * (irn_amd/_lib.py refuses to import it). */
-#define IRN_ABI_VERSION 104
+#define IRN_ABI_VERSION 105
 int irn_version(void);
 const char *irn_last_error(void);
 
@@ -128,6 +128,43 @@ int irn_aff_loss_backward(const float *edge, const float *dp, const uint8_t *lab
 int irn_aff_loss_backward_ordered(const float *edge, const float *dp, const uint8_t *label, int batch, int hp, int wp,
                                   int radius, int ignore_from, const float *coef, float *grad_edge, float *grad_dp, void *ws,
                                   size_t ws_bytes, void *stream);
+
+/* Fused bilinear upsampling + softmax cross-entropy of segmentation training (replaces F.interpolate(scale_factor = factor,
+ * mode = 'bilinear', align_corners = False) followed by F.cross_entropy(ignore_index = 255) without writing any
+ * [batch, C, H, W] tensor), and the arg-max of inference.
+ *   logits dev fp32 [batch, C, h, w], contiguous; z[b, c, Y, X] = their bilinear interpolation at fine pixel (Y, X) of the
+ *   H x W window at the top left of the full upsampling, 1 <= H <= h * factor, 1 <= W <= w * factor, with exactly the
+ *   arithmetic of irn_upsample_bilinear (one piece of device code serves both).  factor 1..64, C 2..IRN_EVAL_MAX_CLASSES (81),
+ *   h and w 1..32768.
+ *   label dev uint8 [batch, H, W]: a byte >= C is ignored (255 = void, or a label of another class list).
+ * irn_seg_loss_forward: per valid pixel l = logsumexp_c z - z[label] with the maximum subtracted (finite logits of any size
+ *   neither overflow nor give NaN): interpolation, maximum, exponentials and their sum in fp32 as torch computes them, the one
+ *   logarithm of a pixel and the additions around it in fp64 (the device's fp32 logarithm is biased, and a bias does not average
+ *   out over a sum).  sums dev fp64 [batch] = the per-image sum of l, counts dev int64 [batch] = the valid pixels per image;
+ *   both are overwritten.  Accumulation in fp64 through per-workgroup partials in the workspace that a second kernel adds in a
+ *   fixed order: no float atomics, identical bits for identical inputs, and sums[b] does not depend on the other images.
+ *   lse dev fp64 [batch, H, W] or NULL: receives the log-sum-exp of every pixel, ignored ones included, for the backward
+ *   (fp64: an fp32 log-sum-exp of logits near 1e4 is off by up to 5e-4, which exp(z - lse) turns into a relative error).
+ * irn_seg_loss_backward: coef dev fp32 [batch], image b's upstream gradient of sums[b] (read on the device, nothing synchronises);
+ *   grad_logits[b, c, y, x] = coef[b] * sum over the valid (Y, X) of wgt((Y, X) -> (y, x)) * (exp(z[b, c, Y, X] - lse[b, Y, X])
+ *   - [label == c]), wgt the weight the interpolation gave coarse cell (y, x) in fine pixel (Y, X).  A gather: a workgroup owns a
+ *   tile of 8 x 8 coarse cells and keeps their logits with a one-cell halo in LDS, every thread adds what reaches its
+ *   (cell, class) over the cell's footprint of at most 2 factor x 2 factor fine pixels, Y ascending and X ascending within a
+ *   row, in fp32.  No atomics of any kind: every element of grad_logits dev fp32 [batch, C, h, w] is written exactly once with
+ *   a plain store, nothing is cleared first, identical inputs give identical bits and an image's gradient does not depend on
+ *   the images batched with it.
+ * irn_seg_argmax: out dev uint8 [batch, H, W] = the first channel that attains the maximum of z; a NaN counts as the maximum
+ *   (torch.argmax, irn_label_epilogue).
+ * ws: irn_seg_loss_workspace_bytes(batch, C, h, w, factor, H, W) bytes of device memory, 8-byte aligned (0 = bad geometry); the
+ *   backward checks it like the forward and leaves it untouched.  Null pointers, batch outside [1, 65535], C, factor, h, w, H or W
+ *   outside their ranges and pointers that are not aligned to their element give IRN_ERR_ARG, a workspace that is too small
+ *   IRN_ERR_STATE, all before any device is touched. */
+size_t irn_seg_loss_workspace_bytes(int batch, int C, int h, int w, int factor, int H, int W);
+int irn_seg_loss_forward(const float *logits, const uint8_t *label, int batch, int C, int h, int w, int factor, int H, int W,
+                         double *sums, int64_t *counts, double *lse, void *ws, size_t ws_bytes, void *stream);
+int irn_seg_loss_backward(const float *logits, const uint8_t *label, const double *lse, const float *coef, int batch, int C, int h,
+                          int w, int factor, int H, int W, float *grad_logits, void *ws, size_t ws_bytes, void *stream);
+int irn_seg_argmax(const float *logits, int batch, int C, int h, int w, int factor, int H, int W, uint8_t *out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Random-walk context  (replaces misc/indexing.py:141-165 `propagate_to_edge` and everything it

@@ -24,7 +24,7 @@ lib = C.CDLL(LIB_PATH)
 
 # The bindings below are by name only, so a library built from another commit would be called with argument lists it
 # does not have.  IRN_ABI_VERSION of include/irn_hip.h moves with every such change; this is the value _SIGS is written for.
-ABI_VERSION = 104
+ABI_VERSION = 105
 lib.irn_version.restype, lib.irn_version.argtypes = C.c_int, []
 if lib.irn_version() != ABI_VERSION:
     raise ImportError("irn_amd: %s reports ABI version %d, these bindings need %d — it was built from another commit; "
@@ -47,6 +47,10 @@ _SIGS = {
     "irn_aff_loss_forward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "irn_aff_loss_backward": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "irn_aff_loss_backward_ordered": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "irn_seg_loss_workspace_bytes": (sz, [i32, i32, i32, i32, i32, i32, i32]),
+    "irn_seg_loss_forward": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
+    "irn_seg_loss_backward": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
+    "irn_seg_argmax": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
     "irn_walk_create": (i32, [i32, C.POINTER(vp)]),
     "irn_walk_destroy": (i32, [vp]),
     "irn_walk_configure": (i32, [vp, i32, pi32, pi32, pi32, C.POINTER(sz)]),

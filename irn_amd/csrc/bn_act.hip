@@ -15,6 +15,7 @@
 // a plane boundary takes the next channel's constants for its upper elements.  Plane and channel of a piece come from
 // multiply-shift divisions by invariant divisors prepared on the host.
 #include "common.hpp"
+#include "upsample.hpp"
 
 #pragma clang fp contract(off)
 
@@ -601,22 +602,15 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float *__restrict__
     const int yo = blockIdx.y * 4 + (threadIdx.x >> 6);
     const unsigned plane = blockIdx.z;
     if (xg * V >= wo || yo >= ho) return;
-    float sy = rscale * ((float)yo + 0.5f) - 0.5f;
-    sy = sy < 0.f ? 0.f : sy;
-    const int y0 = (int)sy;
-    const int y1 = y0 + (y0 < h - 1 ? 1 : 0);
-    const float ly = sy - (float)y0, ly0 = 1.f - ly;
-    const float *r0 = x + ((size_t)plane * h + y0) * w, *r1 = x + ((size_t)plane * h + y1) * w;
+    const UpsampleTap ty = upsample_tap(yo, h, rscale);
+    const float ly = ty.l, ly0 = 1.f - ly;
+    const float *r0 = x + ((size_t)plane * h + ty.i0) * w, *r1 = x + ((size_t)plane * h + ty.i1) * w;
     float o[V];
 #pragma unroll
     for (int v = 0; v < V; ++v) {
-        const int xo = xg * V + v;
-        float sx = rscale * ((float)xo + 0.5f) - 0.5f;
-        sx = sx < 0.f ? 0.f : sx;
-        const int x0 = (int)sx;
-        const int x1 = x0 + (x0 < w - 1 ? 1 : 0);
-        const float lx = sx - (float)x0, lx0 = 1.f - lx;
-        float val = ly0 * (lx0 * r0[x0] + lx * r0[x1]) + ly * (lx0 * r1[x0] + lx * r1[x1]);
+        const UpsampleTap tx = upsample_tap(xg * V + v, w, rscale);
+        const float lx = tx.l, lx0 = 1.f - lx;
+        float val = upsample_blend(r0[tx.i0], r0[tx.i1], r1[tx.i0], r1[tx.i1], lx0, lx, ly0, ly);
         if (RELU) val = val < 0.f ? 0.f : val;
         o[v] = val;
     }
@@ -636,25 +630,13 @@ int launch_upsample(const float *x, float *out, unsigned n_planes, int h, int w,
     return IRN_OK;
 }
 
-// The forward's source rows / columns and weights of output index `o` (the same fp32 expressions as upsample_kernel):
-// taps i0 and i1 = i0 + 1 (clamped to the last index `n - 1`) with weights 1 - l and l.  Returns the weight with which input
-// index `i` enters output `o`: both taps where the clamp folds them onto one index.
-__device__ __forceinline__ float upsample_weight(int o, int i, int n, float rscale) {
-    float s = rscale * ((float)o + 0.5f) - 0.5f;
-    s = s < 0.f ? 0.f : s;
-    const int i0 = (int)s;
-    const int i1 = i0 + (i0 < n - 1 ? 1 : 0);
-    const float l = s - (float)i0;
-    return (i0 == i ? 1.f - l : 0.f) + (i1 == i ? l : 0.f);
-}
-
 // Backward of upsample_kernel, as a gather: one thread owns the input cell (y, x) and adds, rows ascending and columns
 // ascending within a row, grad_out (masked by out > 0 behind the ReLU) times the weight the forward gave the cell; one store.
 // Which outputs touch input index i: those whose first tap i0 is i - 1 or i.  In exact arithmetic i0 = floor((o + 0.5) / f
 // - 0.5) lies in [i - 1, i] for f*i - f/2 - 0.5 <= o < f*i + 3f/2 - 0.5 (the clamp at 0 only moves outputs onto i = 0 that
 // the range already holds; the clamp of the second tap adds none).  The loop runs over that range widened by one output on
-// each side, which covers the rounding of the fp32 mapping, and takes the weights from the forward's own expressions:
-// an output outside the true support weighs exactly 0 and is skipped.
+// each side (upsample_below / upsample_above), which covers the rounding of the fp32 mapping, and takes the weights from the
+// forward's own expressions (upsample_weight, upsample.hpp): an output outside the true support weighs exactly 0 and is skipped.
 template <bool RELU>
 __global__ __launch_bounds__(256) void upsample_backward_kernel(const float *__restrict__ grad_out, const float *__restrict__ out,
                                                                 float *__restrict__ grad_in, int h, int w, int ho, int wo,
@@ -663,7 +645,7 @@ __global__ __launch_bounds__(256) void upsample_backward_kernel(const float *__r
     const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
     const unsigned plane = blockIdx.z;
     if (x >= w || y >= h) return;
-    const int below = factor / 2 + 2, above = (3 * factor + 1) / 2 + 1;
+    const int below = upsample_below(factor), above = upsample_above(factor);
     const int yo0 = max(0, factor * y - below), yo1 = min(ho, factor * y + above);
     const int xo0 = max(0, factor * x - below), xo1 = min(wo, factor * x + above);
     const float *g = grad_out + (size_t)plane * ho * wo;

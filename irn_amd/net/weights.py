@@ -44,6 +44,11 @@ def random_irn_state(seed=2):
     return _fill(EdgeDisplacement(), seed).state_dict()
 
 
+def random_seg_state(seed=3, n_classes=20):
+    from .resnet50_seg import Net
+    return _fill(Net(n_classes=n_classes), seed).state_dict()
+
+
 def _meta_build_covered(factory, state):
     """factory() on the `meta` device (no storage, no initialiser runs, nothing global is patched — safe beside other
     threads that build modules) and whether `state` covers every parameter and buffer of it."""

@@ -14,6 +14,7 @@ as `ops.X`, looked up at call time.
                                    ir_label_confusion, boundary_distance, label_band, label_boundary_counts,
                                    mask_boundary_overlap
     cocomask.py     cocomask.hip   mask_rle, rle_to_string, rle_from_string, rle_decode, mask_polygons, polygon_fill
+    seg_loss.py     seg_loss.hip   seg_loss_sums, seg_cross_entropy, seg_argmax
     gemm.py         conv1x1.cpp, split16.hip    the hipBLASLt convolutions of the trunk
     _host.py        what more than one of them needs: cached buffers, read_back, packed layouts and their staging
 
@@ -55,6 +56,7 @@ from .instance import (PendingDetections, PendingOverlaps, PendingRleDetections,
                        cluster_centroids_batch, detect_batch_count, detect_instance, detect_instance_batch, detect_instance_rle_batch,
                        detection_overlap_batch, find_centroids_batch, find_centroids_with_refinement, label4)
 from .label import cam_merge, label_epilogue, label_sweep_confusion
+from .seg_loss import seg_argmax, seg_cross_entropy, seg_loss_sums
 from .msf import bicubic_plan, bicubic_resize, msf_pack, normalize_lut, rescale_size
 
 # the two helpers tests and tools used to reach under their private names: callers written against those keep working

@@ -253,13 +253,17 @@ class VOC12AffinityDataset(Dataset):
 
     ``raw=True`` makes no resize and no float array in the worker: the item is {'name', 'img': uint8 [H,W,3], 'label_map':
     uint8 [H,W], 'size': (H, W), 'aug': (hs, ws, flip, box)} with the same draws, and `irn_amd.ops.augment_pair_batch` builds
-    the same floats and the same reduced map on the GPU for the whole batch.  Batch such items with `affinity_collate`."""
+    the same floats and the same reduced map on the GPU for the whole batch.  Batch such items with `affinity_collate`.
+
+    ``reduce`` (default 4, the IRNet's grid): the factor the cropped label is reduced by; 1 keeps the label at the crop's size
+    (segmentation training) — hand `augment_pair_batch` the same value."""
 
     def __init__(self, img_name_list_path, label_dir, crop_size, voc12_root, rescale=None,
-                 img_normal=TorchvisionNormalize(), hor_flip=False, crop_method="random", seed=0, raw=False):
+                 img_normal=TorchvisionNormalize(), hor_flip=False, crop_method="random", seed=0, raw=False, reduce=4):
         self.img_name_list = load_img_name_list(img_name_list_path)
         self.voc12_root = voc12_root
         self.label_dir = label_dir
+        self.reduce = int(reduce)
         self.crop_size = crop_size
         self.rescale = rescale
         self.img_normal = img_normal
@@ -315,7 +319,7 @@ class VOC12AffinityDataset(Dataset):
             img, label = imutils.random_crop((img, label), self.crop_size, (0, 255), rng)
         else:
             img, label = imutils.top_left_crop(img, self.crop_size, 0), imutils.top_left_crop(label, self.crop_size, 255)
-        reduced = imutils.pil_rescale(np.ascontiguousarray(label), 0.25, 0)
+        reduced = imutils.pil_rescale(np.ascontiguousarray(label), 1.0 / self.reduce, 0)
         return {"name": name_str, "img": np.ascontiguousarray(imutils.HWC_to_CHW(img)), "label": np.array(reduced)}       # (a copy: PIL hands out read-only memory)
 
 

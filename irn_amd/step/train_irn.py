@@ -5,11 +5,11 @@ Reads  args.train_list, args.infer_list, args.voc12_root, args.ir_label_out_dir 
        args.num_workers, args.seed, args.irn_init_weights, args.irn_augment, args.irn_trunk
 Writes args.irn_weights_name: the state dict the label steps load (EdgeDisplacement through net.weights.load_checkpoint)
 
-The reference's loop with three differences.  The input batch is built on the GPU (`--irn_augment device`, the default):
-the loader workers hand over the decoded image, the IR label map and the augmentation's draws, and `ops.augment_pair_batch`
-rescales, normalises, mirrors and crops the images and gathers the reduced label maps for the whole batch
-(irn_amd/csrc/augment.hip), bit for bit what the PIL / numpy pipeline gives for the same draws — `--irn_augment host` runs
-that pipeline in the workers instead.  The displacement-mean pass follows the same choice.
+The reference's loop (the shared one, irn_amd/step/_train.py) with three differences.  The input batch is built on the GPU
+(`--irn_augment device`, the default): the loader workers hand over the decoded image, the IR label map and the
+augmentation's draws, and `ops.augment_pair_batch` rescales, normalises, mirrors and crops the images and gathers the reduced
+label maps for the whole batch (irn_amd/csrc/augment.hip), bit for bit what the PIL / numpy pipeline gives for the same draws
+— `--irn_augment host` runs that pipeline in the workers instead.  The displacement-mean pass follows the same choice.
 The loss is `AffinityDisplacementLoss.fused_losses`: one HIP pass from the boundary, displacement and reduced label maps to
 the five sums (irn_amd/csrc/aff_loss.hip), so the loader sends one uint8 map per image instead of three [|S|, N] float
 tensors and no [B, |S|, N] tensor exists on the device.  And there is no nn.DataParallel: one device.  In the reproducible
@@ -24,19 +24,16 @@ can be slower than `autograd`.  Initial weights: `--irn_init_weights` (a state d
 non-strictly: an ImageNet trunk, or an earlier checkpoint), else the seeded random state of net.weights; nothing is
 downloaded.
 """
-import os
-
 import torch
-from torch.utils.data import DataLoader
 
 from .. import _tuned
-from ..misc import indexing, pyutils, torchutils
+from ..misc import indexing
 from ..net import weights
 from ..net.resnet50_irn import AffinityDisplacementLoss
 from ..voc12 import dataloader
-from . import _classes
+from . import _classes, _train
 
-MAX_LOADER_WORKERS = 8
+PRINT_EVERY = 50
 
 
 def build_model(args, path_index):
@@ -64,29 +61,9 @@ def make_datasets(args, seed):
     return train, infer
 
 
-def _loader(dataset, args, shuffle, seed):
-    gen = torch.Generator().manual_seed(seed)
-    raw = getattr(dataset, "raw", False)
-    return DataLoader(dataset, batch_size=args.irn_batch_size, shuffle=shuffle, drop_last=True, pin_memory=not raw,
-                      num_workers=max(0, min(int(args.num_workers), MAX_LOADER_WORKERS)), generator=gen,
-                      collate_fn=dataloader.affinity_collate if raw else None)
-
-
-def device_batch(pack, crop, device):
-    """Loader batch of the training set -> (GPU fp32 [B,3,crop,crop], GPU uint8 [B,crop/4,crop/4]): raw items through
-    `ops.augment_pair_batch`, the host pipeline's arrays as they are."""
-    if "aug" in pack:
-        from .. import ops
-        return ops.augment_pair_batch(pack["img"], pack["label_map"], pack["aug"], crop, reduce=4, device=device)
-    return pack["img"].to(device, non_blocking=True), pack["label"].to(device, non_blocking=True)
-
-
-def device_images(pack, crop, device):
-    """Loader batch of the displacement-mean pass -> GPU fp32 [B,3,crop,crop]."""
-    if "aug" in pack:
-        from .. import ops
-        return ops.augment_batch(pack["img"], pack["aug"], crop, device=device)
-    return pack["img"].to(device, non_blocking=True)
+def collate(dataset):
+    """Raw items (lists of unequal images) need `affinity_collate`; the host pipeline's arrays stack by default."""
+    return dataloader.affinity_collate if getattr(dataset, "raw", False) else None
 
 
 def irn_trunk(args):
@@ -124,13 +101,12 @@ def train_step(model, optimizer, img, label, trunk="autograd", n_classes=20):
 
 def displacement_mean(model, loader, device):
     """Mean over the batches of `loader` of the per-batch channel means of the displacement field (step/train_irn.py:97-107)."""
+    _train.max_steps("train_irn", "infer_list", loader.dataset, loader.batch_size, 1)
     means = []
     with torch.no_grad():
         for pack in loader:
-            _, dp = model(device_images(pack, loader.dataset.crop_size, device), False)
+            _, dp = model(_train.device_images(pack, loader.dataset.crop_size, device), False)
             means.append(torch.mean(dp, dim=(0, 2, 3)))
-    if not means:
-        raise RuntimeError("train_irn: infer_list holds fewer images than one batch of %d" % loader.batch_size)
     return torch.mean(torch.stack(means), dim=0)
 
 
@@ -150,47 +126,29 @@ def _run(args):
     device = torch.device("cuda", torch.cuda.current_device())
     seed = int(getattr(args, "seed", 0))
     torch.manual_seed(seed)
-    grid = args.irn_crop_size // 4
-    path_index = indexing.PathIndex(radius=10, default_size=(grid, grid))
-    model = build_model(args, path_index)
+    crop, batch = args.irn_crop_size, args.irn_batch_size
+    model = build_model(args, indexing.PathIndex(radius=10, default_size=(crop // 4, crop // 4)))
 
     trunk = irn_trunk(args)
     n_classes = _classes.num_classes(args)
     train_dataset, infer_dataset = make_datasets(args, seed)
-    max_step = (len(train_dataset) // args.irn_batch_size) * args.irn_num_epoches
-    if max_step == 0:
-        raise RuntimeError("train_irn: train_list holds fewer images than one batch of %d" % args.irn_batch_size)
+    max_step = _train.max_steps("train_irn", "train_list", train_dataset, batch, args.irn_num_epoches)
+    optimizer = _train.two_rate_optimizer(*model.trainable_parameters(), args.irn_learning_rate, args.irn_weight_decay, max_step)
 
-    edge_params, dp_params = model.trainable_parameters()
-    optimizer = torchutils.PolyOptimizer([
-        {"params": edge_params, "lr": 1 * args.irn_learning_rate, "weight_decay": args.irn_weight_decay},
-        {"params": dp_params, "lr": 10 * args.irn_learning_rate, "weight_decay": args.irn_weight_decay},
-    ], lr=args.irn_learning_rate, weight_decay=args.irn_weight_decay, max_step=max_step)
+    def make_loader(dataset, shuffle, seed):
+        return _train.loader(dataset, batch, args.num_workers, shuffle, seed, collate(dataset))
 
-    model = model.to(device)
-    model.train()
-    timer = pyutils.Timer()
-    first, first_counts, pending = None, None, []
-    for ep in range(args.irn_num_epoches):
-        print("Epoch %d/%d" % (ep + 1, args.irn_num_epoches))
-        train_dataset.set_epoch(ep)
-        for it, pack in enumerate(_loader(train_dataset, args, True, seed + ep)):
-            img, label = device_batch(pack, args.irn_crop_size, device)
-            pending.append(train_step(model, optimizer, img, label, trunk, n_classes))
-            if first is None:
-                first = [float(v) for v in pending[0].cpu()]
-                first_counts = [int(v) for v in model.last_pair_counts.cpu()]
-            if (optimizer.global_step - 1) % 50 == 0:
-                timer.update_progress(optimizer.global_step / max_step)
-                mean = torch.stack(pending).mean(0).cpu()          # the one read-back per 50 steps
-                check_split_overflow(trunk)
-                pending = []
-                print("step:%5d/%5d" % (optimizer.global_step - 1, max_step),
-                      "loss:%.4f %.4f %.4f %.4f" % tuple(float(v) for v in mean),
-                      "imps:%.1f" % ((it + 1) * args.irn_batch_size / timer.get_stage_elapsed()),
-                      "lr: %.4f" % (optimizer.param_groups[0]["lr"]),
-                      "etc:%s" % (timer.str_estimated_complete()), flush=True)
-        timer.reset_stage()
+    first_counts = []
+
+    def step(pack):
+        img, label = _train.device_pair(pack, crop, device, reduce=4)
+        losses = train_step(model, optimizer, img, label, trunk, n_classes)
+        if not first_counts:
+            first_counts.extend(int(v) for v in model.last_pair_counts.cpu())
+        return losses
+
+    first = _train.fit(model, optimizer, train_dataset, lambda s: make_loader(train_dataset, True, s), device, args.irn_num_epoches,
+                       batch, seed, PRINT_EVERY, step, "loss:%.4f %.4f %.4f %.4f", on_report=lambda: check_split_overflow(trunk))
 
     check_split_overflow(trunk)                                    # before anything is saved
     model.eval()
@@ -198,12 +156,8 @@ def _run(args):
     # the reference, which always starts from a fresh module; an earlier checkpoint or the seeded random state do not)
     model.mean_shift.running_mean.zero_()
     print("Analyzing displacements mean ... ", end="")
-    model.mean_shift.running_mean = displacement_mean(model, _loader(infer_dataset, args, False, seed), device)
+    model.mean_shift.running_mean = displacement_mean(model, make_loader(infer_dataset, False, seed), device)
     print("done.")
 
-    out_dir = os.path.dirname(args.irn_weights_name)
-    if out_dir:
-        os.makedirs(out_dir, exist_ok=True)
-    torch.save(model.to("cpu").state_dict(), args.irn_weights_name)      # (on the host: the aliased entries stay one storage)
-    torch.cuda.empty_cache()
-    return {"first_losses": first, "first_counts": first_counts, "steps": optimizer.global_step}
+    _train.save_state(model, args.irn_weights_name)
+    return {"first_losses": [float(v) for v in first], "first_counts": first_counts, "steps": optimizer.global_step}

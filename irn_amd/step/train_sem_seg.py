@@ -7,34 +7,29 @@ Reads  args.train_list, args.voc12_root, args.seg_label_dir (default args.sem_se
        args.seg_augment, args.seg_loss, args.num_classes
 Writes args.seg_weights_name + '.pth': the state dict of net.resnet50_seg.Net, which infer_sem_seg loads
 
-train_cam's loop on another network and another loss.  The (image, label) batch is built on the GPU (`--seg_augment device`,
-the default): the loader workers hand over the decoded image, the label map and the augmentation's draws, and
-`ops.augment_pair_batch(..., reduce=1)` rescales, normalises, mirrors and crops both (irn_amd/csrc/augment.hip), bit for bit
-what the PIL / numpy pipeline gives for the same draws — `--seg_augment host` runs that pipeline in the workers instead.  The
-loss is `ops.seg_cross_entropy(model.forward_train(img), label, 16)`: bilinear upsampling of the stride-16 logits, softmax
-cross-entropy over the pixels whose label is a class of the dataset (255, the crop's fill, and any byte above --num_classes are
-ignored) and its backward in one HIP pass each (irn_amd/csrc/seg_loss.hip): no [B, C, crop, crop] tensor exists and no float
-atomic takes part in a gradient.  `--seg_loss composed` is F.interpolate -> F.cross_entropy(ignore_index=255), for comparison:
-three such tensors, and ATen's scattering upsample backward, so not reproducible.  The draws of an item come from (seed, epoch,
-index) and the shuffle from seed + epoch; in the reproducible mode (IRN_DETERMINISTIC, default 1) two runs write the same file
-whatever the number of loader workers.  Initial weights: `--seg_init_weights` (a state dict loaded non-strictly: a bare
-ResNet-50 trunk such as the ImageNet one, a CAM checkpoint, or an earlier file of this step), else the seeded random state of
-net.weights; nothing is downloaded.
+The shared loop (irn_amd/step/_train.py) on its own network and loss.  The (image, label) batch is built on the GPU
+(`--seg_augment device`, the default): the loader workers hand over the decoded image, the label map and the augmentation's
+draws, and `ops.augment_pair_batch(..., reduce=1)` rescales, normalises, mirrors and crops both (irn_amd/csrc/augment.hip),
+bit for bit what the PIL / numpy pipeline gives for the same draws — `--seg_augment host` runs that pipeline in the workers
+instead.  The loss is `ops.seg_cross_entropy(model.forward_train(img), label, 16)`: bilinear upsampling of the stride-16
+logits, softmax cross-entropy over the pixels whose label is a class of the dataset (255, the crop's fill, and any byte above
+--num_classes are ignored) and its backward in one HIP pass each (irn_amd/csrc/seg_loss.hip): no [B, C, crop, crop] tensor
+exists and no float atomic takes part in a gradient.  `--seg_loss composed` is F.interpolate ->
+F.cross_entropy(ignore_index=255), for comparison: three such tensors, and ATen's scattering upsample backward, so not
+reproducible.  In the reproducible mode (IRN_DETERMINISTIC, default 1) two runs write the same file whatever the number of
+loader workers.  Initial weights: `--seg_init_weights` (a state dict loaded non-strictly: a bare ResNet-50 trunk such as the
+ImageNet one, a CAM checkpoint, or an earlier file of this step), else the seeded random state of net.weights; nothing is
+downloaded.
 """
-import os
-
 import torch
 import torch.nn.functional as F
-from torch.utils.data import DataLoader
 
 from .. import _tuned
-from ..misc import pyutils, torchutils
 from ..net import weights
 from ..net.resnet50_seg import OUTPUT_STRIDE, Net
 from ..voc12 import dataloader
-from . import _classes
+from . import _classes, _train
 
-MAX_LOADER_WORKERS = 8
 PRINT_EVERY = 50
 
 
@@ -42,13 +37,8 @@ def build_model(args):
     c = _classes.num_classes(args)
     model = Net(n_classes=c)
     init = getattr(args, "seg_init_weights", None)
-    if init:
-        state = torch.load(init, map_location="cpu", weights_only=True)
-        if "conv1.weight" in state:          # a bare trunk: its keys are the `resnet50.` ones (the stages alias them)
-            state = {"resnet50." + k: v for k, v in state.items() if not k.startswith("fc.")}
-        state = {k: v for k, v in state.items() if not k.startswith("classifier.")}      # a CAM checkpoint's read-out
-    else:
-        state = weights.random_seg_state(n_classes=c)
+    # (`classifier.`: a CAM checkpoint's read-out)
+    state = _train.init_state(init, drop=("classifier.",)) if init else weights.random_seg_state(n_classes=c)
     model.load_state_dict(state, strict=False)
     return model
 
@@ -66,22 +56,6 @@ def make_dataset(args, seed):
                                            hor_flip=True, crop_size=args.seg_crop_size, crop_method="random",
                                            rescale=tuple(getattr(args, "seg_rescale", (0.5, 1.5))), seed=seed,
                                            raw=device_augment(args), reduce=1)
-
-
-def _loader(dataset, args, shuffle, seed):
-    gen = torch.Generator().manual_seed(seed)
-    return DataLoader(dataset, batch_size=args.seg_batch_size, shuffle=shuffle, drop_last=True, pin_memory=not dataset.raw,
-                      num_workers=max(0, min(int(args.num_workers), MAX_LOADER_WORKERS)), generator=gen,
-                      collate_fn=dataloader.affinity_collate)
-
-
-def device_batch(pack, crop, device):
-    """Loader batch -> (GPU fp32 [B,3,crop,crop], GPU uint8 [B,crop,crop]): raw items through `ops.augment_pair_batch`, the
-    host pipeline's arrays as they are."""
-    if "aug" in pack:
-        from .. import ops
-        return ops.augment_pair_batch(pack["img"], pack["label_map"], pack["aug"], crop, reduce=1, device=device)
-    return pack["img"].to(device, non_blocking=True), pack["label"].to(device, non_blocking=True).contiguous()
 
 
 def composed_loss(logits, label, factor):
@@ -126,50 +100,24 @@ def _run(args):
     device = torch.device("cuda", torch.cuda.current_device())
     seed = int(getattr(args, "seed", 0))
     torch.manual_seed(seed)
-    crop = int(args.seg_crop_size)
+    crop, batch = int(args.seg_crop_size), args.seg_batch_size
     if crop % OUTPUT_STRIDE:
         raise ValueError("train_sem_seg: --seg_crop_size %d is no multiple of %d" % (crop, OUTPUT_STRIDE))
     kind = seg_loss(args)
     model = build_model(args)
 
     train_dataset = make_dataset(args, seed)
-    max_step = (len(train_dataset) // args.seg_batch_size) * args.seg_num_epoches
-    if max_step == 0:
-        raise RuntimeError("train_sem_seg: train_list holds fewer images than one batch of %d" % args.seg_batch_size)
+    max_step = _train.max_steps("train_sem_seg", "train_list", train_dataset, batch, args.seg_num_epoches)
+    optimizer = _train.two_rate_optimizer(*model.trainable_parameters(), args.seg_learning_rate, args.seg_weight_decay, max_step)
 
-    backbone_params, new_params = model.trainable_parameters()
-    optimizer = torchutils.PolyOptimizer([
-        {"params": backbone_params, "lr": args.seg_learning_rate, "weight_decay": args.seg_weight_decay},
-        {"params": new_params, "lr": 10 * args.seg_learning_rate, "weight_decay": args.seg_weight_decay},
-    ], lr=args.seg_learning_rate, weight_decay=args.seg_weight_decay, max_step=max_step)
+    def make_loader(seed):
+        return _train.loader(train_dataset, batch, args.num_workers, True, seed, dataloader.affinity_collate)
 
-    model = model.to(device)
-    model.train()
-    timer = pyutils.Timer()
-    first, pending = None, []
-    for ep in range(args.seg_num_epoches):
-        print("Epoch %d/%d" % (ep + 1, args.seg_num_epoches))
-        train_dataset.set_epoch(ep)
-        for it, pack in enumerate(_loader(train_dataset, args, True, seed + ep)):
-            img, label = device_batch(pack, crop, device)
-            pending.append(train_step(model, optimizer, img, label, kind))
-            if first is None:
-                first = float(pending[0])
-            if (optimizer.global_step - 1) % PRINT_EVERY == 0:
-                timer.update_progress(optimizer.global_step / max_step)
-                mean = float(torch.stack(pending).mean())          # the one read-back per 50 steps
-                pending = []
-                print("step:%5d/%5d" % (optimizer.global_step - 1, max_step),
-                      "loss:%.4f" % mean,
-                      "imps:%.1f" % ((it + 1) * args.seg_batch_size / timer.get_stage_elapsed()),
-                      "lr: %.4f" % (optimizer.param_groups[0]["lr"]),
-                      "etc:%s" % (timer.str_estimated_complete()), flush=True)
-        timer.reset_stage()
+    def step(pack):
+        img, label = _train.device_pair(pack, crop, device, reduce=1)
+        return train_step(model, optimizer, img, label, kind)
 
-    out = args.seg_weights_name + ".pth"
-    out_dir = os.path.dirname(out)
-    if out_dir:
-        os.makedirs(out_dir, exist_ok=True)
-    torch.save(model.to("cpu").state_dict(), out)      # (on the host: the aliased entries stay one storage)
-    torch.cuda.empty_cache()
-    return {"first_loss": first, "steps": optimizer.global_step}
+    first = _train.fit(model, optimizer, train_dataset, make_loader, device, args.seg_num_epoches, batch, seed, PRINT_EVERY, step,
+                       "loss:%.4f")
+    _train.save_state(model, args.seg_weights_name + ".pth")
+    return {"first_loss": float(first), "steps": optimizer.global_step}

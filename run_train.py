@@ -33,16 +33,21 @@ def build_parser():
     return p
 
 
+def start(args):
+    """The preamble of the three training commands: the process's mode from --deterministic, the log file, the flags."""
+    if args.deterministic is not None:
+        os.environ["IRN_DETERMINISTIC"] = str(int(args.deterministic))
+    pyutils.Logger(args.log_name + ".log")
+    print(vars(args))
+
+
 def main(argv=None):
     """Runs cam_to_ir_label and train_irn where their pass flags ask for them; returns {step name: what the step returned}."""
     args = build_parser().parse_args(argv)
     if args.train_cam_pass:
         raise SystemExit("--train_cam_pass: CAM training is run by `python run_train_cam.py`, not from here")
     run_sample.apply_split_gemm(args, auto=False)       # training keeps the end-of-step fp16-range check: "auto" runs as 1
-    if args.deterministic is not None:
-        os.environ["IRN_DETERMINISTIC"] = str(int(args.deterministic))
-    pyutils.Logger(args.log_name + ".log")
-    print(vars(args))
+    start(args)
     results = {}
     if args.cam_to_ir_label_pass is True:
         from irn_amd.step import _common, cam_to_ir_label

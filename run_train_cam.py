@@ -9,8 +9,6 @@ The flags are run_train.py's (the `cam_*` hyper-parameters, --train_list, --val_
 --deterministic) plus --cam_init_weights, --cam_resize_long, --cam_augment and --cam_fused_tail.  The step has a command of its own because
 run_sample.py and run_train.py keep refusing `--train_cam_pass True`; the pass flags are parsed and ignored here.
 """
-import os
-
 import run_train
 from irn_amd.misc import pyutils
 
@@ -36,10 +34,7 @@ def main(argv=None):
     """Runs train_cam; returns {"train_cam": what the step returned}."""
     args = build_parser().parse_args(argv)
     args.cam_resize_long = tuple(args.cam_resize_long)
-    if args.deterministic is not None:
-        os.environ["IRN_DETERMINISTIC"] = str(int(args.deterministic))
-    pyutils.Logger(args.log_name + ".log")
-    print(vars(args))
+    run_train.start(args)
     from irn_amd.step import train_cam
     timer = pyutils.Timer("step.train_cam:")  # noqa: F841
     return {"train_cam": train_cam.run(args)}

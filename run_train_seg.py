@@ -12,7 +12,6 @@ The flags are run_train.py's (--train_list, --infer_list, --chainer_eval_set, --
 run_sample.py, run_train.py and run_train_cam.py are unchanged.
 """
 import copy
-import os
 
 import run_sample
 import run_train
@@ -59,10 +58,7 @@ def main(argv=None):
     step returned}."""
     args = build_parser().parse_args(argv)
     args.seg_rescale = tuple(args.seg_rescale)
-    if args.deterministic is not None:
-        os.environ["IRN_DETERMINISTIC"] = str(int(args.deterministic))
-    pyutils.Logger(args.log_name + ".log")
-    print(vars(args))
+    run_train.start(args)
     results = {}
     if args.train_sem_seg_pass is True:
         from irn_amd.step import train_sem_seg

@@ -186,19 +186,18 @@ def test_raw_image_item_is_the_top_left_form(voc):
 
 def test_collate_and_loader_forms(voc):
     import argparse
-    from irn_amd.step import train_irn
+    from irn_amd.step import _train, train_irn
     raw, host = _affinity(voc, True), _affinity(voc, False)
     pack = dataloader.affinity_collate([raw[0], raw[1]])
     assert isinstance(pack["img"], list) and isinstance(pack["label_map"], list) and len(pack["aug"]) == 2 and len(pack["size"]) == 2
     pack = dataloader.affinity_collate([host[0], host[1]])
     assert tuple(pack["img"].shape) == (2, 3, 96, 96) and pack["label"].dtype == torch.uint8 and "aug" not in pack
-    ns = argparse.Namespace(irn_batch_size=2, num_workers=0)
-    a = next(iter(train_irn._loader(host, ns, True, 7)))
-    b = next(iter(train_irn._loader(raw, ns, True, 7)))
+    a = next(iter(_train.loader(host, 2, 0, True, 7, train_irn.collate(host))))
+    b = next(iter(_train.loader(raw, 2, 0, True, 7, train_irn.collate(raw))))
     assert a["name"] == b["name"] and tuple(a["label"].shape) == (2, 24, 24) and len(b["label_map"]) == 2
     root, lst, _ = voc
     img_raw = dataloader.VOC12ImageDataset(lst, voc12_root=root, crop_size=96, raw=True)
-    c = next(iter(train_irn._loader(img_raw, ns, False, 7)))
+    c = next(iter(_train.loader(img_raw, 2, 0, False, 7, train_irn.collate(img_raw))))
     assert "label_map" not in c and len(c["img"]) == 2 and c["aug"][0][2] == 0
     assert train_irn.device_augment(argparse.Namespace()) and not train_irn.device_augment(argparse.Namespace(irn_augment="host"))
     ns = argparse.Namespace(train_list=lst, infer_list=lst, ir_label_out_dir=voc[2], voc12_root=root, irn_crop_size=96, irn_augment="host")

@@ -489,14 +489,13 @@ def test_same_seed_same_first_step(trained):
     and a second run in one process may be served by another MIOpen convolution algorithm than the first (which searched);
     convolutions of up to 2048 x 9 fp32 terms re-associated differ by ~1e-6 relative, so 1e-5 (~150 fp32 ulps) is allowed —
     another seed changes crops and flips and moves the losses in their second digit."""
-    import argparse
-    from irn_amd.step import train_irn
+    from irn_amd.step import _train, train_irn
     from irn_amd.voc12 import dataloader
 
     def first_batch(seed, workers):
         ds = dataloader.VOC12AffinityDataset(trained["lst"], label_dir=trained["label_dir"], voc12_root=trained["root"], hor_flip=True,
                                              crop_size=96, crop_method="random", rescale=(0.5, 1.5), seed=seed)
-        pack = next(iter(train_irn._loader(ds, argparse.Namespace(irn_batch_size=2, num_workers=workers), True, seed)))
+        pack = next(iter(_train.loader(ds, 2, workers, True, seed, train_irn.collate(ds))))
         return pack["name"], pack["img"], pack["label"]
 
     a, b, c = first_batch(4, 2), first_batch(4, 0), first_batch(5, 0)

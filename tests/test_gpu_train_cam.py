@@ -2,9 +2,7 @@
 initial weights.  Two identical steps give identical bits and leave stages 1-2 alone; the training forward with its frozen
 half under `no_grad` is as close to fp64 as the reference's detach formulation; two fresh processes, the loader with and
 without workers, write the same checkpoint; the device and the host input pipelines give the same first loss."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -14,26 +12,14 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _augment_ref as A  # noqa: E402
+from _train_cases import reproducible_mode, run_child  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FROZEN = ("resnet50.conv1.", "resnet50.bn1.", "resnet50.layer1.", "resnet50.layer2.")
 
 
 def _dev():
     return torch.device("cuda", 0)
-
-
-@pytest.fixture()
-def reproducible_mode(monkeypatch):
-    """The process's mode as `train_cam.run` establishes it, put back afterwards."""
-    from irn_amd.net import resnet50 as _r50
-    from irn_amd.step import _common
-    saved = (torch.backends.cudnn.deterministic, _r50.DETERMINISTIC)
-    monkeypatch.setenv("IRN_DETERMINISTIC", "1")
-    _common.apply_deterministic_setting()
-    yield
-    torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
 
 
 @pytest.fixture(scope="module")
@@ -121,14 +107,6 @@ def test_frozen_half_under_no_grad_is_as_close_to_fp64_as_the_detach_formulation
         assert eb <= 4 * ea, "%s: forward_train %.3e against %.3e for the detach formulation" % (what, eb, ea)
 
 
-CHILD = """
-import json, sys
-import run_train_cam
-res = run_train_cam.main(sys.argv[2:])["train_cam"]
-json.dump(res, open(sys.argv[1], "w"))
-"""
-
-
 def _argv(root, lst, out, workers, log, augment="device"):
     return ["--voc12_root", root, "--train_list", lst, "--val_list", lst, "--cam_crop_size", "64", "--cam_batch_size", "2",
             "--cam_num_epoches", "1", "--cam_resize_long", "48", "96", "--num_workers", str(workers), "--cam_weights_name", out,
@@ -146,18 +124,14 @@ def test_two_processes_write_the_same_checkpoint(tmp_path):
     from irn_amd.net.resnet50_cam import CAM, Net
     root = str(tmp_path)
     lst = A.write_voc(root, 4)                                 # four 120x140 images; batch 2 -> 2 steps
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    env.pop("IRN_DETERMINISTIC", None)                         # the default mode is the reproducible one
     runs = []
     for tag, workers in (("a", 0), ("b", 2)):
         out = os.path.join(root, "sess_" + tag, "res50_cam")
         argv = _argv(root, lst, out, workers, os.path.join(root, "log_" + tag))
-        done = subprocess.run([sys.executable, "-c", CHILD, out + ".json"] + argv, cwd=ROOT, env=env, timeout=300,
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert done.returncode == 0, "run %s failed:\n%s" % (tag, done.stdout[-3000:])      # stop at the first failure
-        res = json.load(open(out + ".json"))
+        res, stdout = run_child("run_train_cam", argv, out + ".json")                            # stops at the first failure
+        res = res["train_cam"]
         assert res["steps"] == 2 and len(res["val_losses"]) == 1 and np.isfinite(res["val_losses"]).all()
-        assert "validating ... loss:" in done.stdout and "step:    0/    2 loss:" in done.stdout
+        assert "validating ... loss:" in stdout and "step:    0/    2 loss:" in stdout
         runs.append((res, torch.load(out + ".pth", map_location="cpu", weights_only=True), out + ".pth"))
     (res0, state0, path0), (res1, state1, _) = runs
     print("\nfirst loss a: %r / b: %r" % (res0["first_loss"], res1["first_loss"]))

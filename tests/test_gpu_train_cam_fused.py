@@ -2,10 +2,8 @@
 the shapes of tests/test_gpu_train_cam.py: crop 64, batch 2, random initial weights.  Two identical steps give identical bits
 and leave stages 1-2 alone; logits and every trained parameter's gradient are as close to fp64 as the composed fp32 path's;
 two fresh processes write the same checkpoint; `--cam_fused_tail 0` is the run without the flag."""
-import json
 import os
 import struct
-import subprocess
 import sys
 
 import numpy as np
@@ -15,26 +13,14 @@ import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _augment_ref as A  # noqa: E402
+from _train_cases import reproducible_mode, run_child  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FROZEN = ("resnet50.conv1.", "resnet50.bn1.", "resnet50.layer1.", "resnet50.layer2.")
 
 
 def _dev():
     return torch.device("cuda", 0)
-
-
-@pytest.fixture()
-def reproducible_mode(monkeypatch):
-    """The process's mode as `train_cam.run` establishes it, put back afterwards."""
-    from irn_amd.net import resnet50 as _r50
-    from irn_amd.step import _common
-    saved = (torch.backends.cudnn.deterministic, _r50.DETERMINISTIC)
-    monkeypatch.setenv("IRN_DETERMINISTIC", "1")
-    _common.apply_deterministic_setting()
-    yield
-    torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
 
 
 @pytest.fixture(scope="module")
@@ -126,14 +112,6 @@ def test_fused_tail_is_as_close_to_fp64_as_the_composed_path(reproducible_mode, 
     assert not bad, "fused tail further from fp64 than 4x the composed path: %s" % bad
 
 
-CHILD = """
-import json, sys
-import run_train_cam
-res = run_train_cam.main(sys.argv[2:])["train_cam"]
-json.dump(res, open(sys.argv[1], "w"))
-"""
-
-
 def _argv(root, lst, out, workers, log, extra=()):
     return ["--voc12_root", root, "--train_list", lst, "--val_list", lst, "--cam_crop_size", "64", "--cam_batch_size", "2",
             "--cam_num_epoches", "1", "--cam_resize_long", "48", "96", "--num_workers", str(workers), "--cam_weights_name", out,
@@ -149,17 +127,13 @@ def test_two_processes_with_the_fused_tail_write_the_same_checkpoint(tmp_path):
     from irn_amd.net.resnet50_cam import Net
     root = str(tmp_path)
     lst = A.write_voc(root, 4)                                 # four 120x140 images; batch 2 -> 2 steps
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    env.pop("IRN_DETERMINISTIC", None)                         # the default mode is the reproducible one
     runs = []
     for tag, workers in (("a", 0), ("b", 2)):
         out = os.path.join(root, "sess_" + tag, "res50_cam")
         argv = _argv(root, lst, out, workers, os.path.join(root, "log_" + tag), ("--cam_fused_tail", "1"))
-        done = subprocess.run([sys.executable, "-c", CHILD, out + ".json"] + argv, cwd=ROOT, env=env, timeout=300,
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert done.returncode == 0, "run %s failed:\n%s" % (tag, done.stdout[-3000:])      # stop at the first failure
-        assert "'cam_fused_tail': 1" in done.stdout
-        res = json.load(open(out + ".json"))
+        res, stdout = run_child("run_train_cam", argv, out + ".json")                            # stops at the first failure
+        assert "'cam_fused_tail': 1" in stdout
+        res = res["train_cam"]
         assert res["steps"] == 2 and np.isfinite(res["val_losses"]).all()
         runs.append((res, torch.load(out + ".pth", map_location="cpu", weights_only=True)))
     (res0, state0), (res1, state1) = runs

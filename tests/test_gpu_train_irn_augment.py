@@ -2,9 +2,7 @@
 --train_irn_pass True` in two fresh processes with one seed — `--irn_augment host` without loader workers, `--irn_augment
 device` with two — on four synthetic images (crop 96, batch 2, one epoch) reports the same first-step losses and writes the
 same state dict, tensor for tensor, the displacement mean included."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,23 +11,12 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _aff_loss_ref as R  # noqa: E402
+from _train_cases import run_child  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-CHILD = """
-import json, sys
-import run_train
-res = run_train.main(sys.argv[2:])["train_irn"]
-json.dump(res, open(sys.argv[1], "w"))
-"""
-
-
 def test_device_and_host_pipelines_write_the_same_checkpoint(tmp_path):
     root = str(tmp_path)
     lst, label_dir = R.write_voc(root, 4)                      # four 120x140 images; crop 96 -> grid 24x24; batch 2 -> 2 steps
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    env.pop("IRN_DETERMINISTIC", None)                         # the default mode is the reproducible one
     runs = []
     for augment, workers in (("host", 0), ("device", 2)):
         out = os.path.join(root, "sess_" + augment, "res50_irn.pth")
@@ -37,11 +24,9 @@ def test_device_and_host_pipelines_write_the_same_checkpoint(tmp_path):
                 "--irn_crop_size", "96", "--irn_batch_size", "2", "--irn_num_epoches", "1", "--num_workers", str(workers),
                 "--irn_weights_name", out, "--log_name", os.path.join(root, "log_" + augment), "--train_irn_pass", "True", "--seed", "4",
                 "--irn_augment", augment]
-        done = subprocess.run([sys.executable, "-c", CHILD, out + ".json"] + argv, cwd=ROOT, env=env, timeout=300,
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert done.returncode == 0, "run %s failed:\n%s" % (augment, done.stdout[-3000:])      # stop at the first failure
-        assert "'irn_augment': '%s'" % augment in done.stdout
-        res = json.load(open(out + ".json"))
+        res, stdout = run_child("run_train", argv, out + ".json")                                # stops at the first failure
+        assert "'irn_augment': '%s'" % augment in stdout
+        res = res["train_irn"]
         assert res["steps"] == 2
         runs.append((res["first_losses"], torch.load(out, map_location="cpu", weights_only=True)))
     (losses_h, state_h), (losses_d, state_d) = runs

@@ -3,9 +3,7 @@ shapes of tests/test_gpu_train_reproducible.py: crop 96, batch 2, radius 10.  Th
 heads plain NCHW tensors; outputs and head gradients are as close to fp64 as those of `forward` under autograd, in the
 default layout and through the channels-last -> NCHW seam; two steps give identical bits; two fresh processes write the same
 checkpoint; `--irn_trunk autograd` is the run without the flag."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -14,26 +12,14 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _aff_loss_ref as R  # noqa: E402
+from _train_cases import reproducible_mode, run_child  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADS = ("fc_edge", "fc_dp")
 
 
 def _dev():
     return torch.device("cuda", 0)
-
-
-@pytest.fixture()
-def reproducible_mode(monkeypatch):
-    """The process's mode as `train_irn.run` establishes it, put back afterwards."""
-    from irn_amd.net import resnet50 as _r50
-    from irn_amd.step import _common
-    saved = (torch.backends.cudnn.deterministic, _r50.DETERMINISTIC)
-    monkeypatch.setenv("IRN_DETERMINISTIC", "1")
-    _common.apply_deterministic_setting()
-    yield
-    torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
 
 
 @pytest.fixture(scope="module")
@@ -157,14 +143,6 @@ def test_two_steps_from_one_state_give_identical_gradient_bits(reproducible_mode
         model.fused_losses(img, label, trunk="fast")
 
 
-CHILD = """
-import json, sys
-import run_train
-res = run_train.main(sys.argv[2:])["train_irn"]
-json.dump(res, open(sys.argv[1], "w"))
-"""
-
-
 def _argv(root, lst, label_dir, out, workers, log, extra=()):
     return ["--voc12_root", root, "--train_list", lst, "--infer_list", lst, "--ir_label_out_dir", label_dir, "--irn_crop_size", "96",
             "--irn_batch_size", "2", "--irn_num_epoches", "1", "--num_workers", str(workers), "--irn_weights_name", out,
@@ -176,17 +154,13 @@ def test_two_processes_on_the_inference_trunk_write_the_same_checkpoint(tmp_path
     two: the same first-step losses and the same state dict, tensor for tensor."""
     root = str(tmp_path)
     lst, label_dir = R.write_voc(root, 4)                      # four 120x140 images; crop 96 -> grid 24x24; batch 2 -> 2 steps
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    env.pop("IRN_DETERMINISTIC", None)                         # the default mode is the reproducible one
     runs = []
     for tag, workers in (("a", 0), ("b", 2)):
         out = os.path.join(root, "sess_" + tag, "res50_irn.pth")
         argv = _argv(root, lst, label_dir, out, workers, os.path.join(root, "log_" + tag), ("--irn_trunk", "inference"))
-        done = subprocess.run([sys.executable, "-c", CHILD, out + ".json"] + argv, cwd=ROOT, env=env, timeout=300,
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert done.returncode == 0, "run %s failed:\n%s" % (tag, done.stdout[-3000:])      # stop at the first failure
-        assert "'irn_trunk': 'inference'" in done.stdout
-        res = json.load(open(out + ".json"))
+        res, stdout = run_child("run_train", argv, out + ".json")                                # stops at the first failure
+        assert "'irn_trunk': 'inference'" in stdout
+        res = res["train_irn"]
         assert res["steps"] == 2
         runs.append((res["first_losses"], torch.load(out, map_location="cpu", weights_only=True)))
     (losses0, state0), (losses1, state1) = runs

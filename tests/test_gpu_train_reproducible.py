@@ -1,9 +1,7 @@
 """The reproducible training step on the GPU (`train_irn` in the mode IRN_DETERMINISTIC=1): with the ordered backward of the
 fused loss and the gather backward of the heads' upsampling inside the model, two identical steps give identical gradient
 bits, and three fresh processes — the loader with and without workers — write the same checkpoint."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,25 +10,13 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _aff_loss_ref as R  # noqa: E402
+from _train_cases import reproducible_mode, run_child  # noqa: E402,F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _dev():
     return torch.device("cuda", 0)
-
-
-@pytest.fixture()
-def reproducible_mode(monkeypatch):
-    """The process's mode as `train_irn.run` establishes it, put back afterwards."""
-    from irn_amd.net import resnet50 as _r50
-    from irn_amd.step import _common
-    saved = (torch.backends.cudnn.deterministic, _r50.DETERMINISTIC)
-    monkeypatch.setenv("IRN_DETERMINISTIC", "1")
-    _common.apply_deterministic_setting()
-    yield
-    torch.backends.cudnn.deterministic, _r50.DETERMINISTIC = saved
 
 
 def test_two_steps_on_the_same_state_give_the_same_gradient_bits(reproducible_mode):
@@ -65,31 +51,18 @@ def test_two_steps_on_the_same_state_give_the_same_gradient_bits(reproducible_mo
     assert not differing, "head parameters whose .grad differs between two identical steps: %s" % differing
 
 
-CHILD = """
-import json, sys
-import run_train
-res = run_train.main(sys.argv[2:])["train_irn"]
-json.dump(res, open(sys.argv[1], "w"))
-"""
-
-
 def test_three_processes_write_the_same_checkpoint(tmp_path):
     """`run_train.py --train_irn_pass True` in three fresh processes — the same seed twice with no loader workers, once with
     two — writes the same state dict, tensor for tensor, and reports the same first-step losses."""
     root = str(tmp_path)
     lst, label_dir = R.write_voc(root, 4)                      # four 120x140 images; crop 96 -> grid 24x24; batch 2 -> 2 steps
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    env.pop("IRN_DETERMINISTIC", None)                         # the default mode is the reproducible one
     runs = []
     for tag, workers in (("a", 0), ("b", 0), ("c", 2)):
         out = os.path.join(root, "sess_" + tag, "res50_irn.pth")
         argv = ["--voc12_root", root, "--train_list", lst, "--infer_list", lst, "--ir_label_out_dir", label_dir,
                 "--irn_crop_size", "96", "--irn_batch_size", "2", "--irn_num_epoches", "1", "--num_workers", str(workers),
                 "--irn_weights_name", out, "--log_name", os.path.join(root, "log_" + tag), "--train_irn_pass", "True", "--seed", "4"]
-        done = subprocess.run([sys.executable, "-c", CHILD, out + ".json"] + argv, cwd=ROOT, env=env, timeout=300,
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert done.returncode == 0, "run %s failed:\n%s" % (tag, done.stdout[-3000:])      # stop at the first failure
-        res = json.load(open(out + ".json"))
+        res = run_child("run_train", argv, out + ".json")[0]["train_irn"]                         # stops at the first failure
         assert res["steps"] == 2
         runs.append((tag, res["first_losses"], torch.load(out, map_location="cpu", weights_only=True)))
     tag0, losses0, state0 = runs[0]

@@ -3,9 +3,7 @@ crop 64, batch 2, one epoch over four synthetic images, random initial weights. 
 without workers, the batch built on the host and on the device — write the same checkpoint and see the same first loss; the
 composed loss agrees with the fused one; inference writes one label map per image, the same bytes on a second run, and
 eval_sem_seg scores them."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -13,15 +11,10 @@ import pytest
 import torch
 from PIL import Image
 
-pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _train_cases import run_child  # noqa: E402
 
-CHILD = """
-import json, sys
-import run_train_seg
-res = run_train_seg.main(sys.argv[2:])
-json.dump(res, open(sys.argv[1], "w"), default=lambda v: v.tolist())
-"""
+pytestmark = pytest.mark.gpu
 
 
 def _write_tree(root, n=4):
@@ -53,15 +46,6 @@ def _argv(root, lst, label_dir, tag, workers=0, augment="device", loss="fused"):
                  "--seg_learning_rate", "1e-6"]
 
 
-def _child(argv, out_json):
-    env = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
-    env.pop("IRN_DETERMINISTIC", None)                         # the default mode is the reproducible one
-    done = subprocess.run([sys.executable, "-c", CHILD, out_json] + argv, cwd=ROOT, env=env, timeout=300,
-                          stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert done.returncode == 0, "the run failed:\n%s" % done.stdout[-3000:]
-    return json.load(open(out_json)), done.stdout
-
-
 @pytest.fixture(scope="module")
 def tree(tmp_path_factory):
     root = str(tmp_path_factory.mktemp("seg"))
@@ -75,7 +59,7 @@ def trained(tree):
     runs = {}
     for tag, workers, augment in (("a", 0, "host"), ("b", 2, "device")):
         out, argv = _argv(root, lst, label_dir, tag, workers, augment)
-        res, stdout = _child(argv, out + ".json")
+        res, stdout = run_child("run_train_seg", argv, out + ".json")
         runs[tag] = (res["train_sem_seg"], torch.load(out + ".pth", map_location="cpu", weights_only=True), out, stdout)
     return runs
 
@@ -101,7 +85,7 @@ def test_the_composed_loss_agrees_with_the_fused_one(tree, trained):
     """Two fp32 evaluations of one function on the same first batch: a sanity bound, not a precision claim."""
     root, lst, label_dir, _, _ = tree
     out, argv = _argv(root, lst, label_dir, "c", 0, "device", "composed")
-    res, _ = _child(argv, out + ".json")
+    res, _ = run_child("run_train_seg", argv, out + ".json")
     fused, composed = trained["b"][0]["first_loss"], res["train_sem_seg"]["first_loss"]
     print("\nfirst loss fused %r, composed %r" % (fused, composed))
     assert abs(composed - fused) <= 1e-4 * abs(fused)
@@ -114,7 +98,7 @@ def test_inference_writes_one_map_per_image_twice_the_same_and_is_scored(tree, t
     pred = os.path.join(root, "pred_a")
     runs = []
     for i in range(2):
-        res, stdout = _child(argv, os.path.join(root, "infer_%d.json" % i))
+        res, stdout = run_child("run_train_seg", argv, os.path.join(root, "infer_%d.json" % i))
         assert res["infer_sem_seg"] == {"images": len(names)} and "train_sem_seg" not in res
         assert sorted(os.listdir(pred)) == sorted(n + ".png" for n in names)
         runs.append((res, {n: open(os.path.join(pred, n + ".png"), "rb").read() for n in names}))

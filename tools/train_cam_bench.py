@@ -28,26 +28,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from irn_amd import synth  # noqa: E402
-
-
-def write_tree(root, n):
-    from PIL import Image
-    os.makedirs(os.path.join(root, "JPEGImages"), exist_ok=True)
-    names, labels = [], {}
-    for i in range(n):
-        name = "2008_%06d" % (i + 1)
-        h, w = synth.voc_image_size(i)
-        Image.fromarray(synth.photo(h, w, seed=i)).save(os.path.join(root, "JPEGImages", name + ".jpg"), quality=90)
-        lab = np.zeros(20, np.float32)
-        lab[synth.voc_keys(synth.voc_num_classes(i), i)] = 1
-        labels[int(name.replace("_", ""))] = lab
-        names.append(name)
-    lst = os.path.join(root, "list.txt")
-    with open(lst, "w") as f:
-        f.write("\n".join(names) + "\n")
-    np.save(os.path.join(root, "cls_labels.npy"), labels, allow_pickle=True)
-    return lst
+import _train_bench as TB  # noqa: E402
 
 
 def step_args(root, lst, a, augment):
@@ -90,58 +71,26 @@ def bench_augment(dataset, a, dev):
     return out
 
 
-def bench_host_pipeline(raw, host, n):
-    """The worker's share of a host item beyond the JPEG decode both forms pay: item(raw=False) - item(raw=True)."""
-    t_raw, t_host = [], []
-    for i in range(n):
-        t0 = time.perf_counter()
-        raw[i]
-        t1 = time.perf_counter()
-        host[i]
-        t2 = time.perf_counter()
-        t_raw.append((t1 - t0) * 1e3)
-        t_host.append((t2 - t1) * 1e3)
-    return {"images": n, "decode_only_ms_median": statistics.median(t_raw), "decode_and_augment_ms_median": statistics.median(t_host)}
-
-
 def bench_step(args, a, dev, fused_tail=False):
-    from irn_amd.misc import torchutils
     from irn_amd.net import resnet50 as _r50
-    from irn_amd.step import train_cam
+    from irn_amd.step import _train, train_cam
+    from irn_amd.voc12 import dataloader
     _r50.TRAIN_FUSED_TAIL = bool(fused_tail)
     try:
-        return _bench_step(args, a, dev, torchutils, train_cam, bool(fused_tail))
+        torch.manual_seed(0)
+        model = train_cam.build_model(args).to(dev).train()
+        train, _ = train_cam.make_datasets(args, 0)
+        opt = _train.two_rate_optimizer(*model.trainable_parameters(), 0.01, 1e-4, 10 ** 9)
+
+        def step(pack):
+            img = _train.device_images(pack, args.cam_crop_size, dev)
+            train_cam.train_step(model, opt, img, pack["label"].to(dev, non_blocking=True))
+
+        figures, _ = TB.timed_steps(train, lambda ep: _train.loader(train, a.batch, a.workers, True, ep, dataloader.classification_collate),
+                                    step, a.warmup, a.steps, a.batch)
+        return {"augment": args.cam_augment, "fused_tail": int(bool(fused_tail)), **figures}
     finally:
         _r50.TRAIN_FUSED_TAIL = False
-
-
-def _bench_step(args, a, dev, torchutils, train_cam, fused_tail):
-    torch.manual_seed(0)
-    torch.cuda.reset_peak_memory_stats()
-    model = train_cam.build_model(args).to(dev).train()
-    train, _ = train_cam.make_datasets(args, 0)
-    backbone, new = model.trainable_parameters()
-    opt = torchutils.PolyOptimizer([{"params": backbone, "lr": 0.01, "weight_decay": 1e-4}, {"params": new, "lr": 0.1, "weight_decay": 1e-4}],
-                                   lr=0.01, weight_decay=1e-4, max_step=10 ** 9)
-    done, t0 = 0, None
-    ep = 0
-    while done < a.warmup + a.steps:
-        train.set_epoch(ep)
-        for pack in train_cam._loader(train, args, True, ep):
-            if done == a.warmup:
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-            img = train_cam.device_batch(pack, args.cam_crop_size, dev)
-            train_cam.train_step(model, opt, img, pack["label"].to(dev, non_blocking=True))
-            done += 1
-            if done == a.warmup + a.steps:
-                break
-        ep += 1
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    return {"augment": args.cam_augment, "fused_tail": int(fused_tail), "steps": a.steps, "seconds": dt,
-            "images_per_s": a.steps * a.batch / dt, "ms_per_step": dt / a.steps * 1e3,
-            "max_memory_allocated_mb": torch.cuda.max_memory_allocated() / 2 ** 20}
 
 
 def main(argv=None):
@@ -163,13 +112,13 @@ def main(argv=None):
     from irn_amd.step import train_cam
     dev = torch.device("cuda", torch.cuda.current_device())
     with tempfile.TemporaryDirectory() as root:
-        lst = write_tree(root, a.images)
+        lst, _ = TB.write_tree(root, a.images, labels="cls")
         args = step_args(root, lst, a, "device")
         raw, _ = train_cam.make_datasets(args, 0)
         if not a.skip_pipeline:
             print(json.dumps({"augment": bench_augment(raw, a, dev)}), flush=True)
             host, _ = train_cam.make_datasets(step_args(root, lst, a, "host"), 0)
-            print(json.dumps({"host_pipeline": bench_host_pipeline(raw, host, min(a.images, 64))}), flush=True)
+            print(json.dumps({"host_pipeline": TB.bench_host_pipeline(raw, host, min(a.images, 64))}), flush=True)
         if not a.skip_step:
             with _tuned.process_mode():
                 for augment in () if a.skip_augment_steps else ("device", "host", "device", "host"):   # alternating: the spread shows next to the difference

@@ -32,30 +32,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from irn_amd import synth  # noqa: E402
-
-
-def write_tree(root, n, repeat=1):
-    """n synthetic VOC-size JPEGs with IR label PNGs (0 / class + 1 / 255 in 16-pixel blocks); the list names each `repeat`
-    times, so that one pass over it is long enough to time without a loader start inside; -> (list file, label dir)."""
-    from PIL import Image
-    os.makedirs(os.path.join(root, "JPEGImages"), exist_ok=True)
-    label_dir = os.path.join(root, "ir_label")
-    os.makedirs(label_dir, exist_ok=True)
-    names = []
-    for i in range(n):
-        name = "2008_%06d" % (i + 1)
-        h, w = synth.voc_image_size(i)
-        Image.fromarray(synth.photo(h, w, seed=i)).save(os.path.join(root, "JPEGImages", name + ".jpg"), quality=90)
-        values = np.asarray([0, 255] + [int(k) + 1 for k in synth.voc_keys(synth.voc_num_classes(i), i)], np.uint8)
-        rng = np.random.RandomState(i)
-        lab = rng.choice(values, (h // 16 + 1, w // 16 + 1)).repeat(16, 0).repeat(16, 1)[:h, :w]
-        Image.fromarray(np.ascontiguousarray(lab)).save(os.path.join(label_dir, name + ".png"))
-        names.append(name)
-    lst = os.path.join(root, "list.txt")
-    with open(lst, "w") as f:
-        f.write("\n".join(names * repeat) + "\n")
-    return lst, label_dir
+import _train_bench as TB  # noqa: E402
 
 
 def step_args(root, lst, label_dir, a, augment):
@@ -99,44 +76,22 @@ def bench_augment(dataset, a, dev):
     return out
 
 
-def bench_host_pipeline(raw, host, n):
-    """The worker's share of a host item beyond the decodes both forms pay: item(raw=False) - item(raw=True)."""
-    t_raw, t_host = [], []
-    for i in range(n):
-        t0 = time.perf_counter()
-        raw[i]
-        t1 = time.perf_counter()
-        host[i]
-        t2 = time.perf_counter()
-        t_raw.append((t1 - t0) * 1e3)
-        t_host.append((t2 - t1) * 1e3)
-    return {"images": n, "decode_only_ms_median": statistics.median(t_raw), "decode_and_augment_ms_median": statistics.median(t_host)}
-
-
 def bench_step(args, a, dev, model, optimizer, trunk="autograd"):
     from irn_amd.net import resnet50 as _r50
-    from irn_amd.step import train_irn
+    from irn_amd.step import _train, train_irn
     train, _ = train_irn.make_datasets(args, 0)
-    torch.cuda.reset_peak_memory_stats()
     before = {k: _r50.PASS_STATS[k] for k in ("channels_last", "nchw", "pad_rows")}
     assert len(train) >= (a.warmup + a.steps) * a.batch          # one pass: the loader's start lies in the warm-up
-    done, t0 = 0, None
-    for pack in train_irn._loader(train, args, True, 0):
-        if done == a.warmup:
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-        img, label = train_irn.device_batch(pack, args.irn_crop_size, dev)
+
+    def step(pack):
+        img, label = _train.device_pair(pack, args.irn_crop_size, dev, reduce=4)
         train_irn.train_step(model, optimizer, img, label, trunk)
-        done += 1
-        if done == a.warmup + a.steps:
-            break
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
+
+    figures, _ = TB.timed_steps(train, lambda ep: _train.loader(train, a.batch, a.workers, True, ep, train_irn.collate(train)),
+                                step, a.warmup, a.steps, a.batch)
     train_irn.check_split_overflow(trunk)
-    return {"augment": args.irn_augment, "irn_trunk": trunk, "workers": a.workers, "steps": a.steps, "seconds": dt,
-            "images_per_s": a.steps * a.batch / dt, "ms_per_step": dt / a.steps * 1e3,
-            "trunk_passes": {k: _r50.PASS_STATS[k] - before[k] for k in before},
-            "max_memory_allocated_mb": torch.cuda.max_memory_allocated() / 2 ** 20}
+    return {"augment": args.irn_augment, "irn_trunk": trunk, "workers": a.workers, **figures,
+            "trunk_passes": {k: _r50.PASS_STATS[k] - before[k] for k in before}}
 
 
 def main(argv=None):
@@ -156,18 +111,18 @@ def main(argv=None):
     a = p.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit("train_irn_bench needs a GPU")
-    from irn_amd.misc import indexing, torchutils
     from irn_amd import _tuned
-    from irn_amd.step import train_irn
+    from irn_amd.misc import indexing
+    from irn_amd.step import _train, train_irn
     dev = torch.device("cuda", torch.cuda.current_device())
     with tempfile.TemporaryDirectory() as root:
-        lst, label_dir = write_tree(root, a.images, repeat=-(-(a.warmup + a.steps) * a.batch // a.images))
+        lst, label_dir = TB.write_tree(root, a.images, labels="ir", repeat=-(-(a.warmup + a.steps) * a.batch // a.images))
         args = step_args(root, lst, label_dir, a, "device")
         raw, _ = train_irn.make_datasets(args, 0)
         if not a.skip_pipeline:
             print(json.dumps({"augment_pair": bench_augment(raw, a, dev)}), flush=True)
             host, _ = train_irn.make_datasets(step_args(root, lst, label_dir, a, "host"), 0)
-            print(json.dumps({"host_pipeline": bench_host_pipeline(raw, host, min(a.images, 64))}), flush=True)
+            print(json.dumps({"host_pipeline": TB.bench_host_pipeline(raw, host, min(a.images, 64))}), flush=True)
         if not a.skip_step:
             trunks = ("autograd", "inference") if a.irn_trunk == "both" else (a.irn_trunk,)
             with _tuned.process_mode():
@@ -176,9 +131,7 @@ def main(argv=None):
                 torch.manual_seed(0)
                 grid = a.crop // 4
                 model = train_irn.build_model(args, indexing.PathIndex(radius=10, default_size=(grid, grid))).to(dev).train()
-                edge, dp = model.trainable_parameters()
-                opt = torchutils.PolyOptimizer([{"params": edge, "lr": 0.01, "weight_decay": 1e-4}, {"params": dp, "lr": 0.1, "weight_decay": 1e-4}],
-                                               lr=0.01, weight_decay=1e-4, max_step=10 ** 9)
+                opt = _train.two_rate_optimizer(*model.trainable_parameters(), 0.01, 1e-4, 10 ** 9)
                 for augment in tuple(a.augments) * a.rounds:
                     for trunk in trunks:
                         print(json.dumps({"step": bench_step(step_args(root, lst, label_dir, a, augment), a, dev, model, opt, trunk)}), flush=True)

@@ -14,33 +14,13 @@ import json
 import os
 import sys
 import tempfile
-import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import torch  # noqa: E402
 
-from irn_amd import synth  # noqa: E402
-
-
-def write_tree(root, n):
-    """JPEGs of VOC sizes and blob label maps (0, two classes, 255 between them) as `result/sem_seg` would hold them."""
-    from PIL import Image
-    os.makedirs(os.path.join(root, "JPEGImages"))
-    os.makedirs(os.path.join(root, "sem_seg"))
-    names = []
-    for i in range(n):
-        name = "2008_%06d" % (i + 1)
-        h, w = synth.voc_image_size(i)
-        Image.fromarray(synth.photo(h, w, seed=i)).save(os.path.join(root, "JPEGImages", name + ".jpg"), quality=90)
-        cls, _ = synth.blob_ground_truth(synth.cam_blobs(2, h, w, seed=i), [i % 20, (i + 7) % 20], 0.5, 0.35)
-        Image.fromarray(cls).save(os.path.join(root, "sem_seg", name + ".png"))
-        names.append(name)
-    lst = os.path.join(root, "list.txt")
-    with open(lst, "w") as f:
-        f.write("\n".join(names) + "\n")
-    return lst
+import _train_bench as TB  # noqa: E402
 
 
 def step_args(root, lst, a, loss):
@@ -51,34 +31,21 @@ def step_args(root, lst, a, loss):
 
 
 def bench_step(args, a, dev):
-    from irn_amd.misc import torchutils
-    from irn_amd.step import train_sem_seg
+    from irn_amd.step import _train, train_sem_seg
+    from irn_amd.voc12 import dataloader
     torch.manual_seed(0)
-    torch.cuda.reset_peak_memory_stats()
     model = train_sem_seg.build_model(args).to(dev).train()
     train = train_sem_seg.make_dataset(args, 0)
-    backbone, new = model.trainable_parameters()
     # the seeded random weights give large logits: a rate that keeps every step finite (the step's cost does not depend on it)
-    opt = torchutils.PolyOptimizer([{"params": backbone, "lr": 1e-6, "weight_decay": 5e-4}, {"params": new, "lr": 1e-5, "weight_decay": 5e-4}],
-                                   lr=1e-6, weight_decay=5e-4, max_step=10 ** 9)
-    done, t0, ep, last = 0, None, 0, None
-    while done < a.warmup + a.steps:
-        train.set_epoch(ep)
-        for pack in train_sem_seg._loader(train, args, True, ep):
-            if done == a.warmup:
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-            img, label = train_sem_seg.device_batch(pack, args.seg_crop_size, dev)
-            last = train_sem_seg.train_step(model, opt, img, label, args.seg_loss)
-            done += 1
-            if done == a.warmup + a.steps:
-                break
-        ep += 1
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
-    return {"seg_loss": args.seg_loss, "batch": a.batch, "crop": a.crop, "steps": a.steps, "seconds": dt,
-            "images_per_s": a.steps * a.batch / dt, "ms_per_step": dt / a.steps * 1e3, "last_loss": float(last),
-            "max_memory_allocated_mb": torch.cuda.max_memory_allocated() / 2 ** 20}
+    opt = _train.two_rate_optimizer(*model.trainable_parameters(), 1e-6, 5e-4, 10 ** 9)
+
+    def step(pack):
+        img, label = _train.device_pair(pack, args.seg_crop_size, dev, reduce=1)
+        return train_sem_seg.train_step(model, opt, img, label, args.seg_loss)
+
+    figures, last = TB.timed_steps(train, lambda ep: _train.loader(train, a.batch, a.workers, True, ep, dataloader.affinity_collate),
+                                   step, a.warmup, a.steps, a.batch)
+    return {"seg_loss": args.seg_loss, "batch": a.batch, "crop": a.crop, **figures, "last_loss": float(last)}
 
 
 def main(argv=None):
@@ -96,7 +63,7 @@ def main(argv=None):
     from irn_amd import _tuned
     dev = torch.device("cuda", torch.cuda.current_device())
     with tempfile.TemporaryDirectory() as root:
-        lst = write_tree(root, a.images)
+        lst, _ = TB.write_tree(root, a.images, labels="sem_seg")
         with _tuned.process_mode():
             for loss in ("fused", "composed") * a.rounds:
                 print(json.dumps({"step": bench_step(step_args(root, lst, a, loss), a, dev)}), flush=True)

@@ -43,7 +43,7 @@ extern "C" {
 /* The version of this header's argument lists.  irn_version() returns the IRN_ABI_VERSION the library was built with, and
  * it moves whenever an entry's arguments change: a binding that finds another value has loaded a library of another commit
  * (irn_amd/_lib.py refuses to import it). */
-#define IRN_ABI_VERSION 105
+#define IRN_ABI_VERSION 106
 int irn_version(void);
 const char *irn_last_error(void);
 
@@ -165,6 +165,32 @@ int irn_seg_loss_forward(const float *logits, const uint8_t *label, int batch, i
 int irn_seg_loss_backward(const float *logits, const uint8_t *label, const double *lse, const float *coef, int batch, int C, int h,
                           int w, int factor, int H, int W, float *grad_logits, void *ws, size_t ws_bytes, void *stream);
 int irn_seg_argmax(const float *logits, int batch, int C, int h, int w, int factor, int H, int W, uint8_t *out, void *stream);
+
+/* Multi-scale segmentation inference of ONE image in one launch: the mean over M logit maps of different sizes
+ * of the softmax of their bilinear upsampling to the image's size, and its arg-max, without any [C, H, W] tensor but the one
+ * asked for.
+ *   maps HOST array of M device pointers, 1 <= M <= IRN_SEG_FUSE_MAX_MAPS: maps[m] dev fp32 [C, h[m], w[m]], contiguous.
+ *   h, w, Hs, Ws HOST int32 [M]: the map's size, and the size Hs[m] x Ws[m] of the rescaled image it was computed from.
+ *   stride 1..64 (the network's output stride), C 2..IRN_EVAL_MAX_CLASSES, output H x W, each 1..32768, as are h[m] and w[m].
+ *   1 <= Hs[m] <= h[m] * stride and Hs[m] <= stride * H (a map is never finer than the output), likewise the widths.
+ * Definition (not claimed bit-equal to any torch op):
+ *   ry_m = (float)((double)Hs[m] / ((double)stride * H)), rx_m likewise;
+ *   z_m[c, Y, X] = upsample_blend over upsample_tap(Y, h[m], ry_m) and upsample_tap(X, w[m], rx_m), the device functions of
+ *     irn_upsample_bilinear and irn_seg_argmax (for Hs[m] == H theirs bit for bit), every operation rounded;
+ *   p_m = softmax_c(z_m) in fp32 with the maximum subtracted: exp(z - max) * (1 / sum); finite logits of any size neither
+ *     overflow nor give NaN;
+ *   P = (p_0 + p_1 + ... + p_{M-1}) * (float)(1.0 / M), added in map order in fp32;
+ *   label[Y, X] = the first class that attains the maximum of P, a NaN counting as the maximum (irn_seg_argmax's rule).
+ * Outputs, either may be NULL but not both: label dev uint8 [H, W], prob dev fp32 [C, H, W] (= P).  Every element is written
+ * once with a plain store: no atomics, nothing synchronises, identical inputs give identical bits, and label is the arg-max
+ * of the very P that prob receives.
+ * A workgroup owns a T x T tile of the output and keeps, for all maps at once, the cells its taps touch in LDS; T is the
+ * largest of 32, 16, 8 at which that fits in 64 KB.  Null pointers, M, C, stride or a size outside its range, a misaligned
+ * pointer and a geometry that fits at no T give IRN_ERR_ARG with the entry and the argument named, before any device is
+ * touched. */
+#define IRN_SEG_FUSE_MAX_MAPS 16
+int irn_seg_fuse(const float *const *maps, const int32_t *h, const int32_t *w, const int32_t *Hs, const int32_t *Ws, int M, int C,
+                 int stride, int H, int W, uint8_t *label, float *prob, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Random-walk context  (replaces misc/indexing.py:141-165 `propagate_to_edge` and everything it
@@ -699,6 +725,14 @@ int irn_argmax_rethreshold_batch(int n_images, const float *const *rw_up_dev, co
  *   zeros (Q = 1) and needs no workspace.  c + 1 <= 32.  Bad arguments give IRN_ERR_ARG before any
  *   device work, a short workspace IRN_ERR_STATE.  Nothing synchronises.
  *   workspace: irn_crf_score_sweep_workspace_bytes(h, w, n_labels = c+1, t_count) (0 = unsupported).
+ * irn_crf_prob: the CRF seeded with PROBABILITIES (infer_sem_seg --seg_crf_iters).  prob dev
+ *   fp32 [l][h][w], 2 <= l <= 32 (the prob of irn_seg_fuse): -U_i = log(max(p_i, 1e-5)); a pixel with a NaN
+ *   has s' = 1 at its first NaN channel and 1e-5 at every other one (irn_crf_score_sweep's rule).
+ *   Pairwise terms, the t iterations and the softmax are those above.  labels dev uint8 [h][w] is the
+ *   first maximum of Q, the label index itself; q_dev (dev fp32 [l][h][w], may be NULL) receives Q.
+ *   t == 0 gives the arg-max of the clipped, normalised prob.  Bad arguments give IRN_ERR_ARG before any
+ *   device work, a short workspace IRN_ERR_STATE.  Nothing synchronises.
+ *   workspace: irn_crf_prob_workspace_bytes(h, w, l) (0 = unsupported, l outside 2..32 included).
  * ------------------------------------------------------------------------------------------- */
 #define IRN_CRF_MAX_SWEEP 16
 size_t irn_crf_filter_workspace_bytes(int n, int d, int channels);
@@ -719,6 +753,9 @@ size_t irn_crf_score_sweep_workspace_bytes(int h, int w, int n_labels, int t_cou
 int irn_crf_score_sweep(const uint8_t *rgb_dev, const float *scores_dev, const int64_t *keys_dev, int c, int h, int w,
                         const float *thres, int t_count, int t, uint8_t *planes_dev, float *q_dev, void *ws,
                         size_t ws_bytes, void *stream);
+size_t irn_crf_prob_workspace_bytes(int h, int w, int l);
+int irn_crf_prob(const uint8_t *rgb_dev, const float *prob_dev, int l, int h, int w, int t, uint8_t *labels_dev, float *q_dev,
+                 void *ws, size_t ws_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Evaluation counts  (replace the chainercv counting behind step/eval_cam.py:10-20,

@@ -24,7 +24,7 @@ lib = C.CDLL(LIB_PATH)
 
 # The bindings below are by name only, so a library built from another commit would be called with argument lists it
 # does not have.  IRN_ABI_VERSION of include/irn_hip.h moves with every such change; this is the value _SIGS is written for.
-ABI_VERSION = 105
+ABI_VERSION = 106
 lib.irn_version.restype, lib.irn_version.argtypes = C.c_int, []
 if lib.irn_version() != ABI_VERSION:
     raise ImportError("irn_amd: %s reports ABI version %d, these bindings need %d — it was built from another commit; "
@@ -51,6 +51,7 @@ _SIGS = {
     "irn_seg_loss_forward": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, sz, vp]),
     "irn_seg_loss_backward": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
     "irn_seg_argmax": (i32, [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    "irn_seg_fuse": (i32, [ppv, pi32, pi32, pi32, pi32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "irn_walk_create": (i32, [i32, C.POINTER(vp)]),
     "irn_walk_destroy": (i32, [vp]),
     "irn_walk_configure": (i32, [vp, i32, pi32, pi32, pi32, C.POINTER(sz)]),
@@ -115,6 +116,8 @@ _SIGS = {
     "irn_crf_label_sweep": (i32, [vp, vp, vp, i32, i32, i32, C.POINTER(f32), i32, i32, f32, vp, vp, sz, vp]),
     "irn_crf_score_sweep_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "irn_crf_score_sweep": (i32, [vp, vp, vp, i32, i32, i32, C.POINTER(f32), i32, i32, vp, vp, vp, sz, vp]),
+    "irn_crf_prob_workspace_bytes": (sz, [i32, i32, i32]),
+    "irn_crf_prob": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, vp]),
     "irn_mask_overlap": (i32, [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "irn_ir_label_confusion": (i32, [vp, i32, pi32, i32, pi32, i32, vp, i32, i32, i32, vp, vp, vp]),
     "irn_cam_confusion": (i32, [vp, vp, i32, vp, i32, i32, vp, i32, i32, vp, vp, vp]),

@@ -199,3 +199,30 @@ def crf_score_sweep(img, scores, keys, thres, t=CRF_T, out=None, want_q=False):
                                       None if q is None else q.data_ptr(), None if ws is None else ws.data_ptr(), nbytes,
                                       _stream()))
     return (out, q) if want_q else out
+
+
+def crf_prob(img, prob, t=CRF_T, want_q=False):
+    """The dense CRF seeded with probabilities (irn_crf_prob): -U = log(max(prob, 1e-5)), the pairwise terms,
+    iterations and softmax of `crf_score_sweep`.  `img`: uint8 [H,W,3] RGB as for `crf_score_sweep`; `prob`: GPU fp32
+    [L,H,W], 2 <= L <= 32 (the `prob` of `seg_fuse`).  Returns uint8 [H,W] on the GPU, the first maximum of Q as the label index
+    itself — at t = 0 the arg-max of the clipped `prob` — and with `want_q` also Q fp32 [L,H,W]."""
+    _need_cuda(prob, "crf_prob: prob")
+    dev = prob.device
+    rgb = _crf_rgb(img, dev)
+    h, w = rgb.shape[:2]
+    if prob.dtype != torch.float32 or prob.dim() != 3 or tuple(prob.shape[1:]) != (h, w):
+        raise ValueError("crf_prob: prob %s %s for an image of %dx%d (fp32 [L,H,W])" % (prob.dtype, tuple(prob.shape), h, w))
+    l = int(prob.shape[0])
+    if int(t) < 0:
+        raise ValueError("crf_prob: t = %d iterations" % int(t))
+    nbytes = int(lib.irn_crf_prob_workspace_bytes(h, w, l))
+    if nbytes == 0:
+        raise ValueError("crf_prob: unsupported size %dx%d with %d labels (2..32)" % (h, w, l))
+    pr = prob.contiguous()
+    out = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    q = torch.empty((l, h, w), dtype=torch.float32, device=dev) if want_q else None
+    with torch.cuda.device(dev):
+        ws = _crf_workspace(dev, nbytes)
+        check(lib.irn_crf_prob(rgb.data_ptr(), pr.data_ptr(), l, h, w, int(t), out.data_ptr(), None if q is None else q.data_ptr(),
+                               ws.data_ptr(), ws.numel(), _stream()))
+    return (out, q) if want_q else out

@@ -585,6 +585,24 @@ __global__ void __launch_bounds__(TPB) k_score_unary(const float *__restrict__ s
     }
 }
 
+// -U of the probability-seeded CRF: -U_i = log(max(p_i, eps)), k_score_unary's rule without the threshold
+// column: a pixel with a NaN has s' = 1 at its first NaN channel and eps at every other one.  neg_u is [pixel][label].
+__global__ void __launch_bounds__(TPB) k_prob_unary(const float *__restrict__ prob, int l, int n, float *__restrict__ neg_u) {
+    const int p = blockIdx.x * TPB + threadIdx.x;
+    if (p >= n) return;
+    float *row = neg_u + (size_t)p * l;
+    int first_nan = -1;
+    for (int i = 0; i < l; i++) {
+        const float v = prob[(size_t)i * n + p];
+        if (v != v && first_nan < 0) first_nan = i;
+        row[i] = logf(v != v ? SCORE_EPS : fmaxf(v, SCORE_EPS));
+    }
+    if (first_nan >= 0) {
+        const float le = logf(SCORE_EPS);
+        for (int i = 0; i < l; i++) row[i] = (i == first_nan) ? 0.0f : le;      // log(1) : log(eps)
+    }
+}
+
 // Q of every CRF of a chunk as planes: out [crf][label][pixel] (the tests' view of the sweep)
 __global__ void __launch_bounds__(TPB) k_q_planes(const float *__restrict__ q, int n, int c, float *__restrict__ out) {
     const long total = (long)n * c;
@@ -932,5 +950,33 @@ extern "C" int irn_crf_score_sweep(const uint8_t *rgb_dev, const float *scores_d
             IRN_LAUNCH_CHECK("k_q_planes");
         }
     }
+    return IRN_OK;
+}
+
+extern "C" size_t irn_crf_prob_workspace_bytes(int h, int w, int l) {
+    if (l < 2 || irn_crf_workspace_bytes(h, w, l) == 0) return 0;
+    CrfWs W;
+    return carve_crf(nullptr, W, h, w, l, 0, 1, true);
+}
+
+extern "C" int irn_crf_prob(const uint8_t *rgb_dev, const float *prob_dev, int l, int h, int w, int t, uint8_t *labels_dev,
+                            float *q_dev, void *ws, size_t ws_bytes, void *stream_) {
+    hipStream_t s = (hipStream_t)stream_;
+    if (l < 2) return fail(IRN_ERR_ARG, "irn_crf_prob: l %d outside 2..%d", l, MAX_LABELS);
+    if (t < 0) return fail(IRN_ERR_ARG, "irn_crf_prob: t %d iterations", t);
+    if (!crf_args_ok(h, w, l, "irn_crf_prob")) return IRN_ERR_ARG;
+    if (!rgb_dev || !prob_dev || !labels_dev || !ws) return fail(IRN_ERR_ARG, "irn_crf_prob: a null pointer (rgb, prob, labels or ws)");
+    const size_t need = irn_crf_prob_workspace_bytes(h, w, l);
+    if (ws_bytes < need) return fail(IRN_ERR_STATE, "irn_crf_prob: workspace %zu < %zu bytes", ws_bytes, need);
+    CrfWs W;
+    carve_crf(ws, W, h, w, l, 0, 1, true);
+    const int n = h * w;
+    int rc = build_kernels(W, rgb_dev, h, w, l, t, s);
+    if (rc) return rc;
+    k_prob_unary<<<cdiv(n, TPB), TPB, 0, s>>>(prob_dev, l, n, W.neg_u);
+    IRN_LAUNCH_CHECK("k_prob_unary");
+    if ((rc = iterate_chunk(W, DenseUnary{W.neg_u}, n, 1, l, t, s))) return rc;
+    k_finish<<<cdiv(n, TPB), TPB, 0, s>>>(W.q, n, 1, l, nullptr, nullptr, q_dev, nullptr, labels_dev);
+    IRN_LAUNCH_CHECK("k_finish");
     return IRN_OK;
 }

@@ -14,7 +14,7 @@ struct UpsampleTap {
     float l;
 };
 
-__device__ __forceinline__ UpsampleTap upsample_tap(int o, int n, float rscale) {
+__host__ __device__ __forceinline__ UpsampleTap upsample_tap(int o, int n, float rscale) {
 #pragma clang fp contract(off)
     float s = rscale * ((float)o + 0.5f) - 0.5f;
     s = s < 0.f ? 0.f : s;

@@ -9,12 +9,13 @@ as `ops.X`, looked up at call time.
     instance.py     instance.hip   find_centroids*, cluster_centroids*, label4, detect_instance*, detect_batch_count,
                                    detection_overlap_batch, argmax_rethreshold_batch, the Pending* results
     crf.py          crf.hip        crf_filter, crf_inference_label, crf_ir_label, crf_label_sweep,
-                                   crf_score_sweep
+                                   crf_score_sweep, crf_prob
     eval_counts.py  eval.hip       eval_thresholds, cam_confusion, cam_confusion_matrices, label_confusion, mask_overlap,
                                    ir_label_confusion, boundary_distance, label_band, label_boundary_counts,
                                    mask_boundary_overlap
     cocomask.py     cocomask.hip   mask_rle, rle_to_string, rle_from_string, rle_decode, mask_polygons, polygon_fill
     seg_loss.py     seg_loss.hip   seg_loss_sums, seg_cross_entropy, seg_argmax
+                    seg_fuse.hip   seg_fuse
     gemm.py         conv1x1.cpp, split16.hip    the hipBLASLt convolutions of the trunk
     _host.py        what more than one of them needs: cached buffers, read_back, packed layouts and their staging
 
@@ -45,7 +46,7 @@ from .augment import (AUGMENT_DESC_WORDS, AUGMENT_LABEL_DESC_WORDS, AugmentTable
 from .bn_act import bn_act, bn_act_, bn_act_backward, bn_fold, bn_param_grads, stem_pool, upsample_bilinear
 from .cocomask import mask_polygons, mask_rle, polygon_fill, rle_decode, rle_from_string, rle_to_string
 from .crf import (CRF_GT_PROB, CRF_MAX_SWEEP, CRF_SCORE_EPS, CRF_T, crf_filter, crf_inference_label, crf_ir_label,
-                  crf_label_sweep, crf_score_sweep)
+                  crf_label_sweep, crf_prob, crf_score_sweep)
 from .eval_counts import (BAND_MAX_D, EVAL_CLASSES, EVAL_MAX_CLASSES, EVAL_MAX_THRES, boundary_distance, cam_confusion, cam_confusion_matrices,
                           eval_thresholds, ir_label_confusion, label_band, label_boundary_counts, label_confusion, mask_boundary_overlap,
                           mask_overlap)
@@ -56,7 +57,7 @@ from .instance import (PendingDetections, PendingOverlaps, PendingRleDetections,
                        cluster_centroids_batch, detect_batch_count, detect_instance, detect_instance_batch, detect_instance_rle_batch,
                        detection_overlap_batch, find_centroids_batch, find_centroids_with_refinement, label4)
 from .label import cam_merge, label_epilogue, label_sweep_confusion
-from .seg_loss import seg_argmax, seg_cross_entropy, seg_loss_sums
+from .seg_loss import SEG_FUSE_MAX_MAPS, seg_argmax, seg_cross_entropy, seg_fuse, seg_loss_sums
 from .msf import bicubic_plan, bicubic_resize, msf_pack, normalize_lut, rescale_size
 
 # the two helpers tests and tools used to reach under their private names: callers written against those keep working

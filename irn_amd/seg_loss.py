@@ -1,11 +1,12 @@
-"""Host side of irn_amd/csrc/seg_loss.hip: the fused bilinear-upsampling + softmax cross-entropy of segmentation training
-and the arg-max of segmentation inference.  `irn_amd.ops` re-exports the functions.  GPU tensors in, GPU tensors out; no CPU
-fallback."""
+"""Host side of irn_amd/csrc/seg_loss.hip and seg_fuse.hip: the fused bilinear-upsampling + softmax cross-entropy of
+segmentation training, the arg-max of segmentation inference and its multi-scale fusion.  `irn_amd.ops` re-exports the
+functions.  GPU tensors in, GPU tensors out; no CPU fallback."""
 import torch
 
-from ._lib import _need_cuda, _stream, check, lib
+from ._lib import _need_cuda, _stream, check, i32_array, lib, ptr_array
 
 MAX_CLASSES = 81                      # IRN_EVAL_MAX_CLASSES: background + 80
+SEG_FUSE_MAX_MAPS = 16                # IRN_SEG_FUSE_MAX_MAPS
 
 
 def _need_logits(who, logits, factor):
@@ -101,3 +102,58 @@ def seg_argmax(logits, factor, out_hw):
     with torch.cuda.device(logits.device):
         check(lib.irn_seg_argmax(logits.data_ptr(), b, c, h, w, factor, hh, ww, out.data_ptr(), _stream()))
     return out
+
+
+def _is_int(v):
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def seg_fuse(maps, sizes, stride, out_hw, want_label=True, want_prob=False):
+    """Multi-scale inference of one image in one launch (irn_seg_fuse): every map's logits upsampled bilinearly
+    to ``out_hw`` = (H, W), the softmax of each, their mean P and its arg-max, without any [C, H, W] tensor but the one asked for.
+
+    ``maps``: list of 1..16 GPU fp32 [C, h, w] tensors, contiguous, C in 2..81, one per scale; ``sizes``: list of (Hs, Ws),
+    the size of the rescaled image map m was computed from, with Hs <= h * stride and Hs <= stride * H (likewise the widths):
+    map m is read at ratio Hs / (stride * H).  Returns ``(label, prob)``: uint8 [H, W] = the first class that attains the
+    maximum of P (a NaN counts as the maximum) and fp32 [C, H, W] = P, each None unless asked for.  Bit-reproducible; label is
+    the arg-max of the very P that prob holds."""
+    who = "seg_fuse"
+    if not isinstance(maps, (list, tuple)) or not 1 <= len(maps) <= SEG_FUSE_MAX_MAPS:
+        raise ValueError("%s: maps must be a list of 1..%d tensors" % (who, SEG_FUSE_MAX_MAPS))
+    if not isinstance(sizes, (list, tuple)) or len(sizes) != len(maps):
+        raise ValueError("%s: sizes must be a list of one (Hs, Ws) per map, %d maps" % (who, len(maps)))
+    if not (_is_int(stride) and 1 <= stride <= 64):
+        raise ValueError("%s: integer stride in 1..64 expected, got %r" % (who, stride))
+    if not (want_label or want_prob):
+        raise ValueError("%s: neither the label nor the probabilities are asked for" % who)
+    try:
+        hh, ww = int(out_hw[0]), int(out_hw[1])
+        sizes = [(int(s[0]), int(s[1])) for s in sizes]
+    except (TypeError, ValueError, IndexError):
+        raise ValueError("%s: out_hw and every entry of sizes must be a pair of integers, got %r and %r" % (who, out_hw, sizes))
+    if not (1 <= hh <= 32768 and 1 <= ww <= 32768):
+        raise ValueError("%s: out_hw %s outside 1..32768" % (who, (hh, ww)))
+    for m, t in enumerate(maps):
+        _need_cuda(t, "%s: maps[%d]" % (who, m))
+        if t.dtype != torch.float32 or t.dim() != 3 or not t.is_contiguous():
+            raise ValueError("%s: maps[%d] must be a contiguous fp32 [C, h, w] tensor, got %s %s %s"
+                             % (who, m, t.dtype, tuple(t.shape), t.stride()))
+        if t.device != maps[0].device or t.shape[0] != maps[0].shape[0]:
+            raise ValueError("%s: maps[%d] has %d channels on %s, maps[0] %d on %s"
+                             % (who, m, t.shape[0], t.device, maps[0].shape[0], maps[0].device))
+        hs, ws = sizes[m]
+        if not (1 <= hs <= min(t.shape[1], hh) * stride and 1 <= ws <= min(t.shape[2], ww) * stride):
+            raise ValueError("%s: sizes[%d] = %s does not fit a map of %s and an output of %s at stride %d"
+                             % (who, m, (hs, ws), tuple(t.shape[1:]), (hh, ww), stride))
+    c = int(maps[0].shape[0])
+    if not 2 <= c <= MAX_CLASSES:
+        raise ValueError("%s: %d channels outside 2..%d" % (who, c, MAX_CLASSES))
+    dev = maps[0].device
+    label = torch.empty((hh, ww), dtype=torch.uint8, device=dev) if want_label else None
+    prob = torch.empty((c, hh, ww), dtype=torch.float32, device=dev) if want_prob else None
+    with torch.cuda.device(dev):
+        check(lib.irn_seg_fuse(ptr_array([t.data_ptr() for t in maps]), i32_array([t.shape[1] for t in maps]),
+                               i32_array([t.shape[2] for t in maps]), i32_array([s[0] for s in sizes]),
+                               i32_array([s[1] for s in sizes]), len(maps), c, stride, hh, ww,
+                               None if label is None else label.data_ptr(), None if prob is None else prob.data_ptr(), _stream()))
+    return label, prob

@@ -50,6 +50,13 @@ def build_parser():
                         "comparison (three such tensors, float atomics in the backward: not reproducible)")
     p.add_argument("--seg_pred_dir", default="result/seg_pred", type=str,
                    help="where infer_sem_seg writes its PNGs and --eval_seg_pass reads them")
+    p.add_argument("--seg_infer_scales", default=[1.0], type=float, nargs="+", metavar="S",
+                   help="infer_sem_seg: 1..16 factors in (0, 4] the image is rescaled by (bicubic); the softmax of every scale's "
+                        "logits, upsampled to the image's size, is averaged in one HIP launch (ops.seg_fuse).  Default 1.0 alone: "
+                        "the single-scale arg-max (ops.seg_argmax)")
+    p.add_argument("--seg_crf_iters", default=0, type=int,
+                   help="infer_sem_seg: mean-field iterations of a dense CRF seeded with the averaged probabilities "
+                        "(ops.crf_prob); 0 = off (default); needs --num_classes <= 31")
     return p
 
 
